@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: images/sec of one full training step of UNet_Nested on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -86,7 +86,13 @@ def parse():
                     help="multi-process plumbing only, on the CPU over gloo, with synthetic gradients and NO kernels: "
                          "self-spawn, rendezvous, broadcast, bucketed all-reduce, optimizer, max-over-ranks timing, "
                          "replica check (tests/test_dp_gloo.py); the line it prints is labelled a rehearsal")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step of the configuration named on the command "
+                         "line computed as DIR/<name>.npy (rank 0; see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def usable_cores():
@@ -406,6 +412,47 @@ def other_entry(name, o, r, world):
             "replicas_bit_identical": r["replicas_identical"]}
 
 
+DUMP_BUDGET_BYTES = 64 * 10 ** 6 - (1 << 20)   # --dump-outputs: 64 MB in all, less room for the .npy headers
+
+
+def dump_outputs(out_dir, outputs, loss, model, budget=DUMP_BUDGET_BYTES):
+    """`--dump-outputs DIR`: what the last timed step computed, one DIR/<name>.npy per array -- `loss`, `head<i>` (the outputs
+    train_step returns), `state.<key>` (the state_dict after the optimizer step: parameters and BatchNorm running
+    statistics) and `grad.<name>` (that step's parameter gradients).  Floating arrays are written as float32 (float64 stays
+    float64), integer ones as float64.  When everything would exceed `budget` bytes, every array longer than the largest
+    common length k that fits is replaced by the fixed 1-D sample a.reshape(-1)[idx] with
+    idx = sort(numpy.random.default_rng(0).choice(a.size, k, replace=False)): the same arguments sample the same elements,
+    so two builds can be compared file by file.  Returns the number of bytes of array data written."""
+    import numpy as np
+    import torch
+    heads = outputs if isinstance(outputs, (tuple, list)) else (outputs,)
+    named = [("loss", loss)] + [("head%d" % i, o) for i, o in enumerate(heads)]
+    named += [("state." + k, v) for k, v in model.state_dict().items()]
+    named += [("grad." + n, p.grad) for n, p in model.named_parameters() if p.grad is not None]
+    arrays = []
+    for name, t in named:
+        t = torch.as_tensor(t).detach()
+        dtype = torch.float64 if t.dtype == torch.float64 or not t.is_floating_point() else torch.float32
+        arrays.append((name, t.to(dtype).cpu().numpy()))
+
+    def nbytes(k):
+        return sum(min(a.size, k) * a.itemsize for _, a in arrays)
+
+    cap = max(a.size for _, a in arrays)
+    if nbytes(cap) > budget:
+        lo, hi = 0, cap   # the largest k with nbytes(k) <= budget
+        while lo < hi:
+            mid = (lo + hi + 1) // 2
+            lo, hi = (mid, hi) if nbytes(mid) <= budget else (lo, mid - 1)
+        cap = lo
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays:
+        if a.size > cap:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return nbytes(cap)
+
+
 def measure(args, ctx):
     """Times `args.steps` train steps of ONE configuration (after prewarm + warmup untimed ones) under the contract's
     barrier / synchronize bracket and returns rank 0's result pieces (None on the other ranks)."""
@@ -470,6 +517,8 @@ def measure(args, ctx):
     # (903 vs 1083 img/s at configs[3] with identical per-kernel times, profiles/r4/launch_event_cost.txt).
     events_inside = not (getattr(args, "events_after", False) or getattr(args, "graphed", False))
     host_ms = []  # host time to ENQUEUE a step (no sync inside): when it nears ms_per_step the run is launch-bound
+    dump_dir = getattr(args, "dump_outputs", None) if rank == 0 else None
+    last = None   # (outputs, loss) of the last timed step, kept only for --dump-outputs
     if distributed:
         dist.barrier()
     torch.cuda.synchronize()
@@ -484,8 +533,11 @@ def measure(args, ctx):
         ops.set_timer(timer if (sample or sample_regions) else None)
         sampled_steps += int(sample)
         h0 = time.perf_counter()
-        run_step(model, opt, crit, x, target)
+        ret = run_step(model, opt, crit, x, target)
         host_ms.append(1e3 * (time.perf_counter() - h0))
+        if dump_dir is not None and i == args.steps - 1:
+            last = ret
+        del ret   # no step's outputs outlive it otherwise
     ops.set_timer(None)
     torch.cuda.synchronize()
     if distributed:
@@ -497,6 +549,11 @@ def measure(args, ctx):
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if last is not None:   # before anything else runs on the model: later launches may reuse the outputs' memory
+        written = dump_outputs(dump_dir, last[0], last[1], model)
+        print("bench.py: wrote the last timed step's outputs to %s (%.1f MB)" % (dump_dir, written / 1e6), file=sys.stderr)
+        del last
 
     if not events_inside:
         for _ in range(2):
@@ -707,6 +764,7 @@ def main():
             # eager train_step, like the headline (round 5: the graph replay buys no device time -- DESIGN.md section 8 --
             # and is experimental; `--graphed` opts in)
             o.steps, o.warmup, o.prewarm, o.events_after, o.graphed = max(20, args.other_steps), 10, 15, True, bool(args.graphed)
+            o.dump_outputs = None   # --dump-outputs is the configuration named on the command line
             try:
                 r = measure(o, ctx)
                 entry_ = None if r is None else other_entry(name, o, r, world)

@@ -163,3 +163,60 @@ def test_bench_live_pmc_falls_back_without_a_gpu(tmp_path):
     traffic, busy, source = bench.pmc_counters("gemm_wino_kernel", "h", key)
     assert traffic == round((120 * 3 + 80) / 4) and abs(busy - (0.5 * 30 + 0.25 * 10) / 40) < 1e-4 and source.startswith("live")
     assert bench.pmc_counters("gemm_wino_kernel", "other", key) == (None, None, None)   # a live summary of another build: refused too
+
+
+def test_bench_dump_outputs_is_complete_bounded_and_repeatable(tmp_path):
+    """bench.dump_outputs (`--dump-outputs DIR`): one float32 / float64 .npy per array of the last step (loss, heads, state
+    after the optimizer step, gradients), exact while everything fits; over the budget the long arrays shrink to the same
+    seeded sample on every call, and the files stay within the budget."""
+    import importlib.util
+    import os
+
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_module_dump", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    torch.manual_seed(0)
+    m = UNet_Nested(in_channels=1, n_classes=4, feature_scale=8)
+    for p in m.parameters():
+        p.grad = torch.randn_like(p)
+    heads = tuple(torch.rand(2, 4, 32, 32) for _ in range(3))
+    loss = torch.tensor(0.75)
+    state = m.state_dict()
+
+    full = tmp_path / "full"
+    bench.dump_outputs(str(full), heads, loss, m)
+    names = {f[:-4] for f in os.listdir(full)}
+    assert names == {"loss", "head0", "head1", "head2"} | {"state." + k for k in state} | \
+        {"grad." + n for n, _ in m.named_parameters()}
+    for k, v in state.items():
+        a = np.load(full / ("state.%s.npy" % k))
+        assert a.dtype == (np.float32 if v.is_floating_point() else np.float64) and a.shape == tuple(v.shape)
+        assert np.array_equal(a, v.double().numpy())
+    assert np.array_equal(np.load(full / "head1.npy"), heads[1].numpy())
+    assert float(np.load(full / "loss.npy")) == 0.75
+
+    budget = 4 * heads[0].numel()   # less than the three heads alone: they must be sampled
+    small = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        written = bench.dump_outputs(str(d), heads, loss, m, budget=budget)
+        assert written <= budget
+        small.append({f: np.load(d / f) for f in sorted(os.listdir(d))})
+    assert sum(a.nbytes for a in small[0].values()) <= budget
+    assert small[0].keys() == small[1].keys() and all(np.array_equal(small[0][f], small[1][f]) for f in small[0])
+    h0 = small[0]["head0.npy"]
+    assert h0.ndim == 1 and h0.size < heads[0].numel()
+    idx = np.sort(np.random.default_rng(0).choice(heads[0].numel(), h0.size, replace=False))
+    assert np.array_equal(h0, heads[0].numpy().reshape(-1)[idx])
+
+
+def test_bench_refuses_zero_steps():
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "0"], capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode == 2 and "--steps must be at least 1" in r.stderr
