@@ -417,6 +417,50 @@ int unetpp_keypoints_extract(int32_t stage, const float* heat, int32_t maps, int
                              const float* thr_per_map, int32_t num, int32_t max_regions, int32_t sweeps,
                              void* workspace, int32_t* changed, float* points, int32_t* counts, void* stream);
 
+/* ---- Fused optimizer step (csrc/optim.hip): the reference trainer's AdamW / AdaBound / SGDW
+ * (tools/optimizers/{adamw,adabound,sgdw}.py) as one multi-tensor launch per step.  These symbols, the struct and the
+ * constants below were added at ABI version 11 without changing anything that was there before: the additions are
+ * backward compatible, a caller of the earlier version-11 library sees no difference. ---- */
+#define UNETPP_OPTIM_ADAMW 0
+#define UNETPP_OPTIM_ADABOUND 1
+#define UNETPP_OPTIM_SGDW 2
+#define UNETPP_OPTIM_AMS 1          /* flags: amsgrad / amsbound (aux = max_exp_avg_sq) */
+#define UNETPP_OPTIM_CAPTURABLE 2   /* flags: step counters live on the device (segment.step), advanced by the launch */
+#define UNETPP_OPTIM_HYPER 8        /* doubles per parameter group in the hyper-parameter block: lr, beta1 (SGDW:
+                                       momentum), beta2 (SGDW: dampening), eps, weight_decay, AdaBound's final_lr * lr /
+                                       base_lr, gamma, unused */
+
+/* One parameter tensor (fp32, contiguous) of the step.  Segments are in chunk order: segment i owns chunks
+ * [chunk_begin, chunk_begin + ceil(numel / unetpp_optim_chunk_elems())). */
+typedef struct unetpp_optim_segment {
+  float* param;
+  const float* grad;
+  float* exp_avg;       /* AdamW / AdaBound; NULL for SGDW */
+  float* exp_avg_sq;    /* AdamW / AdaBound; NULL for SGDW */
+  float* aux;           /* max_exp_avg_sq (UNETPP_OPTIM_AMS), momentum_buffer (SGDW, momentum != 0), else NULL */
+  float* step;          /* UNETPP_OPTIM_CAPTURABLE: the float32 count of updates before this one; else NULL */
+  int64_t numel;
+  int64_t chunk_begin;
+  int32_t group;        /* row of the hyper-parameter block */
+  int32_t vec;          /* 1 when param, grad, exp_avg, exp_avg_sq and aux are all 16-byte aligned */
+} unetpp_optim_segment;
+
+/* Elements per chunk of unetpp_optim_step (host only). */
+int64_t unetpp_optim_chunk_elems(void);
+/* unetpp_optim_step: one update of every segment (device table `segments`, n_segments rows; chunk_segment [n_chunks]:
+ * the segment of each chunk).  kind = UNETPP_OPTIM_ADAMW / _ADABOUND / _SGDW; flags = UNETPP_OPTIM_AMS (not with SGDW)
+ * | UNETPP_OPTIM_CAPTURABLE.  hyper [groups * UNETPP_OPTIM_HYPER] (device doubles).  Eager: steps [n_segments] (device
+ * doubles) is the count of updates INCLUDING this one (SGDW: 1 on the momentum buffer's first update), done = NULL.
+ * Capturable: steps = NULL, the count comes from segment.step + 1 and every segment.step is incremented once by the
+ * launch; done is a device int32, zero before the first launch, that the launch leaves zero.
+ * Negative status without touching the device for a null table, zero segments or chunks, a bad kind or bad flags. */
+int unetpp_optim_step(int32_t kind, int32_t flags, const unetpp_optim_segment* segments, int32_t n_segments,
+                      const int32_t* chunk_segment, int64_t n_chunks, const double* hyper, const double* steps,
+                      int32_t* done, void* stream);
+/* unetpp_optim_upload: hipMemcpyAsync host -> device on `stream` (the segment table of a step; with page-locked
+ * `host_src` it is a memcpy node when the stream is being captured, and host_src must then outlive the graph). */
+int unetpp_optim_upload(void* dst, const void* host_src, int64_t bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,7 +15,7 @@ _REPO = os.path.dirname(_PKG_DIR)
 LIB_PATH = os.environ.get("UNETPP_LIB", os.path.join(_PKG_DIR, "libunetpp_hip.so"))  # override: kernel A/B runs
 CSRC = os.path.join(_PKG_DIR, "csrc")
 INCLUDE = os.path.join(_REPO, "include")
-SOURCES = ("gemm_pix.hip", "gemm_fast.hip", "gemm_pw.hip", "gemm_pw_bf16.hip", "gemm_wino.hip", "gemm_bf16.hip", "gemm_bf16_dma.hip", "wgrad_bf16.hip", "pointwise_bf16.hip", "keypoints.hip", "weight_image.hip", "wgrad.hip", "wgrad_fast.hip", "wgrad_dma.hip", "wgrad_pw.hip", "wgrad_wino.hip", "first_layer.hip", "pointwise.hip", "caller.hip")
+SOURCES = ("gemm_pix.hip", "gemm_fast.hip", "gemm_pw.hip", "gemm_pw_bf16.hip", "gemm_wino.hip", "gemm_bf16.hip", "gemm_bf16_dma.hip", "wgrad_bf16.hip", "pointwise_bf16.hip", "keypoints.hip", "weight_image.hip", "wgrad.hip", "wgrad_fast.hip", "wgrad_dma.hip", "wgrad_pw.hip", "wgrad_wino.hip", "first_layer.hip", "pointwise.hip", "caller.hip", "optim.hip")
 HEADERS = ("common.h", "gemm_units.h", "wgrad_reduce.h", "lds_asm.h", "bf16_common.h", "dropout.h", "bn_fused.h",
            "wino_experiments.h", "dma_experiments.h")
 MAX_VIEWS = 8
@@ -109,6 +109,19 @@ class WgradDesc(C.Structure):
     ]
 
 
+class OptimSegment(C.Structure):
+    """mirror of struct unetpp_optim_segment"""
+    _fields_ = [
+        ("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+        ("aux", C.c_void_p), ("step", C.c_void_p),
+        ("numel", C.c_int64), ("chunk_begin", C.c_int64), ("group", C.c_int32), ("vec", C.c_int32),
+    ]
+
+
+OPTIM_ADAMW, OPTIM_ADABOUND, OPTIM_SGDW = 0, 1, 2   # unetpp_optim_step kinds
+OPTIM_AMS, OPTIM_CAPTURABLE = 1, 2                 # unetpp_optim_step flags
+OPTIM_HYPER = 8                                    # doubles per group of the hyper-parameter block
+
 _P, _I32, _I64, _F, _U64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_uint64
 
 # name -> (restype, argtypes); kept in step with include/unetpp_hip.h (tests/test_abi.py checks it)
@@ -174,6 +187,10 @@ SIGNATURES = {
     "unetpp_keypoints_workspace_bytes": (_I64, [_I32, _I32, _I32, _I32]),
     "unetpp_keypoints_extract": (C.c_int, [_I32, _P, _I32, _I32, _I32, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
     "unetpp_head_bwd_bf16": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _F, _U64, _P, _P, _P, _I32, _I32, _P, _P]),
+    # fused optimizer step (optim.hip)
+    "unetpp_optim_chunk_elems": (_I64, []),
+    "unetpp_optim_step": (C.c_int, [_I32, _I32, _P, _I32, _P, _I64, _P, _P, _P, _P]),
+    "unetpp_optim_upload": (C.c_int, [_P, _P, _I64, _P]),
 }
 
 _LIB = None

@@ -1,0 +1,216 @@
+// Fused optimizer step: the reference trainer's own optimizers (tools/optimizers/{adamw,adabound,sgdw}.py) as ONE
+// multi-tensor launch per step.  Every parameter of every group is a segment of a device table; a persistent grid walks
+// fixed-size chunks of the segments (chunk -> segment map built by the caller), float4 where all five streams of a
+// segment are 16-byte aligned, scalar in the tail.
+//
+// Per element the op sequence of the reference's torch calls is restated in their order, each aten op rounded once as
+// aten's CPU kernels round it (the golden fixtures are CPU runs of the reference): add(a, b, alpha) = fma(alpha, b, a),
+// addcmul(a, b, c, s) = fma(s*b, c, a), addcdiv(a, b, c, s) = a + (s*b)/c.  Implicit contraction is off; every fma
+// below is one aten op.
+//   AdamW     m = fma(1-b1, g, m*b1);  v = fma((1-b2)*g, g, v*b2);  [vmax = max(vmax, v)];  denom = sqrt(v|vmax) + eps;
+//             [d = p*wd];  p = p + (-step_size*m)/denom;  [p = p - d]
+//   AdaBound  [g = fma(wd, p, g)];  m, v, vmax, denom as above;  s = clamp(step_size/denom, lo, hi)*m;  p = p - s
+//   SGDW      [buf = first ? 0 + g : fma(1-damp, g, buf*mom)];  [p = fma(-wd, p, p)]   (the reference never applies g)
+// Scalars (bias corrections, step size, AdaBound's bounds) are formed in double from the segment's own step count and
+// rounded to float once, as the reference forms them in Python floats and hands them to aten as float scalars.
+// No floating-point atomics, no cross-workgroup order: every element's result depends on that element alone.
+#include "common.h"
+
+#include <math.h>
+
+#pragma clang fp contract(off)
+
+namespace unetpp {
+namespace {
+
+constexpr int kOptThreads = 256;
+constexpr int kOptVecPerThread = 4;                                      // float4 per thread and stream
+constexpr int64_t kOptChunk = int64_t(kOptThreads) * kOptVecPerThread * 4;   // 4096 elements
+
+enum { H_LR = 0, H_B1 = 1, H_B2 = 2, H_EPS = 3, H_WD = 4, H_FINAL_LR = 5, H_GAMMA = 6 };
+
+struct Scalars {
+  float b1, omb1, b2, omb2, eps, wd, neg_step, step, lo, hi;
+  bool first;
+};
+
+__device__ __forceinline__ Scalars make_scalars(int kind, const double* h, double t) {
+  Scalars s;
+  s.b1 = static_cast<float>(h[H_B1]);
+  s.b2 = static_cast<float>(h[H_B2]);
+  s.omb1 = static_cast<float>(1.0 - h[H_B1]);
+  s.omb2 = static_cast<float>(1.0 - h[H_B2]);   // SGDW: 1 - dampening
+  s.eps = static_cast<float>(h[H_EPS]);
+  s.wd = static_cast<float>(h[H_WD]);
+  s.first = t <= 1.0;
+  s.step = s.neg_step = s.lo = s.hi = 0.f;
+  if (kind != UNETPP_OPTIM_SGDW) {
+    const double bc1 = 1.0 - pow(h[H_B1], t);
+    const double bc2 = 1.0 - pow(h[H_B2], t);
+    const double step_size = h[H_LR] * sqrt(bc2) / bc1;
+    s.step = static_cast<float>(step_size);
+    s.neg_step = static_cast<float>(-step_size);
+    if (kind == UNETPP_OPTIM_ADABOUND) {
+      const double f = h[H_FINAL_LR], gamma = h[H_GAMMA];
+      s.lo = static_cast<float>(f * (1.0 - 1.0 / (gamma * t + 1.0)));
+      s.hi = static_cast<float>(f * (1.0 + 1.0 / (gamma * t)));
+    }
+  }
+  return s;
+}
+
+// one element of every stream; aux = max_exp_avg_sq (AMS) or momentum_buffer (SGDW)
+template <int KIND, bool AMS>
+__device__ __forceinline__ void update(float& p, float g, float& m, float& v, float& a, const Scalars& s, bool decay,
+                                       bool has_aux) {
+  if (KIND == UNETPP_OPTIM_SGDW) {
+    if (has_aux) a = s.first ? 0.f + g : fmaf(s.omb2, g, a * s.b1);
+    if (decay) p = fmaf(-s.wd, p, p);
+    return;
+  }
+  if (KIND == UNETPP_OPTIM_ADABOUND && decay) g = fmaf(s.wd, p, g);
+  m = fmaf(s.omb1, g, m * s.b1);
+  v = fmaf(s.omb2 * g, g, v * s.b2);
+  float denom;
+  if (AMS) {
+    a = fmaxf(a, v);
+    denom = __fsqrt_rn(a) + s.eps;
+  } else {
+    denom = __fsqrt_rn(v) + s.eps;
+  }
+  if (KIND == UNETPP_OPTIM_ADAMW) {
+    const float d = decay ? p * s.wd : 0.f;
+    p = p + (s.neg_step * m) / denom;
+    if (decay) p = p - d;
+  } else {
+    float r = s.step / denom;
+    r = fminf(fmaxf(r, s.lo), s.hi);
+    r = r * m;
+    p = p - r;
+  }
+}
+
+template <int KIND, bool AMS>
+__global__ void __launch_bounds__(kOptThreads) optim_kernel(const unetpp_optim_segment* __restrict__ segs,
+                                                            int32_t n_segments, const int32_t* __restrict__ chunk_seg,
+                                                            int64_t n_chunks, const double* __restrict__ hyper,
+                                                            const double* __restrict__ steps, int32_t* done) {
+  for (int64_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+    const int si = chunk_seg[c];
+    const unetpp_optim_segment sg = segs[si];
+    // (a capturable SGDW segment without momentum has no counter: its count is never used)
+    const double t = sg.step != nullptr ? static_cast<double>(*sg.step) + 1.0 : steps != nullptr ? steps[si] : 2.0;
+    const Scalars s = make_scalars(KIND, hyper + int64_t(sg.group) * UNETPP_OPTIM_HYPER, t);
+    const bool decay = s.wd != 0.f;
+    const bool has_aux = sg.aux != nullptr;
+    const int64_t begin = (c - sg.chunk_begin) * kOptChunk;
+    const int64_t end = begin + kOptChunk < sg.numel ? begin + kOptChunk : sg.numel;
+    float* __restrict__ P = sg.param;
+    const float* __restrict__ G = sg.grad;
+    float* __restrict__ M = sg.exp_avg;
+    float* __restrict__ V = sg.exp_avg_sq;
+    float* __restrict__ A = sg.aux;
+    const bool moments = KIND != UNETPP_OPTIM_SGDW;
+    if (sg.vec) {
+      const int64_t vend = begin + ((end - begin) & ~int64_t(3));
+#pragma unroll
+      for (int k = 0; k < kOptVecPerThread; ++k) {
+        const int64_t i = begin + (int64_t(k) * kOptThreads + threadIdx.x) * 4;
+        if (i >= vend) break;
+        f32x4 p = *reinterpret_cast<const f32x4*>(P + i);
+        const f32x4 g = *reinterpret_cast<const f32x4*>(G + i);
+        f32x4 m = {0.f, 0.f, 0.f, 0.f}, v = m, a = m;
+        if (moments) {
+          m = *reinterpret_cast<const f32x4*>(M + i);
+          v = *reinterpret_cast<const f32x4*>(V + i);
+        }
+        if (has_aux && (AMS || KIND == UNETPP_OPTIM_SGDW)) a = *reinterpret_cast<const f32x4*>(A + i);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          float pe = p[e], me = m[e], ve = v[e], ae = a[e];
+          update<KIND, AMS>(pe, g[e], me, ve, ae, s, decay, has_aux);
+          p[e] = pe, m[e] = me, v[e] = ve, a[e] = ae;
+        }
+        if (KIND != UNETPP_OPTIM_SGDW || decay) *reinterpret_cast<f32x4*>(P + i) = p;
+        if (moments) {
+          *reinterpret_cast<f32x4*>(M + i) = m;
+          *reinterpret_cast<f32x4*>(V + i) = v;
+        }
+        if (has_aux && (AMS || KIND == UNETPP_OPTIM_SGDW)) *reinterpret_cast<f32x4*>(A + i) = a;
+      }
+      for (int64_t i = vend + threadIdx.x; i < end; i += kOptThreads) {   // < 4 elements: the segment's tail
+        float pe = P[i], me = moments ? M[i] : 0.f, ve = moments ? V[i] : 0.f, ae = has_aux ? A[i] : 0.f;
+        update<KIND, AMS>(pe, G[i], me, ve, ae, s, decay, has_aux);
+        P[i] = pe;
+        if (moments) M[i] = me, V[i] = ve;
+        if (has_aux) A[i] = ae;
+      }
+    } else {
+      for (int64_t i = begin + threadIdx.x; i < end; i += kOptThreads) {
+        float pe = P[i], me = moments ? M[i] : 0.f, ve = moments ? V[i] : 0.f, ae = has_aux ? A[i] : 0.f;
+        update<KIND, AMS>(pe, G[i], me, ve, ae, s, decay, has_aux);
+        P[i] = pe;
+        if (moments) M[i] = me, V[i] = ve;
+        if (has_aux) A[i] = ae;
+      }
+    }
+  }
+  if (done == nullptr) return;
+  // capturable: the device step counters advance once every workgroup has read them -- the last workgroup to arrive
+  // (integer arrival counter, reset for the next launch) does it; nothing floating-point depends on the order
+  __shared__ int last;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    __threadfence();
+    last = atomicAdd(done, 1) == static_cast<int>(gridDim.x) - 1;
+  }
+  __syncthreads();
+  if (!last) return;
+  for (int i = threadIdx.x; i < n_segments; i += kOptThreads)
+    if (segs[i].step != nullptr) segs[i].step[0] = segs[i].step[0] + 1.f;
+  if (threadIdx.x == 0) *done = 0;
+}
+
+template <int KIND, bool AMS>
+void launch(const unetpp_optim_segment* segs, int32_t n, const int32_t* chunk_seg, int64_t n_chunks,
+            const double* hyper, const double* steps, int32_t* done, hipStream_t st) {
+  const int cus = device_cu_count();
+  const int64_t cap = int64_t(cus > 0 ? cus : 256) * 8;
+  const unsigned grid = static_cast<unsigned>(n_chunks < cap ? n_chunks : cap);
+  hipLaunchKernelGGL((optim_kernel<KIND, AMS>), dim3(grid), dim3(kOptThreads), 0, st, segs, n, chunk_seg, n_chunks,
+                     hyper, steps, done);
+}
+
+}  // namespace
+}  // namespace unetpp
+
+using namespace unetpp;
+
+extern "C" int64_t unetpp_optim_chunk_elems(void) { return kOptChunk; }
+
+extern "C" int unetpp_optim_step(int32_t kind, int32_t flags, const unetpp_optim_segment* segments, int32_t n_segments,
+                                 const int32_t* chunk_segment, int64_t n_chunks, const double* hyper,
+                                 const double* steps, int32_t* done, void* stream) {
+  if (segments == nullptr || n_segments <= 0 || chunk_segment == nullptr || n_chunks <= 0 || hyper == nullptr)
+    return UNETPP_EINVAL;
+  if (kind < UNETPP_OPTIM_ADAMW || kind > UNETPP_OPTIM_SGDW) return UNETPP_EINVAL;
+  if ((flags & ~(UNETPP_OPTIM_AMS | UNETPP_OPTIM_CAPTURABLE)) != 0) return UNETPP_EINVAL;
+  const bool ams = (flags & UNETPP_OPTIM_AMS) != 0, capturable = (flags & UNETPP_OPTIM_CAPTURABLE) != 0;
+  if (ams && kind == UNETPP_OPTIM_SGDW) return UNETPP_EINVAL;
+  if (capturable ? (done == nullptr || steps != nullptr) : (steps == nullptr || done != nullptr)) return UNETPP_EINVAL;
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  switch (kind * 2 + (ams ? 1 : 0)) {
+    case UNETPP_OPTIM_ADAMW * 2: launch<UNETPP_OPTIM_ADAMW, false>(segments, n_segments, chunk_segment, n_chunks, hyper, steps, done, st); note_kernel("optim_adamw"); break;
+    case UNETPP_OPTIM_ADAMW * 2 + 1: launch<UNETPP_OPTIM_ADAMW, true>(segments, n_segments, chunk_segment, n_chunks, hyper, steps, done, st); note_kernel("optim_adamw_amsgrad"); break;
+    case UNETPP_OPTIM_ADABOUND * 2: launch<UNETPP_OPTIM_ADABOUND, false>(segments, n_segments, chunk_segment, n_chunks, hyper, steps, done, st); note_kernel("optim_adabound"); break;
+    case UNETPP_OPTIM_ADABOUND * 2 + 1: launch<UNETPP_OPTIM_ADABOUND, true>(segments, n_segments, chunk_segment, n_chunks, hyper, steps, done, st); note_kernel("optim_adabound_amsbound"); break;
+    default: launch<UNETPP_OPTIM_SGDW, false>(segments, n_segments, chunk_segment, n_chunks, hyper, steps, done, st); note_kernel("optim_sgdw"); break;
+  }
+  return launch_status();
+}
+
+extern "C" int unetpp_optim_upload(void* dst, const void* host_src, int64_t bytes, void* stream) {
+  if (dst == nullptr || host_src == nullptr || bytes <= 0) return UNETPP_EINVAL;
+  return hipMemcpyAsync(dst, host_src, static_cast<size_t>(bytes), hipMemcpyHostToDevice,
+                        static_cast<hipStream_t>(stream)) == hipSuccess ? UNETPP_OK : UNETPP_ELAUNCH;
+}

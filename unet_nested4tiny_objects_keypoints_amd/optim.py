@@ -1,0 +1,385 @@
+"""The reference trainer's own optimizers with a HIP hot path: one fused launch per ``step()``.
+
+Drop-in for tools/optimizers/{adamw,adabound,sgdw}.py of the reference (trainer/trainer.py:344-379 maps its
+``--optimizer`` names adamw / adabound / sgdw to them):
+
+    from unet_nested4tiny_objects_keypoints_amd.optim import AdamW, AdaBound, SGDW
+
+Constructor signatures, defaults, ``ValueError`` checks, param-group keys and (in the default eager mode) the state
+format are the reference's: ``state['step']`` is a Python int per parameter beside ``exp_avg`` / ``exp_avg_sq`` /
+``max_exp_avg_sq`` or ``momentum_buffer``, so ``.tar`` checkpoints (checkpoint.py) move between these classes and the
+reference's in both directions.  Steps are counted per parameter: a parameter whose ``grad`` is None is skipped and its
+count does not advance.  ``group['lr']`` is read at every step (LR schedulers work unchanged).
+
+What ``step()`` does on the device (csrc/optim.hip, ``unetpp_optim_step``): every parameter with a gradient is a segment
+of one device table, and one launch updates them all, element by element in the reference's op order.  The table is
+built once per set of data pointers (parameters, their CURRENT gradients, state tensors) and cached, so a gradient
+buffer that moves (the data-parallel averager swaps ``p.grad`` between two flat buffers, dp.py) gets its own table.
+Eager mode: per step one small host -> device copy (the hyper-parameters and each segment's step count) and one
+launch.  The update writes through raw pointers, as the reference writes through ``p.data``: ``p._version`` does not
+move (the weight-image pack plan is rebuilt every pass).
+
+``capturable=True``: ``state['step']`` is a float32 device scalar per parameter, the bias corrections and AdaBound's
+bounds are formed on the device and the launch itself advances the counters -- no host sync, no host decision on device
+data, so ``GraphedTrainStep(..., capture_optimizer=True)`` captures the step.  The hyper-parameters are read from a
+small device block: an eager ``step()`` refreshes it, a captured one does not, so after changing ``group['lr']`` (an LR
+scheduler) call ``refresh_hyperparameters()`` before the next replay.
+
+fp32 CUDA tensors only: anything else raises (this path has no CPU fallback).
+"""
+from __future__ import annotations
+
+import collections
+import ctypes as C
+
+import numpy as np
+import torch
+from torch.optim.optimizer import Optimizer, required
+
+from . import _lib
+
+_SEG_BYTES = C.sizeof(_lib.OptimSegment)
+_MAX_TABLES = 8     # cached device tables (the data-parallel averager alternates between two)
+
+
+class _Table:
+    """One cached device table: segments, chunk -> segment map, the arrival counter of capturable launches."""
+    __slots__ = ("dev", "host", "n_seg", "n_chunks", "chunk_off", "done_off", "block", "pinned", "rows_used")
+
+
+class _FusedOptimizer(Optimizer):
+    """Common host side of the three classes: state bookkeeping, the cached segment table, the launch."""
+    _KIND = None
+    _AMS_KEY = None          # group key that selects max_exp_avg_sq
+    _MOMENTS = True          # exp_avg / exp_avg_sq (AdamW, AdaBound)
+
+    def _init_fused(self, capturable: bool):
+        self.capturable = bool(capturable)
+        self._tables = collections.OrderedDict()
+        self._state_epoch = 0
+        self._hyper_dev = None
+        self._spare_host = None
+
+    # ---- hyper-parameters -------------------------------------------------------------------------------------------
+    def _hyper_row(self, gi: int, group) -> list:
+        raise NotImplementedError
+
+    def _hyper(self) -> np.ndarray:
+        rows = [self._hyper_row(gi, g) for gi, g in enumerate(self.param_groups)]
+        return np.asarray(rows, dtype=np.float64).reshape(-1)
+
+    def refresh_hyperparameters(self):
+        """capturable mode: copy the groups' current hyper-parameters (lr, betas, ...) to the device block the captured
+        launch reads.  An eager step() does it itself; call it before graph replays after a scheduler changed lr."""
+        if not self.capturable:
+            return
+        h = self._hyper()
+        dev = self._device()
+        if dev is None:
+            return
+        if self._hyper_dev is None or self._hyper_dev.numel() != h.size or self._hyper_dev.device != dev:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("capturable %s: run one eager step() before capturing it" % type(self).__name__)
+            self._hyper_dev = torch.zeros(h.size, dtype=torch.float64, device=dev)
+        host = torch.from_numpy(h).pin_memory()
+        self._hyper_dev.copy_(host, non_blocking=True)
+
+    def _device(self):
+        for g in self.param_groups:
+            for p in g["params"]:
+                return p.device
+        return None
+
+    # ---- state -----------------------------------------------------------------------------------------------------
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        self._state_epoch += 1
+        self._tables.clear()
+        for st in self.state.values():      # reference checkpoints carry int steps; capturable mode keeps them on the device
+            if "step" not in st:
+                if self.capturable and "momentum_buffer" in st:     # SGDW's reference state has no count
+                    st["step"] = 1
+                else:
+                    continue
+            s = st["step"]
+            if self.capturable:
+                dev = next((v.device for v in st.values() if torch.is_tensor(v) and v.is_cuda), None)
+                if not torch.is_tensor(s) or s.device != dev or s.dtype != torch.float32:
+                    st["step"] = torch.tensor(float(s), dtype=torch.float32, device=dev)
+            elif torch.is_tensor(s):
+                st["step"] = int(s.item())
+
+    # ---- step -------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def step(self, closure=None):
+        """Performs a single optimization step (the reference's semantics; see the module docstring)."""
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        rows, ptrs, steps = [], [], []
+        capturable = self.capturable
+        for gi, group in enumerate(self.param_groups):
+            for p in group["params"]:
+                g = p.grad
+                if g is None:
+                    continue
+                if g.is_sparse:
+                    raise RuntimeError("Adam does not support sparse gradients, please consider SparseAdam instead")
+                state = self.state[p]
+                t = self._advance(p, group, state)
+                rows.append((p, g, state, gi))
+                ptrs.append(p.data_ptr())
+                ptrs.append(g.data_ptr())
+                steps.append(t)
+        if not rows:
+            return loss
+        key = (self._state_epoch, tuple(ptrs))
+        table = self._tables.get(key)
+        if table is None:
+            table = self._build_table(rows)
+            self._tables[key] = table
+            while len(self._tables) > _MAX_TABLES:
+                old = next(k for k, v in self._tables.items() if not v.pinned)   # captured tables stay alive
+                del self._tables[old]
+        else:
+            self._tables.move_to_end(key)
+        L = _lib.lib()
+        stream = C.c_void_p(torch.cuda.current_stream(table.dev.device).cuda_stream)
+        base = table.dev.data_ptr()
+        if capturable:
+            if not torch.cuda.is_current_stream_capturing():
+                self.refresh_hyperparameters()
+            elif self._hyper_dev is None:
+                raise RuntimeError("capturable %s: run one eager step() before capturing it" % type(self).__name__)
+            status = L.unetpp_optim_step(self._KIND, self._flags() | _lib.OPTIM_CAPTURABLE, C.c_void_p(base), table.n_seg,
+                                         C.c_void_p(base + table.chunk_off), table.n_chunks,
+                                         C.c_void_p(self._hyper_dev.data_ptr()), None, C.c_void_p(base + table.done_off),
+                                         stream)
+        else:
+            h = self._hyper()
+            host = torch.empty(h.size + len(steps), dtype=torch.float64, pin_memory=True)
+            arr = host.numpy()
+            arr[:h.size] = h
+            arr[h.size:] = [steps[i] for i in table.rows_used] if table.rows_used is not None else steps
+            table.block.copy_(host, non_blocking=True)
+            blk = table.block.data_ptr()
+            status = L.unetpp_optim_step(self._KIND, self._flags(), C.c_void_p(base), table.n_seg,
+                                         C.c_void_p(base + table.chunk_off), table.n_chunks, C.c_void_p(blk),
+                                         C.c_void_p(blk + 8 * h.size), None, stream)
+        _lib.check(status, "unetpp_optim_step")
+        return loss
+
+    def _flags(self) -> int:
+        return 0
+
+    def _advance(self, p, group, state):
+        """Creates missing state and advances the count of this parameter; returns the eager count of this update."""
+        raise NotImplementedError
+
+    def _build_table(self, rows) -> _Table:
+        from .ops import _need
+        L = _lib.lib()
+        chunk = int(L.unetpp_optim_chunk_elems())
+        segs, chunk_seg, used = [], [], []
+        for i, (p, g, state, gi) in enumerate(rows):
+            _need(p, "%s parameter" % type(self).__name__)
+            _need(g, "%s gradient" % type(self).__name__)
+            if g.shape != p.shape or g.device != p.device:
+                raise ValueError("gradient of shape %s on %s for a parameter of shape %s on %s"
+                                 % (tuple(g.shape), g.device, tuple(p.shape), p.device))
+            n = p.numel()
+            if n == 0:
+                continue
+            s = _lib.OptimSegment()
+            s.param, s.grad = p.data_ptr(), g.data_ptr()
+            tensors = [p, g]
+            if self._MOMENTS:
+                m, v = state["exp_avg"], state["exp_avg_sq"]
+                s.exp_avg, s.exp_avg_sq = _need(m, "exp_avg").data_ptr(), _need(v, "exp_avg_sq").data_ptr()
+                tensors += [m, v]
+            aux = self._aux(state, self.param_groups[gi])
+            if aux is not None:
+                s.aux = _need(aux, "optimizer state").data_ptr()
+                tensors.append(aux)
+            if self.capturable and "step" in state:        # (SGDW without momentum keeps no state)
+                st = state["step"]
+                s.step = _need(st, "state['step']").data_ptr()
+            for t in tensors:
+                if t.numel() != n or t.device != p.device:
+                    raise ValueError("optimizer state does not match its parameter's shape or device")
+            s.numel, s.chunk_begin, s.group = n, len(chunk_seg), gi
+            s.vec = int(all(t.data_ptr() % 16 == 0 for t in tensors))
+            chunk_seg += [len(segs)] * ((n + chunk - 1) // chunk)
+            segs.append(s)
+            used.append(i)
+        if not segs:
+            raise ValueError("no parameter with elements to update")
+        n_seg, n_chunks = len(segs), len(chunk_seg)
+        chunk_off = n_seg * _SEG_BYTES
+        done_off = chunk_off + 4 * n_chunks
+        nbytes = done_off + 8
+        dev = rows[0][0].device
+        capturing = torch.cuda.is_current_stream_capturing()
+        if capturing:
+            # no page-locked allocation inside a capture: the staging buffer reserved by the last eager build is used
+            # (the captured copy reads it at every replay: it stays with the table, unchanged, as long as the optimizer)
+            host = self._spare_host
+            if host is None or host.numel() < nbytes:
+                raise RuntimeError("capturable %s: run one eager step() before capturing it" % type(self).__name__)
+            self._spare_host = None
+        else:
+            host = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+            self._spare_host = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+        arr = host.numpy()
+        C.memmove(host.data_ptr(), (_lib.OptimSegment * n_seg)(*segs), chunk_off)
+        arr[chunk_off:done_off] = np.asarray(chunk_seg, dtype=np.int32).view(np.uint8)
+        arr[done_off:nbytes] = 0
+        t = _Table()
+        t.dev = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        t.host, t.n_seg, t.n_chunks, t.chunk_off, t.done_off = host, n_seg, n_chunks, chunk_off, done_off
+        t.pinned = capturing
+        t.rows_used = None if len(used) == len(rows) else used
+        t.block = None if self.capturable else torch.empty(len(self.param_groups) * _lib.OPTIM_HYPER + len(used),
+                                                          dtype=torch.float64, device=dev)
+        _lib.check(L.unetpp_optim_upload(C.c_void_p(t.dev.data_ptr()), C.c_void_p(host.data_ptr()), nbytes,
+                                         C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "unetpp_optim_upload")
+        return t
+
+    def _aux(self, state, group):
+        return None
+
+    def _new_step(self, p):
+        return torch.zeros((), dtype=torch.float32, device=p.device) if self.capturable else 0
+
+
+
+class AdamW(_FusedOptimizer):
+    """AdamW of the reference (tools/optimizers/adamw.py): decoupled weight decay taken from the parameter BEFORE the
+    update (``d = p*wd; p = p - step_size*m/denom; p = p - d``), ``step_size = lr*sqrt(1-beta2^t)/(1-beta1^t)``.
+
+    Arguments as the reference's, plus ``capturable`` (keyword; see the module docstring)."""
+    _KIND = _lib.OPTIM_ADAMW
+    _AMS_KEY = "amsgrad"
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *,
+                 capturable=False):
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError("Invalid beta parameter at index 0: {}".format(betas[0]))
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError("Invalid beta parameter at index 1: {}".format(betas[1]))
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad)
+        super().__init__(params, defaults)
+        self._init_fused(capturable)
+        self._check_ams()
+
+    def _check_ams(self):
+        if len({bool(g[self._AMS_KEY]) for g in self.param_groups}) > 1:
+            raise ValueError("%s: %s must be the same in every parameter group of the fused step"
+                             % (type(self).__name__, self._AMS_KEY))
+
+    def _flags(self) -> int:
+        return _lib.OPTIM_AMS if self.param_groups[0][self._AMS_KEY] else 0
+
+    def _hyper_row(self, gi, group):
+        b1, b2 = group["betas"]
+        return [group["lr"], b1, b2, group["eps"], group["weight_decay"], 0.0, 0.0, 0.0]
+
+    def _advance(self, p, group, state):
+        if len(state) == 0:
+            state["step"] = self._new_step(p)
+            state["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            if group[self._AMS_KEY]:
+                state["max_exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            self._state_epoch += 1
+        if self.capturable:
+            return 0
+        state["step"] += 1
+        return state["step"]
+
+    def _aux(self, state, group):
+        return state["max_exp_avg_sq"] if group[self._AMS_KEY] else None
+
+
+class AdaBound(AdamW):
+    """AdaBound of the reference (tools/optimizers/adabound.py): L2 weight decay into a temporary gradient
+    (``p.grad`` is not modified), bounds ``final_lr*lr/base_lr * (1 -+ 1/(gamma*t (+1)))``, and
+    ``p = p - clamp(step_size/denom, lo, hi)*m``.  ``base_lrs`` are the groups' lr at construction, as there."""
+    _KIND = _lib.OPTIM_ADABOUND
+    _AMS_KEY = "amsbound"
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), final_lr=0.1, gamma=1e-3, eps=1e-8, weight_decay=0,
+                 amsbound=False, *, capturable=False):
+        if not 0.0 <= lr:
+            raise ValueError("Invalid learning rate: {}".format(lr))
+        if not 0.0 <= eps:
+            raise ValueError("Invalid epsilon value: {}".format(eps))
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError("Invalid beta parameter at index 0: {}".format(betas[0]))
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError("Invalid beta parameter at index 1: {}".format(betas[1]))
+        if not 0.0 <= final_lr:
+            raise ValueError("Invalid final learning rate: {}".format(final_lr))
+        if not 0.0 <= gamma < 1.0:
+            raise ValueError("Invalid gamma parameter: {}".format(gamma))
+        defaults = dict(lr=lr, betas=betas, final_lr=final_lr, gamma=gamma, eps=eps, weight_decay=weight_decay,
+                        amsbound=amsbound)
+        Optimizer.__init__(self, params, defaults)
+        self._init_fused(capturable)
+        self._check_ams()
+        self.base_lrs = list(map(lambda group: group["lr"], self.param_groups))
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        for group in self.param_groups:
+            group.setdefault("amsbound", False)
+
+    def _hyper_row(self, gi, group):
+        b1, b2 = group["betas"]
+        final_lr = group["final_lr"] * group["lr"] / self.base_lrs[gi]
+        return [group["lr"], b1, b2, group["eps"], group["weight_decay"], final_lr, group["gamma"], 0.0]
+
+
+class SGDW(_FusedOptimizer):
+    r"""SGDW of the reference (tools/optimizers/sgdw.py), reproduced AS IT IS: the reference never applies the gradient.
+    A step updates the momentum buffer (``buf = grad`` on its first update, then ``buf = momentum*buf +
+    (1-dampening)*grad``; none with momentum 0) and then only decays the weights, ``p = p - weight_decay*p``; ``lr``
+    and ``nesterov`` change nothing.  The trainer's call (momentum 0) is therefore a pure weight decay.
+
+    Arguments as the reference's, plus ``capturable`` (keyword; see the module docstring)."""
+    _KIND = _lib.OPTIM_SGDW
+    _MOMENTS = False
+
+    def __init__(self, params, lr=required, momentum=0, dampening=0, weight_decay=0, nesterov=False, *,
+                 capturable=False):
+        defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov)
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        super().__init__(params, defaults)
+        self._init_fused(capturable)
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        for group in self.param_groups:
+            group.setdefault("nesterov", False)
+
+    def _hyper_row(self, gi, group):
+        return [0.0, group["momentum"], group["dampening"], 0.0, group["weight_decay"], 0.0, 0.0, 0.0]
+
+    def _advance(self, p, group, state):
+        if group["momentum"] == 0:
+            return 2
+        first = "momentum_buffer" not in state
+        if first:
+            state["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            if self.capturable:
+                state["step"] = self._new_step(p)
+            self._state_epoch += 1
+        return 1 if first else 2
+
+    def _aux(self, state, group):
+        return state["momentum_buffer"] if group["momentum"] != 0 else None
+
+
+__all__ = ["AdamW", "AdaBound", "SGDW"]
