@@ -258,3 +258,108 @@ def install_hip_gates_plain(oracle_model, hip_saved):
         d.mpconv[0] = pool
         gated.append(pool)
     return gated
+
+
+# ---------------------------------------------------------------------------------------------
+# Reduced persistent grids and a-priori element-wise error bounds (tests/test_gpu_persistent.py).
+class usable_cus:
+    """with usable_cus(n): every persistent grid of the library is sized for n CUs (unetpp_set_reserved_cus(physical -
+    n), the data-parallel knob); n = None or the physical count leaves all of them.  The library floors the usable
+    count at 8 (common.h device_cu_count); the reservation goes back to 0 on exit, whatever the body did."""
+
+    def __init__(self, n=None):
+        self.n = n
+
+    def __enter__(self):
+        import ctypes
+
+        from unet_nested4tiny_objects_keypoints_amd import _lib
+        lib = _lib.lib()
+        phys = ctypes.c_int32(0)
+        lib.unetpp_usable_cus(ctypes.byref(phys))
+        self.physical = phys.value
+        n = self.physical if self.n is None else self.n
+        assert 8 <= n <= self.physical, (n, self.physical)
+        lib.unetpp_set_reserved_cus(self.physical - n)
+        try:
+            got = int(lib.unetpp_usable_cus(None))
+            assert got == n, (got, n)
+        except BaseException:
+            lib.unetpp_set_reserved_cus(0)
+            raise
+        self.cus = n
+        return self
+
+    def __exit__(self, *exc):
+        from unet_nested4tiny_objects_keypoints_amd import _lib
+        _lib.lib().unetpp_set_reserved_cus(0)
+        return False
+
+
+U32 = 2.0 ** -24   # unit roundoff of fp32
+
+
+def gamma(n):
+    """gamma_n = n u / (1 - n u) (Higham): |fl(sum of n products) - exact| <= gamma_n * sum |products|, any order."""
+    nu = n * U32
+    assert nu < 0.5, n
+    return nu / (1.0 - nu)
+
+
+def conv_magnitude(x_abs, w_abs, bias_abs=None, padding=1):
+    """conv(|x|, |w|) + |b| in float64 (NCHW): the sum of absolute terms a direct or pointwise GEMM adds up."""
+    import torch.nn.functional as F
+    m = F.conv2d(x_abs.double(), w_abs.double(), None, padding=padding)
+    if bias_abs is not None:
+        m = m + bias_abs.double().view(1, -1, 1, 1)
+    return m
+
+
+# F(2x2, 3x3) (Lavin & Gray): Y = A^T [ (G g G^T) . (B^T d B) ] A over 4x4 input tiles at stride 2
+_WINO_BT = [[1, 0, -1, 0], [0, 1, 1, 0], [0, -1, 1, 0], [0, 1, 0, -1]]
+_WINO_G = [[1, 0, 0], [0.5, 0.5, 0.5], [0.5, -0.5, 0.5], [0, 0, 1]]
+_WINO_AT = [[1, 1, 1, 0], [0, 1, -1, -1]]
+WINO_FACTOR = 4.0   # estimate (never measured before): multiplies gamma_(K + 16) in wino_bound
+
+
+def wino_magnitude(x_abs, w_abs, bias_abs=None):
+    """|A^T| [ sum_k (|G||g||G^T|) . (|B^T||d||B|) ] |A| + |b| in float64 (NCHW, 3x3, padding 1): the magnitude of
+    every term the Winograd kernel adds, through the transforms taken on absolute values."""
+    import torch.nn.functional as F
+    x = x_abs.double()
+    n, c, h, w = x.shape
+    th, tw = (h + 1) // 2, (w + 1) // 2
+    xp = F.pad(x, (1, 2 * tw - w + 1, 1, 2 * th - h + 1))        # 4x4 tiles at stride 2 cover the padded image
+    bt = torch.tensor(_WINO_BT, dtype=torch.float64).abs()
+    # |B^T| |d| |B| as 16 fixed 4x4 filters per channel: filter (r, s)[a, b] = |B^T|[r, a] |B^T|[s, b]
+    filt = torch.einsum("ra,sb->rsab", bt, bt).reshape(16, 1, 4, 4)
+    u = F.conv2d(xp.reshape(n * c, 1, xp.shape[2], xp.shape[3]), filt, stride=2).reshape(n, c, 16, th, tw)
+    gm = torch.tensor(_WINO_G, dtype=torch.float64).abs()
+    v = torch.einsum("ra,oiab,sb->oirs", gm, w_abs.double(), gm).reshape(w_abs.shape[0], c, 16)
+    m = torch.einsum("ncetu,oce->notue", u, v).reshape(n, -1, th, tw, 4, 4)
+    at = torch.tensor(_WINO_AT, dtype=torch.float64).abs()
+    y = torch.einsum("pr,notyrs,qs->notypq", at, m, at)           # [n, o, th, tw, 2, 2]
+    y = y.permute(0, 1, 2, 4, 3, 5).reshape(n, -1, 2 * th, 2 * tw)[:, :, :h, :w]
+    if bias_abs is not None:
+        y = y + bias_abs.double().view(1, -1, 1, 1)
+    return y
+
+
+def bound_ratio(got, want, bound):
+    """max over elements of |got - want| / bound (float64; a NaN anywhere in got is infinite).  <= 1 passes."""
+    got = torch.as_tensor(got).double().cpu()
+    want = torch.as_tensor(want).double().cpu()
+    bound = torch.as_tensor(bound).double().cpu()
+    if not bool(torch.isfinite(got).all()):
+        return float("inf")
+    err = (got - want).abs()
+    return float((err / bound.clamp_min(1e-300)).max())
+
+
+def report_ratio(case, what, ratio, extra=None):
+    """Print the worst err / bound of a case as one JSON line (run pytest with -s to see it in the log)."""
+    import json
+    line = {"case": case, "what": what, "ratio": ratio}
+    if extra:
+        line.update(extra)
+    print("err/bound:", json.dumps(line))

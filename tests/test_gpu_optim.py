@@ -93,12 +93,30 @@ def _compare(name, step, params, opt, z):
 @pytest.mark.parametrize("capturable", [False, True], ids=["eager", "capturable"])
 @pytest.mark.parametrize("name", list(gm.CONFIGS))
 def test_matches_reference_fixture(name, capturable, dev):
+    _check_fixture(name, capturable, dev)
+
+
+@pytest.mark.parametrize("capturable", [False, True], ids=["eager", "capturable"])
+@pytest.mark.parametrize("name", list(gm.CONFIGS))
+def test_matches_reference_fixture_on_eight_cus(name, capturable, dev):
+    """The same fixture check with the persistent grid sized for 8 CUs (the data-parallel reservation knob): the grid
+    is min(chunks, 8 x 8) workgroups, so every workgroup walks several chunks (grid-stride loop) and the capturable
+    arrival counter counts fewer arrivals than chunks."""
+    from tests.helpers import usable_cus
+    with usable_cus(8) as u:
+        opt = _check_fixture(name, capturable, dev)
+        n_chunks = max(t.n_chunks for t in opt._tables.values())
+        assert n_chunks > 8 * u.cus, (n_chunks, u.cus)   # optim.hip launch(): grid = min(n_chunks, 8 * cus)
+
+
+def _check_fixture(name, capturable, dev):
     z = np.load(os.path.join(GOLDEN, "optim_%s.npz" % name))
     worst = []
-    _run(name, dev, capturable, on_step=lambda step, params, opt: worst.append(_compare(name, step, params, opt, z))
-         if step in gm.RECORD else None)
+    _, opt = _run(name, dev, capturable, on_step=lambda step, params, opt: worst.append(_compare(name, step, params, opt, z))
+                  if step in gm.RECORD else None)
     WORST_ULP[(name, capturable)] = max(worst)
     print("%s %s: worst parameter error %.1f ulp" % (name, "capturable" if capturable else "eager", max(worst)))
+    return opt
 
 
 @pytest.mark.parametrize("name", ["adamw_amsgrad", "adabound", "sgdw_nesterov"])
