@@ -461,6 +461,24 @@ int unetpp_optim_step(int32_t kind, int32_t flags, const unetpp_optim_segment* s
  * `host_src` it is a memcpy node when the stream is being captured, and host_src must then outlive the graph). */
 int unetpp_optim_upload(void* dst, const void* host_src, int64_t bytes, void* stream);
 
+/* ---- Validation matcher (csrc/validate.hip): HeatmapPattern.match_distmin (tools/misc/heatmap.py:57-79, unfinished
+ * there) and the landmark loss of the validation loop (trainer/trainer.py:220-221) for every head in one launch.  Added
+ * at ABI version 11 without changing anything that was there before. ---- */
+#define UNETPP_MATCH_MAX 64   /* most labels per map (pattern list) and most predictions per map */
+
+/* unetpp_match_points: points [heads*N*C, K, 2] (x, y) in peak order, found [heads*N*C] (device int32: the first found[m]
+ * points of map m are its predictions), labels [N, S, 2] (x, y), pattern as map_points / map_begin [C + 1] (device int32,
+ * as unetpp_heatmap_pattern; every index in 0..S-1, at most UNETPP_MATCH_MAX per map, no index twice).  Per (head, image,
+ * map) the labels of the map's list are matched to its predictions greedily by the global minimum of (d, label position,
+ * prediction index), d = float64 squared distance of the float32 differences.  Out: matched [heads, N, S, 2] = the
+ * prediction assigned to label s or (-1, -1); mask [heads, N, S] = 1 where label s is matched, else 0; loss [heads] =
+ * float32(sum of d over the matched labels / (2 * count)) summed in float64 in a fixed order (csrc/validate.hip), NaN
+ * when count is 0; count [heads] = matched labels.  One workgroup per head, deterministic.  Negative status without
+ * touching the device for a null pointer, a size <= 0 or K > UNETPP_MATCH_MAX. */
+int unetpp_match_points(const float* points, const int32_t* found, int32_t heads, int32_t N, int32_t C, int32_t K,
+                        const float* labels, int32_t S, const int32_t* map_points, const int32_t* map_begin,
+                        float* matched, uint8_t* mask, float* loss, int32_t* count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,7 +15,7 @@ _REPO = os.path.dirname(_PKG_DIR)
 LIB_PATH = os.environ.get("UNETPP_LIB", os.path.join(_PKG_DIR, "libunetpp_hip.so"))  # override: kernel A/B runs
 CSRC = os.path.join(_PKG_DIR, "csrc")
 INCLUDE = os.path.join(_REPO, "include")
-SOURCES = ("gemm_pix.hip", "gemm_fast.hip", "gemm_pw.hip", "gemm_pw_bf16.hip", "gemm_wino.hip", "gemm_bf16.hip", "gemm_bf16_dma.hip", "wgrad_bf16.hip", "pointwise_bf16.hip", "keypoints.hip", "weight_image.hip", "wgrad.hip", "wgrad_fast.hip", "wgrad_dma.hip", "wgrad_pw.hip", "wgrad_wino.hip", "first_layer.hip", "pointwise.hip", "caller.hip", "optim.hip")
+SOURCES = ("gemm_pix.hip", "gemm_fast.hip", "gemm_pw.hip", "gemm_pw_bf16.hip", "gemm_wino.hip", "gemm_bf16.hip", "gemm_bf16_dma.hip", "wgrad_bf16.hip", "pointwise_bf16.hip", "keypoints.hip", "weight_image.hip", "wgrad.hip", "wgrad_fast.hip", "wgrad_dma.hip", "wgrad_pw.hip", "wgrad_wino.hip", "first_layer.hip", "pointwise.hip", "caller.hip", "optim.hip", "validate.hip")
 HEADERS = ("common.h", "gemm_units.h", "wgrad_reduce.h", "lds_asm.h", "bf16_common.h", "dropout.h", "bn_fused.h",
            "wino_experiments.h", "dma_experiments.h")
 MAX_VIEWS = 8
@@ -121,6 +121,7 @@ class OptimSegment(C.Structure):
 OPTIM_ADAMW, OPTIM_ADABOUND, OPTIM_SGDW = 0, 1, 2   # unetpp_optim_step kinds
 OPTIM_AMS, OPTIM_CAPTURABLE = 1, 2                 # unetpp_optim_step flags
 OPTIM_HYPER = 8                                    # doubles per group of the hyper-parameter block
+MATCH_MAX = 64                                     # UNETPP_MATCH_MAX: labels / predictions per map of the matcher
 
 _P, _I32, _I64, _F, _U64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_uint64
 
@@ -191,6 +192,8 @@ SIGNATURES = {
     "unetpp_optim_chunk_elems": (_I64, []),
     "unetpp_optim_step": (C.c_int, [_I32, _I32, _P, _I32, _P, _I64, _P, _P, _P, _P]),
     "unetpp_optim_upload": (C.c_int, [_P, _P, _I64, _P]),
+    # validation matcher (validate.hip)
+    "unetpp_match_points": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _P, _I32, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 _LIB = None

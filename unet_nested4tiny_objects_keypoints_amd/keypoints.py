@@ -13,7 +13,9 @@ cores, ``cv2.watershed`` of the binary mask seeded with them).  ``segmentation="
 step: blobs that touch through a thin neck are split, a blob without a core is dropped, the frame of the map (first /
 last row and column) belongs to no region, as ``cv2.watershed`` leaves it; ``segmentation="components"`` keeps the round-2
 stand-in (a region = an 8-connected component of the mask).  The reference's matcher ``match_distmin`` is unfinished and returns ``[]`` (:56-79): ``transfer_points`` returns
-the extracted points in peak order instead of an empty tensor.
+the extracted points in peak order instead of an empty tensor.  ``match_points`` (and ``match_distmin``, the reference's
+single-map signature) finishes the matcher on the device: predictions are assigned to the map's labels by the greedy
+global minimum of the squared distance (csrc/validate.hip); ``validate.validate_step`` runs it for every head of a batch.
 
 Known differences of ``"watershed"`` from ``cv2.watershed`` (none of them can be pinned without OpenCV): (1) there is no
 level-255 phase -- unknown pixels of a hole narrower than 5 px that is enclosed by core pixels (mask value 0, reachable only
@@ -29,7 +31,7 @@ import logging
 
 import torch
 
-from . import ops
+from . import _lib, ops
 
 
 class Heatmap:
@@ -81,7 +83,8 @@ class Heatmap:
     def transfer_points(self, preds, targets=None, threshold=0.5):
         """preds [N, C, H, W] -> (points [N, C, max_num, 2] CUDA float32 as (x, y), -1 padded; counts [N, C] int32 =
         points found per map).  `targets` is accepted for signature compatibility (heatmap.py:241): the reference
-        only uses it in its unfinished matcher."""
+        only uses it in its unfinished matcher.  The points stay in peak order; ``match_points(points, counts, targets)``
+        assigns them to the labels."""
         preds = self._cuda(preds)
         if preds.dim() != 4:
             raise AssertionError("preds shape should be [N, C, H, W]")
@@ -101,3 +104,41 @@ class Heatmap:
         slot = torch.arange(max(nums), device=points.device).view(1, 1, -1)
         points = torch.where((slot < found.unsqueeze(-1)).unsqueeze(-1), points, torch.full_like(points, -1.0))
         return points, found
+
+    def match_points(self, points, found, targets):
+        """points [N, C, K, 2] and found [N, C] as ``transfer_points`` returns them, targets [N, S, 2] as (x, y) ->
+        (matched [N, S, 2] CUDA float32: the prediction assigned to label s, (-1, -1) where none; mask [N, S] bool).
+        The rule the reference's ``match_distmin`` left open (heatmap.py:57-79): per map, min(labels, predictions) times
+        the pair of an unassigned label of ``pattern[c]`` and an unused prediction with the smallest (squared distance,
+        position of the label in the map's list, prediction index) is assigned (csrc/validate.hip).  Labels that no map
+        of the pattern holds are never matched."""
+        points, targets = self._cuda(points), self._cuda(targets)
+        found = torch.as_tensor(found).to(device=points.device, dtype=torch.int32).contiguous()
+        if points.dim() != 4 or points.shape[3] != 2 or points.shape[1] != len(self.pattern):
+            raise ValueError("points must be [N, len(pattern), K, 2]")
+        if tuple(found.shape) != tuple(points.shape[:2]):
+            raise ValueError("found must be [N, len(pattern)]")
+        if targets.dim() != 3 or targets.shape[2] != 2 or targets.shape[0] != points.shape[0]:
+            raise ValueError("targets must be [N, S, 2] with the batch size of points")
+        n, c, k = points.shape[:3]
+        matched, mask, _, _ = ops.match_points(points.reshape(n * c, k, 2), found.view(-1), targets, self.pattern)
+        return matched[0], mask[0]
+
+    def match_distmin(self, predpoints, targets, index_list):
+        """The reference's single-map matcher (heatmap.py:57-79): predicted points of one map (list of [x, y]), all key
+        points of the image (targets [S, 2]) and the map's label indices -> a list of [x, y] in ``index_list`` order, the
+        prediction matched to each label or [-1, -1].  Same rule and same kernel as ``match_points``."""
+        pred = torch.as_tensor(predpoints, dtype=torch.float32).reshape(-1, 2)
+        if pred.shape[0] > _lib.MATCH_MAX:
+            raise ValueError("at most %d predicted points per map" % _lib.MATCH_MAX)
+        labels = torch.as_tensor(targets, dtype=torch.float32)
+        if labels.dim() != 2 or labels.shape[1] != 2:
+            raise ValueError("targets must be [S, 2]")
+        index_list = [int(i) for i in index_list]
+        ops.check_match_pattern([index_list], labels.shape[0])
+        padded = torch.full((1, max(1, pred.shape[0]), 2), -1.0)
+        padded[0, :pred.shape[0]] = pred
+        points = self._cuda(padded)
+        found = torch.full((1,), pred.shape[0], dtype=torch.int32, device=points.device)
+        matched, _, _, _ = ops.match_points(points, found, self._cuda(labels).unsqueeze(0), [index_list])
+        return matched[0, 0, index_list].tolist()

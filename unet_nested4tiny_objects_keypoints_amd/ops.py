@@ -7,6 +7,7 @@ here is plumbing only: device memory and the stream.  Activations are NHWC ``[N,
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
 from dataclasses import dataclass
 from typing import Optional, Sequence
@@ -891,3 +892,64 @@ def keypoints_extract(heat: torch.Tensor, num: int, threshold: float = 0.5, max_
         points = torch.where(empty.view(-1, 1, 1), points, keep_points)
         counts = torch.where(empty, counts, keep_counts)
     return points, counts
+
+
+def check_match_pattern(pattern, n_labels: int) -> None:
+    """The matcher's limits on a pattern (list of lists of label indices), checked on the host before any launch."""
+    flat = [i for hmap in pattern for i in hmap]
+    if not pattern:
+        raise ValueError("the pattern needs at least one map")
+    if any(len(hmap) > _lib.MATCH_MAX for hmap in pattern):
+        raise ValueError("a map of the pattern holds at most %d key points" % _lib.MATCH_MAX)
+    if any(not 0 <= int(i) < n_labels for i in flat):
+        raise ValueError("pattern indexes labels 0..%d (labels are [N, %d, 2])" % (n_labels - 1, n_labels))
+    if len(set(flat)) != len(flat):
+        raise ValueError("a label index appears twice in the pattern")
+
+
+@functools.lru_cache(maxsize=16)
+def _pattern_tensors(pattern, device):
+    begins = [0]
+    for hmap in pattern:
+        begins.append(begins[-1] + len(hmap))
+    flat = [i for hmap in pattern for i in hmap] or [0]
+    mp = torch.tensor(flat, dtype=torch.int32, device=device)
+    mb = torch.tensor(begins, dtype=torch.int32, device=device)
+    return mp, mb, mb[1:] - mb[:-1]
+
+
+def match_pattern_tensors(pattern, device):
+    """(map_points, map_begin, lengths) of a pattern as device int32 tensors, uploaded once per pattern and device."""
+    return _pattern_tensors(tuple(tuple(int(i) for i in hmap) for hmap in pattern), torch.device(device))
+
+
+def match_points(points: torch.Tensor, found: torch.Tensor, labels: torch.Tensor, pattern, heads: int = 1):
+    """Min-distance matching of extracted key points to labels and the landmark loss, every head in one launch
+    (include/unetpp_hip.h: unetpp_match_points; the rule and the summation order are in csrc/validate.hip).
+    points [heads*N*C, K, 2] (x, y) fp32, found [heads*N*C] int32 (predictions per map), labels [N, S, 2] fp32, pattern =
+    C lists of label indices -> (matched [heads, N, S, 2] fp32, (-1, -1) where unmatched; mask [heads, N, S] bool;
+    loss [heads] fp32: MSELoss over the matched coordinates, NaN when none; count [heads] int32)."""
+    if points.dim() != 3 or points.shape[2] != 2:
+        raise ValueError("points must be [maps, K, 2]")
+    if labels.dim() != 3 or labels.shape[2] != 2:
+        raise ValueError("labels must be [N, S, 2]")
+    n, s = int(labels.shape[0]), int(labels.shape[1])
+    c, k = len(pattern), int(points.shape[1])
+    check_match_pattern(pattern, s)
+    if heads < 1 or points.shape[0] != heads * n * c or tuple(found.shape) != (heads * n * c,):
+        raise ValueError("points [heads*N*C, K, 2] and found [heads*N*C] for %d heads, N = %d, C = %d" % (heads, n, c))
+    if not 1 <= k <= _lib.MATCH_MAX:
+        raise ValueError("1 to %d points per map" % _lib.MATCH_MAX)
+    _need(points, "points")
+    _need(found, "found", torch.int32)
+    _need(labels, "labels")
+    lib = _lib.lib()
+    dev = labels.device
+    mp, mb, _ = match_pattern_tensors(pattern, dev)
+    matched = torch.empty(heads, n, s, 2, dtype=torch.float32, device=dev)
+    mask = torch.empty(heads, n, s, dtype=torch.bool, device=dev)
+    loss = torch.empty(heads, dtype=torch.float32, device=dev)
+    count = torch.empty(heads, dtype=torch.int32, device=dev)
+    check(lib.unetpp_match_points(_ptr(points), _ptr(found), heads, n, c, k, _ptr(labels), s, _ptr(mp), _ptr(mb),
+                                  _ptr(matched), _ptr(mask), _ptr(loss), _ptr(count), _stream()), "unetpp_match_points")
+    return matched, mask, loss, count
