@@ -153,7 +153,7 @@ enum Opt {
   OPT_BF16_DMA_SPLIT,      // 1: split-tail second launch (experiment, off)
   OPT_BF16_WGRAD_QUAD,     // 0: wide bf16 weight gradients on the pair kernel
   OPT_WINO_NO_LEAN,        // 1: the general Winograd instantiation for every launch
-  OPT_WINO_ONE_PER_CU,     // 1: (stamped / experiment builds) one Winograd workgroup per CU
+  OPT_WINO_ONE_PER_CU,     // 1: (experiment builds) one Winograd workgroup per CU
   OPT_MEMSET_NODES,        // 1: unused workspace rows cleared by hipMemsetAsync instead of zero_rows_kernel (graph probe only)
   OPT_BF16_PW_PLAIN,       // 0: plain-output bf16 pointwise launches on the two-per-CU instantiation (round-4 form)
   OPT_PW_DIRECT,           // 0: fp32 pointwise GEMMs back on gemm_fast_kernel<1> (tests compare the two kernels)

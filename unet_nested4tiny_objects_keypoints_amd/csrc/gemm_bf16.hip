@@ -23,22 +23,6 @@
 namespace unetpp {
 namespace {
 
-// In-kernel phase stamps (profiling builds only: -DUNETPP_BF16_STAMPS, tools/gbf_stamps.py): wave 0 of every workgroup adds
-// the cycles it spent in each phase of its (unit, chunk) stream to a global table.
-#ifdef UNETPP_BF16_STAMPS
-__device__ unsigned long long g_gbf_stamps[16];
-#define GBF_STAMP(i)                           \
-  do {                                         \
-    const unsigned long long now_ = clock64(); \
-    st_acc[i] += now_ - st_last;               \
-    st_last = now_;                            \
-  } while (0)
-#else
-#define GBF_STAMP(i) \
-  do {               \
-  } while (0)
-#endif
-
 // Workgroups per CU = the register budget.  Round 5: TWO everywhere (256 registers, no spills, no scratch).  Until round 4
 // the one-tile and the statistics instantiations ran three per CU at 168 registers with 3-23 registers spilled; since the
 // LDS-DMA kernel took the plain launches (gemm_bf16_dma.hip) this kernel only runs the launches with a load transform --
@@ -480,13 +464,7 @@ __global__ __launch_bounds__(kThreads, STATS ? UNETPP_BF16_STATS_WGS : UNETPP_BF
 
   long c_unit = 0;
   int c_chunk = 0;
-#ifdef UNETPP_BF16_STAMPS
-  unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long st_last = clock64();
-  unsigned long long n_chunks_done = 0;
-#endif
   while (true) {
-    GBF_STAMP(0);  // 0: loop bookkeeping / prologue
     bool more = true;
     {
       int s2 = p_s, c2 = p_c0 + BKC;
@@ -514,7 +492,6 @@ __global__ __launch_bounds__(kThreads, STATS ? UNETPP_BF16_STATS_WGS : UNETPP_BF
       }
     }
     load_chunk();  // unconditional (the cursor stays on the last chunk)
-    GBF_STAMP(1);  // 1: cursor advance (unit decode, offsets) + load issue
     Frag cur = read_frag(0);
 #ifdef UNETPP_BF16_EXP_NO_MFMA
     if (cur.a0[0] == 0x12345678u) acc[0][0][0] = 1.f;
@@ -540,9 +517,7 @@ __global__ __launch_bounds__(kThreads, STATS ? UNETPP_BF16_STATS_WGS : UNETPP_BF
       cur = nxt;
     }
 #endif
-    GBF_STAMP(2);  // 2: LDS fragment reads + MFMAs
     __syncthreads();
-    GBF_STAMP(3);  // 3: barrier after the MFMA loop
     if (c_chunk + 1 == a.n_chunks) {
       // Collect the prefetched chunk BEFORE the epilogue issues its stores: vmcnt counts in order, so the wait hipcc puts
       // in front of the next staging store would otherwise also wait for this unit's output to reach memory.
@@ -550,7 +525,6 @@ __global__ __launch_bounds__(kThreads, STATS ? UNETPP_BF16_STATS_WGS : UNETPP_BF
       for (int q = 0; q < IN_ITEMS; ++q) asm volatile("" : "+v"(reg_in[q]));
 #pragma unroll
       for (int q = 0; q < W_ITEMS; ++q) asm volatile("" : "+v"(reg_w[q]));
-      GBF_STAMP(4);  // 4: wait for the prefetched loads
 #ifndef UNETPP_BF16_EXP_NO_EPILOGUE  // experiment builds only (tools/README.md): where does a unit's time go
       if constexpr (STATS) epilogue_stats();
       else epilogue_direct();
@@ -566,45 +540,19 @@ __global__ __launch_bounds__(kThreads, STATS ? UNETPP_BF16_STATS_WGS : UNETPP_BF
           }
 #endif
       if constexpr (STATS) __syncthreads();  // the transposing epilogue used the input tile as scratch
-      GBF_STAMP(5);  // 5: epilogue
       step_unit(c_ug, c_index);
       ++c_unit;
       c_chunk = 0;
     } else {
       ++c_chunk;
     }
-#ifdef UNETPP_BF16_STAMPS
-    ++n_chunks_done;
-#endif
     if (!more) break;
     store_chunk();
-    GBF_STAMP(6);  // 6: staging stores (waits for the loads when no epilogue collected them)
     __syncthreads();
-    GBF_STAMP(7);  // 7: barrier after the staging stores
   }
-#ifdef UNETPP_BF16_STAMPS
-  if (tid == 0) {
-    for (int i = 0; i < 8; ++i) atomicAdd(&g_gbf_stamps[i], st_acc[i]);
-    atomicAdd(&g_gbf_stamps[8], n_chunks_done);
-    atomicAdd(&g_gbf_stamps[9], static_cast<unsigned long long>(my_units));
-    atomicAdd(&g_gbf_stamps[10], 1ull);
-  }
-#endif
 }
 
 }  // namespace
-
-#ifdef UNETPP_BF16_STAMPS
-extern "C" int unetpp_debug_gbf_stamps(unsigned long long* out16, int reset) {  // profiling builds only
-  if (out16 != nullptr && hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_gbf_stamps), sizeof(g_gbf_stamps)) != hipSuccess)
-    return UNETPP_ELAUNCH;
-  if (reset) {
-    const unsigned long long zero[16] = {};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_gbf_stamps), zero, sizeof(zero)) != hipSuccess) return UNETPP_ELAUNCH;
-  }
-  return UNETPP_OK;
-}
-#endif
 
 bool bf16_gemm_args(const unetpp_gemm_desc* d, FastArgs& a) {
   if (d == nullptr || (d->flags & UNETPP_GEMM_BF16) == 0) return false;

@@ -46,9 +46,9 @@
 //   * deferred output stores for the forward launches (no gate / accumulate operands: their 64 registers hold the packed
 //     tile, whose eight store instructions are issued one behind every second MFMA step of the NEXT chunk): 1.4-1.9 %
 //     SLOWER on both bf16 steps -- once more: what a CU's memory path moves per unit is the bound, not when it moves it.
-// tools/dma_stamps.py (stamped build): per 32-channel chunk of [64 x 5] -> 64 at 384 x 384 x 4 wave 0 spends 600 cycles in
-// the cursor, 1 860 issuing its ten DMA pieces, 2 650 in LDS reads + MFMAs, 435 in the epilogue (per-chunk average) and
-// 2 450 in the barrier, most of which is the second wave of its SIMD running ITS MFMAs.
+// Round 4 clock stamps (a profiling build since removed): per 32-channel chunk of [64 x 5] -> 64 at 384 x 384 x 4 wave 0
+// spends 600 cycles in the cursor, 1 860 issuing its ten DMA pieces, 2 650 in LDS reads + MFMAs, 435 in the epilogue
+// (per-chunk average) and 2 450 in the barrier, most of which is the second wave of its SIMD running ITS MFMAs.
 #include <cstdlib>
 
 #include "bf16_common.h"
@@ -59,22 +59,6 @@
 
 namespace unetpp {
 namespace {
-
-// In-kernel phase stamps (profiling builds only: -DUNETPP_DMA_STAMPS, tools/dma_stamps.py): wave 0 of every workgroup adds
-// the cycles it spent in each phase of its (unit, chunk) stream to a global table.
-#ifdef UNETPP_DMA_STAMPS
-__device__ unsigned long long g_dma_stamps[16];
-#define DMA_STAMP(i)                                            \
-  do {                                                          \
-    const unsigned long long now_ = __builtin_amdgcn_s_memtime(); \
-    st_acc[i] += now_ - st_last;                                \
-    st_last = now_;                                             \
-  } while (0)
-#else
-#define DMA_STAMP(i) \
-  do {               \
-  } while (0)
-#endif
 
 constexpr int DKC = 32;        // channels per K chunk (64 bytes per pixel = 4 octets of 16 bytes)
 constexpr int DSTEP = 1024;    // bytes of one (tap, g) weight step: 32 columns x 16 k x 2 B
@@ -568,19 +552,12 @@ __global__ __launch_bounds__(64 * WAVES, RMW ? 2 : 3) void gemm_bf16_dma_kernel(
 
   int c_chunk = 0, in_cur = 0, w_cur = 0;
   bool more = advance();
-#ifdef UNETPP_DMA_STAMPS
-  unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long st_last = __builtin_amdgcn_s_memtime();
-  unsigned long long n_chunks_done = 0;
-#endif
   while (true) {
-    DMA_STAMP(0);  // 0: cursor advance (end of the previous iteration)
     const bool need_in = more && !(in_reuse && p_same_patch), need_w = more && !w_resident;
     if (more) dma_chunk(in_cur ^ 1, w_cur ^ 1, need_in, need_w);
     if constexpr (!STATS) {
       if (c_chunk + 1 == a.n_chunks) fetch_epilogue_operands();  // uniform
     }
-    DMA_STAMP(1);  // 1: DMA issue + epilogue operand requests
     const unsigned lds0 = static_cast<unsigned>(reinterpret_cast<uintptr_t>(smem));
     const unsigned in_base = lds0 + static_cast<unsigned>(in_cur) * IN_BYTES;
     const unsigned w_base = lds0 + 2 * IN_BYTES + static_cast<unsigned>(w_resident ? c_ug.group * a.n_chunks + c_chunk : w_cur) * W_BYTES;
@@ -609,7 +586,6 @@ __global__ __launch_bounds__(64 * WAVES, RMW ? 2 : 3) void gemm_bf16_dma_kernel(
       __builtin_amdgcn_sched_barrier(0);
       if constexpr (step + 1 < TAPS * 2) wait_frag(fr[ns]);
     });
-    DMA_STAMP(2);  // 2: LDS fragment reads + MFMAs
     // this wave's share of chunk c+1 has landed, and the epilogue's operands (requested before the MFMAs) are in
     if constexpr (STATS) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -623,10 +599,6 @@ __global__ __launch_bounds__(64 * WAVES, RMW ? 2 : 3) void gemm_bf16_dma_kernel(
         }
       }
     }
-    DMA_STAMP(3);  // 3: wait for the DMA (and whatever is older: the previous unit's stores)
-#ifdef UNETPP_DMA_STAMPS
-    ++n_chunks_done;
-#endif
     if (c_chunk + 1 == a.n_chunks) {
       if constexpr (STATS) {
         __syncthreads();  // the transposing epilogue uses the buffer just computed from as scratch: all waves are done with it
@@ -652,7 +624,6 @@ __global__ __launch_bounds__(64 * WAVES, RMW ? 2 : 3) void gemm_bf16_dma_kernel(
     } else {
       ++c_chunk;
     }
-    DMA_STAMP(4);  // 4: epilogue (arithmetic + store issue)
     if (!more) break;
     // raw barrier: __syncthreads() carries a fence that drains vmcnt(0), i.e. would wait for this unit's output stores.
     // What the barrier has to order is already complete in every wave: its fragment reads of buffer `cur` (collected by
@@ -661,36 +632,15 @@ __global__ __launch_bounds__(64 * WAVES, RMW ? 2 : 3) void gemm_bf16_dma_kernel(
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    DMA_STAMP(5);  // 5: barrier (= the MFMA phase of the other wave of this SIMD, mostly)
     if (need_in) in_cur ^= 1;
     if (need_w) w_cur ^= 1;
     more = advance();
   }
-#ifdef UNETPP_DMA_STAMPS
-  if (tid == 0) {
-    for (int i = 0; i < 8; ++i) atomicAdd(&g_dma_stamps[i], st_acc[i]);
-    atomicAdd(&g_dma_stamps[8], n_chunks_done);
-    atomicAdd(&g_dma_stamps[9], static_cast<unsigned long long>(my_units));
-    atomicAdd(&g_dma_stamps[10], 1ull);
-  }
-#endif
 }
 
 bool dma_env_off() { return opt_value(OPT_BF16_NO_DMA, 0) != 0; }  // unetpp_debug_set: tests compare the two kernels
 
 }  // namespace
-
-#ifdef UNETPP_DMA_STAMPS
-extern "C" int unetpp_debug_dma_stamps(unsigned long long* out16, int reset) {  // profiling builds only
-  if (out16 != nullptr && hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_dma_stamps), sizeof(g_dma_stamps)) != hipSuccess)
-    return UNETPP_ELAUNCH;
-  if (reset) {
-    unsigned long long zero[16] = {};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_dma_stamps), zero, sizeof(zero)) != hipSuccess) return UNETPP_ELAUNCH;
-  }
-  return UNETPP_OK;
-}
-#endif
 
 // UNETPP_OK after launching; 1 when the descriptor is not one this kernel takes (the caller falls back to gemm_bf16.hip)
 int launch_gemm_bf16_dma(const unetpp_gemm_desc* d, hipStream_t st) {

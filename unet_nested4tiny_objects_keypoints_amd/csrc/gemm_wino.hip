@@ -96,22 +96,7 @@ constexpr int WNC = 32;     // columns per unit
 constexpr int WP = 10;      // LDS pixel stride of the input patch (floats): 8 channels + 2 pad
 constexpr int WIMG = 4096;  // floats of one (column tile, chunk) weight image
 
-// In-kernel phase stamps (profiling builds only: -DUNETPP_WINO_STAMPS, see tools/wino_stamps.py): every wave adds the
-// s_memtime cycles it spent in each phase of its (unit, chunk) stream to a global table.
 #define WINO_FENCE() __builtin_amdgcn_sched_barrier(0)
-#ifdef UNETPP_WINO_STAMPS
-__device__ unsigned long long g_wino_stamps[16];
-#define WINO_STAMP(i)                          \
-  do {                                         \
-    const unsigned long long now_ = clock64(); \
-    st_acc[i] += now_ - st_last;               \
-    st_last = now_;                            \
-  } while (0)
-#else
-#define WINO_STAMP(i) \
-  do {                \
-  } while (0)
-#endif
 
 // NH = 16-column halves of the tile that are computed: 2, or 1 when no output view is wider than 16 channels (narrow
 // networks, e.g. the reference's default base width 16) -- the second half would multiply zero weights.
@@ -412,10 +397,6 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_wino_kernel(const FastArgs a
     }
   };
 
-#ifdef UNETPP_WINO_STAMPS
-  unsigned long long st_acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long st_last = 0;
-#endif
   // ---- epilogue of a finished unit: output transform, bias / ReLU / gate / accumulate, BatchNorm partial sums ----
   // The MFMAs take the weight fragment as their A operand and the transformed window as B, so register rr of acc[xi][nh]
   // of lane (t16, g) belongs to THIS lane's tile (16 * wave + t16, the tile whose windows it transforms) and to column
@@ -454,7 +435,6 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_wino_kernel(const FastArgs a
           acc[5][nh][rr] += col < tc.n_cnt ? d.bias[tc.n0 + col] : 0.f;
         }
     }
-    WINO_STAMP(9);  // 9: epilogue: geometry, bias
     // this lane's tile inside the patch, and its first column
     const unsigned ty2 = 2 * (my_tile / TXN), tx2 = 2 * (my_tile % TXN);
     // 2x2 outputs of (nh, rr) for output row ap: y[0], y[1] = the two pixels of the row
@@ -530,7 +510,6 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_wino_kernel(const FastArgs a
               if constexpr (wino_exp::kNoOutStore) asm volatile("" ::"v"(yv[bp][nh]), "v"(off[bp][nh]));  // (ablation builds)
               else *reinterpret_cast<f32x4*>(obase + off[bp][nh]) = yv[bp][nh];
             }
-          WINO_STAMP(10 + ap);  // 10, 11: epilogue rows
           continue;
         }
 #pragma unroll
@@ -552,7 +531,6 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_wino_kernel(const FastArgs a
             }
             *reinterpret_cast<f32x4*>(obase + off[bp][nh]) = v;
           }
-        WINO_STAMP(10 + ap);
       }
     } else {
       // ---- general path (ragged patches, partial or unaligned column tiles): one predicated dword per value ----
@@ -627,9 +605,6 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_wino_kernel(const FastArgs a
     dst[1] = t2;
   };
 
-#ifdef UNETPP_WINO_STAMPS
-  st_last = clock64();
-#endif
   // ---- pipeline: at the top of chunk c the registers hold the inputs of chunk c+1 (loaded a whole chunk ago); they
   // go to the other LDS buffer, its weight image follows by DMA, the inputs of chunk c+2 are requested, and then the
   // 64 MFMAs of chunk c run without interruption.  One barrier per chunk. ----
@@ -645,7 +620,6 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_wino_kernel(const FastArgs a
   load_inputs();
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(IN_ITEMS) : "memory");  // the weight DMA has landed (the loads are younger)
   __syncthreads();
-  WINO_STAMP(0);  // 0: prologue
 
   int c_chunk = 0, c_unit = 0;  // compute side: chunk of unit c_ug currently in LDS
   int cur = 0;                  // buffer being computed from
@@ -684,7 +658,6 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_wino_kernel(const FastArgs a
       advance();
       load_inputs();
     }
-    WINO_STAMP(1);  // 1: staging store, cursor, load issue
     // LEAN: the staging of the next chunk is a hundred instructions; they are spread over the first three MFMA groups below,
     // where they issue in the shadow of this wave's own MFMAs.  Order: the LDS stores of the inputs requested most of a
     // chunk ago, then the weight DMA (hipcc makes any LDS store that follows a DMA wait for vmcnt(0)), the cursor, and
@@ -757,13 +730,11 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_wino_kernel(const FastArgs a
       }
       if constexpr (g + 1 < 8) lds_wait(us[ns][0], us[ns][1]);
       if constexpr (g == 3) {
-        WINO_STAMP(2);  // 2: first half of the MFMA phase
         if constexpr (LEAN) wino_input_transform_pk(dpn, V);
         else wino_input_transform(ddn, V);  // (inside group 4's fences it interleaves with the MFMAs, and is 1 % slower)
       }
     });
     __builtin_amdgcn_s_setprio(0);
-    WINO_STAMP(4);  // 4: second half of the MFMA phase
     // Raw barrier: __syncthreads() carries a workgroup fence for which hipcc emits `s_waitcnt vmcnt(0) lgkmcnt(0)` in
     // front of the s_barrier of THIS loop (the epilogue's global stores of an earlier iteration may be outstanding): that
     // also drains the three input loads of the chunk after next, which were requested in MFMA group 2 of this very chunk
@@ -779,7 +750,6 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_wino_kernel(const FastArgs a
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
     }
-    WINO_STAMP(5);  // 5: barrier
     if (c_chunk + 1 == a.n_chunks) {
       // Collect the prefetched inputs BEFORE the epilogue issues its stores: vmcnt counts in order, so a wait for
       // these loads placed after the stores (hipcc puts vmcnt(0) in front of the next staging store) would also wait
@@ -797,12 +767,10 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_wino_kernel(const FastArgs a
       } else {
         epilogue();  // stores drain while the next unit computes
       }
-      WINO_STAMP(6);  // 6: epilogue
       if (d.stats_partial != nullptr) {  // uniform: the per-wave sums are in LDS; the next epilogue is a chunk barrier away
         __syncthreads();
         flush_stats();
       }
-      WINO_STAMP(7);  // 7: barrier after the epilogue
       step_unit(c_ug);
       c_chunk = 0;
       if (++c_unit == n_units) break;
@@ -813,13 +781,6 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_wino_kernel(const FastArgs a
     in_tile = smem + cur * BUF;
     w_tile = in_tile + IN_FLOATS;
   }
-#ifdef UNETPP_WINO_STAMPS
-  if (lane == 0) {
-    for (int i = 0; i < 16; ++i)
-      if (i != 8) atomicAdd(&g_wino_stamps[i], st_acc[i]);
-    atomicAdd(&g_wino_stamps[8], 1ull);
-  }
-#endif
   if constexpr (BNF) {
     __syncthreads();  // the last unit's sums are in
     bn_rows_store<kThreads>(d.stats_partial, a.Ncols, stat_lds + RUN0);
@@ -827,18 +788,6 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_wino_kernel(const FastArgs a
 }
 
 }  // namespace
-
-#ifdef UNETPP_WINO_STAMPS
-extern "C" int unetpp_debug_wino_stamps(unsigned long long* out16, int reset) {  // profiling builds only
-  if (out16 != nullptr && hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_wino_stamps), sizeof(g_wino_stamps)) != hipSuccess)
-    return UNETPP_ELAUNCH;
-  if (reset) {
-    const unsigned long long zero[16] = {};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_wino_stamps), zero, sizeof(zero)) != hipSuccess) return UNETPP_ELAUNCH;
-  }
-  return UNETPP_OK;
-}
-#endif
 
 bool wino_applies(const unetpp_gemm_desc* d) {
   return d != nullptr && d->taps == 9 && (d->flags & (UNETPP_GEMM_DIRECT | UNETPP_GEMM_BF16)) == 0;
@@ -851,7 +800,7 @@ int launch_gemm_wino(const unetpp_gemm_desc* d, hipStream_t st, long* bn_rows) {
   const int cus = device_cu_count();
   if (cus <= 0) return UNETPP_ELAUNCH;
   long workers = (2L * cus) & ~7L;  // persistent grid: two workgroups per CU (= the kernel's launch bounds)
-#if defined(UNETPP_WINO_STAMPS) || defined(UNETPP_WINO_EXP)
+#ifdef UNETPP_WINO_EXP
   if (opt_value(OPT_WINO_ONE_PER_CU, 0) == 1) workers = cus & ~7L;  // waves alone on their SIMD
 #endif
   if (workers < 8) workers = 8;

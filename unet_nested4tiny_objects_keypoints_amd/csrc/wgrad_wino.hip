@@ -28,21 +28,6 @@
 namespace unetpp {
 namespace {
 
-// In-kernel phase stamps (profiling builds only: -DUNETPP_WWINO_STAMPS, tools/wino_stamps.py --wgrad)
-#ifdef UNETPP_WWINO_STAMPS
-__device__ unsigned long long g_wwino_stamps[16];
-#define WW_STAMP(i)                            \
-  do {                                         \
-    const unsigned long long now_ = clock64(); \
-    st_acc[i] += now_ - st_last;               \
-    st_last = now_;                            \
-  } while (0)
-#else
-#define WW_STAMP(i) \
-  do {              \
-  } while (0)
-#endif
-
 constexpr int kWThreads = 512;
 constexpr int kTW = 32, kTH = 8, kHWp = kTW + 2, kHHp = kTH + 2;
 constexpr int kXRow = 36;                          // LDS row stride of the x patch in pixels (34 + 2 unused): two rows
@@ -448,51 +433,28 @@ __global__ __launch_bounds__(kWThreads, 2) void wgrad_wino_kernel(const WWinoArg
   const unsigned t0 = blockIdx.x;
   const unsigned n_tiles_all = static_cast<unsigned>(a.n_pix_tiles);
   const int n_my = (t0 < n_tiles_all) ? static_cast<int>((n_tiles_all - t0 + stride - 1) / stride) : 0;
-#ifdef UNETPP_WWINO_STAMPS
-  unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long st_last = clock64();
-#endif
   if (n_my > 0) issue_tile(t0, buf_a);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  WW_STAMP(0);  // 0: prologue
   // Waves w and w+4 share a SIMD: waves 0-3 issue the next patch's DMAs before their MFMAs, waves 4-7 half way through.
   const bool late = wave >= 4;
   for (int i = 0; i < n_my; i += 2) {
     if (!late && i + 1 < n_my) issue_tile(t0 + (i + 1) * stride, buf_b);
-    WW_STAMP(1);  // 1: DMA issue (early waves)
     compute(buf_a, IC<0>{});
-    WW_STAMP(2);  // 2: MFMA half 0
     if (late && i + 1 < n_my) issue_tile(t0 + (i + 1) * stride, buf_b);
-    WW_STAMP(3);  // 3: DMA issue (late waves)
     compute(buf_a, IC<1>{});
-    WW_STAMP(4);  // 4: MFMA half 1
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    WW_STAMP(5);  // 5: wait for the DMAs
     __syncthreads();
-    WW_STAMP(6);  // 6: barrier
     if (i + 1 < n_my) {
       if (!late && i + 2 < n_my) issue_tile(t0 + (i + 2) * stride, buf_a);
-      WW_STAMP(1);
       compute(buf_b, IC<0>{});
-      WW_STAMP(2);
       if (late && i + 2 < n_my) issue_tile(t0 + (i + 2) * stride, buf_a);
-      WW_STAMP(3);
       compute(buf_b, IC<1>{});
-      WW_STAMP(4);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      WW_STAMP(5);
       __syncthreads();
-      WW_STAMP(6);
     }
   }
 
-#ifdef UNETPP_WWINO_STAMPS
-  if (lane == 0) {
-    for (int i = 0; i < 8; ++i) atomicAdd(&g_wwino_stamps[i], st_acc[i]);
-    atomicAdd(&g_wwino_stamps[8], 1ull);
-  }
-#endif
   // ---- fixed-order tree over the 4 tile groups of each channel half: (tg0 + tg2) + (tg1 + tg3).  A region holds
   // the 32 float4 accumulators of a wave lane-linearly (32 KB); two regions per buffer. ----
   constexpr int R = 32 * 64 * 4;  // floats per region
@@ -644,18 +606,6 @@ bool x_view_ok(const unetpp_view& v) {
 }
 
 }  // namespace
-
-#ifdef UNETPP_WWINO_STAMPS
-extern "C" int unetpp_debug_wwino_stamps(unsigned long long* out16, int reset) {  // profiling builds only
-  if (out16 != nullptr && hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_wwino_stamps), sizeof(g_wwino_stamps)) != hipSuccess)
-    return UNETPP_ELAUNCH;
-  if (reset) {
-    const unsigned long long zero[16] = {};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_wwino_stamps), zero, sizeof(zero)) != hipSuccess) return UNETPP_ELAUNCH;
-  }
-  return UNETPP_OK;
-}
-#endif
 
 // 3x3, Winograd not forbidden, 32-wide patches, every view plain and 16-byte aligned, 32-bit byte offsets inside a patch
 bool wgrad_wino_applies(const unetpp_wgrad_desc* d) {
