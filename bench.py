@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: images/sec of one full training step of UNet_Nested on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -17,25 +17,31 @@ GPU, spawns N children of this script with RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* s
 non-zero if any rank failed (the reference's multi-GPU entry is in-process nn.DataParallel: one command, N GPUs,
 trainer/trainer.py:281-287,336-340).
 
+A plain run does what its headline figure needs and nothing else: it sets up, runs the untimed prewarm and W warm-up
+steps, times the K steps, writes --dump-outputs and prints the line.  `--full` adds everything else the benchmark
+measures or checks: the rocprofv3 --pmc passes behind `roofline.traffic`, `other_configs`, `cpu_baseline`, the eval-mode
+`fwd_ms_per_img` and, with N > 1, `replicas_bit_identical`; in a plain run those are null (or, for `traffic`, read
+from the committed summary).
+
 Rank 0 prints ONE JSON line.  Extra objects:
   roofline      the dominant kernel (most device time) timed live with HIP events on the launch stream over the
                 timed steps.  `achieved` = multiply-adds the matrix pipe EXECUTES (x2) / summed launch duration,
                 `frac` = achieved / dense fp32 MFMA peak (157.3 TFLOP/s, MI355X_MICROARCH.md) -- a fraction of a
                 hardware limit, <= 1.  For the Winograd kernels the executed work is 16/36 of the algorithmic
                 2*9*Cin*Cout per pixel; the algorithmic rate is reported beside it (`achieved_algorithmic`).
-                `traffic` (HBM bytes per launch from PMC counters) cannot be collected from inside the process: the
-                default single-GPU run of the headline workload therefore starts, BEFORE it touches the GPU itself,
+                `traffic` (HBM bytes per launch from PMC counters) cannot be collected from inside the process: a
+                --full single-GPU run of the headline workload therefore starts, BEFORE it touches the GPU itself,
                 three short children of this script per configuration under `rocprofv3 --pmc` (FETCH_SIZE, WRITE_SIZE,
                 SQ/GRBM: separate passes, 3 train steps each; ~3 s per pass) and summarises them with tools/pmc_traffic.py (`traffic_source`: "live");
-                without rocprofv3, for other workloads or with --no-live-pmc the numbers are read from
+                in a plain run, without rocprofv3, for other workloads or with --no-live-pmc they are read from
                 profiles/pmc_hbm_traffic_latest.json when that file was made from THIS build (build hash).  Beside
                 it `traffic_algorithmic` (every operand read/written once) and their ratio.
   roofline_x00  the X_0,0 conv block forward (1.2457 GFLOP and 42.2 MB algorithmic per image):
                 frac = max(compute floor, HBM floor) / measured block time.
-  other_configs the default run (the headline workload) then times BASELINE configs[3] (512x512, bf16 storage, batch 8) and
+  other_configs (--full) the headline workload's run then times BASELINE configs[3] (512x512, bf16 storage, batch 8) and
                 configs[4] (depth 5, base 64, 3 -> 5 channels, 384x384, bf16 storage, batch 4) for >= 20 steps each with
                 the same bracket, and attaches value / ms_per_step / roofline / top kernels per configuration.
-  cpu_baseline  the CPU oracle (oracle/, a PyTorch restatement of the reference proven equal to it on golden
+  cpu_baseline  (--full) the CPU oracle (oracle/, a PyTorch restatement of the reference proven equal to it on golden
                 fixtures) timed on this host's cores on a bounded sample of the same workload (batch 4).
 """
 import argparse
@@ -67,15 +73,19 @@ def parse():
     ap.add_argument("--n-classes", type=int, default=4)
     ap.add_argument("--dtype", choices=("f32", "bf16"), default="f32",
                     help="activation storage: f32 (configs[1], reference numerics) or bf16 with fp32 accumulation (configs[3]/[4])")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the rocprofv3 --pmc passes behind "
+                         "roofline.traffic, `other_configs`, `cpu_baseline`, the eval-mode `fwd_ms_per_img` and, with N > 1, "
+                         "`replicas_bit_identical` (a plain run leaves them null)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip `cpu_baseline`")
     ap.add_argument("--cpu-steps", type=int, default=3, help="timed CPU-oracle steps (BASELINE.md section 4: >= 3)")
     ap.add_argument("--prewarm", type=int, default=10, help="untimed steps before the W warm-up steps (see main)")
     ap.add_argument("--no-launch-timing", action="store_true", help="skip per-launch HIP events (roofline = null)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the bf16 configurations (BASELINE configs[3], configs[4]) the default run times after the "
-                         "headline and attaches under `other_configs`")
+                    help="with --full: skip the bf16 configurations (BASELINE configs[3], configs[4]) timed after the "
+                         "headline and attached under `other_configs`")
     ap.add_argument("--no-live-pmc", action="store_true",
-                    help="do not run the rocprofv3 --pmc passes the default single-GPU headline run starts before its own "
+                    help="with --full: do not run the rocprofv3 --pmc passes a single-GPU headline run starts before its own "
                          "measurement (roofline.traffic / mfma_busy_pmc then come from profiles/pmc_hbm_traffic_latest.json)")
     ap.add_argument("--other-steps", type=int, default=30, help="timed steps of each `other_configs` entry (>= 20)")
     ap.add_argument("--graphed", action="store_true",
@@ -565,21 +575,23 @@ def measure(args, ctx):
         ops.set_timer(None)
         torch.cuda.synchronize()
 
-    replicas_identical = replicas_bit_identical(model, dist) if distributed else None
+    replicas_identical = replicas_bit_identical(model, dist) if distributed and args.full else None
 
     # eval-mode forward latency (the reference's "high-speed inference" claim; BASELINE metric part 2)
-    model.eval()
-    with torch.no_grad():
-        for _ in range(2):
-            model(x)
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        reps = 5
-        for _ in range(reps):
-            model(x)
-        torch.cuda.synchronize()
-        fwd_ms_per_img = 1e3 * (time.perf_counter() - t1) / (reps * args.batch)
-    model.train()
+    fwd_ms_per_img = None
+    if args.full:
+        model.eval()
+        with torch.no_grad():
+            for _ in range(2):
+                model(x)
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            reps = 5
+            for _ in range(reps):
+                model(x)
+            torch.cuda.synchronize()
+            fwd_ms_per_img = 1e3 * (time.perf_counter() - t1) / (reps * args.batch)
+        model.train()
 
     peak_mem_gb = torch.cuda.max_memory_allocated(dev) / 1e9
     dp_info = None if averager is None else {"grad_allreduce_buckets": len(averager.buckets_last_step),
@@ -706,7 +718,7 @@ def main():
         return rehearse_cpu(args)
     under_profiler = "rocprof" in os.environ.get("LD_PRELOAD", "").lower() or any(
         k.startswith(("ROCPROF", "ROCP_")) for k in os.environ)   # this process is itself being profiled: no nesting
-    if (args.gpus == 1 and "WORLD_SIZE" not in os.environ and is_headline(args) and not args.no_live_pmc
+    if (args.full and args.gpus == 1 and "WORLD_SIZE" not in os.environ and is_headline(args) and not args.no_live_pmc
             and not args.no_launch_timing and not under_profiler and os.environ.get("UNETPP_BENCH_LIVE_PMC", "1") != "0"):
         # children under rocprofv3, finished before this process initialises the GPU; the two other configurations too
         todo = [args] + ([] if args.no_other_configs else [argparse.Namespace(**dict(vars(args), **over)) for _, over in OTHER_CONFIGS])
@@ -754,10 +766,10 @@ def main():
     ctx = {"torch": torch, "dist": dist, "dev": dev, "world": world, "rank": rank, "distributed": distributed}
     others_first = os.environ.get("UNETPP_BENCH_OTHERS_FIRST") == "1"   # diagnostic (never set by the driver): order effects
     res = None if others_first else measure(args, ctx)
-    # BASELINE configs[3] and configs[4] (bf16 storage) in the same run, attached to the same line: every rank takes part
-    # (they are data-parallel steps like the headline), a failure there must not cost the headline line
+    # --full: BASELINE configs[3] and configs[4] (bf16 storage) in the same run, attached to the same line: every rank takes
+    # part (they are data-parallel steps like the headline), a failure there must not cost the headline line
     others = None
-    if not args.no_other_configs and is_headline(args):
+    if args.full and not args.no_other_configs and is_headline(args):
         others = []
         for name, over in OTHER_CONFIGS:
             o = argparse.Namespace(**dict(vars(args), **over))
@@ -787,7 +799,7 @@ def main():
     roofline, roofline_x00, kernels = res["roofline"], res["roofline_x00"], res["kernels"]
     dp_info, replicas_identical, n_cls = res["dp"] or {}, res["replicas_identical"], res["n_cls"]
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(args, n_cls)
     line = {
         "metric": "images/sec (train step) UNet++ L=4 256x256",
@@ -810,6 +822,7 @@ def main():
         "vs_baseline": None,
         "dtype": args.dtype,
         "data": "synthetic",
+        "full": args.full,
         "config": {"workload": workload_name(args),
                    "global_batch": world * args.batch, "per_gpu_batch": args.batch,
                    "parallelism": "dp%d" % world if distributed else "single",
@@ -819,7 +832,7 @@ def main():
                    "grad_bucket_bytes": dp_info.get("grad_bucket_bytes"),
                    "gradient_bytes": dp_info.get("gradient_bytes"),
                    "replicas_bit_identical": replicas_identical},
-        "fwd_ms_per_img": round(fwd_ms_per_img, 4),
+        "fwd_ms_per_img": None if fwd_ms_per_img is None else round(fwd_ms_per_img, 4),
         "roofline": roofline,
         "roofline_x00": roofline_x00,
         "kernels": kernels,

@@ -108,7 +108,7 @@ def test_graphed_train_step_refuses_cpu_tensors_and_eval_models():
 
 
 def test_bench_other_configs_name_the_baseline_configurations():
-    """bench.py's default run attaches BASELINE.json's configs[3] and configs[4] (as single-GPU geometries) to the headline
+    """`bench.py --full` attaches BASELINE.json's configs[3] and configs[4] (as single-GPU geometries) to the headline
     line; the table that says which is host logic."""
     import importlib.util
     import json
@@ -220,3 +220,63 @@ def test_bench_refuses_zero_steps():
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "0"], capture_output=True, text=True,
                        timeout=120)
     assert r.returncode == 2 and "--steps must be at least 1" in r.stderr
+
+
+def test_bench_plain_run_leaves_the_extras_to_full(monkeypatch, capsys):
+    """A plain `bench.py` run measures the configuration named on the command line and nothing else: no rocprofv3 --pmc
+    passes, no `other_configs`, no CPU baseline.  `--full` adds all three.  The GPU side (build, measure) is stubbed, so
+    this is the run's plan only."""
+    import argparse
+    import importlib.util
+    import json
+    import os
+    import sys
+
+    import __graft_entry__
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_module_plan", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    calls = {"pmc": [], "measure": [], "cpu": 0}
+
+    def fake_measure(args, ctx):
+        calls["measure"].append(bench.config_key(args))
+        return {"peak_mem_gb": 1.0, "step_runner": "eager", "host_enqueue_ms": 1.0, "host_enqueue_ms_min": 1.0,
+                "value": 1000.0, "ms_per_step": 32.0, "fwd_ms_per_img": 0.2 if args.full else None, "roofline": None,
+                "roofline_x00": None, "kernels": None, "dp": None, "replicas_identical": None, "n_cls": args.n_classes,
+                "fs": args.feature_scale}
+
+    def fake_cpu(args, n_cls):
+        calls["cpu"] += 1
+        return {"value": 2.0}
+
+    monkeypatch.setattr(bench, "live_pmc", lambda cfg: calls["pmc"].append(bench.config_key(cfg)))   # None: no profiler
+    monkeypatch.setattr(bench, "measure", fake_measure)
+    monkeypatch.setattr(bench, "cpu_baseline", fake_cpu)
+    monkeypatch.setattr(__graft_entry__, "build", lambda: None)
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: True)
+    monkeypatch.setattr(torch.cuda, "set_device", lambda index: None)
+    for k in list(os.environ):
+        if k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "UNETPP_BENCH_LIVE_PMC", "UNETPP_BENCH_OTHERS_FIRST") or \
+                k.startswith(("ROCPROF", "ROCP_")):
+            monkeypatch.delenv(k)
+    monkeypatch.setenv("UNETPP_BENCH_NO_SWEEP", "1")
+    headline = bench.config_key(argparse.Namespace(dtype="f32", size=256, batch=32, feature_scale=1, depth=4,
+                                                   in_channels=1, n_classes=4))
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "2", "--warmup", "1"])
+    bench.main()
+    line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert calls == {"pmc": [], "measure": [headline], "cpu": 0}
+    assert line["full"] is False and line["cpu_baseline"] is None and line["other_configs"] is None
+    assert line["fwd_ms_per_img"] is None and "speedup_vs_cpu_baseline" not in line
+    assert (line["value"], line["ms_per_step"], line["steps"], line["warmup"]) == (1000.0, 32.0, 2, 1)
+
+    calls.update(pmc=[], measure=[], cpu=0)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "2", "--warmup", "1", "--full"])
+    bench.main()
+    line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    others = [bench.config_key(argparse.Namespace(**dict(vars(bench.parse()), **over))) for _, over in bench.OTHER_CONFIGS]
+    assert calls == {"pmc": [headline], "measure": [headline] + others, "cpu": 1}
+    assert line["full"] is True and line["cpu_baseline"] == {"value": 2.0} and line["fwd_ms_per_img"] == 0.2
+    assert [o["config"] for o in line["other_configs"]] == [n for n, _ in bench.OTHER_CONFIGS]
