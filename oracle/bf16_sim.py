@@ -125,8 +125,9 @@ def routing_of(hip_saved):
     return gates, pools
 
 
-def forward_bf16_sim(model, inputs, training=True, dtype=torch.float64, routing=None, stats=None):
-    """model: a UNetNestedOracle.  Dropout must be off (model.drop_out.eval() / p = 0).
+def forward_bf16_sim(model, inputs, training=True, dtype=torch.float64, routing=None, stats=None, dropout=None):
+    """model: a UNetNestedOracle.  Its own dropout is not applied (model.drop_out.eval() / p = 0); dropout = None, or a
+    callable applied to every head's input in head order (oracle/dropout_oracle.py KeepMaskDropout).
     routing = routing_of(hip_saved) or None; stats (dict) receives the counts of differing gates / winners."""
     d = model.depth
     x = inputs.to(dtype)
@@ -153,5 +154,6 @@ def forward_bf16_sim(model, inputs, training=True, dtype=torch.float64, routing=
     outs = []
     for j in range(1, d):
         head = getattr(model, "final_%d" % j)
-        outs.append(torch.sigmoid(F.conv2d(X[0][j], head.weight.to(dtype), head.bias.to(dtype))))
+        xh = X[0][j] if dropout is None else dropout(X[0][j])
+        outs.append(torch.sigmoid(F.conv2d(xh, head.weight.to(dtype), head.bias.to(dtype))))
     return tuple(outs)

@@ -649,10 +649,12 @@ def test_maxpool_bwd_bf16(dev, b, h, w, c):
 BF16_GRAD_VS_FP32_ORACLE_ROUTED = 0.10   # relative L2 of any parameter gradient (stated bf16 tolerance, see the test below)
 
 
-def _bf16_vs_oracle(dev, ctor, b, h, w, seed, probe=False):
+def _bf16_vs_oracle(dev, ctor, b, h, w, seed, probe=False, dropout=False):
     """One train step (dropout off) of the HIP model with bf16 activation storage against (a) the fp32 CPU oracle and
     (b) the same oracle evaluated with the bf16 path's roundings (oracle/bf16_sim.py, float64), on the same fp32
-    parameters and inputs.  Returns the error figures the callers bound."""
+    parameters and inputs.  Returns the error figures the callers bound.
+    dropout=True: the step runs with the product's dropout (keep masks drawn in the head kernels); every oracle applies
+    the restated masks of the seeds the step used (oracle/dropout_oracle.py), so the HIP step runs first."""
     from oracle.bf16_sim import forward_bf16_sim, routing_of
     from oracle.step_oracle import focal_bce_2d_oracle
     from oracle.unet_nested_oracle import UNetNestedOracle
@@ -665,7 +667,8 @@ def _bf16_vs_oracle(dev, ctor, b, h, w, seed, probe=False):
     m = UNet_Nested(**ctor)
     m.load_state_dict(state)
     m = m.to(dev).train().set_activation_dtype(BF)
-    m.drop_out.eval()
+    if not dropout:
+        m.drop_out.eval()
     m._debug_keep_saved = True
     x = torch.randn(b, ctor["in_channels"], h, w)
     target = torch.rand(b, ctor["n_classes"], h, w)
@@ -677,17 +680,30 @@ def _bf16_vs_oracle(dev, ctor, b, h, w, seed, probe=False):
     else:
         loss_cpu = lambda outs, tg: sum(focal_bce_2d_oracle(o, tg.to(o.dtype)) for o in outs) / len(outs)  # noqa: E731
         loss_dev = lambda outs, tg: sum(crit(o, tg) for o in outs) / len(outs)                          # noqa: E731
+    drop = None
+    if dropout:
+        from oracle.dropout_oracle import KeepMaskDropout
+        assert m.drop_out.training and m.drop_out.p > 0 and m.dropout_masks is None
+        outs = m(x.to(dev))
+        loss = loss_dev(outs, target.to(dev))
+        loss.backward()
+        torch.cuda.synchronize()
+        assert m._debug_saved.masks is None and len(m._debug_saved.seeds) == len(outs)
+        drop = KeepMaskDropout(m._debug_saved.seeds, b, h, w, m.filters[0], m.drop_out.p)
+        ref.drop_out = drop
     ro = ref(x)
     rl = loss_cpu(ro, target)
     rl.backward()
     g32 = {k: p.grad.double().clone() for k, p in ref.named_parameters()}
     bufs32 = {k: v.clone() for k, v in ref.named_buffers()}
-    outs = m(x.to(dev))
-    loss = loss_dev(outs, target.to(dev))
-    loss.backward()
+    if not dropout:
+        outs = m(x.to(dev))
+        loss = loss_dev(outs, target.to(dev))
+        loss.backward()
     ref.zero_grad()
     flips = {}
-    so = forward_bf16_sim(ref, x, routing=routing_of(m._debug_saved), stats=flips)  # backward with the HIP gates / winners
+    so = forward_bf16_sim(ref, x, routing=routing_of(m._debug_saved), stats=flips,  # backward with the HIP gates / winners
+                          dropout=drop)
     sl = loss_cpu(so, target)
     sl.backward()
     gsim = {k: p.grad.double().clone() for k, p in ref.named_parameters()}
@@ -699,6 +715,8 @@ def _bf16_vs_oracle(dev, ctor, b, h, w, seed, probe=False):
     routed.load_state_dict(state)
     routed = routed.double().train()
     routed.drop_out.eval()
+    if drop is not None:
+        routed.drop_out = drop
     install_hip_gates(routed, m._debug_saved)
     loss_cpu(routed(x.double()), target.double()).backward()
     grouted = {k: p.grad.double().clone() for k, p in routed.named_parameters()}
@@ -742,7 +760,7 @@ def _bf16_vs_oracle(dev, ctor, b, h, w, seed, probe=False):
     (dict(in_channels=1, n_classes=4, feature_scale=4, is_deconv=False, is_batchnorm=False, depth=3), 2, 32, 48),
 ], ids=["base32", "d5-base64-rgb5", "base8", "configs3-512x512", "configs4-d5-base64-384x384", "bilinear", "no-batchnorm",
         "bilinear-no-batchnorm-d3"])
-def test_bf16_train_step_vs_oracles(dev, ctor, b, h, w):
+def test_bf16_train_step_vs_oracles(dev, ctor, b, h, w, dropout=False):
     """The separately stated bf16 tolerance (north_star's 1e-4 is the fp32 bar).
 
     Against the fp32 oracle: every stored activation carries 8 mantissa bits (2^-9 relative), ~20 stored tensors on the
@@ -756,11 +774,11 @@ def test_bf16_train_step_vs_oracles(dev, ctor, b, h, w):
     and in DESIGN.md, not bounded.)"""
     import json
     import os
-    res = _bf16_vs_oracle(dev, ctor, b, h, w, 51)
+    res = _bf16_vs_oracle(dev, ctor, b, h, w, 51, dropout=dropout)
     worst = max(res["sim_grad_l2"].items(), key=lambda kv: kv[1])
     worst32 = max(res["grad_l2"].items(), key=lambda kv: kv[1])
     worst_routed = max(res["routed_grad_l2"].items(), key=lambda kv: kv[1])
-    line = {"case": str(sorted(ctor.items())), "out_max": res["out_max"], "out_mean": res["out_mean"], "loss_rel": res["loss_rel"],
+    line = {"case": str(sorted(ctor.items())) + (" dropout" if dropout else ""), "out_max": res["out_max"], "out_mean": res["out_mean"], "loss_rel": res["loss_rel"],
             "sim_out_max": res["sim_out_max"], "sim_out_mean": res["sim_out_mean"], "sim_loss_rel": res["sim_loss_rel"],
             "bn_rel": res["bn_rel"], "routing_differences": res["flips"], "worst_grad_l2_vs_bf16_sim": worst, "min_cos_vs_bf16_sim": min(res["cos"].values()),
             "worst_grad_l2_vs_fp32_oracle": worst32, "worst_grad_l2_vs_fp32_oracle_with_hip_routing": worst_routed}
@@ -779,6 +797,12 @@ def test_bf16_train_step_vs_oracles(dev, ctor, b, h, w):
     # weights to bf16 gives 0.22, and keeping the encoder's pre-BatchNorm outputs -- or the whole encoder -- in fp32
     # leaves 0.27 / 0.22 (tests/bf16_gap_experiment.py, CPU, no HIP code)
     assert worst_routed[1] <= BF16_GRAD_VS_FP32_ORACLE_ROUTED, line
+
+
+def test_bf16_train_step_with_generated_dropout_vs_oracles(dev):
+    """test_bf16_train_step_vs_oracles' base-32 case with the product's dropout: the heads draw their keep masks in the
+    kernels, every oracle applies the restated masks of the step's seeds (oracle/dropout_oracle.py); the same bounds."""
+    test_bf16_train_step_vs_oracles(dev, dict(in_channels=1, n_classes=4, feature_scale=1), 2, 64, 64, dropout=True)
 
 
 def test_bf16_training_tracks_fp32(dev):

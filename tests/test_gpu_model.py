@@ -296,6 +296,38 @@ def test_dropout_path_vs_oracle_with_shared_mask(dev):
         assert rel_err(o.detach().cpu(), r.detach()) < TOL
 
 
+@pytest.mark.parametrize("case", [c for c in ORACLE_CASES if c[0] == dict(in_channels=1, n_classes=4, feature_scale=1)
+                                  and c[1:4] in ((2, 64, 64), (4, 256, 256))], ids=["base32-b2-64x64", "configs1-b4-256x256"])
+def test_train_step_with_generated_dropout_vs_oracle(dev, case):
+    """The product's dropout: the heads draw their keep masks in the kernels (no dropout_masks).  The oracle's drop-out
+    applies, head by head, the restated mask (oracle/dropout_oracle.py) of the seeds the step used; outputs and every
+    parameter gradient against it.  At 4 x 256 x 256 the head forward runs above the stream kernel's grid cap."""
+    from oracle.dropout_oracle import KeepMaskDropout
+    from oracle.unet_nested_oracle import UNetNestedOracle
+    ctor, b, h, w = case[:4]
+    grad_dtype = case[4] if len(case) > 4 else torch.float32
+    torch.manual_seed(15)
+    ref = UNetNestedOracle(**ctor).train()
+    state = {k: v.clone() for k, v in ref.state_dict().items()}
+    m = _hip_model(ctor, state, dev).train()
+    assert m.drop_out.training and m.drop_out.p > 0 and m.dropout_masks is None
+    m._debug_keep_saved = True
+    x = torch.randn(b, ctor["in_channels"], h, w)
+    target = torch.rand(b, ctor["n_classes"], h, w)
+    outs = m(x.to(dev))
+    loss = _loss(outs, target.to(dev))
+    loss.backward()
+    torch.cuda.synchronize()
+    seeds = m._debug_saved.seeds
+    assert m._debug_saved.masks is None and len(seeds) == len(outs)
+    drop = KeepMaskDropout(seeds, b, h, w, m.filters[0], m.drop_out.p)
+    _, ro = _check_grads_gate_aware(m, ctor, state, x, target, masks=drop, dtype=grad_dtype,
+                                    label="generated dropout b%d %dx%d" % (b, h, w))
+    assert drop.calls == len(outs)
+    for o, r in zip(outs, ro):
+        assert rel_err(o.detach().cpu(), r.detach()) < TOL
+
+
 def test_dropout_generator_statistics_and_determinism(dev):
     from unet_nested4tiny_objects_keypoints_amd import UNet_Nested
     torch.manual_seed(3)

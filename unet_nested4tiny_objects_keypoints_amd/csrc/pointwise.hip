@@ -1438,10 +1438,13 @@ extern "C" int unetpp_head_fwd(const float* x, const float* weight, const float*
     const long ppb = kThreads / g4;
     const long want = (pixels + ppb - 1) / ppb;
     const dim3 grid(static_cast<unsigned>(want < 256 * 16 ? want : 256 * 16));
-#define UNETPP_HEAD_STREAM_D(L, PC, D)                                                                              \
-  hipLaunchKernelGGL((head_fwd_stream_kernel<L, PC, D>), grid, dim3(kThreads), 0, ST(stream), x, weight, bias,         \
-                     static_cast<unsigned>(pixels), static_cast<unsigned>(H * W), n_cls, 1.0f / (1.0f - p_drop),        \
-                     keep_threshold(p_drop), seed, mask, seed_dev, out_nchw)
+#define UNETPP_HEAD_STREAM_D(L, PC, D)                                                                                \
+  do {                                                                                                              \
+    note_kernel("head_fwd_stream<" #L "," #PC "," #D ">");                                                          \
+    hipLaunchKernelGGL((head_fwd_stream_kernel<L, PC, D>), grid, dim3(kThreads), 0, ST(stream), x, weight, bias,     \
+                       static_cast<unsigned>(pixels), static_cast<unsigned>(H * W), n_cls, 1.0f / (1.0f - p_drop),    \
+                       keep_threshold(p_drop), seed, mask, seed_dev, out_nchw);                                     \
+  } while (0)
 #define UNETPP_HEAD_STREAM(L, PC)                              \
   do {                                                         \
     if (!use_drop) UNETPP_HEAD_STREAM_D(L, PC, 0);             \
@@ -1469,11 +1472,13 @@ extern "C" int unetpp_head_fwd(const float* x, const float* weight, const float*
   if ((C & 3) == 0 && aligned16(x)) {
     const long tiles = (pixels + 63) / 64;
     const unsigned blocks = static_cast<unsigned>(tiles < 256 * 16 ? tiles : 256 * 16);
+    note_kernel("head_fwd_tiled");
     hipLaunchKernelGGL(head_fwd_tiled_kernel, dim3(blocks), dim3(64), 64 * (C + 1) * sizeof(float), ST(stream), x, weight,
                        bias, pixels, H * W, C,
                        n_cls, 1.0f / (1.0f - p_drop), keep_threshold(p_drop), seed, mask, seed_dev, use_drop, out_nchw);
     return launch_status();
   }
+  note_kernel("head_fwd");
   hipLaunchKernelGGL(head_fwd_kernel, dim3(grid_for(pixels)), dim3(kThreads), 0, ST(stream), x, weight, bias, pixels,
                      H * W, C, n_cls, 1.0f / (1.0f - p_drop), keep_threshold(p_drop), seed, mask, seed_dev, use_drop, out_nchw);
   return launch_status();
@@ -1504,10 +1509,14 @@ extern "C" int unetpp_head_bwd(const float* d_out_nchw, const float* out_nchw, c
     if (n_cls <= 4) UNETPP_HEAD_BWD_P(L, D, 4);  \
     else UNETPP_HEAD_BWD_P(L, D, 8);             \
   } while (0)
-#define UNETPP_HEAD_BWD_P(L, D, PC)                                                                                 \
-  hipLaunchKernelGGL((head_bwd_pow2_kernel<L, D, PC>), grid, dim3(kThreads), lds, ST(stream), d_out_nchw, out_nchw, x, \
-                     weight, static_cast<unsigned>(pixels), static_cast<unsigned>(H * W), n_cls, 1.0f / (1.0f - p_drop), \
-                     keep_threshold(p_drop), seed, mask, seed_dev, dx, accumulate, gate_x, partial)
+#define UNETPP_HEAD_BWD_P(L, D, PC)                                                                                   \
+  do {                                                                                                              \
+    note_kernel("head_bwd_pow2<" #L "," #D "," #PC ">");                                                            \
+    hipLaunchKernelGGL((head_bwd_pow2_kernel<L, D, PC>), grid, dim3(kThreads), lds, ST(stream), d_out_nchw, out_nchw, \
+                       x, weight, static_cast<unsigned>(pixels), static_cast<unsigned>(H * W), n_cls,                \
+                       1.0f / (1.0f - p_drop), keep_threshold(p_drop), seed, mask, seed_dev, dx, accumulate, gate_x,  \
+                       partial);                                                                                    \
+  } while (0)
 #define UNETPP_HEAD_BWD_L(L)              \
   do {                                    \
     if (drop == 0) UNETPP_HEAD_BWD(L, 0); \
@@ -1528,11 +1537,13 @@ extern "C" int unetpp_head_bwd(const float* d_out_nchw, const float* out_nchw, c
   }
   if ((C & 3) == 0 && aligned16(x) && aligned16(dx)) {
     const size_t lds = (64 * (C + 1) + 64 * kHeadMaxCls + kHeadMaxCls * C + 2 * n_cls * C) * sizeof(float);
+    note_kernel("head_bwd_vec");
     hipLaunchKernelGGL(head_bwd_vec_kernel, dim3(static_cast<unsigned>(unetpp_head_bwd_blocks(pixels))), dim3(kThreads),
                        lds, ST(stream), d_out_nchw, out_nchw, x, weight, pixels, H * W, C, n_cls, 1.0f / (1.0f - p_drop),
                        keep_threshold(p_drop), seed, mask, seed_dev, use_drop, dx, accumulate, gate_x, partial);
     return launch_status();
   }
+  note_kernel("head_bwd");
   hipLaunchKernelGGL(head_bwd_kernel, dim3(static_cast<unsigned>(unetpp_head_bwd_blocks(pixels))), dim3(kThreads), 0,
                      ST(stream), d_out_nchw, out_nchw, x, weight, pixels, H * W, C, n_cls, 1.0f / (1.0f - p_drop),
                      keep_threshold(p_drop), seed, mask, seed_dev, use_drop, dx, accumulate, gate_x, partial);

@@ -634,9 +634,12 @@ extern "C" int unetpp_head_fwd_bf16(const void* x, const float* weight, const fl
   const int drop = p_drop > 0.f ? (mask == nullptr ? 1 : 2) : 0;
   if (drop == 2 && (reinterpret_cast<uintptr_t>(mask) & 7) != 0) return UNETPP_EINVAL;  // mask octets are read as 8 bytes
 #define UNETPP_HEAD_BF(L, D, PC)                                                                                          \
-  hipLaunchKernelGGL((head_fwd_bf16_kernel<L, D, PC>), grid, dim3(kThreads), 0, ST(stream), static_cast<const bf16_t*>(x), \
-                     weight, bias, pixels, H * W, n_cls, 1.0f / (1.0f - p_drop), keep_threshold(p_drop), seed, mask, seed_dev,       \
-                     out_nchw)
+  do {                                                                                                                    \
+    note_kernel("head_fwd_bf16<" #L "," #D "," #PC ">");                                                                  \
+    hipLaunchKernelGGL((head_fwd_bf16_kernel<L, D, PC>), grid, dim3(kThreads), 0, ST(stream), static_cast<const bf16_t*>(x), \
+                       weight, bias, pixels, H * W, n_cls, 1.0f / (1.0f - p_drop), keep_threshold(p_drop), seed, mask,     \
+                       seed_dev, out_nchw);                                                                               \
+  } while (0)
 #define UNETPP_HEAD_BF_D(L, D)            \
   do {                                    \
     if (n_cls <= 4) UNETPP_HEAD_BF(L, D, 4); \
@@ -699,11 +702,14 @@ extern "C" int unetpp_head_bwd_bf16(const float* d_out_nchw, const float* out_nc
     else if (n_cls <= 6) UNETPP_HEAD_BWD_BF_P(L, D, 6);             \
     else UNETPP_HEAD_BWD_BF_P(L, D, 8);                             \
   } while (0)
-#define UNETPP_HEAD_BWD_BF_P(L, D, PC)                                                                                 \
-  hipLaunchKernelGGL((head_bwd_bf16_kernel<L, D, PC>), grid, dim3(kThreads), lds, ST(stream), d_out_nchw, out_nchw,     \
-                     static_cast<const bf16_t*>(x), weight, static_cast<unsigned>(pixels), static_cast<unsigned>(H * W), \
-                     n_cls, 1.0f / (1.0f - p_drop), keep_threshold(p_drop), seed, mask, seed_dev, static_cast<bf16_t*>(dx),       \
-                     accumulate, gate_x, partial, active)
+#define UNETPP_HEAD_BWD_BF_P(L, D, PC)                                                                                   \
+  do {                                                                                                                    \
+    note_kernel("head_bwd_bf16<" #L "," #D "," #PC ">");                                                                  \
+    hipLaunchKernelGGL((head_bwd_bf16_kernel<L, D, PC>), grid, dim3(kThreads), lds, ST(stream), d_out_nchw, out_nchw,   \
+                       static_cast<const bf16_t*>(x), weight, static_cast<unsigned>(pixels), static_cast<unsigned>(H * W), \
+                       n_cls, 1.0f / (1.0f - p_drop), keep_threshold(p_drop), seed, mask, seed_dev,                     \
+                       static_cast<bf16_t*>(dx), accumulate, gate_x, partial, active);                                   \
+  } while (0)
 #define UNETPP_HEAD_BWD_BF_L(L)              \
   do {                                       \
     if (drop == 0) UNETPP_HEAD_BWD_BF(L, 0); \
