@@ -136,9 +136,12 @@ typedef struct unetpp_wgrad_desc {
 int unetpp_abi_version(void);
 const char* unetpp_build_arch(void); /* "gfx950" */
 
-/* Name of the device kernel the calling thread's most recent unetpp_gemm_fwd / unetpp_wgrad call launched
- * (profiling labels; equals the rocprofv3 kernel name up to template arguments).  Static string, "" before the
- * first call.  Diagnostic only (thread-local). */
+/* Name of the device kernel (and, where a launcher has several, of the form) that the calling thread's most recent
+ * launching call chose: the GEMMs and weight gradients, the heads, the optimizer, the matcher and the streaming
+ * launchers (BatchNorm finalize / apply / backward, pool passes, bilinear x2, layout converters).  unetpp_gemm_fwd keeps
+ * its GEMM's label over an attached BatchNorm finalize; unetpp_sum_partials, the packers and the loss set none.  Read it
+ * right after the call in question: any later labelled call replaces it.  Profiling labels (the rocprofv3 kernel name
+ * up to template arguments, or name/form).  Static string, "" before the first call.  Diagnostic only (thread-local). */
 const char* unetpp_last_kernel_name(void);
 
 /* Dispatcher switches for A/B measurements and for tests that hold two kernels against each other inside one process

@@ -65,6 +65,21 @@ def sub(z, prefix):
     return {k[plen:]: torch.from_numpy(np.asarray(z[k])) for k in z.files if k.startswith(prefix + "/")}
 
 
+def close_bf16(got, want, what=""):
+    """One rounding of the stored result to bf16 (tests/test_gpu_bf16.py: 2^-8 relative + 1e-5 of the scale)."""
+    got, want = got.double().cpu(), want.double().cpu()
+    err = (got - want).abs()
+    bound = 2.0 ** -8 * want.abs() + 1e-5 * float(want.abs().max())
+    bad = err > bound
+    assert not bool(bad.any()), (what, int(bad.sum()), float(err.max()), float(want.abs().max()))
+
+
+def close_f32(got, want, tol=1e-4, what=""):
+    got, want = got.double().cpu(), want.double().cpu()
+    assert float((got - want).abs().max()) <= tol * float(want.abs().max()) + 1e-30, (
+        what, float((got - want).abs().max()), float(want.abs().max()))
+
+
 def rel_err(a, b):
     """max |a-b| / max(|b|) -- the 'relative fp32' measure used for the 1e-4 bar."""
     a = torch.as_tensor(a, dtype=torch.float64)

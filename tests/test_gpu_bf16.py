@@ -13,6 +13,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests.helpers import close_bf16, close_f32  # noqa: F401  (other test files import them from here)
+
 pytestmark = pytest.mark.gpu
 
 BF = torch.bfloat16
@@ -28,20 +30,6 @@ def dev():
 def rb(t):
     """round to bf16, keep as float64 (the operand values the kernels see)"""
     return t.to(BF).double()
-
-
-def close_bf16(got, want, what=""):
-    got, want = got.double().cpu(), want.double().cpu()
-    err = (got - want).abs()
-    bound = 2.0 ** -8 * want.abs() + 1e-5 * float(want.abs().max())
-    bad = err > bound
-    assert not bool(bad.any()), (what, int(bad.sum()), float(err.max()), float(want.abs().max()))
-
-
-def close_f32(got, want, tol=1e-4, what=""):
-    got, want = got.double().cpu(), want.double().cpu()
-    assert float((got - want).abs().max()) <= tol * float(want.abs().max()) + 1e-30, (
-        what, float((got - want).abs().max()), float(want.abs().max()))
 
 
 def nhwc(t):  # NCHW float64 -> NHWC

@@ -320,8 +320,12 @@ extern "C" int unetpp_gemm_fwd(const unetpp_gemm_desc* d, void* stream) {
   const int rc = gemm_fwd_dispatch(d, stream, &bn_rows);
   if (rc != UNETPP_OK) return rc;
   const int64_t rows = bn_rows > 0 ? bn_rows : unetpp_gemm_pixel_blocks(d->N, d->H, d->W);
-  return unetpp_bn_finalize(d->stats_partial, rows, d->out[0].c_len, bn.count, bn.gamma, bn.beta, bn.eps, bn.momentum,
-                            bn.running_mean, bn.running_var, bn.mean, bn.invstd, bn.scale, bn.shift, stream);
+  const char* gemm_name = g_last_kernel;  // the call keeps the label of its GEMM, not that of the attached finalize
+  const int fin = unetpp_bn_finalize(d->stats_partial, rows, d->out[0].c_len, bn.count, bn.gamma, bn.beta, bn.eps,
+                                     bn.momentum, bn.running_mean, bn.running_var, bn.mean, bn.invstd, bn.scale, bn.shift,
+                                     stream);
+  note_kernel(gemm_name);
+  return fin;
 }
 
 namespace {

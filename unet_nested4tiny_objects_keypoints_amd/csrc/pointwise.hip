@@ -1145,6 +1145,10 @@ __global__ __launch_bounds__(kThreads) void nhwc_to_nchw_kernel(const float* __r
 inline unsigned fin_threads(long n_blocks) {  // workgroup size of the per-channel reductions over partial rows
   return n_blocks >= 4096 ? 1024u : n_blocks >= 1024 ? 512u : 256u;
 }
+inline const char* fin_label(long n_blocks, const char* l256, const char* l512, const char* l1024) {  // name of that form
+  const unsigned t = fin_threads(n_blocks);
+  return t == 1024u ? l1024 : t == 512u ? l512 : l256;
+}
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
@@ -1161,6 +1165,7 @@ extern "C" int unetpp_bn_finalize(const float* partial, int64_t n_blocks, int32_
     return UNETPP_EINVAL;
   if ((running_mean == nullptr) != (running_var == nullptr)) return UNETPP_EINVAL;
   if ((reinterpret_cast<uintptr_t>(partial) & 7) != 0) return UNETPP_EINVAL;  // rows are read as (sum, sum of squares) pairs
+  note_kernel(fin_label(n_blocks, "bn_finalize/256", "bn_finalize/512", "bn_finalize/1024"));
   hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(fin_threads(n_blocks)), 0, ST(stream), partial, n_blocks, C,
                      count, gamma, beta, eps, momentum, running_mean, running_var, mean, invstd, scale, shift);
   return launch_status();
@@ -1170,6 +1175,7 @@ extern "C" int unetpp_bn_eval_coeffs(const float* gamma, const float* beta, cons
                                      const float* running_var, float eps, int32_t C, float* scale, float* shift,
                                      void* stream) {
   if (!gamma || !beta || !running_mean || !running_var || C < 1 || !scale || !shift) return UNETPP_EINVAL;
+  note_kernel("bn_eval_coeffs");
   hipLaunchKernelGGL(bn_eval_coeffs_kernel, dim3((C + 63) / 64), dim3(64), 0, ST(stream), gamma, beta, running_mean,
                      running_var, eps, C, scale, shift);
   return launch_status();
@@ -1193,10 +1199,12 @@ extern "C" int unetpp_affine_relu_pool(const float* y, const float* scale, const
     const long pixels = static_cast<long>(N) * H * W;
     if (vec) {
       const long items = pixels * (C / 4);
+      note_kernel("affine_relu<4>");
       hipLaunchKernelGGL(affine_relu_kernel<4>, dim3(grid_for(items)), dim3(kThreads), 0, ST(stream), y, scale, shift,
                          relu, items, C / 4, act);
     } else {
       const long items = pixels * C;
+      note_kernel("affine_relu<1>");
       hipLaunchKernelGGL(affine_relu_kernel<1>, dim3(grid_for(items)), dim3(kThreads), 0, ST(stream), y, scale, shift,
                          relu, items, C, act);
     }
@@ -1218,6 +1226,7 @@ extern "C" int unetpp_affine_relu_pool(const float* y, const float* scale, const
     }
     const long win = static_cast<long>(N) * (H / 2) * (W / 2);
     const bool v4 = (C % 4 == 0) && aligned16(src) && aligned16(pooled);
+    note_kernel(v4 ? "affine_relu_pool<4>" : "affine_relu_pool<1>");
     if (v4)
       hipLaunchKernelGGL(affine_relu_pool_kernel<4>, dim3(grid_for(win * (C / 4))), dim3(kThreads), 0, ST(stream), src, scale,
                          shift, relu, N, H, W, C / 4, static_cast<float*>(nullptr), pooled, pool_idx);
@@ -1228,8 +1237,10 @@ extern "C" int unetpp_affine_relu_pool(const float* y, const float* scale, const
   }
   const long windows = static_cast<long>(N) * (H / 2) * (W / 2);
   const unsigned rows = static_cast<unsigned>(N * (H / 2)), row_items = static_cast<unsigned>((W / 2) * (C / 4));
-  if (vec && rows_form_ok(N, H, W, C) && (scale == nullptr || (aligned16(scale) && aligned16(shift))) &&
-      (reinterpret_cast<uintptr_t>(pool_idx) & 3) == 0)
+  const bool rows_form = vec && rows_form_ok(N, H, W, C) && (scale == nullptr || (aligned16(scale) && aligned16(shift))) &&
+                         (reinterpret_cast<uintptr_t>(pool_idx) & 3) == 0;
+  note_kernel(rows_form ? "affine_relu_pool_rows" : vec ? "affine_relu_pool<4>" : "affine_relu_pool<1>");
+  if (rows_form)
     hipLaunchKernelGGL(affine_relu_pool_rows_kernel, dim3(rows < 16384u ? rows : 16384u), dim3(kThreads), 0, ST(stream),
                        reinterpret_cast<const f32x4*>(y), reinterpret_cast<const f32x4*>(scale),
                        reinterpret_cast<const f32x4*>(shift), relu, rows, static_cast<unsigned>(W / 2),
@@ -1249,8 +1260,10 @@ extern "C" int unetpp_maxpool_bwd(const float* d_pooled, const uint8_t* pool_idx
   if (!d_pooled || !pool_idx || !d_act || N < 1 || H < 2 || W < 2 || C < 1) return UNETPP_EINVAL;
   const long windows = static_cast<long>(N) * (H / 2) * (W / 2);  // odd H / W: the last row / column is in no window (floor)
   const unsigned rows = static_cast<unsigned>(N * (H / 2));
-  if (!(H & 1) && !(W & 1) && C % 4 == 0 && rows_form_ok(N, H, W, C) && aligned16(d_pooled) && aligned16(d_act) &&
-      (reinterpret_cast<uintptr_t>(pool_idx) & 3) == 0)
+  const bool rows_form = !(H & 1) && !(W & 1) && C % 4 == 0 && rows_form_ok(N, H, W, C) && aligned16(d_pooled) &&
+                         aligned16(d_act) && (reinterpret_cast<uintptr_t>(pool_idx) & 3) == 0;
+  note_kernel(rows_form ? "maxpool_bwd_rows" : C % 4 == 0 ? "maxpool_bwd<4>" : "maxpool_bwd<1>");
+  if (rows_form)
     hipLaunchKernelGGL(maxpool_bwd_rows_kernel, dim3(rows < 16384u ? rows : 16384u), dim3(kThreads), 0, ST(stream),
                        reinterpret_cast<const f32x4*>(d_pooled), reinterpret_cast<const uint32_t*>(pool_idx), rows,
                        static_cast<unsigned>(W / 2), static_cast<unsigned>(C / 4), reinterpret_cast<f32x4*>(d_act));
@@ -1315,6 +1328,7 @@ extern "C" int unetpp_bn_bwd_reduce(const float* d_act, const float* y, const fl
   const long rows = unetpp_bn_bwd_blocks(pixels, C);
   const long blocks = bn_bwd_blocks_for(pixels, C, vec);
   if (blocks < rows) zero_rows(partial + blocks * C * 2, (rows - blocks) * C * 2, ST(stream));
+  note_kernel(vec ? "bn_bwd_reduce<4>" : "bn_bwd_reduce<1>");
   if (vec)
     hipLaunchKernelGGL(bn_bwd_reduce_kernel<4>, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, ST(stream),
                        d_act, y, scale, shift, mean, invstd, pixels * (C / 4), C / 4, partial);
@@ -1328,6 +1342,7 @@ extern "C" int unetpp_bn_bwd_finalize(const float* partial, int64_t n_blocks, in
                                       void* stream) {
   if (!partial || n_blocks < 1 || C < 1 || !dgamma || !dbeta) return UNETPP_EINVAL;
   if ((reinterpret_cast<uintptr_t>(partial) & 7) != 0) return UNETPP_EINVAL;
+  note_kernel(fin_label(n_blocks, "bn_bwd_finalize/256", "bn_bwd_finalize/512", "bn_bwd_finalize/1024"));
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(fin_threads(n_blocks)), 0, ST(stream), partial, n_blocks, C,
                      dgamma, dbeta);
   return launch_status();
@@ -1340,6 +1355,7 @@ extern "C" int unetpp_bn_bwd_apply(const float* d_act, const float* y, const flo
     return UNETPP_EINVAL;
   const bool vec = (C % 4 == 0) && aligned16(d_act) && aligned16(y) && aligned16(dy);
   const float inv_count = 1.0f / static_cast<float>(pixels);
+  note_kernel(vec ? "bn_bwd_apply<4>" : "bn_bwd_apply<1>");
   if (vec) {
     const long items = pixels * (C / 4);
     hipLaunchKernelGGL(bn_bwd_apply_kernel<4>, dim3(grid_for(items)), dim3(kThreads), 0, ST(stream), d_act, y, scale,
@@ -1383,6 +1399,7 @@ extern "C" int unetpp_bn_bwd_reduce_pool(const float* d_act, const float* y, con
   const long img_rows = static_cast<long>(N) * H;
   const long grid = img_rows < rows_buf ? img_rows : rows_buf;
   if (grid < rows_buf) zero_rows(partial + grid * C * 2, (rows_buf - grid) * C * 2, ST(stream));
+  note_kernel("bn_bwd_reduce_pool");
   hipLaunchKernelGGL(bn_bwd_reduce_pool_kernel, dim3(static_cast<unsigned>(grid)), dim3(kThreads), 0, ST(stream),
                      reinterpret_cast<const f32x4*>(d_act), reinterpret_cast<const f32x4*>(y),
                      reinterpret_cast<const f32x4*>(scale), reinterpret_cast<const f32x4*>(shift),
@@ -1406,6 +1423,7 @@ extern "C" int unetpp_bn_bwd_apply_pool(const float* d_act, const float* y, cons
     return UNETPP_EINVAL;
   const long img_rows = static_cast<long>(N) * H;
   const float inv_count = 1.0f / static_cast<float>(img_rows * W);
+  note_kernel("bn_bwd_apply_pool");
   hipLaunchKernelGGL(bn_bwd_apply_pool_kernel, dim3(static_cast<unsigned>(img_rows < 16384 ? img_rows : 16384)),
                      dim3(kThreads), 0, ST(stream), reinterpret_cast<const f32x4*>(d_act),
                      reinterpret_cast<const f32x4*>(y), reinterpret_cast<const f32x4*>(scale),
@@ -1552,6 +1570,7 @@ extern "C" int unetpp_head_bwd(const float* d_out_nchw, const float* out_nchw, c
 
 extern "C" int unetpp_sum_partials(const float* partial, int64_t n_blocks, int64_t len, float* out, void* stream) {
   if (!partial || !out || n_blocks < 1 || len < 1) return UNETPP_EINVAL;
+  // (one form, and no note_kernel: this launch finishes a head's backward, whose label the caller reads afterwards)
   hipLaunchKernelGGL(sum_partials_kernel, dim3(static_cast<unsigned>((len + 15) / 16)), dim3(1024), 0, ST(stream),
                      partial, n_blocks, len, out);
   return launch_status();
@@ -1560,6 +1579,7 @@ extern "C" int unetpp_sum_partials(const float* partial, int64_t n_blocks, int64
 extern "C" int unetpp_bilinear2x_fwd(const float* x, int32_t N, int32_t H, int32_t W, int32_t C, float* y, void* stream) {
   if (!x || !y || N < 1 || H < 1 || W < 1 || C < 1) return UNETPP_EINVAL;
   const long items = static_cast<long>(N) * 4 * H * W * C;
+  note_kernel("bilinear2x_fwd");
   hipLaunchKernelGGL(bilinear2x_fwd_kernel, dim3(grid_for(items)), dim3(kThreads), 0, ST(stream), x, N, H, W, C, y);
   return launch_status();
 }
@@ -1568,6 +1588,7 @@ extern "C" int unetpp_bilinear2x_bwd(const float* dy, int32_t N, int32_t H, int3
                                      int32_t accumulate, void* stream) {
   if (!dy || !dx || N < 1 || H < 1 || W < 1 || C < 1) return UNETPP_EINVAL;
   const long items = static_cast<long>(N) * H * W * C;
+  note_kernel("bilinear2x_bwd");
   hipLaunchKernelGGL(bilinear2x_bwd_kernel, dim3(grid_for(items)), dim3(kThreads), 0, ST(stream), dy, N, H, W, C, dx, accumulate);
   return launch_status();
 }
@@ -1575,6 +1596,7 @@ extern "C" int unetpp_bilinear2x_bwd(const float* dy, int32_t N, int32_t H, int3
 extern "C" int unetpp_nchw_to_nhwc(const float* src, int32_t N, int32_t C, int32_t H, int32_t W, float* dst, void* stream) {
   if (!src || !dst || N < 1 || C < 1 || H < 1 || W < 1) return UNETPP_EINVAL;
   const long items = static_cast<long>(N) * C * H * W;
+  note_kernel("nchw_to_nhwc");
   hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(grid_for(items)), dim3(kThreads), 0, ST(stream), src, N, C,
                      static_cast<long>(H) * W, dst);
   return launch_status();
@@ -1583,6 +1605,7 @@ extern "C" int unetpp_nchw_to_nhwc(const float* src, int32_t N, int32_t C, int32
 extern "C" int unetpp_nhwc_to_nchw(const float* src, int32_t N, int32_t C, int32_t H, int32_t W, float* dst, void* stream) {
   if (!src || !dst || N < 1 || C < 1 || H < 1 || W < 1) return UNETPP_EINVAL;
   const long items = static_cast<long>(N) * C * H * W;
+  note_kernel("nhwc_to_nchw");
   hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3(grid_for(items)), dim3(kThreads), 0, ST(stream), src, N, C,
                      static_cast<long>(H) * W, dst);
   return launch_status();

@@ -561,6 +561,7 @@ extern "C" int unetpp_affine_relu_pool_bf16(const void* y, const float* scale, c
   const int CG = C >> 3;
   if (pooled == nullptr) {
     const long items = static_cast<long>(N) * H * W * CG;
+    note_kernel("affine_relu_bf16");
     hipLaunchKernelGGL(affine_relu_bf16_kernel, dim3(grid_for8(items)), dim3(kThreads), 0, ST(stream),
                        static_cast<const bf16_t*>(y), scale, shift, relu, items, CG, static_cast<bf16_t*>(act));
     return launch_status();
@@ -568,6 +569,7 @@ extern "C" int unetpp_affine_relu_pool_bf16(const void* y, const float* scale, c
   if ((H & 1) || (W & 1) || !pool_idx || !a16(pooled) || (reinterpret_cast<uintptr_t>(pool_idx) & 7)) return UNETPP_EINVAL;
   const long items = static_cast<long>(N) * (H / 2) * (W / 2) * CG;
   if (items >= 0x7fffffffL) return UNETPP_EINVAL;
+  note_kernel("affine_relu_pool_bf16");
   hipLaunchKernelGGL(affine_relu_pool_bf16_kernel, dim3(grid_for8(items)), dim3(kThreads), 0, ST(stream),
                      static_cast<const bf16_t*>(y), scale, shift, relu, N, H, W, CG, static_cast<bf16_t*>(act),
                      static_cast<bf16_t*>(pooled), pool_idx);
@@ -591,6 +593,7 @@ extern "C" int unetpp_bn_bwd_reduce_bf16(const void* d_act, const void* y, const
   if ((d_pooled == nullptr) != (pool_idx == nullptr) || (d_pooled != nullptr && ((H | W) & 1))) return UNETPP_EINVAL;
   const long pixels = static_cast<long>(N) * H * W;
   if (pixels * (C >> 3) >= 0x7fffffffL) return UNETPP_EINVAL;
+  note_kernel(d_pooled != nullptr ? "bn_bwd_reduce_bf16/pool" : "bn_bwd_reduce_bf16");
   hipLaunchKernelGGL(bn_bwd_reduce_bf16_kernel, dim3(static_cast<unsigned>(unetpp_bn_bwd_blocks_bf16(pixels, C))),
                      dim3(kThreads), 0, ST(stream), static_cast<const bf16_t*>(d_act), static_cast<const bf16_t*>(y), scale,
                      shift, mean, invstd, static_cast<const bf16_t*>(d_pooled), pool_idx, pixels * (C >> 3), C >> 3, H, W,
@@ -609,6 +612,7 @@ extern "C" int unetpp_bn_bwd_apply_bf16(const void* d_act, const void* y, const 
   const long pixels = static_cast<long>(N) * H * W;
   const long items = pixels * (C >> 3);
   if (items >= 0x7fffffffL) return UNETPP_EINVAL;
+  note_kernel(d_pooled != nullptr ? "bn_bwd_apply_bf16/pool" : "bn_bwd_apply_bf16");
   hipLaunchKernelGGL(bn_bwd_apply_bf16_kernel, dim3(grid_for8(items)), dim3(kThreads), 0, ST(stream),
                      static_cast<const bf16_t*>(d_act), static_cast<const bf16_t*>(y), scale, shift, mean, invstd, gamma,
                      dgamma, dbeta, static_cast<const bf16_t*>(d_pooled), pool_idx, 1.0f / static_cast<float>(pixels), items,
@@ -735,6 +739,7 @@ extern "C" int unetpp_maxpool_bwd_bf16(const void* d_pooled, const uint8_t* pool
   if (!a16(d_pooled) || !a16(d_act) || (gate && !a16(gate)) || (reinterpret_cast<uintptr_t>(pool_idx) & 7)) return UNETPP_EINVAL;
   const long items = static_cast<long>(N) * H * W * (C >> 3);
   if (items >= 0x7fffffffL) return UNETPP_EINVAL;
+  note_kernel("maxpool_bwd_bf16");
   hipLaunchKernelGGL(maxpool_bwd_bf16_kernel, dim3(grid_for8(items)), dim3(kThreads), 0, ST(stream),
                      static_cast<const bf16_t*>(d_pooled), pool_idx, N, H, W, C >> 3, static_cast<bf16_t*>(d_act),
                      static_cast<const bf16_t*>(gate));
@@ -744,6 +749,7 @@ extern "C" int unetpp_maxpool_bwd_bf16(const void* d_pooled, const uint8_t* pool
 extern "C" int unetpp_bilinear2x_fwd_bf16(const void* x, int32_t N, int32_t H, int32_t W, int32_t C, void* y, void* stream) {
   if (!x || !y || N < 1 || H < 1 || W < 1 || C < 8 || (C & 7) || !a16(x) || !a16(y)) return UNETPP_EINVAL;
   const long items = static_cast<long>(N) * 4 * H * W * (C >> 3);
+  note_kernel("bilinear2x_fwd_bf16");
   hipLaunchKernelGGL(bilinear2x_fwd_bf16_kernel, dim3(grid_for8(items)), dim3(kThreads), 0, ST(stream),
                      static_cast<const bf16_t*>(x), N, H, W, C >> 3, static_cast<bf16_t*>(y));
   return launch_status();
@@ -753,6 +759,7 @@ extern "C" int unetpp_bilinear2x_bwd_bf16(const void* dy, int32_t N, int32_t H, 
                                           int32_t accumulate, const void* gate, void* stream) {
   if (!dy || !dx || N < 1 || H < 1 || W < 1 || C < 8 || (C & 7) || !a16(dy) || !a16(dx) || (gate && !a16(gate))) return UNETPP_EINVAL;
   const long items = static_cast<long>(N) * H * W * (C >> 3);
+  note_kernel("bilinear2x_bwd_bf16");
   hipLaunchKernelGGL(bilinear2x_bwd_bf16_kernel, dim3(grid_for8(items)), dim3(kThreads), 0, ST(stream),
                      static_cast<const bf16_t*>(dy), N, H, W, C >> 3, static_cast<bf16_t*>(dx), accumulate,
                      static_cast<const bf16_t*>(gate));
