@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define UNETPP_ABI_VERSION 11
+#define UNETPP_ABI_VERSION 12
 #define UNETPP_MAX_VIEWS 8
 
 #define UNETPP_OK 0
@@ -120,7 +120,8 @@ typedef struct unetpp_gemm_desc {
 /* weight gradient:  dW[tap][k][n] = sum_p x[p (+) tap, k] * dy[p, n]  (+ db[n] = sum_p dy[p, n]).
  * Replaces the weight/bias gradient of nn.Conv2d 3x3 / 1x1 and nn.ConvTranspose2d 2x2 s2
  * (autograd of models/unet.py:132,140,187,191).  Split over pixel blocks: each of the
- * `n_split` blocks per (k-tile, n-tile) writes one partial slab; unetpp_wgrad_finish sums them. */
+ * `n_split` blocks per (k-tile, n-tile) writes one partial slab; unetpp_wgrad_finish sums them.
+ * unetpp_wgrad_plan chooses n_split and tells how large the slabs are. */
 typedef struct unetpp_wgrad_desc {
   int32_t N, H, W;
   int32_t taps;
@@ -128,9 +129,9 @@ typedef struct unetpp_wgrad_desc {
   int32_t n_dy;
   unetpp_view x[UNETPP_MAX_VIEWS];  /* K = sum c_len */
   unetpp_view dy[UNETPP_MAX_VIEWS]; /* Ncols = sum c_len (several views: the 4 pixel phases of a 2x2 deconv) */
-  int32_t n_split;                  /* partial slabs (<= unetpp_wgrad_max_split) */
+  int32_t n_split;                  /* partial slabs (unetpp_wgrad_plan) */
   int32_t flags;                    /* UNETPP_GEMM_DIRECT: direct summation only (no Winograd) */
-  float* slabs;                    /* [n_split][planes*K + 1][Ncols], planes = unetpp_wgrad_slab_planes(); last row = db */
+  float* slabs;                    /* [n_split][planes*K + 1][Ncols] (unetpp_wgrad_plan: slab_floats); last row = db */
 } unetpp_wgrad_desc;
 
 int unetpp_abi_version(void);
@@ -149,7 +150,8 @@ const char* unetpp_last_kernel_name(void);
  * BF16_DMA_MIN8, BF16_DMA_FORM, BF16_DMA_SMALL, BF16_DMA_STATS, BF16_DMA_POINTWISE, BF16_DMA_SPLIT, BF16_WGRAD_QUAD,
  * WINO_NO_LEAN, WINO_ONE_PER_CU, MEMSET_NODES, BF16_PW_PLAIN, PW_DIRECT (0: fp32 pointwise launches back on the LDS-staged
  * kernels), PW_NT (fp32 pointwise GEMM: 1 / 0 = non-temporal / plain stores whatever the output size),
- * HEAD_WGS_PER_CU (bf16 head backward: at most this many workgroups per CU take tiles, default 4; 0 = the whole grid).  set != 0: the switch takes `value`; set == 0: back to the
+ * HEAD_WGS_PER_CU (bf16 head backward: at most this many workgroups per CU take tiles, default 4; 0 = the whole grid),
+ * SMALL_WGRAD_BLOCKS (unetpp_wgrad_plan: slabs aimed at for a single x view on a 1..4-channel tensor, default 1024).  set != 0: the switch takes `value`; set == 0: back to the
  * dispatcher's built-in default.  The environment variable UNETPP_<name>, if present when the library first looks a
  * switch up, is the initial setting.  Process-wide; results never depend on a switch beyond the summation order of the
  * kernel it selects.  UNETPP_EINVAL for an unknown name. */
@@ -162,14 +164,13 @@ int unetpp_debug_get(const char* name, int64_t* value);
 /* Data-parallel co-scheduling knob (v8).  Every hot kernel is a persistent launch sized to fill all CUs at 2-3 workgroups
  * per CU, so a collective kernel (RCCL all-reduce of a gradient bucket on a side stream, trainer/trainer.py:338's
  * replicas replaced by one process per GPU) only gets waves when a compute kernel ends.  n > 0 makes the persistent
- * grids leave n CUs' worth of workgroups unlaunched (a caller of unetpp_wgrad sizes n_split itself and should aim at
- * CUs - n workgroups, as the Python layer does); 0 (default,
+ * grids leave n CUs' worth of workgroups unlaunched (unetpp_wgrad_plan scales n_split likewise); 0 (default,
  * or the UNETPP_RESERVED_CUS environment variable read at the first call) = use every CU.  Process-wide, takes effect
  * at the next launch; results do not depend on it.  Returns the value now in force (n clamped to [0, CUs - 8]);
  * unetpp_set_reserved_cus(-1) only reads it. */
 int32_t unetpp_set_reserved_cus(int32_t n);
 /* CUs of the current device a persistent grid may fill (physical - reserved, at least 8); *physical (may be NULL) gets
- * the device's CU count.  A caller that sizes unetpp_wgrad's n_split scales its target by usable / physical (v9). */
+ * the device's CU count (v9). */
 int32_t unetpp_usable_cus(int32_t* physical);
 
 /* ---- multi-view pixel GEMM on MFMA (v_mfma_f32_32x32x2_f32 / v_mfma_f32_16x16x4_f32) ------ */
@@ -209,15 +210,27 @@ typedef struct unetpp_pack_job {
 int unetpp_gemm_pack_weight_images(const unetpp_pack_job* jobs_device, int32_t n_jobs, int64_t max_image_floats,
                                    void* stream);
 
-int32_t unetpp_wgrad_max_split(int32_t N, int32_t H, int32_t W);
-/* Planes per slab the kernel chosen for this descriptor writes: `taps` for direct summation, 16 for the Winograd
- * F(2x2,3x3) kernel (3x3, plain 16-byte aligned views, images at least 17 wide, no UNETPP_GEMM_DIRECT in flags): it
- * accumulates transform-domain products and unetpp_wgrad_finish(taps = 16) maps them back to the 9 taps. */
-int32_t unetpp_wgrad_slab_planes(const unetpp_wgrad_desc* d);
-/* (32-channel, 32-column) tile pairs one workgroup of the kernel chosen for this descriptor owns: 1, or 4 for the bf16
- * kernel of layers whose views are all multiples of 64 channels wide (one workgroup per CU).  unetpp_wgrad launches
- * n_split * pairs / this workgroups; the caller sizes n_split with it. */
-int32_t unetpp_wgrad_pairs_per_workgroup(const unetpp_wgrad_desc* d);
+/* What a weight-gradient launch needs settled before it runs (v12).  The library looks at the descriptor once and
+ * decides which of its kernels takes it; n_split, the slab layout and the label all follow from that one decision, and
+ * unetpp_wgrad launches the same kernel for the same descriptor. */
+typedef struct unetpp_wgrad_sizes {
+  int32_t n_split;             /* goes into unetpp_wgrad_desc.n_split */
+  int32_t planes;              /* per slab: `taps` for direct summation, 16 for the Winograd F(2x2,3x3) kernel (it accumulates
+                                  transform-domain products); the `taps` argument of unetpp_wgrad_finish */
+  int32_t pairs_per_workgroup; /* (32-channel, 32-column) tile pairs a workgroup owns: 1, 4 (bf16, every view a multiple of
+                                  64 channels wide) or 8 (fp32 pointwise blocks) */
+  int32_t reserved;
+  int64_t slab_floats;         /* n_split * (planes * K + 1) * Ncols: what d->slabs must hold */
+  const char* kernel;          /* label unetpp_last_kernel_name() reports after unetpp_wgrad(d) (static string) */
+} unetpp_wgrad_sizes;
+/* d->n_split and d->slabs are ignored; everything else, pointers included (their alignment selects kernels), must be
+ * what unetpp_wgrad will get.  target_blocks = workgroups to aim at, <= 0: the library's default (256).  The plan aims
+ * at 1024 slabs for a single x view on a 1..4-channel tensor whatever target_blocks says, scales the target by usable /
+ * physical CUs (unetpp_set_reserved_cus), and never plans more slabs than there are 256-pixel tiles, or 4096.  Touches
+ * no device memory and launches nothing.  UNETPP_EINVAL for a NULL argument or a descriptor unetpp_wgrad would refuse.
+ * Any n_split from 1 to the number of pixel tiles (at most 4096) is valid for unetpp_wgrad; planes and kernel do not
+ * depend on it. */
+int unetpp_wgrad_plan(const unetpp_wgrad_desc* d, int32_t target_blocks, unetpp_wgrad_sizes* out);
 int unetpp_wgrad(const unetpp_wgrad_desc* d, void* stream);
 /* `taps` = planes per slab.  column n = o*n_inner + i:  dw[t*d_t + k*d_k + i*d_n + o*d_o] = sum_s slabs[s][t*K + k][n];
  * db[i] = sum_o sum_s slabs[s][taps*K][o*n_inner + i]   (n_inner = Ncols for a plain convolution) */

@@ -41,7 +41,7 @@ def test_exported_symbols_are_plain_c(built_lib):
     out = subprocess.run(["nm", "-D", "--defined-only", built_lib.LIB_PATH], capture_output=True, text=True).stdout
     exported = {ln.split()[-1] for ln in out.splitlines() if " T " in ln}
     assert set(_declared_functions()) <= exported
-    assert built_lib.lib().unetpp_abi_version() == built_lib.ABI_VERSION == 11
+    assert built_lib.lib().unetpp_abi_version() == built_lib.ABI_VERSION == 12
     assert built_lib.lib().unetpp_build_arch() == b"gfx950"
 
 
@@ -49,13 +49,14 @@ def test_struct_layout_matches_header(built_lib, tmp_path):
     """sizeof/offsetof from a C compile of the header vs the ctypes mirrors."""
     src = tmp_path / "layout.c"
     src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "unetpp_hip.h"\nint main(void){'
-                   'printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(unetpp_view), offsetof(unetpp_view, gate),'
+                   'printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(unetpp_view), offsetof(unetpp_view, gate),'
                    'offsetof(unetpp_view, gate_sum), sizeof(unetpp_gemm_desc), offsetof(unetpp_gemm_desc, out),'
                    'offsetof(unetpp_gemm_desc, weight_image), sizeof(unetpp_wgrad_desc), offsetof(unetpp_wgrad_desc, dy),'
                    'offsetof(unetpp_wgrad_desc, slabs), sizeof(unetpp_weight_src), offsetof(unetpp_weight_src, k_inner),'
                    'sizeof(unetpp_pack_job), offsetof(unetpp_pack_job, image), offsetof(unetpp_pack_job, out_len),'
                    'sizeof(unetpp_bn_fused), offsetof(unetpp_bn_fused, count), offsetof(unetpp_bn_fused, momentum),'
-                   'offsetof(unetpp_gemm_desc, bn));return 0;}')
+                   'offsetof(unetpp_gemm_desc, bn), sizeof(unetpp_wgrad_sizes), offsetof(unetpp_wgrad_sizes, slab_floats),'
+                   'offsetof(unetpp_wgrad_sizes, kernel));return 0;}')
     exe = tmp_path / "layout"
     subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
     got = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
@@ -64,7 +65,8 @@ def test_struct_layout_matches_header(built_lib, tmp_path):
             L.GemmDesc.out.offset, L.GemmDesc.weight_image.offset, ctypes.sizeof(L.WgradDesc), L.WgradDesc.dy.offset,
             L.WgradDesc.slabs.offset, ctypes.sizeof(L.WeightSrc), L.WeightSrc.k_inner.offset, ctypes.sizeof(L.PackJob),
             L.PackJob.image.offset, L.PackJob.out_len.offset, ctypes.sizeof(L.BnFused), L.BnFused.count.offset,
-            L.BnFused.momentum.offset, L.GemmDesc.bn.offset]
+            L.BnFused.momentum.offset, L.GemmDesc.bn.offset, ctypes.sizeof(L.WgradSizes), L.WgradSizes.slab_floats.offset,
+            L.WgradSizes.kernel.offset]
     assert got == want
 
 
@@ -74,17 +76,29 @@ def test_argument_validation_without_gpu(built_lib):
     assert lib.unetpp_gemm_pixel_blocks(32, 256, 256) == 32 * 32 * 8
     assert lib.unetpp_gemm_pixel_blocks(0, 256, 256) == 0
     assert lib.unetpp_gemm_stats_rows(32, 256, 256) == 32 * 32 * 8 and lib.unetpp_gemm_stats_rows(1, 64, 64) == 2048
-    assert lib.unetpp_wgrad_max_split(1, 8, 8) == 1
     wd = built_lib.WgradDesc()   # which kernel a weight-gradient descriptor gets is decided on the host
-    wd.N, wd.H, wd.W, wd.taps, wd.n_x, wd.n_dy = 2, 32, 32, 9, 2, 1
-    for v, c in ((wd.x[0], 64), (wd.x[1], 128), (wd.dy[0], 64)):
-        v.C = v.c_len = c
-    assert lib.unetpp_wgrad_pairs_per_workgroup(ctypes.byref(wd)) == 1     # fp32: one tile pair per workgroup
+    plan = built_lib.WgradSizes()
+
+    def fill(n, h, w, views):    # (the plan validates the views as the launch does: a pointer and the tensor's size)
+        wd.N, wd.H, wd.W = n, h, w
+        for v, c in views:
+            v.ptr, v.C, v.c_len, v.Hs, v.Ws, v.sy, v.sx = 0x1000, c, c, h, w, 1, 1
+
+    wd.taps, wd.n_x, wd.n_dy = 9, 1, 1
+    fill(1, 8, 8, ((wd.x[0], 8), (wd.dy[0], 8)))
+    assert lib.unetpp_wgrad_plan(ctypes.byref(wd), 4096, ctypes.byref(plan)) == 0 and plan.n_split == 1   # one pixel tile
+    wd.n_x = 2
+    fill(2, 32, 32, ((wd.x[0], 64), (wd.x[1], 128), (wd.dy[0], 64)))
+    assert lib.unetpp_wgrad_plan(ctypes.byref(wd), 0, ctypes.byref(plan)) == 0
+    assert plan.pairs_per_workgroup == 1     # fp32: one tile pair per workgroup
     wd.flags = built_lib.GEMM_BF16
-    assert lib.unetpp_wgrad_pairs_per_workgroup(ctypes.byref(wd)) == 4     # bf16, every view a multiple of 64 wide
+    assert lib.unetpp_wgrad_plan(ctypes.byref(wd), 0, ctypes.byref(plan)) == 0
+    assert plan.pairs_per_workgroup == 4     # bf16, every view a multiple of 64 wide
     wd.x[1].C = wd.x[1].c_len = 96
-    assert lib.unetpp_wgrad_pairs_per_workgroup(ctypes.byref(wd)) == 1
-    assert lib.unetpp_wgrad_pairs_per_workgroup(None) == 0
+    assert lib.unetpp_wgrad_plan(ctypes.byref(wd), 0, ctypes.byref(plan)) == 0
+    assert plan.pairs_per_workgroup == 1
+    assert lib.unetpp_wgrad_plan(None, 0, ctypes.byref(plan)) == -1
+    assert lib.unetpp_wgrad_plan(ctypes.byref(wd), 0, None) == -1
     assert lib.unetpp_head_bwd_blocks(100) == 2
     assert lib.unetpp_bn_bwd_blocks(32 * 256 * 256, 32) % 8 == 0
     d = built_lib.GemmDesc()

@@ -467,8 +467,8 @@ def test_pointwise_wgrad_direct_kernel(dev, case):
         dy = torch.randn(b, co, h, w, generator=g, dtype=torch.float64)
         F.conv2d(torch.cat(xs, 1), wt, bias).backward(dy)
         dw, db = torch.empty(co, sum(ci), 1, 1, device=dev), torch.empty(co, device=dev)
-        ops.wgrad(b, h, w, 1, [V(nhwc(x.float())) for x in xs], [V(nhwc(dy.float()))], dw, (0, 1, sum(ci), 0), db,
-                  target_blocks=target_blocks)
+        plan = ops.wgrad(b, h, w, 1, [V(nhwc(x.float())) for x in xs], [V(nhwc(dy.float()))], dw, (0, 1, sum(ci), 0), db,
+                         target_blocks=target_blocks)
         k, n = sum(ci), co
     else:
         x = torch.randn(b, ci, h, w, generator=g, dtype=torch.float64)
@@ -477,10 +477,11 @@ def test_pointwise_wgrad_direct_kernel(dev, case):
         dy = torch.randn(b, co, 2 * h, 2 * w, generator=g, dtype=torch.float64)
         F.conv_transpose2d(x, wt, bias, stride=2).backward(dy)
         dw, db = torch.empty(ci, co, 2, 2, device=dev), torch.empty(co, device=dev)
-        ops.wgrad(b, h, w, 1, [V(nhwc(x.float()))], engine._phase_views(nhwc(dy.float())), dw, (0, 4 * co, 4, 1), db,
-                  n_inner=co, target_blocks=target_blocks)
+        plan = ops.wgrad(b, h, w, 1, [V(nhwc(x.float()))], engine._phase_views(nhwc(dy.float())), dw, (0, 4 * co, 4, 1), db,
+                         n_inner=co, target_blocks=target_blocks)
         k, n = ci, 4 * co
     name = _lib.lib().unetpp_last_kernel_name().decode()
+    assert plan.kernel.decode() == name   # the plan names the kernel that ran
     assert name == ("wgrad_pw_kernel" if (k % 64 == 0 and n % 128 == 0) else "wgrad_dma_kernel<1>"), name
     assert rel_err(dw.cpu(), wt.grad.float()) < TOL
     assert rel_err(db.cpu(), bias.grad.float()) < TOL
@@ -499,7 +500,7 @@ def test_pointwise_wgrad_direct_kernel(dev, case):
                                    (1, 8, 8, [40, 5], 33), (3, 64, 64, [16], 16), (2, 32, 64, [1], 32),
                                    (1, 24, 40, [3], 8)])
 def test_conv3x3_wgrad(dev, shape):
-    from unet_nested4tiny_objects_keypoints_amd import ops
+    from unet_nested4tiny_objects_keypoints_amd import _lib, ops
     from unet_nested4tiny_objects_keypoints_amd.ops import V
     b, h, w, cins, co = shape
     g = torch.Generator().manual_seed(5)
@@ -513,8 +514,10 @@ def test_conv3x3_wgrad(dev, shape):
     db = torch.empty(co, device=dev)
     ci = sum(cins)
     for target_blocks in (1024, 3):  # many slabs / few slabs with a long per-block pixel loop
-        ops.wgrad(b, h, w, 9, [V(nhwc(s.float())) for s in srcs], [V(nhwc(dy.float()), gate=nhwc(act.float()))],
-                  dw, (1, 9, ci * 9, 0), db, target_blocks=target_blocks)
+        plan = ops.wgrad(b, h, w, 9, [V(nhwc(s.float())) for s in srcs], [V(nhwc(dy.float()), gate=nhwc(act.float()))],
+                         dw, (1, 9, ci * 9, 0), db, target_blocks=target_blocks)
+        # a ReLU gate on dy: the generic kernel, and the plan names the kernel that ran
+        assert plan.kernel.decode() == _lib.lib().unetpp_last_kernel_name().decode() == "wgrad_kernel<9>"
         assert rel_err(dw.cpu(), wt.grad.float()) < TOL
         assert rel_err(db.cpu(), bias.grad.float()) < TOL
 
@@ -540,9 +543,10 @@ def test_conv3x3_wgrad_plain_views(dev, shape, direct):
     for target_blocks in (1024, 3):
         dw = torch.full((co, ci, 3, 3), float("nan"), device=dev)
         db = torch.full((co,), float("nan"), device=dev)
-        ops.wgrad(b, h, w, 9, [V(nhwc(s.float())) for s in srcs], [V(nhwc(dy.float()))], dw, (1, 9, ci * 9, 0), db,
-                  target_blocks=target_blocks, direct=direct)
+        plan = ops.wgrad(b, h, w, 9, [V(nhwc(s.float())) for s in srcs], [V(nhwc(dy.float()))], dw, (1, 9, ci * 9, 0), db,
+                         target_blocks=target_blocks, direct=direct)
         name = _lib.lib().unetpp_last_kernel_name().decode()
+        assert plan.kernel.decode() == name and plan.planes == (16 if name == "wgrad_wino_kernel" else 9)
         assert name == ("wgrad_wino_kernel" if (not direct and w > 16) else "wgrad_dma_kernel<9>")
         assert rel_err(dw.cpu(), wt.grad.float()) < TOL
         assert rel_err(db.cpu(), bias.grad.float()) < TOL
@@ -568,9 +572,10 @@ def test_conv3x3_wgrad_folded_batchnorm_view(dev, shape, direct):
     F.conv2d(xin, wt, bias, padding=1).backward(dy)
     dw = torch.full((co, ci, 3, 3), float("nan"), device=dev)
     db = torch.full((co,), float("nan"), device=dev)
-    ops.wgrad(b, h, w, 9, [V(nhwc(y1.float()), scale=scale.float().cuda(), shift=shift.float().cuda(), relu=True)],
-              [V(nhwc(dy.float()))], dw, (1, 9, ci * 9, 0), db, direct=direct)
+    plan = ops.wgrad(b, h, w, 9, [V(nhwc(y1.float()), scale=scale.float().cuda(), shift=shift.float().cuda(), relu=True)],
+                     [V(nhwc(dy.float()))], dw, (1, 9, ci * 9, 0), db, direct=direct)
     name = _lib.lib().unetpp_last_kernel_name().decode()
+    assert plan.kernel.decode() == name
     assert name == ("wgrad_fast_kernel<9>" if direct else "wgrad_wino_kernel")
     assert rel_err(dw.cpu(), wt.grad.float()) < TOL
     assert rel_err(db.cpu(), bias.grad.float()) < TOL
@@ -579,7 +584,7 @@ def test_conv3x3_wgrad_folded_batchnorm_view(dev, shape, direct):
 @pytest.mark.parametrize("shape", [(2, 32, 64, 1, 32), (1, 24, 40, 3, 8), (3, 16, 16, 4, 128), (2, 8, 8, 2, 4)])
 def test_first_layer_wgrad(dev, shape):
     """The 1..4-channel first convolution's dedicated weight-gradient kernel (plain dy, no gate)."""
-    from unet_nested4tiny_objects_keypoints_amd import ops
+    from unet_nested4tiny_objects_keypoints_amd import _lib, ops
     from unet_nested4tiny_objects_keypoints_amd.ops import V
     b, h, w, ci, co = shape
     g = torch.Generator().manual_seed(15)
@@ -590,7 +595,8 @@ def test_first_layer_wgrad(dev, shape):
     F.conv2d(x, wt, bias, padding=1).backward(dy)
     dw = torch.empty(co, ci, 3, 3, device=dev)
     db = torch.empty(co, device=dev)
-    ops.wgrad(b, h, w, 9, [V(nhwc(x.float()))], [V(nhwc(dy.float()))], dw, (1, 9, ci * 9, 0), db)
+    plan = ops.wgrad(b, h, w, 9, [V(nhwc(x.float()))], [V(nhwc(dy.float()))], dw, (1, 9, ci * 9, 0), db)
+    assert plan.kernel.decode() == _lib.lib().unetpp_last_kernel_name().decode() == "small_cin_wgrad_kernel"
     assert rel_err(dw.cpu(), wt.grad.float()) < TOL
     assert rel_err(db.cpu(), bias.grad.float()) < TOL
 

@@ -452,6 +452,21 @@ WGRAD_CASES = [
     ("wgrad-bf16", "wgrad_bf16_kernel<9>", (2, 32, 32, 32, 32), "bf16"),
     ("wgrad-bf16-quad", "wgrad_bf16_quad_kernel<9>", (2, 32, 64, 64, 64), "bf16"),
 ]
+# case -> (pairs_per_workgroup, max_split) as commit 83ca35a's unetpp_wgrad_pairs_per_workgroup / unetpp_wgrad_max_split
+# answered for the descriptors of WGRAD_CASES (recorded on the CPU from that commit's library)
+WGRAD_RECORDED = {"wgrad-wino": (1, 16), "wgrad-dma9": (1, 16), "wgrad-fast9": (1, 8), "wgrad-pw": (8, 4), "wgrad-dma1": (1, 1),
+                  "wgrad-bf16": (1, 8), "wgrad-bf16-quad": (4, 16)}
+
+
+def split_before_the_plan(target, pairs, pairs_per_workgroup, max_split, usable, physical, bf16, one_narrow_x=False):
+    """n_split as ops.wgrad of commit 83ca35a computed it in Python, rule for rule"""
+    if one_narrow_x:
+        target = 1024
+    if 0 < usable < physical:
+        target = max(8, target * usable // physical)
+    if bf16 and target == 256 and pairs_per_workgroup == 1:
+        target = 512
+    return max(1, min(max_split, target // max(1, pairs // max(1, pairs_per_workgroup))))
 
 
 @pytest.mark.parametrize("case,kernel,spec,form", WGRAD_CASES, ids=[c[0] for c in WGRAD_CASES])
@@ -486,15 +501,20 @@ def test_wgrad_default_split_at_reduced_grids(dev, case, kernel, spec, form):
             dw = torch.full(tuple(wt.shape), float("nan"), device=dev)
             db = torch.full((co,), float("nan"), device=dev)
             if form == "deconv":
-                ops.wgrad(b, h, w, 1, [V(nhwc(x).to(dev))], engine._phase_views(nhwc(dy).to(dev)), dw, (0, 4 * co, 4, 1), db,
-                          n_inner=co)
+                plan = ops.wgrad(b, h, w, 1, [V(nhwc(x).to(dev))], engine._phase_views(nhwc(dy).to(dev)), dw, (0, 4 * co, 4, 1),
+                                 db, n_inner=co)
             elif form == "bf16":
-                ops.wgrad(b, h, w, 9, [V(nhwc(x).to(BF).to(dev))], [V(nhwc(dy).to(BF).to(dev))], dw, (1, 9, ci * 9, 0), db)
+                plan = ops.wgrad(b, h, w, 9, [V(nhwc(x).to(BF).to(dev))], [V(nhwc(dy).to(BF).to(dev))], dw, (1, 9, ci * 9, 0), db)
             else:
                 xv = V(nhwc(x).to(dev)) if scale is None else V(nhwc(x).to(dev), scale=scale.to(dev), shift=shift.to(dev), relu=True)
-                ops.wgrad(b, h, w, 9, [xv], [V(nhwc(dy).to(dev))], dw, (1, 9, ci * 9, 0), db, direct=form != "plain")
+                plan = ops.wgrad(b, h, w, 9, [xv], [V(nhwc(dy).to(dev))], dw, (1, 9, ci * 9, 0), db, direct=form != "plain")
             torch.cuda.synchronize()
             assert last_kernel() == kernel, (case, u.cus, last_kernel())
+            assert plan.kernel.decode() == last_kernel(), (case, u.cus, plan.kernel)   # the plan names the kernel that ran
+            pairs = -(-ci // 32) * -(-co // 32) * (4 if form == "deconv" else 1)
+            want_split = split_before_the_plan(256, pairs, *WGRAD_RECORDED[case], u.cus, u.physical, form == "bf16")
+            assert plan.n_split == want_split, (case, u.cus, plan.n_split, want_split)
+            assert plan.pairs_per_workgroup == WGRAD_RECORDED[case][0]
             if u.cus < u.physical:
                 SEEN.add(kernel)
             r1, r2 = rel_err(dw.cpu(), wt.grad), rel_err(db.cpu(), bias.grad)

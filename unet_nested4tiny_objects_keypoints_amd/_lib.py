@@ -19,7 +19,7 @@ SOURCES = ("gemm_pix.hip", "gemm_fast.hip", "gemm_pw.hip", "gemm_pw_bf16.hip", "
 HEADERS = ("common.h", "gemm_units.h", "wgrad_reduce.h", "lds_asm.h", "bf16_common.h", "dropout.h", "bn_fused.h",
            "wino_experiments.h", "dma_experiments.h")
 MAX_VIEWS = 8
-ABI_VERSION = 11
+ABI_VERSION = 12
 # packed-f32 VALU (SLP-vectorised add pairs) costs issue slots beside MFMAs: keep the Winograd transforms scalar
 EXTRA_FLAGS = {"gemm_wino.hip": ("-fno-slp-vectorize",), "wgrad_wino.hip": ("-fno-slp-vectorize",)}
 GEMM_DIRECT = 1  # unetpp_gemm_desc.flags: direct summation only (no Winograd)
@@ -109,6 +109,15 @@ class WgradDesc(C.Structure):
     ]
 
 
+class WgradSizes(C.Structure):
+    """mirror of struct unetpp_wgrad_sizes"""
+    _fields_ = [
+        ("n_split", C.c_int32), ("planes", C.c_int32), ("pairs_per_workgroup", C.c_int32), ("reserved", C.c_int32),
+        ("slab_floats", C.c_int64),
+        ("kernel", C.c_char_p),
+    ]
+
+
 class OptimSegment(C.Structure):
     """mirror of struct unetpp_optim_segment"""
     _fields_ = [
@@ -141,9 +150,7 @@ SIGNATURES = {
     "unetpp_gemm_pack_weight_image": (C.c_int, [C.POINTER(GemmDesc), _P, _P]),
     "unetpp_gemm_pack_weight_image_from": (C.c_int, [C.POINTER(GemmDesc), C.POINTER(WeightSrc), _P, _P]),
     "unetpp_gemm_pack_weight_images": (C.c_int, [_P, _I32, _I64, _P]),
-    "unetpp_wgrad_max_split": (_I32, [_I32, _I32, _I32]),
-    "unetpp_wgrad_slab_planes": (_I32, [C.POINTER(WgradDesc)]),
-    "unetpp_wgrad_pairs_per_workgroup": (_I32, [C.POINTER(WgradDesc)]),
+    "unetpp_wgrad_plan": (C.c_int, [C.POINTER(WgradDesc), _I32, C.POINTER(WgradSizes)]),
     "unetpp_wgrad": (C.c_int, [C.POINTER(WgradDesc), _P]),
     "unetpp_wgrad_finish": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _P, _I64, _I64, _I64, _I64, _P, _P]),
     "unetpp_pack_weight": (C.c_int, [_P, _P, _I32, _I32, _I32, _I64, _I64, _I64, _I64, _I64, _I64, _I32, _P]),

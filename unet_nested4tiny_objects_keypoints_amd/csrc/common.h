@@ -159,6 +159,7 @@ enum Opt {
   OPT_PW_DIRECT,           // 0: fp32 pointwise GEMMs back on gemm_fast_kernel<1> (tests compare the two kernels)
   OPT_PW_NT,               // fp32 pointwise GEMM: 1 / 0 = non-temporal / plain stores whatever the output size
   OPT_HEAD_WGS_PER_CU,     // bf16 head backward: at most this many workgroups per CU take tiles (default 4; 0 = every workgroup of the grid, as until round 6)
+  OPT_SMALL_WGRAD_BLOCKS,  // weight gradient: slabs aimed at when the single x view's tensor has 1..4 channels (default 1024)
   OPT_COUNT
 };
 bool opt_is_set(Opt o);
@@ -180,25 +181,46 @@ int launch_gemm_bf16(const unetpp_gemm_desc* d, hipStream_t st);
 // gemm_bf16_dma.hip: the same GEMM with both operands staged by LDS-DMA (plain input views, 32-channel slices); returns 1
 // when the descriptor is not one it takes (same weight image as gemm_bf16.hip)
 int launch_gemm_bf16_dma(const unetpp_gemm_desc* d, hipStream_t st);
-// wgrad_bf16.hip: bf16-storage weight gradient (UNETPP_GEMM_BF16); UNETPP_EINVAL when the views do not fit
-int launch_wgrad_bf16(const unetpp_wgrad_desc* d, int Ktot, int Ncols, int n_tiles_cols, int k_tiles, hipStream_t st);
-bool wgrad_bf16_quads(const unetpp_wgrad_desc* d);  // the bf16 kernel will give a workgroup 2 x 2 (channel, column) tile pairs
-// wgrad_fast.hip: 8-wave double-buffered kernel for plain aligned views; returns 1 when it does not apply
-int launch_wgrad_fast(const unetpp_wgrad_desc* d, int Ktot, int Ncols, int n_tiles_cols, int k_tiles, hipStream_t st);
-// wgrad_dma.hip: LDS-DMA staged kernel for views without load transforms; returns 1 when it does not apply
-int launch_wgrad_dma(const unetpp_wgrad_desc* d, int Ktot, int Ncols, int n_tiles_cols, int k_tiles, hipStream_t st);
-// wgrad_pw.hip: pointwise fp32 weight gradient with both operands loaded straight into the MFMA operand registers (64-channel
-// x 128-column blocks of dW per wave); launch returns 1 when it does not apply, wgrad_pw_pairs 0
-int wgrad_pw_pairs(const unetpp_wgrad_desc* d);
+// ---- weight gradient: wgrad_select (wgrad.hip) decides ONCE, from the descriptor alone, which kernel takes it and what
+// follows from that; unetpp_wgrad_plan sizes n_split and the slabs from it, unetpp_wgrad launches what it says.
+enum WgradKernel {  // in the order of precedence
+  WGRAD_FIRST_LAYER, WGRAD_BF16_QUAD, WGRAD_BF16_PAIR, WGRAD_PW, WGRAD_WINO, WGRAD_DMA, WGRAD_FAST, WGRAD_GENERIC
+};
+struct WgradSel {
+  WgradKernel kernel;
+  const char* label;        // what unetpp_last_kernel_name() reports after the launch
+  int planes;               // per slab: taps, or 16 (Winograd)
+  int pairs_per_workgroup;  // (32-channel, 32-column) tile pairs a workgroup owns: 1, 4 (bf16 quad) or 8 (pointwise)
+  int max_split;            // n_split may be 1 .. max_split
+  int Ktot, Ncols;          // channels of all x views, columns of all dy views
+  int k_tiles, n_tiles_cols;  // 32-wide tiles of those, summed per view
+};
+int wgrad_select(const unetpp_wgrad_desc* d, WgradSel& s);  // UNETPP_OK or UNETPP_EINVAL; ignores d->n_split, d->slabs
+// Each kernel file exports a predicate -- EVERY reason its kernel cannot take a descriptor that passed wgrad_select's
+// argument checks -- and a launcher that launches.  The generic kernel (wgrad.hip) takes what is left.
+// first_layer.hip: VALU kernel of the 1..4-channel first 3x3 convolution
+bool small_cin_wgrad_applies(const unetpp_wgrad_desc* d);
+int launch_small_cin_wgrad(const unetpp_wgrad_desc* d, hipStream_t st);
+// wgrad_bf16.hip: bf16 storage (UNETPP_GEMM_BF16) has these two kernels only; wgrad_bf16_views_ok false = UNETPP_EINVAL
+bool wgrad_bf16_views_ok(const unetpp_wgrad_desc* d);
+bool wgrad_bf16_quads(const unetpp_wgrad_desc* d);  // a workgroup owns 2 x 2 tile pairs (every view a multiple of 64 wide)
+int launch_wgrad_bf16(const unetpp_wgrad_desc* d, const WgradSel& s, hipStream_t st);
+// wgrad_pw.hip: pointwise fp32, both operands loaded straight into the MFMA operand registers (64-channel x 128-column
+// blocks of dW per workgroup)
+bool wgrad_pw_applies(const unetpp_wgrad_desc* d);
 int launch_wgrad_pw(const unetpp_wgrad_desc* d, hipStream_t st);
-// wgrad_wino.hip: Winograd F(2x2,3x3) weight gradient (16 transform-domain planes per slab); launch returns 1 when
-// it does not apply
+// wgrad_wino.hip: Winograd F(2x2,3x3) (16 transform-domain planes per slab) and the finish that maps them back
 bool wgrad_wino_applies(const unetpp_wgrad_desc* d);
-int launch_wgrad_wino(const unetpp_wgrad_desc* d, int Ktot, int Ncols, int n_tiles_cols, int k_tiles, hipStream_t st);
+int launch_wgrad_wino(const unetpp_wgrad_desc* d, const WgradSel& s, hipStream_t st);
 int launch_wgrad_finish_wino(const float* slabs, int n_split, int K, int Ncols, float* dw, long d_t, long d_k, long d_n,
                              float* db, hipStream_t st);
-// first_layer.hip: VALU kernels for the 1..4-channel first convolution; return 1 when they do not apply
+// wgrad_dma.hip: LDS-DMA staged direct sum for views without load transforms
+bool wgrad_dma_applies(const unetpp_wgrad_desc* d);
+int launch_wgrad_dma(const unetpp_wgrad_desc* d, const WgradSel& s, hipStream_t st);
+// wgrad_fast.hip: 8-wave double-buffered direct sum for aligned views (x may carry the folded BatchNorm)
+bool wgrad_fast_applies(const unetpp_wgrad_desc* d);
+int launch_wgrad_fast(const unetpp_wgrad_desc* d, const WgradSel& s, hipStream_t st);
+// first_layer.hip: VALU kernel for the forward of the 1..4-channel first convolution; returns 1 when it does not apply
 int launch_small_cin_fwd(const unetpp_gemm_desc* d, hipStream_t st, long* bn_rows);
-int launch_small_cin_wgrad(const unetpp_wgrad_desc* d, hipStream_t st);
 
 }  // namespace unetpp

@@ -419,15 +419,18 @@ int launch_small_cin_fwd(const unetpp_gemm_desc* d, hipStream_t st, long* bn_row
   return launch_status();
 }
 
-// weight gradient of the same layer.  Returns 1 when the descriptor does not fit this path.
+// weight gradient of the same layer: 3x3, one plain x view that is its whole 1..4-channel tensor, one plain dy view
+bool small_cin_wgrad_applies(const unetpp_wgrad_desc* d) {
+  if (d->taps != 9 || d->n_x != 1 || d->n_dy != 1) return false;
+  const unetpp_view& DY = d->dy[0];
+  return small_shape_ok(d->x[0], DY, d->H, d->W) && DY.gate == nullptr && DY.scale == nullptr && !DY.relu;
+}
+
 int launch_small_cin_wgrad(const unetpp_wgrad_desc* d, hipStream_t st) {
-  if (d->taps != 9 || d->n_x != 1 || d->n_dy != 1) return 1;
   const unetpp_view& X = d->x[0];
   const unetpp_view& DY = d->dy[0];
-  if (!small_shape_ok(X, DY, d->H, d->W) || DY.gate != nullptr || DY.scale != nullptr || DY.relu) return 1;
   SmallArgs a = {};
   fill_geom(a, d->N, d->H, d->W);
-  if (d->n_split < 1 || d->n_split > a.n_patches) return 1;
   const bool bf = (d->flags & UNETPP_GEMM_BF16) != 0;
   a.x = X.ptr;
   a.dy = bf ? reinterpret_cast<const float*>(reinterpret_cast<const bf16_t*>(DY.ptr) + DY.c_off) : DY.ptr + DY.c_off;
@@ -448,7 +451,6 @@ int launch_small_cin_wgrad(const unetpp_wgrad_desc* d, hipStream_t st) {
     UNETPP_SMALL_WGRAD(false)
   }
 #undef UNETPP_SMALL_WGRAD
-  note_kernel("small_cin_wgrad_kernel");
   return launch_status();
 }
 

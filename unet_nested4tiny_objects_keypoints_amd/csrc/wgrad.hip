@@ -323,82 +323,133 @@ __global__ __launch_bounds__(256) void copy_jobs_kernel(const unetpp_copy_job* _
 
 using namespace unetpp;
 
-extern "C" int32_t unetpp_wgrad_max_split(int32_t N, int32_t H, int32_t W) {
-  if (N <= 0 || H <= 0 || W <= 0) return 0;
-  const TileGeom g = tile_geom(H, W);
-  const int64_t t = static_cast<int64_t>(N) * g.tiles_y * g.tiles_x;
-  return static_cast<int32_t>(t > 4096 ? 4096 : t);
-}
-
-extern "C" int32_t unetpp_wgrad_slab_planes(const unetpp_wgrad_desc* d) {
-  if (d == nullptr) return 0;
-  // the 1..4-channel first layer keeps its own kernel (tap slabs) whatever the flags say
-  const bool small = d->taps == 9 && d->n_x == 1 && d->x[0].c_len <= 4;
-  if (d->flags & UNETPP_GEMM_BF16) return d->taps;  // bf16 storage: direct summation only
-  return (!small && wgrad_wino_applies(d)) ? 16 : d->taps;
-}
-
-extern "C" int32_t unetpp_wgrad_pairs_per_workgroup(const unetpp_wgrad_desc* d) {
-  if (d == nullptr) return 0;
-  const int pw = wgrad_pw_pairs(d);
-  if (pw > 0) return pw;
-  return wgrad_bf16_quads(d) ? 4 : 1;
-}
-
-extern "C" int unetpp_wgrad(const unetpp_wgrad_desc* d, void* stream) {
+// The one place that decides which kernel takes a weight-gradient descriptor.  Precedence: first layer, bf16 (quad,
+// pair), pointwise, Winograd, LDS-DMA, fast, generic.
+int unetpp::wgrad_select(const unetpp_wgrad_desc* d, WgradSel& s) {
   if (d == nullptr || d->N <= 0 || d->H <= 0 || d->W <= 0) return UNETPP_EINVAL;
   if (d->taps != 9 && d->taps != 1) return UNETPP_EINVAL;
-  if (d->n_x < 1 || d->n_x > UNETPP_MAX_VIEWS || d->slabs == nullptr) return UNETPP_EINVAL;
-  if (d->n_dy < 1 || d->n_dy > UNETPP_MAX_VIEWS) return UNETPP_EINVAL;
-  WgradArgs a;
-  a.d = *d;
-  a.Ktot = 0;
-  int k_tiles = 0;
+  if (d->n_x < 1 || d->n_x > UNETPP_MAX_VIEWS || d->n_dy < 1 || d->n_dy > UNETPP_MAX_VIEWS) return UNETPP_EINVAL;
+  s.Ktot = s.k_tiles = 0;
   for (int i = 0; i < d->n_x; ++i) {
     if (!view_ok(d->x[i]) || !view_covers(d->x[i], d->H, d->W)) return UNETPP_EINVAL;
-    a.Ktot += d->x[i].c_len;
-    k_tiles += (d->x[i].c_len + 31) / 32;
+    s.Ktot += d->x[i].c_len;
+    s.k_tiles += (d->x[i].c_len + 31) / 32;
   }
-  a.Ncols = 0;
-  a.n_tiles_cols = 0;
+  s.Ncols = s.n_tiles_cols = 0;
   for (int i = 0; i < d->n_dy; ++i) {
     if (!view_ok(d->dy[i]) || !view_covers(d->dy[i], d->H, d->W)) return UNETPP_EINVAL;
-    a.Ncols += d->dy[i].c_len;
-    a.n_tiles_cols += (d->dy[i].c_len + 31) / 32;
+    s.Ncols += d->dy[i].c_len;
+    s.n_tiles_cols += (d->dy[i].c_len + 31) / 32;
   }
+  if (static_cast<long>(s.k_tiles) * s.n_tiles_cols > 65535) return UNETPP_EINVAL;  // grid.y
+  const TileGeom g = tile_geom(d->H, d->W);
+  const long n_pix_tiles = static_cast<long>(d->N) * g.tiles_y * g.tiles_x;
+  s.max_split = static_cast<int>(n_pix_tiles > 4096 ? 4096 : n_pix_tiles);  // every slab gets at least one pixel tile
+  const bool t9 = d->taps == 9;
+  s.planes = d->taps;
+  s.pairs_per_workgroup = 1;
+  if (small_cin_wgrad_applies(d)) {
+    s.kernel = WGRAD_FIRST_LAYER;
+    s.label = "small_cin_wgrad_kernel";
+  } else if (d->flags & UNETPP_GEMM_BF16) {  // bf16 storage: direct summation only
+    if (!wgrad_bf16_views_ok(d)) return UNETPP_EINVAL;
+    if (wgrad_bf16_quads(d)) {
+      s.kernel = WGRAD_BF16_QUAD;
+      s.label = t9 ? "wgrad_bf16_quad_kernel<9>" : "wgrad_bf16_quad_kernel<1>";
+      s.pairs_per_workgroup = 4;
+    } else {
+      s.kernel = WGRAD_BF16_PAIR;
+      s.label = t9 ? "wgrad_bf16_kernel<9>" : "wgrad_bf16_kernel<1>";
+    }
+  } else if (wgrad_pw_applies(d)) {
+    s.kernel = WGRAD_PW;
+    s.label = "wgrad_pw_kernel";
+    s.pairs_per_workgroup = 8;  // one 64 x 128 block
+  } else if (wgrad_wino_applies(d)) {
+    s.kernel = WGRAD_WINO;
+    s.label = "wgrad_wino_kernel";
+    s.planes = 16;
+  } else if (wgrad_dma_applies(d)) {
+    s.kernel = WGRAD_DMA;
+    s.label = t9 ? "wgrad_dma_kernel<9>" : "wgrad_dma_kernel<1>";
+  } else if (wgrad_fast_applies(d)) {
+    s.kernel = WGRAD_FAST;
+    s.label = t9 ? "wgrad_fast_kernel<9>" : "wgrad_fast_kernel<1>";
+  } else {
+    s.kernel = WGRAD_GENERIC;
+    s.label = t9 ? "wgrad_kernel<9>" : "wgrad_kernel<1>";
+  }
+  return UNETPP_OK;
+}
+
+namespace {
+int launch_wgrad_generic(const unetpp_wgrad_desc* d, const WgradSel& s, hipStream_t st) {
+  WgradArgs a;
+  a.d = *d;
+  a.Ktot = s.Ktot;
+  a.Ncols = s.Ncols;
+  a.n_tiles_cols = s.n_tiles_cols;
   const TileGeom g = tile_geom(d->H, d->W);
   a.log2tw = g.log2tw;
   a.tiles_x = g.tiles_x;
   a.tiles_y = g.tiles_y;
   a.n_pix_tiles = static_cast<long>(d->N) * g.tiles_y * g.tiles_x;
-  if (d->n_split < 1 || d->n_split > a.n_pix_tiles || d->n_split > 4096) return UNETPP_EINVAL;
-  const long pairs = static_cast<long>(k_tiles) * a.n_tiles_cols;
-  if (pairs > 65535) return UNETPP_EINVAL;
-  const dim3 grid(static_cast<unsigned>(d->n_split), static_cast<unsigned>(pairs));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int small = launch_small_cin_wgrad(d, st);  // 1..4-channel first layer
-  if (small != 1) return small;
-  if (d->flags & UNETPP_GEMM_BF16) return launch_wgrad_bf16(d, a.Ktot, a.Ncols, a.n_tiles_cols, k_tiles, st);
-  {
-    const int pw = launch_wgrad_pw(d, st);  // plain pointwise launches in 64 x 128 blocks: operands straight into registers
-    if (pw != 1) return pw;
-  }
-  {
-    const int wino = launch_wgrad_wino(d, a.Ktot, a.Ncols, a.n_tiles_cols, k_tiles, st);  // 16-plane slabs
-    if (wino != 1) return wino;
-  }
-  {
-    const int dma = launch_wgrad_dma(d, a.Ktot, a.Ncols, a.n_tiles_cols, k_tiles, st);  // plain views, direct sum
-    if (dma != 1) return dma;
-  }
-  const int fast = launch_wgrad_fast(d, a.Ktot, a.Ncols, a.n_tiles_cols, k_tiles, st);
-  if (fast != 1) return fast;  // launched (or failed to); 1 = views need the generic kernel
+  const dim3 grid(static_cast<unsigned>(d->n_split), static_cast<unsigned>(s.k_tiles * s.n_tiles_cols));
   if (d->taps == 9)
     hipLaunchKernelGGL(wgrad_kernel<9>, grid, dim3(kThreads), 0, st, a);
   else
     hipLaunchKernelGGL(wgrad_kernel<1>, grid, dim3(kThreads), 0, st, a);
-  note_kernel(d->taps == 9 ? "wgrad_kernel<9>" : "wgrad_kernel<1>");
   return launch_status();
+}
+}  // namespace
+
+// How many slabs: enough workgroups to fill the device, few enough that the finish stays short.
+extern "C" int unetpp_wgrad_plan(const unetpp_wgrad_desc* d, int32_t target_blocks, unetpp_wgrad_sizes* out) {
+  WgradSel s;
+  if (out == nullptr || wgrad_select(d, s) != UNETPP_OK) return UNETPP_EINVAL;
+  long target = target_blocks > 0 ? target_blocks : 256;
+  // a single x view on a 1..4-channel tensor (the network input): every workgroup of the first layer's VALU kernel ends
+  // in a 28-row cross-thread sum that costs more than a patch of its arithmetic.  1024 (four per CU) instead of 2048:
+  // 84 -> 69 us (fp32 headline), 106 -> 80 us (3 channels); 768 / 512 / 256 are slower again (75-145 us)
+  if (d->n_x == 1 && d->x[0].C <= 4) target = opt_value(OPT_SMALL_WGRAD_BLOCKS, 1024);
+  const long physical = physical_cu_count(), usable = device_cu_count();  // data parallel: CUs not left to the collective
+  if (0 < usable && usable < physical) {
+    target = target * usable / physical;
+    if (target < 8) target = 8;
+  }
+  // the bf16 pair kernel runs two 4-wave workgroups per CU (the quad kernel one workgroup)
+  if ((d->flags & UNETPP_GEMM_BF16) && target == 256 && s.pairs_per_workgroup == 1) target = 512;
+  long workgroups = static_cast<long>(s.k_tiles) * s.n_tiles_cols / s.pairs_per_workgroup;  // per slab
+  if (workgroups < 1) workgroups = 1;
+  long n_split = target / workgroups;
+  if (n_split > s.max_split) n_split = s.max_split;
+  if (n_split < 1) n_split = 1;
+  out->n_split = static_cast<int32_t>(n_split);
+  out->planes = s.planes;
+  out->pairs_per_workgroup = s.pairs_per_workgroup;
+  out->reserved = 0;
+  out->slab_floats = n_split * (static_cast<int64_t>(s.planes) * s.Ktot + 1) * s.Ncols;
+  out->kernel = s.label;
+  return UNETPP_OK;
+}
+
+extern "C" int unetpp_wgrad(const unetpp_wgrad_desc* d, void* stream) {
+  WgradSel s;
+  if (wgrad_select(d, s) != UNETPP_OK) return UNETPP_EINVAL;
+  if (d->slabs == nullptr || d->n_split < 1 || d->n_split > s.max_split) return UNETPP_EINVAL;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  note_kernel(s.label);
+  switch (s.kernel) {
+    case WGRAD_FIRST_LAYER: return launch_small_cin_wgrad(d, st);
+    case WGRAD_BF16_QUAD:
+    case WGRAD_BF16_PAIR: return launch_wgrad_bf16(d, s, st);
+    case WGRAD_PW: return launch_wgrad_pw(d, st);
+    case WGRAD_WINO: return launch_wgrad_wino(d, s, st);
+    case WGRAD_DMA: return launch_wgrad_dma(d, s, st);
+    case WGRAD_FAST: return launch_wgrad_fast(d, s, st);
+    case WGRAD_GENERIC: break;
+  }
+  return launch_wgrad_generic(d, s, st);
 }
 
 extern "C" int unetpp_wgrad_finish(const float* slabs, int32_t n_split, int32_t taps, int32_t K, int32_t Ncols,
@@ -406,7 +457,7 @@ extern "C" int unetpp_wgrad_finish(const float* slabs, int32_t n_split, int32_t 
                                    float* db, void* stream) {
   if (slabs == nullptr || n_split < 1 || taps < 1 || K < 1 || Ncols < 1) return UNETPP_EINVAL;
   if (n_inner < 1 || Ncols % n_inner != 0) return UNETPP_EINVAL;
-  if (taps == 16) {  // Winograd-domain slabs (unetpp_wgrad_slab_planes() == 16): sum, then G^T . G -> 9 taps
+  if (taps == 16) {  // Winograd-domain slabs (unetpp_wgrad_plan: planes == 16): sum, then G^T . G -> 9 taps
     if (n_inner != Ncols) return UNETPP_EINVAL;
     return launch_wgrad_finish_wino(slabs, n_split, K, Ncols, dw, d_t, d_k, d_n, db, static_cast<hipStream_t>(stream));
   }

@@ -405,7 +405,6 @@ int launch_one(const WBfArgs& a, dim3 grid, hipStream_t st) {
     opted_in[device >> 6].fetch_or(bit, std::memory_order_release);
   }
   hipLaunchKernelGGL((wgrad_bf16_kernel<TAPS, LOG2TW>), grid, dim3(kWThreads), lds, st, a);
-  note_kernel(TAPS == 9 ? "wgrad_bf16_kernel<9>" : "wgrad_bf16_kernel<1>");
   return launch_status();
 }
 
@@ -822,7 +821,6 @@ int launch_quad(const WBfArgs& a, dim3 grid, hipStream_t st) {
     opted_in[device >> 6].fetch_or(bit, std::memory_order_release);
   }
   hipLaunchKernelGGL((wgrad_bf16_quad_kernel<TAPS, LOG2TW>), grid, dim3(QuadShape<TAPS>::THREADS), lds, st, a);
-  note_kernel(TAPS == 9 ? "wgrad_bf16_quad_kernel<9>" : "wgrad_bf16_quad_kernel<1>");
   return launch_status();
 }
 
@@ -833,7 +831,6 @@ int launch_quad(const WBfArgs& a, dim3 grid, hipStream_t st) {
 bool wgrad_bf16_quads(const unetpp_wgrad_desc* d) {
   // (unetpp_debug_set("BF16_WGRAD_QUAD", 0): the tests compare the quad and the pair kernel inside one process)
   if (opt_value(OPT_BF16_WGRAD_QUAD, 1) == 0 || !(d->flags & UNETPP_GEMM_BF16)) return false;
-  if (d->taps == 9 && d->n_x == 1 && d->x[0].c_len <= 4) return false;  // first layer: its own kernel
   auto fits = [&](const unetpp_view& v) { return v.c_len > 0 && (v.c_len & 63) == 0; };
   for (int i = 0; i < d->n_x; ++i)
     if (!fits(d->x[i])) return false;
@@ -842,29 +839,34 @@ bool wgrad_bf16_quads(const unetpp_wgrad_desc* d) {
   return true;
 }
 
-// UNETPP_OK after launching, UNETPP_EINVAL when the views are not 8-channel aligned plain bf16 views (x may carry an
-// affine + ReLU load transform; ReLU gates on load are not supported in bf16)
-int launch_wgrad_bf16(const unetpp_wgrad_desc* d, int Ktot, int Ncols, int n_tiles_cols, int k_tiles, hipStream_t st) {
+// the views are 8-channel aligned plain bf16 views (x may carry an affine + ReLU load transform; ReLU gates on load are
+// not supported in bf16) with 31-bit byte offsets inside an image and 31-bit tile indices
+bool wgrad_bf16_views_ok(const unetpp_wgrad_desc* d) {
   for (int i = 0; i < d->n_x; ++i)
-    if (!bf16_view_aligned(d->x[i]) || d->x[i].gate != nullptr) return UNETPP_EINVAL;
+    if (!bf16_view_aligned(d->x[i]) || d->x[i].gate != nullptr) return false;
   for (int i = 0; i < d->n_dy; ++i)
     if (!bf16_view_aligned(d->dy[i]) || d->dy[i].gate != nullptr || d->dy[i].scale != nullptr || d->dy[i].relu)
-      return UNETPP_EINVAL;
+      return false;
+  const TileGeom g = tile_geom(d->H, d->W);
+  if (static_cast<long>(d->N) * g.tiles_y * g.tiles_x > 0x7fffffffL) return false;
+  for (int i = 0; i < d->n_x; ++i)   // (buffer resources, one per image)
+    if (static_cast<long>(d->x[i].Hs) * d->x[i].Ws * d->x[i].C * 2 > 0x7fffffffL) return false;
+  for (int i = 0; i < d->n_dy; ++i)
+    if (static_cast<long>(d->dy[i].Hs) * d->dy[i].Ws * d->dy[i].C * 2 > 0x7fffffffL) return false;
+  return true;
+}
+
+int launch_wgrad_bf16(const unetpp_wgrad_desc* d, const WgradSel& s, hipStream_t st) {
   WBfArgs a;
   a.d = *d;
-  a.Ktot = Ktot;
-  a.Ncols = Ncols;
-  a.n_tiles_cols = n_tiles_cols;
+  a.Ktot = s.Ktot;
+  a.Ncols = s.Ncols;
+  a.n_tiles_cols = s.n_tiles_cols;
   const TileGeom g = tile_geom(d->H, d->W);
   a.tiles_x = g.tiles_x;
   a.tiles_y = g.tiles_y;
   a.n_pix_tiles = static_cast<long>(d->N) * g.tiles_y * g.tiles_x;
-  if (a.n_pix_tiles > 0x7fffffffL) return UNETPP_EINVAL;
-  for (int i = 0; i < d->n_x; ++i)   // 31-bit byte offsets inside an image (buffer resources, one per image)
-    if (static_cast<long>(d->x[i].Hs) * d->x[i].Ws * d->x[i].C * 2 > 0x7fffffffL) return UNETPP_EINVAL;
-  for (int i = 0; i < d->n_dy; ++i)
-    if (static_cast<long>(d->dy[i].Hs) * d->dy[i].Ws * d->dy[i].C * 2 > 0x7fffffffL) return UNETPP_EINVAL;
-  if (wgrad_bf16_quads(d)) {
+  if (s.kernel == WGRAD_BF16_QUAD) {
     int kq = 0, nq = 0;
     for (int i = 0; i < d->n_x; ++i) kq += d->x[i].c_len >> 6;
     for (int i = 0; i < d->n_dy; ++i) nq += d->dy[i].c_len >> 6;
@@ -879,7 +881,7 @@ int launch_wgrad_bf16(const unetpp_wgrad_desc* d, int Ktot, int Ncols, int n_til
     if (g.log2tw == 4) return launch_quad<1, 4>(a, qgrid, st);
     return launch_quad<1, 3>(a, qgrid, st);
   }
-  const dim3 grid(static_cast<unsigned>(d->n_split), static_cast<unsigned>(static_cast<long>(k_tiles) * n_tiles_cols));
+  const dim3 grid(static_cast<unsigned>(d->n_split), static_cast<unsigned>(static_cast<long>(s.k_tiles) * s.n_tiles_cols));
   if (d->taps == 9) {
     if (g.log2tw == 5) return launch_one<9, 5>(a, grid, st);
     if (g.log2tw == 4) return launch_one<9, 4>(a, grid, st);

@@ -243,22 +243,26 @@ bool plain_aligned(const unetpp_view& v) {
 
 }  // namespace
 
-// returns UNETPP_OK after launching, or 1 when the descriptor needs another kernel (any load transform)
-int launch_wgrad_dma(const unetpp_wgrad_desc* d, int Ktot, int Ncols, int n_tiles_cols, int k_tiles, hipStream_t st) {
+// every view plain (no load transform) and 16-byte aligned
+bool wgrad_dma_applies(const unetpp_wgrad_desc* d) {
   for (int i = 0; i < d->n_x; ++i)
-    if (!plain_aligned(d->x[i])) return 1;
+    if (!plain_aligned(d->x[i])) return false;
   for (int i = 0; i < d->n_dy; ++i)
-    if (!plain_aligned(d->dy[i])) return 1;
+    if (!plain_aligned(d->dy[i])) return false;
+  return true;
+}
+
+int launch_wgrad_dma(const unetpp_wgrad_desc* d, const WgradSel& s, hipStream_t st) {
   WDmaArgs a;
   a.d = *d;
-  a.Ktot = Ktot;
-  a.Ncols = Ncols;
-  a.n_tiles_cols = n_tiles_cols;
+  a.Ktot = s.Ktot;
+  a.Ncols = s.Ncols;
+  a.n_tiles_cols = s.n_tiles_cols;
   const TileGeom g = tile_geom(d->H, d->W);
   a.tiles_x = g.tiles_x;
   a.tiles_y = g.tiles_y;
   a.n_pix_tiles = static_cast<long>(d->N) * g.tiles_y * g.tiles_x;
-  const dim3 grid(static_cast<unsigned>(d->n_split), static_cast<unsigned>(static_cast<long>(k_tiles) * n_tiles_cols));
+  const dim3 grid(static_cast<unsigned>(d->n_split), static_cast<unsigned>(static_cast<long>(s.k_tiles) * s.n_tiles_cols));
   const dim3 block(kWThreads);
 #define UNETPP_LAUNCH_WDMA(T)                                                                     \
   do {                                                                                            \
@@ -269,7 +273,6 @@ int launch_wgrad_dma(const unetpp_wgrad_desc* d, int Ktot, int Ncols, int n_tile
   if (d->taps == 9) UNETPP_LAUNCH_WDMA(9);
   else UNETPP_LAUNCH_WDMA(1);
 #undef UNETPP_LAUNCH_WDMA
-  note_kernel(d->taps == 9 ? "wgrad_dma_kernel<9>" : "wgrad_dma_kernel<1>");
   return launch_status();
 }
 

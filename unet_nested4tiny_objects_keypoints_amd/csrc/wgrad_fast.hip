@@ -258,28 +258,31 @@ int launch_one(const WFastArgs& a, dim3 grid, hipStream_t st) {
                           hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) != hipSuccess)
     return UNETPP_ELAUNCH;
   hipLaunchKernelGGL((wgrad_fast_kernel<TAPS, LOG2TW>), grid, dim3(kWThreads), lds, st, a);
-  note_kernel(TAPS == 9 ? "wgrad_fast_kernel<9>" : "wgrad_fast_kernel<1>");
   return launch_status();
 }
 
 }  // namespace
 
-// returns UNETPP_OK after launching, or 1 when the descriptor needs the generic kernel
-int launch_wgrad_fast(const unetpp_wgrad_desc* d, int Ktot, int Ncols, int n_tiles_cols, int k_tiles, hipStream_t st) {
+// every view 16-byte aligned and without a ReLU gate; dy views plain
+bool wgrad_fast_applies(const unetpp_wgrad_desc* d) {
   for (int i = 0; i < d->n_x; ++i)
-    if (!aligned_view(d->x[i], true)) return 1;
+    if (!aligned_view(d->x[i], true)) return false;
   for (int i = 0; i < d->n_dy; ++i)
-    if (!aligned_view(d->dy[i], false)) return 1;
+    if (!aligned_view(d->dy[i], false)) return false;
+  return true;
+}
+
+int launch_wgrad_fast(const unetpp_wgrad_desc* d, const WgradSel& s, hipStream_t st) {
   WFastArgs a;
   a.d = *d;
-  a.Ktot = Ktot;
-  a.Ncols = Ncols;
-  a.n_tiles_cols = n_tiles_cols;
+  a.Ktot = s.Ktot;
+  a.Ncols = s.Ncols;
+  a.n_tiles_cols = s.n_tiles_cols;
   const TileGeom g = tile_geom(d->H, d->W);
   a.tiles_x = g.tiles_x;
   a.tiles_y = g.tiles_y;
   a.n_pix_tiles = static_cast<long>(d->N) * g.tiles_y * g.tiles_x;
-  const dim3 grid(static_cast<unsigned>(d->n_split), static_cast<unsigned>(static_cast<long>(k_tiles) * n_tiles_cols));
+  const dim3 grid(static_cast<unsigned>(d->n_split), static_cast<unsigned>(static_cast<long>(s.k_tiles) * s.n_tiles_cols));
   if (d->taps == 9) {
     if (g.log2tw == 5) return launch_one<9, 5>(a, grid, st);
     if (g.log2tw == 4) return launch_one<9, 4>(a, grid, st);

@@ -218,16 +218,14 @@ bool wgrad_pw_shape(const unetpp_wgrad_desc* d, WPwArgs& a) {
 
 }  // namespace
 
-// (32 x 32) pairs of dW a workgroup covers, 0 when the kernel does not take the descriptor (unetpp_wgrad_pairs_per_workgroup)
-int wgrad_pw_pairs(const unetpp_wgrad_desc* d) {
+bool wgrad_pw_applies(const unetpp_wgrad_desc* d) {
   WPwArgs a;
-  return wgrad_pw_shape(d, a) ? 8 : 0;  // one 64 x 128 block
+  return wgrad_pw_shape(d, a);
 }
 
-// returns UNETPP_OK after launching, or 1 when the descriptor needs another kernel
 int launch_wgrad_pw(const unetpp_wgrad_desc* d, hipStream_t st) {
   WPwArgs a;
-  if (!wgrad_pw_shape(d, a)) return 1;
+  if (!wgrad_pw_shape(d, a)) return UNETPP_EINVAL;  // (the block structure; wgrad_select has asked wgrad_pw_applies)
   a.d = *d;
   static bool raised[64] = {};
   int dev = 0;
@@ -241,7 +239,6 @@ int launch_wgrad_pw(const unetpp_wgrad_desc* d, hipStream_t st) {
   }
   const dim3 grid(static_cast<unsigned>(d->n_split) * static_cast<unsigned>(a.kb_count * a.nb_count));
   hipLaunchKernelGGL(wgrad_pw_kernel, grid, dim3(kPwThreads), lds_bytes, st, a);
-  note_kernel("wgrad_pw_kernel");
   return launch_status();
 }
 

@@ -605,9 +605,20 @@ bool x_view_ok(const unetpp_view& v) {
   return v.scale == nullptr ? !v.relu : (v.shift != nullptr && v.relu != 0);
 }
 
+// every view's image below 2 GB: the plain-view kernel reads its operands through per-image buffer resources
+bool images_below_2gb(const unetpp_wgrad_desc* d) {
+  for (int i = 0; i < d->n_x; ++i)
+    if (static_cast<long>(d->x[i].Hs) * d->x[i].Ws * d->x[i].C * 4 > 0x7fffffffL) return false;
+  for (int i = 0; i < d->n_dy; ++i)
+    if (static_cast<long>(d->dy[i].Hs) * d->dy[i].Ws * d->dy[i].C * 4 > 0x7fffffffL) return false;
+  return true;
+}
+
 }  // namespace
 
-// 3x3, Winograd not forbidden, 32-wide patches, every view plain and 16-byte aligned, 32-bit byte offsets inside a patch
+// 3x3, Winograd not forbidden, 32-wide patches, every view plain and 16-byte aligned (x views: all plain or all with
+// the folded BatchNorm), 32-bit byte offsets inside a patch and 32-bit tile indices; plain views of 2 GB or more per
+// image go to the direct-sum kernels
 bool wgrad_wino_applies(const unetpp_wgrad_desc* d) {
   if (d == nullptr || d->taps != 9 || (d->flags & UNETPP_GEMM_DIRECT) != 0) return false;
   if (d->N <= 0 || d->H <= 0 || d->W <= 0 || tile_geom(d->H, d->W).log2tw != 5) return false;
@@ -623,37 +634,30 @@ bool wgrad_wino_applies(const unetpp_wgrad_desc* d) {
     if (!view_ok(v) || !plain_aligned(v)) return false;
     if (static_cast<long>(kHHp) * v.sy * v.Ws * v.C * 4 >= 0x7fffffffL) return false;
   }
+  const TileGeom g = tile_geom(d->H, d->W);
+  if (static_cast<long>(d->N) * g.tiles_y * g.tiles_x >= 0x7fffffffL) return false;
+#ifndef UNETPP_WWINO_EXP_OLD_STAGING
+  if (d->x[0].scale == nullptr && !images_below_2gb(d)) return false;
+#endif
   return true;
 }
 
-// returns UNETPP_OK after launching, or 1 when the descriptor needs another kernel
-int launch_wgrad_wino(const unetpp_wgrad_desc* d, int Ktot, int Ncols, int n_tiles_cols, int k_tiles, hipStream_t st) {
-  if (!wgrad_wino_applies(d)) return 1;
+int launch_wgrad_wino(const unetpp_wgrad_desc* d, const WgradSel& s, hipStream_t st) {
   WWinoArgs a;
   a.d = *d;
-  a.Ktot = Ktot;
-  a.Ncols = Ncols;
-  a.n_tiles_cols = n_tiles_cols;
+  a.Ktot = s.Ktot;
+  a.Ncols = s.Ncols;
+  a.n_tiles_cols = s.n_tiles_cols;
   const TileGeom g = tile_geom(d->H, d->W);
   a.tiles_x = g.tiles_x;
   a.tiles_y = g.tiles_y;
   a.n_pix_tiles = static_cast<long>(d->N) * g.tiles_y * g.tiles_x;
-  if (a.n_pix_tiles >= 0x7fffffffL) return 1;  // 32-bit tile indices in the kernel
-  a.rsrc_ok = 1;
-  for (int i = 0; i < d->n_x; ++i)
-    if (static_cast<long>(d->x[i].Hs) * d->x[i].Ws * d->x[i].C * 4 > 0x7fffffffL) a.rsrc_ok = 0;
-  for (int i = 0; i < d->n_dy; ++i)
-    if (static_cast<long>(d->dy[i].Hs) * d->dy[i].Ws * d->dy[i].C * 4 > 0x7fffffffL) a.rsrc_ok = 0;
-  const bool xform = d->x[0].scale != nullptr;  // all views or none (wgrad_wino_applies)
-#ifndef UNETPP_WWINO_EXP_OLD_STAGING
-  if (!xform && !a.rsrc_ok) return 1;  // plain views above 2 GB per image: the direct-sum kernels
-#endif
-  const dim3 grid(static_cast<unsigned>(d->n_split), static_cast<unsigned>(static_cast<long>(k_tiles) * n_tiles_cols));
+  a.rsrc_ok = images_below_2gb(d) ? 1 : 0;
+  const dim3 grid(static_cast<unsigned>(d->n_split), static_cast<unsigned>(static_cast<long>(s.k_tiles) * s.n_tiles_cols));
   if (d->x[0].scale != nullptr)
     hipLaunchKernelGGL(wgrad_wino_kernel<true>, grid, dim3(kWThreads), 0, st, a);
   else
     hipLaunchKernelGGL(wgrad_wino_kernel<false>, grid, dim3(kWThreads), 0, st, a);
-  note_kernel("wgrad_wino_kernel");
   return launch_status();
 }
 

@@ -170,10 +170,6 @@ class V:
 
 
 USE_FAST_GEMM = True  # tests flip this to exercise the generic kernel on the same shapes
-# workgroups of the first layer's weight gradient (A/B knob).  Round 5: 1024 (four per CU) instead of 2048 -- every
-# workgroup ends in a 28-row cross-thread sum that costs more than a patch of its arithmetic: 84 -> 69 us (fp32 headline),
-# 106 -> 80 us (configs[4], 3 channels); 768 / 512 / 256 are slower again (75-145 us)
-_SMALL_WGRAD_BLOCKS = int(os.environ.get("UNETPP_SMALL_WGRAD_BLOCKS", "1024"))
 USE_WINOGRAD = os.environ.get("UNETPP_NO_WINOGRAD") is None  # 3x3 fast path: Winograd F(2x2,3x3) unless disabled
 
 
@@ -510,38 +506,29 @@ def pack_weight(dst: torch.Tensor, src: torch.Tensor, t: int, k: int, n: int, ds
 
 def wgrad(n: int, h: int, w: int, taps: int, xs: Sequence[V], dys: Sequence[V], dw: Optional[torch.Tensor],
           dw_strides, db: Optional[torch.Tensor], n_inner: Optional[int] = None, target_blocks: int = 256,
-          direct: bool = False) -> None:
+          direct: bool = False) -> _lib.WgradSizes:
     """dw / db are written (not accumulated).  dw_strides = (d_t, d_k, d_n, d_o) into the torch-layout gradient.
-    direct=True forbids the Winograd form of the 3x3 kernel."""
+    direct=True forbids the Winograd form of the 3x3 kernel.  Returns the library's plan of the launch (kernel label,
+    n_split, slab layout: unetpp_wgrad_plan)."""
     lib = _lib.lib()
     d = WgradDesc()
     d.N, d.H, d.W, d.taps = n, h, w, taps
     d.n_x, d.n_dy = len(xs), len(dys)
     k = sum(v.fill(d.x[i]) for i, v in enumerate(xs))
     nc = sum(v.fill(d.dy[i]) for i, v in enumerate(dys))
-    pairs = sum((v.c_len + 31) // 32 for v in d.x[:len(xs)]) * sum((v.c_len + 31) // 32 for v in d.dy[:len(dys)])
-    if len(xs) == 1 and xs[0].t.shape[3] <= 4:
-        target_blocks = _SMALL_WGRAD_BLOCKS  # the 1..4-channel first layer: a VALU kernel with an expensive per-workgroup sum
     d.flags = (_lib.GEMM_DIRECT if (direct or not USE_WINOGRAD) else 0) | _storage_flag(dys, xs)
-    wg_pairs = int(lib.unetpp_wgrad_pairs_per_workgroup(C.byref(d)))
-    phys = C.c_int32(0)
-    usable = int(lib.unetpp_usable_cus(C.byref(phys)))   # data parallel: CUs not left to the collective (all unless asked)
-    if 0 < usable < phys.value:
-        target_blocks = max(8, target_blocks * usable // phys.value)
-    if dys[0].t.dtype == torch.bfloat16 and target_blocks == 256 and wg_pairs == 1:
-        target_blocks = 512  # the bf16 pair kernel runs two 4-wave workgroups per CU (the quad kernel one of 8 waves)
-    split = max(1, min(int(lib.unetpp_wgrad_max_split(n, h, w)), target_blocks // max(1, pairs // max(1, wg_pairs))))
-    d.n_split = split
-    planes = int(lib.unetpp_wgrad_slab_planes(C.byref(d)))  # taps, or 16 for the Winograd kernel
-    slabs = torch.empty(split * (planes * k + 1) * nc, dtype=torch.float32, device=xs[0].t.device)
-    d.slabs = slabs.data_ptr()
+    plan = _lib.WgradSizes()
+    check(lib.unetpp_wgrad_plan(C.byref(d), target_blocks, C.byref(plan)), "unetpp_wgrad_plan")
+    slabs = torch.empty(plan.slab_floats, dtype=torch.float32, device=xs[0].t.device)
+    d.n_split, d.slabs = plan.n_split, slabs.data_ptr()
     _timed_call(None, 2.0 * n * h * w * taps * k * nc,
                 lambda: check(lib.unetpp_wgrad(C.byref(d), _stream()), "unetpp_wgrad"),
                 (2.0 if d.flags & _lib.GEMM_BF16 else 4.0) * n * h * w * (k + nc))
     if n_inner is None:
         n_inner = nc
-    check(lib.unetpp_wgrad_finish(_ptr(slabs), split, planes, k, nc, n_inner, _ptr(dw), dw_strides[0], dw_strides[1],
-                                  dw_strides[2], dw_strides[3], _ptr(db), _stream()), "unetpp_wgrad_finish")
+    check(lib.unetpp_wgrad_finish(_ptr(slabs), plan.n_split, plan.planes, k, nc, n_inner, _ptr(dw), dw_strides[0],
+                                  dw_strides[1], dw_strides[2], dw_strides[3], _ptr(db), _stream()), "unetpp_wgrad_finish")
+    return plan
 
 
 def bn_finalize(partial, n_blocks, c, count, gamma, beta, eps, momentum, running_mean, running_var):
