@@ -351,6 +351,27 @@ typedef struct unetpp_focal_heads {
 } unetpp_focal_heads;
 int unetpp_focal_bce_heads(const unetpp_focal_heads* heads, const float* target, int64_t n, int64_t rows, float gamma,
                            float* partial, float* loss, void* stream);
+/* ---- ensemble head of an eval forward (added within v12: new entry points only, nothing existing changes) ----
+ * The output selection the UNet++ authors left as comments in models/unet.py:293-298: the mean of the first n_heads
+ * deep-supervision heads, out = (((s_1 + s_2) + ...) + s_n) / (float)n with s_h = 1 / (1 + exp(-(bias_h + x_h . w_h)))
+ * per pixel and class, in ONE pass: every feature tensor x_h (NHWC [N,H,W,C]; fp32, or bf16 for the _bf16 entry) is
+ * read once, the fp32 NCHW [N,n_cls,H,W] mean is written once, the individual head maps never exist.  No dropout (eval
+ * only), fp32 accumulation, fixed summation order.  weight_h [n_cls, C], bias_h [n_cls], fp32.  Returns UNETPP_EINVAL
+ * without touching the device for a NULL descriptor / pointer, n_heads outside 1..UNETPP_MAX_HEADS, N/H/W/C < 1,
+ * C > 128 or n_cls outside 1..8 (the limits of unetpp_head_fwd). */
+typedef struct unetpp_head_src {
+  const void* x;        /* NHWC features of this head's node X_0j */
+  const float* weight;  /* [n_cls, C] */
+  const float* bias;    /* [n_cls] */
+} unetpp_head_src;
+typedef struct unetpp_heads_mean {
+  unetpp_head_src head[UNETPP_MAX_HEADS];
+  int32_t n_heads, reserved;
+} unetpp_heads_mean;
+int unetpp_heads_mean_fwd(const unetpp_heads_mean* heads, int32_t N, int32_t H, int32_t W, int32_t C, int32_t n_cls,
+                          float* out_nchw, void* stream);
+int unetpp_heads_mean_fwd_bf16(const unetpp_heads_mean* heads, int32_t N, int32_t H, int32_t W, int32_t C,
+                               int32_t n_cls, float* out_nchw, void* stream);
 /* create_heatmap (tools/misc/helper.py:87-172): key points [N][P][2] as (x, y), P >= 6 -> float32 [N,4,H,W]:
  * ch0 = point 0, ch1 = points 1..3 summed / max, ch2 = point 4, ch3 = points 5..P-1 summed / max, each map
  * exp(-0.5 sqrt(dx^2 + dy^2) / radius) (the reference uses radius 3).  workspace: unetpp_heatmap_workspace_bytes(). */

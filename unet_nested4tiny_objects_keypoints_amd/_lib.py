@@ -17,7 +17,7 @@ CSRC = os.path.join(_PKG_DIR, "csrc")
 INCLUDE = os.path.join(_REPO, "include")
 SOURCES = ("gemm_pix.hip", "gemm_fast.hip", "gemm_pw.hip", "gemm_pw_bf16.hip", "gemm_wino.hip", "gemm_bf16.hip", "gemm_bf16_dma.hip", "wgrad_bf16.hip", "pointwise_bf16.hip", "keypoints.hip", "weight_image.hip", "wgrad.hip", "wgrad_fast.hip", "wgrad_dma.hip", "wgrad_pw.hip", "wgrad_wino.hip", "first_layer.hip", "pointwise.hip", "caller.hip", "optim.hip", "validate.hip")
 HEADERS = ("common.h", "gemm_units.h", "wgrad_reduce.h", "lds_asm.h", "bf16_common.h", "dropout.h", "bn_fused.h",
-           "wino_experiments.h", "dma_experiments.h")
+           "wino_experiments.h", "dma_experiments.h", "heads_mean.h")
 MAX_VIEWS = 8
 ABI_VERSION = 12
 # packed-f32 VALU (SLP-vectorised add pairs) costs issue slots beside MFMAs: keep the Winograd transforms scalar
@@ -98,6 +98,16 @@ class FocalHeads(C.Structure):
     ]
 
 
+class HeadSrc(C.Structure):
+    """mirror of struct unetpp_head_src"""
+    _fields_ = [("x", C.c_void_p), ("weight", C.c_void_p), ("bias", C.c_void_p)]
+
+
+class HeadsMean(C.Structure):
+    """mirror of struct unetpp_heads_mean"""
+    _fields_ = [("head", HeadSrc * MAX_HEADS), ("n_heads", C.c_int32), ("reserved", C.c_int32)]
+
+
 class WgradDesc(C.Structure):
     """mirror of struct unetpp_wgrad_desc"""
     _fields_ = [
@@ -172,6 +182,9 @@ SIGNATURES = {
     "unetpp_focal_bce_blocks": (_I64, [_I64]),
     "unetpp_focal_bce": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, _P]),
     "unetpp_focal_bce_heads": (C.c_int, [C.POINTER(FocalHeads), _P, _I64, _I64, _F, _P, _P, _P]),
+    # ensemble head of the eval forward (added within ABI 12)
+    "unetpp_heads_mean_fwd": (C.c_int, [C.POINTER(HeadsMean), _I32, _I32, _I32, _I32, _I32, _P, _P]),
+    "unetpp_heads_mean_fwd_bf16": (C.c_int, [C.POINTER(HeadsMean), _I32, _I32, _I32, _I32, _I32, _P, _P]),
     "unetpp_copy_jobs": (C.c_int, [_P, _I32, _I64, _P]),
     "unetpp_heatmap_workspace_bytes": (_I64, [_I32, _I32, _I32]),
     "unetpp_create_heatmap": (C.c_int, [_P, _I32, _I32, _I32, _I32, _F, _P, _P, _P]),

@@ -5,6 +5,7 @@
 #include "common.h"
 #include "lds_asm.h"
 #include "dropout.h"
+#include "heads_mean.h"
 
 namespace unetpp {
 namespace {
@@ -576,6 +577,41 @@ __global__ __launch_bounds__(64) void head_fwd_tiled_kernel(const float* __restr
   }
 }
 
+// One pixel's logits in the streaming layout (lane = (pixel, channel quad), G = 2^LOG2G lanes per pixel): the P per-class
+// partial dot products of the lane's quad, summed over the pixel's lanes by a reduce-scatter in a fixed order.  Returns
+// the total (without the bias) of class `cls`, the one this lane ends up with; G / P lanes (at least one) hold each class.
+// Shared by head_fwd_stream_kernel and heads_mean_stream_kernel: both produce the same bits for the same operands.
+template <int LOG2G, int P>
+__device__ __forceinline__ float head_pixel_logit(const f32x4& v, const f32x4 (&wq)[P], int gq, int& cls) {
+  constexpr int G = 1 << LOG2G;
+  float acc[P];
+#pragma unroll
+  for (int k = 0; k < P; ++k)
+    acc[k] = fmaf(v[0], wq[k][0], fmaf(v[1], wq[k][1], fmaf(v[2], wq[k][2], v[3] * wq[k][3])));
+  // reduce-scatter over the G lanes of the pixel: with `live` classes left, a lane keeps the half selected by its
+  // bit `off` and adds the partner's partials of that half; once one class is left, a plain butterfly sum
+  int c = 0;
+  static_for<LOG2G>([&](auto sc) {
+    constexpr int step = decltype(sc)::v, off = G >> (1 + step);
+    constexpr int live = (P >> step) > 1 ? (P >> step) : 1;  // classes a lane still carries before this step
+    if constexpr (live > 1) {
+      constexpr int half = live >> 1;
+      const bool upper = (gq & off) != 0;
+#pragma unroll
+      for (int i = 0; i < half; ++i) {
+        const float send = upper ? acc[i] : acc[half + i];
+        const float keep = upper ? acc[half + i] : acc[i];
+        acc[i] = keep + xor_lane<off>(send);
+      }
+      c += upper ? half : 0;
+    } else {
+      acc[0] += xor_lane<off>(acc[0]);
+    }
+  });
+  cls = c;
+  return acc[0];
+}
+
 // Forward head, streaming form for power-of-two channel-quad counts (C = 4 .. 128): lane = (pixel, channel quad), one
 // coalesced 16-byte load per item, the class weights of the quad in registers.  The P per-class partial dot products
 // of a lane are summed over the C/4 lanes of the pixel by a reduce-scatter (each exchange step halves the classes a
@@ -625,30 +661,8 @@ __global__ __launch_bounds__(kThreads) void head_fwd_stream_kernel(const float* 
 #pragma unroll
         for (int q = 0; q < 4; ++q) v[u][q] = ((m4 >> (8 * q)) & 0xffu) != 0 ? v[u][q] * keep_scale : 0.f;
       }
-      float acc[P];
-#pragma unroll
-      for (int k = 0; k < P; ++k)
-        acc[k] = fmaf(v[u][0], wq[k][0], fmaf(v[u][1], wq[k][1], fmaf(v[u][2], wq[k][2], v[u][3] * wq[k][3])));
-      // reduce-scatter over the G lanes of the pixel: with `live` classes left, a lane keeps the half selected by its
-      // bit `off` and adds the partner's partials of that half; once one class is left, a plain butterfly sum
-      int cls = 0;  // class this lane ends up with
-      static_for<LOG2G>([&](auto sc) {
-        constexpr int step = decltype(sc)::v, off = G >> (1 + step);
-        constexpr int live = (P >> step) > 1 ? (P >> step) : 1;  // classes a lane still carries before this step
-        if constexpr (live > 1) {
-          constexpr int half = live >> 1;
-          const bool upper = (gq & off) != 0;
-#pragma unroll
-          for (int i = 0; i < half; ++i) {
-            const float send = upper ? acc[i] : acc[half + i];
-            const float keep = upper ? acc[half + i] : acc[i];
-            acc[i] = keep + xor_lane<off>(send);
-          }
-          cls += upper ? half : 0;
-        } else {
-          acc[0] += xor_lane<off>(acc[0]);
-        }
-      });
+      int cls;  // class this lane ends up with
+      const float logit = head_pixel_logit<LOG2G, P>(v[u], wq, gq, cls);
       // this item's (image, position): u steps of `span` from the thread's first pixel of the iteration
       unsigned n = n0 + u * span_n, hw = hw0 + u * span_hw;
 #pragma unroll
@@ -659,9 +673,74 @@ __global__ __launch_bounds__(kThreads) void head_fwd_stream_kernel(const float* 
       }
       constexpr int kDup = (G > P) ? G / P : 1;  // lanes that end with the same class total
       if (valid && cls < n_cls && (gq & (kDup - 1)) == 0)
-        out[(static_cast<long>(n) * n_cls + cls) * HW + hw] = 1.0f / (1.0f + __expf(-(acc[0] + bias[cls])));
+        out[(static_cast<long>(n) * n_cls + cls) * HW + hw] = 1.0f / (1.0f + __expf(-(logit + bias[cls])));
     }
     // advance the carried position by U spans
+    n0 += U * span_n;
+    hw0 += U * span_hw;
+#pragma unroll
+    for (int c = 0; c < U; ++c) {
+      const bool carry = hw0 >= HW;
+      hw0 -= carry ? HW : 0u;
+      n0 += carry ? 1u : 0u;
+    }
+  }
+}
+
+// Ensemble head (unetpp_heads_mean_fwd), streaming form: the layout, the loop and the per-pixel logit of
+// head_fwd_stream_kernel without dropout, with the heads as an inner loop -- for every iteration's U pixels each head's
+// quad is loaded once (16 bytes), its class weights come from the L1-resident [n_cls, C] table (no LDS tile), and the
+// sigmoids are added in head order; the mean is stored once.  32-bit element offsets (launcher: < 2^31 elements).
+template <int LOG2G, int P>
+__global__ __launch_bounds__(kThreads) void heads_mean_stream_kernel(const unetpp_heads_mean hd, unsigned pixels, unsigned HW,
+                                                                     int n_cls, float* __restrict__ out) {
+  constexpr int G = 1 << LOG2G;
+  const int gq = threadIdx.x & (G - 1);
+  constexpr unsigned ppb = kThreads >> LOG2G;
+  constexpr int U = 4;
+  const unsigned span = gridDim.x * ppb, outer = U * span;
+  const unsigned pl = threadIdx.x >> LOG2G;
+  const unsigned span_n = span / HW, span_hw = span - span_n * HW;
+  const int n_heads = hd.n_heads;
+  const float count = static_cast<float>(n_heads);
+  unsigned p0 = blockIdx.x * ppb + pl;
+  unsigned n0 = p0 / HW, hw0 = p0 - n0 * HW;
+  for (; p0 - pl < pixels; p0 += outer) {  // wave-uniform trip count
+    float sum[U] = {0.f, 0.f, 0.f, 0.f};  // 0 + s_1 is s_1: the sum is ((s_1 + s_2) + ...) in head order
+    int cls = 0;
+    for (int h = 0; h < n_heads; ++h) {
+      const float* __restrict__ x = static_cast<const float*>(hd.head[h].x);
+      const float* __restrict__ weight = hd.head[h].weight;
+      f32x4 v[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const unsigned p = p0 + u * span;
+        v[u] = (p < pixels) ? *reinterpret_cast<const f32x4*>(x + ((p << (LOG2G + 2)) + 4 * gq)) : f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+      f32x4 wq[P];
+#pragma unroll
+      for (int k = 0; k < P; ++k)
+        wq[k] = (k < n_cls) ? *reinterpret_cast<const f32x4*>(weight + k * 4 * G + 4 * gq) : f32x4{0.f, 0.f, 0.f, 0.f};
+      float logit[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) logit[u] = head_pixel_logit<LOG2G, P>(v[u], wq, gq, cls);
+      const float b = cls < n_cls ? hd.head[h].bias[cls] : 0.f;
+#pragma unroll
+      for (int u = 0; u < U; ++u) sum[u] += 1.0f / (1.0f + __expf(-(logit[u] + b)));
+    }
+    constexpr int kDup = (G > P) ? G / P : 1;  // lanes that end with the same class total
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      unsigned n = n0 + u * span_n, hw = hw0 + u * span_hw;
+#pragma unroll
+      for (int c = 0; c < U - 1; ++c) {  // at most u carries
+        const bool carry = c < u && hw >= HW;
+        hw -= carry ? HW : 0u;
+        n += carry ? 1u : 0u;
+      }
+      if (p0 + u * span < pixels && cls < n_cls && (gq & (kDup - 1)) == 0)
+        out[(static_cast<long>(n) * n_cls + cls) * HW + hw] = sum[u] / count;
+    }
     n0 += U * span_n;
     hw0 += U * span_hw;
 #pragma unroll
@@ -1499,6 +1578,54 @@ extern "C" int unetpp_head_fwd(const float* x, const float* weight, const float*
   note_kernel("head_fwd");
   hipLaunchKernelGGL(head_fwd_kernel, dim3(grid_for(pixels)), dim3(kThreads), 0, ST(stream), x, weight, bias, pixels,
                      H * W, C, n_cls, 1.0f / (1.0f - p_drop), keep_threshold(p_drop), seed, mask, seed_dev, use_drop, out_nchw);
+  return launch_status();
+}
+
+/* ---- ensemble head: mean of the first n_heads sigmoid heads in one pass (eval only) ---- */
+extern "C" int unetpp_heads_mean_fwd(const unetpp_heads_mean* heads, int32_t N, int32_t H, int32_t W, int32_t C,
+                                     int32_t n_cls, float* out_nchw, void* stream) {
+  if (!heads || !out_nchw || heads->n_heads < 1 || heads->n_heads > UNETPP_MAX_HEADS || !head_args_ok(N, H, W, C, n_cls, 0.f))
+    return UNETPP_EINVAL;
+  bool vec = (C & 3) == 0;
+  for (int h = 0; h < heads->n_heads; ++h) {
+    const unetpp_head_src& s = heads->head[h];
+    if (!s.x || !s.weight || !s.bias) return UNETPP_EINVAL;
+    vec = vec && aligned16(s.x) && aligned16(s.weight);
+  }
+  const long pixels = static_cast<long>(N) * H * W;
+  const int g4 = C >> 2;
+  const int pcls = n_cls <= 4 ? 4 : 8;
+  // the stream form addresses elements with 32 bits: it never takes a tensor of 2^31 elements or more
+  if (vec && (g4 & (g4 - 1)) == 0 && g4 <= 32 && pcls <= g4 && pixels * C < 0x7fffffffL) {
+    const long ppb = kThreads / g4;
+    const long want = (pixels + ppb - 1) / ppb;
+    const dim3 grid(static_cast<unsigned>(want < 256 * 16 ? want : 256 * 16));
+#define UNETPP_HEADS_MEAN(L, PC)                                                                                      \
+  do {                                                                                                                \
+    note_kernel("heads_mean_stream<" #L "," #PC ">");                                                                 \
+    hipLaunchKernelGGL((heads_mean_stream_kernel<L, PC>), grid, dim3(kThreads), 0, ST(stream), *heads,                 \
+                       static_cast<unsigned>(pixels), static_cast<unsigned>(H * W), n_cls, out_nchw);                 \
+  } while (0)
+    if (pcls == 4) {
+      switch (g4) {
+        case 4: UNETPP_HEADS_MEAN(2, 4); break;
+        case 8: UNETPP_HEADS_MEAN(3, 4); break;
+        case 16: UNETPP_HEADS_MEAN(4, 4); break;
+        default: UNETPP_HEADS_MEAN(5, 4); break;
+      }
+    } else {
+      switch (g4) {
+        case 8: UNETPP_HEADS_MEAN(3, 8); break;
+        case 16: UNETPP_HEADS_MEAN(4, 8); break;
+        default: UNETPP_HEADS_MEAN(5, 8); break;
+      }
+    }
+#undef UNETPP_HEADS_MEAN
+    return launch_status();
+  }
+  note_kernel("heads_mean");
+  hipLaunchKernelGGL(heads_mean_general_kernel<float>, dim3(grid_for(pixels)), dim3(kThreads), 0, ST(stream), *heads, pixels, H * W, C,
+                     n_cls, out_nchw);
   return launch_status();
 }
 

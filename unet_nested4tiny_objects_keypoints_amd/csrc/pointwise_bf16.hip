@@ -16,6 +16,7 @@
 #include "common.h"
 #include "lds_asm.h"
 #include "dropout.h"
+#include "heads_mean.h"
 
 namespace unetpp {
 namespace {
@@ -201,6 +202,19 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_apply_bf16_kernel(const bf16_
 // DPP / ds_swizzle moves (xor_lane: the ds_bpermute shuffles of __shfl_xor made this kernel, like its fp32 twin,
 // instruction bound at a third of the HBM rate).  DROP: 0 = none, 1 = counter hash, 2 = mask tensor -- separate
 // instantiations keep the loop body straight-line.
+// One class's logit (without the bias) of one pixel in the octet layout (lane = (pixel, channel octet), CG = 2^LOG2CG
+// lanes per pixel): the lane's octet against the class's weight row in LDS, then the CG partial sums folded across the
+// lanes in a fixed order; every lane of the pixel ends with the total.  Shared by head_fwd_bf16_kernel and
+// heads_mean_bf16_kernel: both produce the same bits for the same operands.
+template <int LOG2CG>
+__device__ __forceinline__ float head_pixel_logit_bf16(const float (&f)[8], const float* wrow, int cg) {
+  float s = 0.f;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) s = fmaf(f[e], wrow[cg * 8 + e], s);
+  static_for<LOG2CG>([&](auto mc) { s += xor_lane<(1 << decltype(mc)::v)>(s); });
+  return s;
+}
+
 template <int LOG2CG, int DROP, int PCLS>  // PCLS = classes padded to 4, 6 or 8 (5 key-point maps: configs[4]): the class loops carry no n_cls branches
 __global__ __launch_bounds__(kThreads) void head_fwd_bf16_kernel(const bf16_t* __restrict__ x, const float* __restrict__ weight,
                                                                  const float* __restrict__ bias, long pixels, int HW,
@@ -242,13 +256,53 @@ __global__ __launch_bounds__(kThreads) void head_fwd_bf16_kernel(const bf16_t* _
     float* obase = out + static_cast<long>(n) * n_cls * uhw + hw;
 #pragma unroll
     for (int k = 0; k < PCLS; ++k) {
-      float s = 0.f;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) s = fmaf(f[e], wsm[k * C + cg * 8 + e], s);
-      static_for<LOG2CG>([&](auto mc) { s += xor_lane<(1 << decltype(mc)::v)>(s); });  // every lane of the pixel holds the logit
+      const float s = head_pixel_logit_bf16<LOG2CG>(f, wsm + k * C, cg);  // every lane of the pixel holds the logit
       if (live && k < n_cls && (k & (CG - 1)) == cg)                // classes are dealt to the pixel's lanes round robin
         obase[static_cast<long>(k) * uhw] = 1.0f / (1.0f + __expf(-(s + bias[k])));
     }
+  }
+}
+
+// Ensemble head (unetpp_heads_mean_fwd_bf16): head_fwd_bf16_kernel's layout and per-pixel logit without dropout, the
+// heads as an inner loop -- every head's octet is loaded once (16 bytes), the sigmoids are added in head order and the
+// mean is stored once.  LDS holds one zero-padded weight tile per head ([n_heads][PCLS * C], sized by the launcher).
+template <int LOG2CG, int PCLS>
+__global__ __launch_bounds__(kThreads) void heads_mean_bf16_kernel(const unetpp_heads_mean hd, long pixels, int HW, int n_cls,
+                                                                   float* __restrict__ out) {
+  constexpr int CG = 1 << LOG2CG, C = 8 * CG;
+  extern __shared__ float hm_wsm[];
+  const int n_heads = hd.n_heads;
+  const float count = static_cast<float>(n_heads);
+  for (int h = 0; h < n_heads; ++h) {
+    const float* __restrict__ weight = hd.head[h].weight;
+    for (int i = threadIdx.x; i < PCLS * C; i += kThreads) hm_wsm[h * PCLS * C + i] = i < n_cls * C ? weight[i] : 0.f;
+  }
+  __syncthreads();
+  constexpr int ppb = kThreads >> LOG2CG;
+  const int cg = threadIdx.x & (CG - 1), pl = threadIdx.x >> LOG2CG;
+  const unsigned npix = static_cast<unsigned>(pixels), uhw = static_cast<unsigned>(HW);  // < 2^31 (launcher)
+  const unsigned passes = (npix + ppb - 1) / ppb;
+  for (unsigned ps = blockIdx.x; ps < passes; ps += gridDim.x) {  // all lanes stay in the loop: lane exchanges below
+    const unsigned p = ps * ppb + pl;
+    const bool live = p < npix;
+    float sum[PCLS];
+#pragma unroll
+    for (int k = 0; k < PCLS; ++k) sum[k] = 0.f;  // 0 + s_1 is s_1: the sum is ((s_1 + s_2) + ...) in head order
+    for (int h = 0; h < n_heads; ++h) {
+      float f[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      if (live) unpack8(static_cast<const u32x4*>(hd.head[h].x)[(static_cast<long>(p) << LOG2CG) + cg], f);
+      const float* __restrict__ bias = hd.head[h].bias;
+#pragma unroll
+      for (int k = 0; k < PCLS; ++k) {
+        const float s = head_pixel_logit_bf16<LOG2CG>(f, hm_wsm + (h * PCLS + k) * C, cg);
+        if (k < n_cls && (k & (CG - 1)) == cg) sum[k] += 1.0f / (1.0f + __expf(-(s + bias[k])));  // the lane that stores class k
+      }
+    }
+    const unsigned n = p / uhw, hw = p - n * uhw;
+    float* obase = out + static_cast<long>(n) * n_cls * uhw + hw;
+#pragma unroll
+    for (int k = 0; k < PCLS; ++k)
+      if (live && k < n_cls && (k & (CG - 1)) == cg) obase[static_cast<long>(k) * uhw] = sum[k] / count;
   }
 }
 
@@ -666,6 +720,53 @@ extern "C" int unetpp_head_fwd_bf16(const void* x, const float* weight, const fl
 #undef UNETPP_HEAD_BF_L
 #undef UNETPP_HEAD_BF_D
 #undef UNETPP_HEAD_BF
+  return launch_status();
+}
+
+extern "C" int unetpp_heads_mean_fwd_bf16(const unetpp_heads_mean* heads, int32_t N, int32_t H, int32_t W, int32_t C,
+                                          int32_t n_cls, float* out_nchw, void* stream) {
+  if (!heads || !out_nchw || heads->n_heads < 1 || heads->n_heads > UNETPP_MAX_HEADS || N < 1 || H < 1 || W < 1 || C < 1 ||
+      C > kHeadMaxC || n_cls < 1 || n_cls > kHeadMaxCls)
+    return UNETPP_EINVAL;
+  bool vec = true;
+  for (int h = 0; h < heads->n_heads; ++h) {
+    const unetpp_head_src& s = heads->head[h];
+    if (!s.x || !s.weight || !s.bias || (reinterpret_cast<uintptr_t>(s.x) & 1) != 0) return UNETPP_EINVAL;
+    vec = vec && a16(s.x);
+  }
+  const long pixels = static_cast<long>(N) * H * W;
+  const int CG = C >> 3;
+  // the octet form counts pixels in 32 bits (its element offsets are 64-bit)
+  if (vec && (C & 7) == 0 && (CG & (CG - 1)) == 0 && pixels < 0x7fffffffL) {
+    const long passes = (pixels + kThreads / CG - 1) / (kThreads / CG);
+    const dim3 grid(static_cast<unsigned>(passes < 256 * 16 ? passes : 256 * 16));
+#define UNETPP_HEADS_MEAN_BF(L, PC)                                                                                     \
+  do {                                                                                                                  \
+    note_kernel("heads_mean_bf16<" #L "," #PC ">");                                                                     \
+    hipLaunchKernelGGL((heads_mean_bf16_kernel<L, PC>), grid, dim3(kThreads),                                            \
+                       static_cast<size_t>(heads->n_heads) * PC * C * sizeof(float), ST(stream), *heads, pixels, H * W,  \
+                       n_cls, out_nchw);                                                                                \
+  } while (0)
+#define UNETPP_HEADS_MEAN_BF_L(L)                    \
+  do {                                               \
+    if (n_cls <= 4) UNETPP_HEADS_MEAN_BF(L, 4);      \
+    else if (n_cls <= 6) UNETPP_HEADS_MEAN_BF(L, 6); \
+    else UNETPP_HEADS_MEAN_BF(L, 8);                 \
+  } while (0)
+    switch (CG) {
+      case 1: UNETPP_HEADS_MEAN_BF_L(0); break;
+      case 2: UNETPP_HEADS_MEAN_BF_L(1); break;
+      case 4: UNETPP_HEADS_MEAN_BF_L(2); break;
+      case 8: UNETPP_HEADS_MEAN_BF_L(3); break;
+      default: UNETPP_HEADS_MEAN_BF_L(4); break;
+    }
+#undef UNETPP_HEADS_MEAN_BF_L
+#undef UNETPP_HEADS_MEAN_BF
+    return launch_status();
+  }
+  note_kernel("heads_mean_bf16_general");
+  hipLaunchKernelGGL(heads_mean_general_kernel<bf16_t>, dim3(grid_for8(pixels)), dim3(kThreads), 0, ST(stream), *heads, pixels,
+                     H * W, C, n_cls, out_nchw);
   return launch_status();
 }
 

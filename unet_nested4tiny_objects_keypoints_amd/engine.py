@@ -96,7 +96,7 @@ def tile_bias4(b):
     co = b.numel()
     plan = ops.current_plan()
     if plan is not None and USE_PLAN_COPIES and b.is_contiguous():
-        dst, ready = plan.copy_for(("bias4", b.data_ptr()), plan.phase, (b.data_ptr(), co),
+        dst, ready = plan.copy_for(("bias4", b.data_ptr()) + ops.phase_tag(plan.phase), plan.phase, (b.data_ptr(), co),
                                    lambda: (_empty(4 * co, b), [b], [(b, 0, 0, 4, co, 0, co)]))
         if ready:
             return dst
@@ -265,22 +265,64 @@ def _dropout_config(model, training):
     return p, seeds, masks, seed_dev
 
 
-def forward_impl(model, x, training: bool, save: bool):
-    """Runs the forward DAG of models/unet.py:255-300.  Returns (outputs, saved-for-backward or None)."""
+def needed_nodes(depth: int, head: int) -> List[Tuple[int, int]]:
+    """The nodes X_ij that head `head` (1 .. depth-1) depends on -- those with i + j <= head -- in the order the full
+    forward visits them: the encoder column top down, then the decoder columns left to right, each top down.  Every
+    input of a listed node (X_{i-1,0} of an encoder node; X_{i+1,j-1} and X_i0 .. X_{i,j-1} of a decoder node) is listed
+    before it.  ``needed_nodes(depth, depth - 1)`` is the whole graph."""
+    head = check_head(depth, head)
+    return [(i, 0) for i in range(head + 1)] + [(i, j) for j in range(1, head + 1) for i in range(head + 1 - j)]
+
+
+def check_head(depth: int, head) -> int:
+    """`head` as an int in 1 .. depth-1 (None = depth-1); anything else -- a bool and a float included -- is a ValueError."""
+    if head is None:
+        return depth - 1
+    if isinstance(head, bool) or not isinstance(head, int) or not 1 <= head <= depth - 1:
+        raise ValueError("head must be an int in 1..%d (or None for the last head), got %r" % (depth - 1, head))
+    return head
+
+
+def plan_phase(depth: int, head=None) -> str:
+    """The weight-image plan's name for a forward pass that runs needed_nodes(depth, head): "fwd" for the whole graph, a
+    name of its own per pruned depth -- such a pass records, and from then on packs in one launch, only the weights of the
+    nodes it runs (ops.phase_tag); whole and pruned passes on one model rebuild their own images each time they begin."""
+    head = check_head(depth, head)
+    return "fwd" if head == depth - 1 else "fwd/%d" % head
+
+
+def forward_impl(model, x, training: bool, save: bool, head: Optional[int] = None, ensemble: bool = False):
+    """Runs the forward DAG of models/unet.py:255-300.  Returns (outputs, saved-for-backward or None).
+    head = None: the whole graph and every head (``forward``).  head = J (``infer``): only needed_nodes(depth, J), and one
+    output -- head J, or the mean of heads 1 .. J when `ensemble`."""
     _check_input(model, x)
     _PENDING_COUNTERS.clear()
     try:
         if not USE_PACK_PLAN:
-            return _forward_impl(model, x, training, save)
+            return _forward_impl(model, x, training, save, head, ensemble)
         plan = _plan_of(model)
-        plan.begin("fwd")  # every weight image of the pass in one launch (after the first pass recorded the jobs)
+        plan.begin(plan_phase(model.depth, head))  # every weight image of the pass in one launch (after the first pass recorded the jobs)
         ops.set_pack_plan(plan)
         try:
-            return _forward_impl(model, x, training, save)
+            return _forward_impl(model, x, training, save, head, ensemble)
         finally:
             ops.set_pack_plan(None)
     finally:
         flush_batch_counters()
+
+
+def infer(model, x, head=None, ensemble: bool = False):
+    """The body of UNet_Nested.infer."""
+    top = check_head(model.depth, head)
+    if model.training:
+        raise RuntimeError("UNet_Nested.infer is the eval forward: call model.eval() first")
+    pruned_to = getattr(model, "pruned_to", None)
+    if pruned_to is not None and top > pruned_to:
+        raise RuntimeError("this model holds a checkpoint pruned to head %d: the nodes head %d needs were never loaded"
+                           % (pruned_to, top))
+    with torch.no_grad():
+        outs, _ = forward_impl(model, x, False, save=False, head=top, ensemble=bool(ensemble))
+    return outs[0]
 
 
 def _plan_of(model) -> "ops.PackPlan":
@@ -291,23 +333,24 @@ def _plan_of(model) -> "ops.PackPlan":
     return plan
 
 
-def _forward_impl(model, x, training: bool, save: bool):
+def _forward_impl(model, x, training: bool, save: bool, head: Optional[int] = None, ensemble: bool = False):
     b, _, h0, w0 = x.shape
     d = model.depth
+    top = d - 1 if head is None else head   # the last diagonal that runs; its encoder node is the deepest and is not pooled
     adt = _activation_dtype(model)
     x_nhwc = ops.nchw_to_nhwc(x.detach().contiguous())
     X: Dict[Tuple[int, int], torch.Tensor] = {}
     pairs: Dict[Tuple[int, int], _PairRec] = {}
     ups: Dict[Tuple[int, int], _UpRec] = {}
     inp, h, w = x_nhwc, h0, w0
-    for i in range(d):  # encoder column (:257-265)
-        with ops.region("X%d0.fwd" % i):
-            r = _pair_fwd(getattr(model, "conv%d0" % i), [V(inp)], b, h, w, training, pool=(i < d - 1), adt=adt)
-        pairs[(i, 0)], X[(i, 0)] = r, r.out
-        if i < d - 1:
-            inp, h, w = r.pooled, h // 2, w // 2
-    for j in range(1, d):  # decoder columns (:268-280)
-        for i in range(d - j):
+    for (i, j) in needed_nodes(d, top):
+        if j == 0:  # encoder column (:257-265)
+            with ops.region("X%d0.fwd" % i):
+                r = _pair_fwd(getattr(model, "conv%d0" % i), [V(inp)], b, h, w, training, pool=(i < top), adt=adt)
+            pairs[(i, 0)], X[(i, 0)] = r, r.out
+            if i < top:
+                inp, h, w = r.pooled, h // 2, w // 2
+        else:  # decoder columns (:268-280)
             mod = getattr(model, "up_concat%d%d" % (i, j))
             hi, wi = h0 >> i, w0 >> i
             u = _up_fwd(mod.up, model.is_deconv, X[(i + 1, j - 1)], b, hi // 2, wi // 2, adt)
@@ -316,10 +359,17 @@ def _forward_impl(model, x, training: bool, save: bool):
             ups[(i, j)], pairs[(i, j)], X[(i, j)] = u, r, r.out
     p_drop, seeds, masks, seed_dev = _dropout_config(model, training)
     outs = []
-    for j in range(1, d):  # heads (:283-286)
-        head = getattr(model, "final_%d" % j)
+    if head is not None and ensemble:  # the mean of heads 1 .. head in one launch; the head maps are never written
+        finals = [getattr(model, "final_%d" % j) for j in range(1, head + 1)]
         o = torch.empty((b, model.n_classes, h0, w0), dtype=torch.float32, device=x.device)
-        ops.head_fwd(X[(0, j)], head.weight.detach().view(model.n_classes, -1), head.bias.detach(), p_drop,
+        ops.heads_mean_fwd([X[(0, j)] for j in range(1, head + 1)],
+                           [f.weight.detach().view(model.n_classes, -1) for f in finals],
+                           [f.bias.detach() for f in finals], o)
+        outs.append(o)
+    for j in (range(1, d) if head is None else () if ensemble else (head,)):  # heads (:283-286)
+        final = getattr(model, "final_%d" % j)
+        o = torch.empty((b, model.n_classes, h0, w0), dtype=torch.float32, device=x.device)
+        ops.head_fwd(X[(0, j)], final.weight.detach().view(model.n_classes, -1), final.bias.detach(), p_drop,
                      seeds[j - 1], None if masks is None else masks[j - 1], o, seed_dev=seed_dev)
         outs.append(o)
     if not save:

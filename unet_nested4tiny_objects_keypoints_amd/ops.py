@@ -384,6 +384,13 @@ def current_plan() -> Optional[PackPlan]:
     return _PLAN if (_PLAN is not None and _PLAN.phase is not None) else None
 
 
+def phase_tag(phase) -> tuple:
+    """() for the two whole-network passes, (phase,) for a pruned inference pass (engine.plan_phase): part of the key of
+    whatever a plan records, so that a pruned pass owns its images and its copies -- its ``begin`` packs the weights of
+    the nodes it runs and nothing else, and the entries of the whole-network passes stay exactly what they were."""
+    return () if phase in ("fwd", "bwd") else (phase,)
+
+
 def gemm_pixel_blocks(n: int, h: int, w: int) -> int:
     return int(_lib.lib().unetpp_gemm_pixel_blocks(n, h, w))
 
@@ -459,7 +466,7 @@ def gemm_fwd(n: int, h: int, w: int, taps: int, ins: Sequence[V], outs: Sequence
             if from_src and _PLAN is not None and _PLAN.phase is not None:
                 sig = (weight.t.data_ptr(), weight.s_t, weight.s_k, weight.s_ko, weight.s_n, weight.s_no, weight.k_inner,
                        weight.n_inner, weight.flip, taps, d.flags, tuple(v.c_len for v in d.inp[:d.n_in]),
-                       tuple(v.c_len for v in d.out[:d.n_out]))
+                       tuple(v.c_len for v in d.out[:d.n_out])) + phase_tag(_PLAN.phase)
                 image, ready = _PLAN.image_for(sig, n_img, weight, d)
             else:
                 image = torch.empty(n_img, dtype=torch.float32, device=weight.device)
@@ -640,6 +647,32 @@ def head_fwd(x, weight, bias, p_drop, seed, mask, out_nchw, seed_dev=None):
     fn = _lib.lib().unetpp_head_fwd_bf16 if _is_bf16(x) else _lib.lib().unetpp_head_fwd
     check(fn(_ptr(x), _ptr(weight), _ptr(bias), n, h, w, c, n_cls, float(p_drop), C.c_uint64(seed), _ptr(mask),
              _ptr(seed_dev), _ptr(out_nchw), _stream()), "unetpp_head_fwd")
+
+
+def heads_mean_fwd(xs, weights, biases, out_nchw):
+    """out_nchw [N, n_cls, H, W] fp32 = (((s_1 + s_2) + ...) + s_n) / float(n), s_h = sigmoid(bias_h + x_h . weight_h): the
+    mean of n = len(xs) <= 8 sigmoid heads in ONE launch that reads every NHWC feature tensor xs[h] (all fp32, or all
+    bf16) once and never writes the individual head maps.  weights[h] [n_cls, C], biases[h] [n_cls]; no dropout."""
+    n_heads = len(xs)
+    if not (1 <= n_heads <= _lib.MAX_HEADS) or len(weights) != n_heads or len(biases) != n_heads:
+        raise ValueError("heads_mean_fwd takes 1..%d heads with one weight and one bias each" % _lib.MAX_HEADS)
+    adt = xs[0].dtype
+    if adt not in _ACT_DTYPES:
+        raise TypeError("features must be float32 or bfloat16, got %s" % adt)
+    n, h, w, c = xs[0].shape
+    n_cls = weights[0].shape[0]
+    d = _lib.HeadsMean()
+    d.n_heads = n_heads
+    for i, (x, wt, b) in enumerate(zip(xs, weights, biases)):
+        if tuple(_need(x, "head features", adt).shape) != (n, h, w, c):
+            raise ValueError("every head reads a feature tensor of the same shape")
+        if tuple(_need(wt, "head weight").shape) != (n_cls, c) or _need(b, "head bias").numel() != n_cls:
+            raise ValueError("head weight must be [n_cls, C] and bias [n_cls]")
+        d.head[i].x, d.head[i].weight, d.head[i].bias = x.data_ptr(), wt.data_ptr(), b.data_ptr()
+    if tuple(_need(out_nchw, "output").shape) != (n, n_cls, h, w):
+        raise ValueError("output must be [N, n_cls, H, W]")
+    fn = _lib.lib().unetpp_heads_mean_fwd_bf16 if adt == torch.bfloat16 else _lib.lib().unetpp_heads_mean_fwd
+    check(fn(C.byref(d), n, h, w, c, n_cls, _ptr(out_nchw), _stream()), "unetpp_heads_mean_fwd")
 
 
 def head_bwd(d_out, out, x, weight, p_drop, seed, mask, dx, accumulate, gate_x=False, seed_dev=None):

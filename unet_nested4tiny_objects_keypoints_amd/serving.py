@@ -19,20 +19,28 @@ class GraphedForward:
     """outs = GraphedForward(model, example)(x) -- eval forward of ``model`` for inputs shaped like ``example``.
 
     The returned tensors are the graph's static outputs: they are overwritten by the next call (clone what must live
-    longer)."""
+    longer).  ``head=J`` (UNet_Nested only) captures ``model.infer(example, J, ensemble)`` instead -- the network cut at
+    head J, or the mean of heads 1 .. J -- and returns that single static tensor; ``head=None`` is the full forward."""
 
-    def __init__(self, model: torch.nn.Module, example: torch.Tensor, warmup: int = 3):
+    def __init__(self, model: torch.nn.Module, example: torch.Tensor, warmup: int = 3, head=None, ensemble: bool = False):
         if not example.is_cuda:
             raise RuntimeError("GraphedForward needs a GPU input: this path has no CPU fallback")
         if model.training:
             raise RuntimeError("GraphedForward captures the eval forward: call model.eval() first")
+        phase = "fwd"
+        if head is not None:
+            from . import engine
+            phase = engine.plan_phase(model.depth, head)   # (ValueError for a head the model does not have)
+            run = lambda t: model.infer(t, head, ensemble)  # noqa: E731
+        else:
+            run = model
         self.model = model
         self._x = example.clone()
         side = torch.cuda.Stream(device=example.device)   # warm-up AND capture run on this one stream (as graph.py)
         side.wait_stream(torch.cuda.current_stream(example.device))
         with torch.no_grad(), torch.cuda.stream(side):
             for _ in range(max(1, warmup)):  # first passes record the weight-image jobs and size the allocator pools
-                model(self._x)
+                run(self._x)
         side.synchronize()
         # The captured launches carry raw pointers into the model's weight-image plan (the images and the device job
         # table of the in-graph pack launch): pin the plan so that neither is evicted / freed while this graph lives,
@@ -43,11 +51,13 @@ class GraphedForward:
             self._plan.pin()
         self._graph = torch.cuda.CUDAGraph()
         with torch.no_grad(), torch.cuda.graph(self._graph, stream=side):
-            outs = model(self._x)
+            outs = run(self._x)
         torch.cuda.current_stream(example.device).wait_stream(side)
+        # (the plan's copy tables -- the bias rows' launch -- are not held here: the plan keeps a replaced one alive while
+        # it is pinned, and the plan itself lives in the model, which this object references)
         self._held = None
         if self._plan is not None:
-            self._held = (self._plan._tables.get("fwd"), [e.image for e in self._plan.entries.values()])
+            self._held = (self._plan._tables.get(phase), [e.image for e in self._plan.entries.values()])
         self._param_ptrs = [p.data_ptr() for p in model.parameters()]
         self._outs: Tuple[torch.Tensor, ...] = tuple(outs) if isinstance(outs, (tuple, list)) else (outs,)
         self._single = not isinstance(outs, (tuple, list))

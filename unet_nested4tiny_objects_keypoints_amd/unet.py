@@ -145,6 +145,9 @@ class UNet_Nested(nn.Module):
         # storage type of the activations and their gradients in HBM: fp32 (reference numerics), or bf16 with fp32
         # accumulation / statistics / parameter gradients (BASELINE configs[3]/[4]); parameters stay fp32 either way
         self.activation_dtype = torch.float32
+        # head J when the parameters came from a pruned checkpoint (checkpoint.load_pruned): only the nodes head J needs
+        # hold trained weights, so forward() and infer(head > J) refuse to run.  None = every node is usable.
+        self.pruned_to = None
 
     def set_activation_dtype(self, dtype):
         if dtype not in (torch.float32, torch.bfloat16):
@@ -153,7 +156,26 @@ class UNet_Nested(nn.Module):
         return self
 
     def forward(self, inputs):
+        if getattr(self, "pruned_to", None) is not None:
+            raise RuntimeError("this model holds a checkpoint pruned to head %d: the other nodes were never loaded; use "
+                               "infer(x, head <= %d), or load a full state_dict" % (self.pruned_to, self.pruned_to))
         return engine.run(self, inputs)
+
+    def infer(self, inputs, head=None, ensemble=False):
+        """Eval-only inference cut at a deep-supervision head: fp32 ``[B, n_classes, H, W]``, no ``grad_fn``.
+
+        A nested U-Net is trained with one head per decoder column so that it can be cut afterwards: head ``J`` depends
+        only on the nodes ``X_ij`` with ``i + j <= J`` (``engine.needed_nodes``).  ``head`` is an int in ``1 .. depth-1``
+        (``None`` = the last head).
+
+        * ``ensemble=False`` -- the fast mode: runs only those nodes and that one head.  Every node issues the launches
+          of the full graph with the same operands, so the result is bit-identical to ``model(x)[head - 1]`` in eval mode.
+        * ``ensemble=True`` -- the accurate mode, the selection models/unet.py:293-298 keeps as comments: the mean of heads
+          ``1 .. head``, ``(((s_1 + s_2) + ...) + s_n) / n``, by one kernel that never writes the individual maps.
+
+        Raises ``RuntimeError`` in training mode and ``ValueError`` for any other ``head``; input checks as ``forward``.
+        ``validate_step(model, ..., forward=lambda x: (model.infer(x, 1),))`` validates a pruned network."""
+        return engine.infer(self, inputs, head, ensemble)
 
     # ---- weight-image cache control (ops.PackPlan) ------------------------------------------------
     def freeze_weight_images(self, frozen: bool = True):
@@ -178,6 +200,8 @@ class UNet_Nested(nn.Module):
     def load_state_dict(self, *args, **kwargs):
         out = super().load_state_dict(*args, **kwargs)
         self.invalidate_weight_images()
+        if not getattr(out, "missing_keys", None):   # a full load: every node holds loaded weights again
+            self.pruned_to = None
         return out
 
     def train(self, mode: bool = True):
