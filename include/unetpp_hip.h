@@ -267,6 +267,11 @@ int unetpp_bn_finalize(const float* partial, int64_t n_blocks, int32_t C, int64_
 int unetpp_bn_eval_coeffs(const float* gamma, const float* beta, const float* running_mean,
                           const float* running_var, float eps, int32_t C, float* scale, float* shift,
                           void* stream);
+/* the same coefficients (the same kernel: identical bits) plus what the backward of a frozen layer needs: invstd =
+ * 1/sqrt(running_var + eps) and a snapshot of running_mean, both [C] (added within ABI 12) */
+int unetpp_bn_eval_coeffs_stats(const float* gamma, const float* beta, const float* running_mean,
+                                const float* running_var, float eps, int32_t C, float* scale, float* shift,
+                                float* mean, float* invstd, void* stream);
 /* act = relu?(y*scale + shift) (scale may be NULL = identity);  optional fused nn.MaxPool2d(2)
  * (models/unet.py:219): pooled [N,H/2,W/2,C] and pool_idx (uint8 window index 0..3, first max wins).
  * act may be NULL when only the pooled output is wanted; pool_idx may be NULL when the winners are not (forward-only
@@ -305,6 +310,24 @@ int unetpp_bn_bwd_apply_pool(const float* d_act, const float* y, const float* sc
                              const float* mean, const float* invstd, const float* gamma, const float* dgamma,
                              const float* dbeta, const float* d_pooled, const uint8_t* pool_idx, int32_t N, int32_t H,
                              int32_t W, int32_t C, float* dy, void* stream);
+
+/* BatchNorm + ReLU backward of a FROZEN layer -- one that normalised with its running statistics (eval mode, or
+ * BatchNormParams.eval() inside a training model); added within ABI 12.  With fixed statistics dy does not depend on
+ * the channel sums, so ONE streaming pass (two reads, one write) replaces reduce + finalize + apply:
+ *     g  = d_act (+ d_pooled where this pixel won its 2x2 window; d_pooled / pool_idx both NULL = no pooled consumer)
+ *     gg = (fma(y, scale, shift) > 0) ? g : 0          scale / shift: unetpp_bn_eval_coeffs[_stats], the forward's bits
+ *     dy = gg * scale                                  dy may alias d_act
+ * partial != NULL: also partial[block][c] = (sum gg, sum gg * (y - mean) * invstd) in a fixed order (no float atomics),
+ * unetpp_bn_frozen_bwd_blocks(N*H*W, C) rows (unused ones zeroed), finished into dbeta / dgamma by
+ * unetpp_bn_bwd_finalize; mean / invstd from unetpp_bn_eval_coeffs_stats.  partial == NULL (gamma and beta frozen too):
+ * no sums, no LDS, mean / invstd may be NULL, and dy has the same bits.  Forms: 16-byte vectors (C % 4 == 0, aligned
+ * d_act / y / dy), scalar, and with d_pooled the row-structured routing form, which needs unetpp_bn_bwd_pool_ok and
+ * 16-byte aligned coefficients (otherwise: unetpp_maxpool_bwd into d_act first, then d_pooled = NULL).
+ * UNETPP_EINVAL without touching the device for NULL operands, C < 1 or N*H*W < 1. */
+int64_t unetpp_bn_frozen_bwd_blocks(int64_t pixels, int32_t C);
+int unetpp_bn_frozen_bwd(const float* d_act, const float* y, const float* scale, const float* shift,
+                         const float* mean, const float* invstd, const float* d_pooled, const uint8_t* pool_idx,
+                         int32_t N, int32_t H, int32_t W, int32_t C, float* dy, float* partial, void* stream);
 
 /* ---- deep-supervision head: sigmoid(Conv1x1(Dropout(x))) (models/unet.py:242-244,254,283-286) ---- */
 /* x NHWC [P, C]; weight [n_cls, C]; out NCHW [N, n_cls, H, W].  Dropout: keep mask regenerated from
@@ -400,6 +423,12 @@ int unetpp_bn_bwd_apply_bf16(const void* d_act, const void* y, const float* scal
                              const float* mean, const float* invstd, const float* gamma, const float* dgamma,
                              const float* dbeta, const void* d_pooled, const uint8_t* pool_idx,
                              int32_t N, int32_t H, int32_t W, int32_t C, void* dy, void* stream);
+/* frozen-layer BatchNorm backward on bf16 octets (see unetpp_bn_frozen_bwd): fp32 arithmetic and sums, dy rounded to
+ * bf16 once; routing of d_pooled (even H, W) inside the same kernel; C = 8 * 2^k <= 2048, 16-byte aligned tensors */
+int64_t unetpp_bn_frozen_bwd_blocks_bf16(int64_t pixels, int32_t C);
+int unetpp_bn_frozen_bwd_bf16(const void* d_act, const void* y, const float* scale, const float* shift,
+                              const float* mean, const float* invstd, const void* d_pooled, const uint8_t* pool_idx,
+                              int32_t N, int32_t H, int32_t W, int32_t C, void* dy, float* partial, void* stream);
 int unetpp_head_fwd_bf16(const void* x, const float* weight, const float* bias, int32_t N, int32_t H, int32_t W,
                          int32_t C, int32_t n_cls, float p_drop, uint64_t seed, const uint8_t* mask, const uint64_t* seed_dev,
                          float* out_nchw, void* stream);

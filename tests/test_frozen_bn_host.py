@@ -1,0 +1,91 @@
+"""Host side of the frozen BatchNorm feature (no GPU): argument validation of the new entry points, the unchanged ABI
+version, and UNet_Nested.freeze_batchnorm / UNet.freeze_batchnorm as flag bookkeeping."""
+import ctypes
+
+import pytest
+import torch
+
+
+def _lib():
+    from unet_nested4tiny_objects_keypoints_amd import _lib
+    _lib.build_library()
+    return _lib, _lib.lib()
+
+
+def test_new_entry_points_validate_without_a_device():
+    mod, lib = _lib()
+    assert lib.unetpp_abi_version() == 12 == mod.ABI_VERSION
+    buf = (ctypes.c_float * 64)()
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    for fn in (lib.unetpp_bn_frozen_bwd, lib.unetpp_bn_frozen_bwd_bf16):
+        good = [p, p, p, p, p, p, None, None, 1, 2, 2, 8, p, p, None]
+        for i in (0, 1, 2, 3, 12):                      # d_act, y, scale, shift, dy
+            bad = list(good)
+            bad[i] = None
+            assert fn(*bad) == -1, (fn, i)
+        for i in (4, 5):                                # the sums need mean and invstd
+            bad = list(good)
+            bad[i] = None
+            assert fn(*bad) == -1, (fn, i)
+        for i, v in ((8, 0), (9, 0), (10, 0), (11, 0), (11, -8)):   # pixels < 1, C < 1
+            bad = list(good)
+            bad[i] = v
+            assert fn(*bad) == -1, (fn, i, v)
+        bad = list(good)
+        bad[6] = p                                      # d_pooled without pool_idx
+        assert fn(*bad) == -1
+    assert lib.unetpp_bn_frozen_bwd_bf16(p, p, p, p, p, p, None, None, 1, 2, 2, 12, p, p, None) == -1   # C != 8 * 2^k
+    good = [p, p, p, p, 1e-5, 8, p, p, p, p, None]
+    for i in (0, 1, 2, 3, 6, 7, 8, 9):
+        bad = list(good)
+        bad[i] = None
+        assert lib.unetpp_bn_eval_coeffs_stats(*bad) == -1, i
+    bad = list(good)
+    bad[5] = 0
+    assert lib.unetpp_bn_eval_coeffs_stats(*bad) == -1
+    assert lib.unetpp_bn_frozen_bwd_blocks(0, 8) == 0 and lib.unetpp_bn_frozen_bwd_blocks(8, 0) == 0
+    assert lib.unetpp_bn_frozen_bwd_blocks_bf16(0, 8) == 0 and lib.unetpp_bn_frozen_bwd_blocks_bf16(8, 12) == 0
+
+
+def test_block_queries_follow_the_stated_formulas():
+    _, lib = _lib()
+
+    def blocks_for(pixels, c, vec):
+        cg = c // 4 if vec else c
+        want = max(1, min(2048, -(-pixels * cg // 256)))
+        return -(-want // cg) * cg
+    for pixels, c in ((1, 1), (60, 8), (70, 6), (16384, 32), (131 * 128, 128), (90000, 6), (24, 1024), (1 << 22, 32)):
+        want = max(blocks_for(pixels, c, True) if c % 4 == 0 else 0, blocks_for(pixels, c, False))
+        assert lib.unetpp_bn_frozen_bwd_blocks(pixels, c) == want, (pixels, c)
+    for pixels, c in ((1, 8), (192, 128), (131 * 128, 256), (1 << 22, 32)):
+        assert lib.unetpp_bn_frozen_bwd_blocks_bf16(pixels, c) == max(1, min(2048, -(-pixels * (c // 8) // 256)))
+
+
+def _models():
+    from unet_nested4tiny_objects_keypoints_amd import UNet, UNet_Nested
+    return [UNet_Nested(in_channels=1, n_classes=4, feature_scale=8),
+            UNet(n_classes=2, n_channels=1, widths=(4, 4, 8, 8, 8))]
+
+
+@pytest.mark.parametrize("which", [0, 1], ids=["UNet_Nested", "UNet"])
+def test_freeze_batchnorm_sets_exactly_the_batchnorm_flags(which):
+    from unet_nested4tiny_objects_keypoints_amd.unet import BatchNormParams
+    m = _models()[which].train()
+    bns = [mod for mod in m.modules() if isinstance(mod, BatchNormParams)]
+    bn_params = {id(p) for mod in bns for p in mod.parameters()}
+    others = [mod for mod in m.modules() if not isinstance(mod, BatchNormParams)]
+    assert bns and m.freeze_batchnorm() is m
+    assert all(not mod.training for mod in bns) and all(mod.training for mod in others)
+    assert all(p.requires_grad == (id(p) not in bn_params) for p in m.parameters())
+    assert m.freeze_batchnorm(False) is m                       # back: modes and requires_grad
+    assert all(mod.training for mod in m.modules()) and all(p.requires_grad for p in m.parameters())
+    m.freeze_batchnorm(affine=False)                            # modes only
+    assert all(not mod.training for mod in bns) and all(p.requires_grad for p in m.parameters())
+    m.freeze_batchnorm()
+    m.train()                                                   # torch semantics: train() un-freezes the modes ...
+    assert all(mod.training for mod in m.modules())
+    assert all(p.requires_grad == (id(p) not in bn_params) for p in m.parameters())   # ... and leaves requires_grad alone
+    m.eval().freeze_batchnorm(False, affine=False)              # a layer in training mode inside an eval model
+    assert all(mod.training for mod in bns) and not any(mod.training for mod in others)
+    for mod in bns:                                             # buffers and values untouched throughout
+        assert int(mod.num_batches_tracked) == 0 and torch.equal(mod.running_var, torch.ones_like(mod.running_var))

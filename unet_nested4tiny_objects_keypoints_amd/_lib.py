@@ -185,6 +185,12 @@ SIGNATURES = {
     # ensemble head of the eval forward (added within ABI 12)
     "unetpp_heads_mean_fwd": (C.c_int, [C.POINTER(HeadsMean), _I32, _I32, _I32, _I32, _I32, _P, _P]),
     "unetpp_heads_mean_fwd_bf16": (C.c_int, [C.POINTER(HeadsMean), _I32, _I32, _I32, _I32, _I32, _P, _P]),
+    # backward of a BatchNorm layer that normalised with its running statistics (added within ABI 12)
+    "unetpp_bn_eval_coeffs_stats": (C.c_int, [_P, _P, _P, _P, _F, _I32, _P, _P, _P, _P, _P]),
+    "unetpp_bn_frozen_bwd_blocks": (_I64, [_I64, _I32]),
+    "unetpp_bn_frozen_bwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P]),
+    "unetpp_bn_frozen_bwd_blocks_bf16": (_I64, [_I64, _I32]),
+    "unetpp_bn_frozen_bwd_bf16": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P]),
     "unetpp_copy_jobs": (C.c_int, [_P, _I32, _I64, _P]),
     "unetpp_heatmap_workspace_bytes": (_I64, [_I32, _I32, _I32]),
     "unetpp_create_heatmap": (C.c_int, [_P, _I32, _I32, _I32, _I32, _F, _P, _P, _P]),

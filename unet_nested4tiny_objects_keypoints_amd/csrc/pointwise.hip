@@ -114,14 +114,20 @@ __global__ __launch_bounds__(kFinThreads) void bn_finalize_kernel(const float* p
   }
 }
 
+// mean_out / invstd_out (both or neither): what the frozen BatchNorm backward needs besides the coefficients -- a snapshot
+// of the running mean and 1/sqrt(running_var + eps).  One kernel for both entry points: scale and shift have the same bits.
 __global__ void bn_eval_coeffs_kernel(const float* gamma, const float* beta, const float* rm, const float* rv, float eps,
-                                      int C, float* scale, float* shift) {
+                                      int C, float* scale, float* shift, float* mean_out, float* invstd_out) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
   const float is = 1.0f / sqrtf(rv[c] + eps);
   const float sc = gamma[c] * is;
   scale[c] = sc;
   shift[c] = beta[c] - rm[c] * sc;
+  if (mean_out != nullptr) {
+    mean_out[c] = rm[c];
+    invstd_out[c] = is;
+  }
 }
 
 __global__ __launch_bounds__(kFinThreads) void bn_bwd_finalize_kernel(const float* partial, long n_blocks, int C,
@@ -477,6 +483,115 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_apply_pool_kernel(
       dy[row * row_items + j] = out;  // may alias d_act: the item was read by this thread above
     }
   }
+}
+
+// ---- BatchNorm backward of a FROZEN layer (normalised with its running statistics): dy does not depend on the channel
+// sums, so one streaming pass does everything -- gg = (fma(y, scale, shift) > 0) ? g : 0, dy = gg * scale -- and the
+// (sum gg, sum gg * xhat) rows for dgamma / dbeta are a by-product (SUMS; without it no LDS, no partial rows).
+// Grid stride is a multiple of CG, so a thread keeps one channel group and its coefficients in registers.
+// dy may alias d_act (neither is __restrict__): an item is read and written by the same thread.
+// the workgroup's row of the partial buffer: thread t holds channel group (base + t) % CG; fixed order, no atomics
+template <int VEC>
+__device__ __forceinline__ void frozen_block_sums(float (&sm)[kThreads][VEC * 2], const float (&s1)[VEC],
+                                                  const float (&s2)[VEC], int CG, int base, float* __restrict__ partial) {
+#pragma unroll
+  for (int k = 0; k < VEC; ++k) {
+    sm[threadIdx.x][2 * k] = s1[k];
+    sm[threadIdx.x][2 * k + 1] = s2[k];
+  }
+  __syncthreads();
+  const int C = CG * VEC;
+  for (int cc = threadIdx.x; cc < C; cc += kThreads) {
+    const int cg = cc / VEC, k = cc % VEC;
+    float a = 0.f, b = 0.f;
+    for (int t = (cg - base + CG) % CG; t < kThreads; t += CG) {
+      a += sm[t][2 * k];
+      b += sm[t][2 * k + 1];
+    }
+    partial[(static_cast<long>(blockIdx.x) * C + cc) * 2 + 0] = a;
+    partial[(static_cast<long>(blockIdx.x) * C + cc) * 2 + 1] = b;
+  }
+}
+
+template <int VEC, bool SUMS>
+__global__ __launch_bounds__(kThreads) void bn_frozen_bwd_kernel(const float* d_act, const float* __restrict__ y,
+                                                                 const float* __restrict__ scale,
+                                                                 const float* __restrict__ shift,
+                                                                 const float* __restrict__ mean,
+                                                                 const float* __restrict__ invstd, long items, int CG,
+                                                                 float* dy, float* __restrict__ partial) {
+  using P = typename Pack<VEC>::T;
+  __shared__ float sm[SUMS ? kThreads : 1][VEC * 2];
+  const long first = blockIdx.x * static_cast<long>(kThreads) + threadIdx.x;
+  const int c = static_cast<int>(first % CG) * VEC;
+  float sc[VEC], sh[VEC], mu[VEC], is[VEC], s1[VEC], s2[VEC];
+#pragma unroll
+  for (int k = 0; k < VEC; ++k) {
+    sc[k] = scale[c + k];
+    sh[k] = shift[c + k];
+    mu[k] = SUMS ? mean[c + k] : 0.f;
+    is[k] = SUMS ? invstd[c + k] : 0.f;
+    s1[k] = 0.f;
+    s2[k] = 0.f;
+  }
+  for (long i = first; i < items; i += static_cast<long>(gridDim.x) * kThreads) {
+    const P g = reinterpret_cast<const P*>(d_act)[i];
+    const P v = reinterpret_cast<const P*>(y)[i];
+    P out;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+      const float yy = lane_of<VEC>(v, k);
+      const float gg = (fmaf(yy, sc[k], sh[k]) > 0.f) ? lane_of<VEC>(g, k) : 0.f;
+      if constexpr (SUMS) {
+        s1[k] += gg;
+        s2[k] += gg * (yy - mu[k]) * is[k];
+      }
+      lane_of<VEC>(out, k) = gg * sc[k];
+    }
+    reinterpret_cast<P*>(dy)[i] = out;
+  }
+  if constexpr (SUMS) {
+    const int base = static_cast<int>((blockIdx.x * static_cast<long>(kThreads)) % CG);
+    frozen_block_sums<VEC>(sm, s1, s2, CG, base, partial);
+  }
+}
+
+// the pooled consumer's gradient routed to its argmax while d_act is read (routed_grad); row structured, conditions of
+// bn_bwd_pool_ok.  thread t holds quad t & (CG - 1) for all its items
+template <bool SUMS>
+__global__ __launch_bounds__(kThreads) void bn_frozen_bwd_pool_kernel(
+    const f32x4* d_act, const f32x4* __restrict__ y, const f32x4* __restrict__ scale, const f32x4* __restrict__ shift,
+    const f32x4* __restrict__ mean, const f32x4* __restrict__ invstd, const f32x4* __restrict__ d_pooled,
+    const uint32_t* __restrict__ pool_idx, unsigned rows, unsigned W, unsigned log2CG, f32x4* dy,
+    float* __restrict__ partial) {
+  __shared__ float sm[SUMS ? kThreads : 1][8];
+  const unsigned CG = 1u << log2CG, cg = threadIdx.x & (CG - 1), row_items = W << log2CG;
+  const f32x4 sc = scale[cg], sh = shift[cg];
+  f32x4 mu = {0.f, 0.f, 0.f, 0.f}, is = {0.f, 0.f, 0.f, 0.f};
+  if constexpr (SUMS) {
+    mu = mean[cg];
+    is = invstd[cg];
+  }
+  float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
+  for (unsigned row = blockIdx.x; row < rows; row += gridDim.x) {
+    for (unsigned j = threadIdx.x; j < row_items; j += kThreads) {
+      const f32x4 g = routed_grad(d_act, d_pooled, pool_idx, row, j >> log2CG, cg, log2CG, row_items);
+      const f32x4 v = y[row * row_items + j];
+      f32x4 out;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const float gg = (fmaf(v[k], sc[k], sh[k]) > 0.f) ? g[k] : 0.f;
+        if constexpr (SUMS) {
+          s1[k] += gg;
+          s2[k] += gg * (v[k] - mu[k]) * is[k];
+        }
+        out[k] = gg * sc[k];
+      }
+      dy[row * row_items + j] = out;  // may alias d_act: the item was read by this thread above
+    }
+  }
+  if constexpr (SUMS)
+    frozen_block_sums<4>(sm, s1, s2, static_cast<int>(CG), 0, partial);
 }
 
 
@@ -1256,7 +1371,18 @@ extern "C" int unetpp_bn_eval_coeffs(const float* gamma, const float* beta, cons
   if (!gamma || !beta || !running_mean || !running_var || C < 1 || !scale || !shift) return UNETPP_EINVAL;
   note_kernel("bn_eval_coeffs");
   hipLaunchKernelGGL(bn_eval_coeffs_kernel, dim3((C + 63) / 64), dim3(64), 0, ST(stream), gamma, beta, running_mean,
-                     running_var, eps, C, scale, shift);
+                     running_var, eps, C, scale, shift, static_cast<float*>(nullptr), static_cast<float*>(nullptr));
+  return launch_status();
+}
+
+extern "C" int unetpp_bn_eval_coeffs_stats(const float* gamma, const float* beta, const float* running_mean,
+                                           const float* running_var, float eps, int32_t C, float* scale, float* shift,
+                                           float* mean, float* invstd, void* stream) {
+  if (!gamma || !beta || !running_mean || !running_var || C < 1 || !scale || !shift || !mean || !invstd)
+    return UNETPP_EINVAL;
+  note_kernel("bn_eval_coeffs/stats");
+  hipLaunchKernelGGL(bn_eval_coeffs_kernel, dim3((C + 63) / 64), dim3(64), 0, ST(stream), gamma, beta, running_mean,
+                     running_var, eps, C, scale, shift, mean, invstd);
   return launch_status();
 }
 
@@ -1512,6 +1638,89 @@ extern "C" int unetpp_bn_bwd_apply_pool(const float* d_act, const float* y, cons
                      reinterpret_cast<const f32x4*>(d_pooled), reinterpret_cast<const uint32_t*>(pool_idx), inv_count,
                      static_cast<unsigned>(img_rows), static_cast<unsigned>(W), ilog2(static_cast<unsigned>(C >> 2)),
                      reinterpret_cast<f32x4*>(dy));
+  return launch_status();
+}
+
+namespace {
+// blocks of the frozen BatchNorm backward: one item per thread up to kFrozenCap workgroups, then a grid-stride loop; a
+// multiple of the channel-group count so that the grid stride keeps every thread on one channel group
+constexpr long kFrozenCap = 2048;
+inline long bn_frozen_blocks_for(long pixels, int C, bool vec) {
+  const int CG = vec ? C / 4 : C;
+  const long items = pixels * CG;
+  long want = (items + kThreads - 1) / kThreads;
+  if (want > kFrozenCap) want = kFrozenCap;
+  if (want < 1) want = 1;
+  return ((want + CG - 1) / CG) * CG;
+}
+}  // namespace
+
+extern "C" int64_t unetpp_bn_frozen_bwd_blocks(int64_t pixels, int32_t C) {
+  if (pixels < 1 || C < 1) return 0;
+  // rows of the partial buffer: the upper bound over the vector, scalar and pool-routing forms (the last runs
+  // min(N * H, this) workgroups)
+  const long a = (C % 4 == 0) ? bn_frozen_blocks_for(pixels, C, true) : 0;
+  const long b = bn_frozen_blocks_for(pixels, C, false);
+  return a > b ? a : b;
+}
+
+extern "C" int unetpp_bn_frozen_bwd(const float* d_act, const float* y, const float* scale, const float* shift,
+                                    const float* mean, const float* invstd, const float* d_pooled,
+                                    const uint8_t* pool_idx, int32_t N, int32_t H, int32_t W, int32_t C, float* dy,
+                                    float* partial, void* stream) {
+  if (!d_act || !y || !scale || !shift || !dy || C < 1 || N < 1 || H < 1 || W < 1) return UNETPP_EINVAL;
+  if (partial != nullptr && (!mean || !invstd)) return UNETPP_EINVAL;
+  if ((d_pooled == nullptr) != (pool_idx == nullptr)) return UNETPP_EINVAL;
+  const long pixels = static_cast<long>(N) * H * W;
+  const long rows_buf = unetpp_bn_frozen_bwd_blocks(pixels, C);  // rows of the partial buffer; unused ones are zeroed
+  if (d_pooled != nullptr) {
+    if (!bn_bwd_pool_ok(N, H, W, C)) return UNETPP_EINVAL;
+    if (!aligned16(d_act) || !aligned16(y) || !aligned16(dy) || !aligned16(scale) || !aligned16(shift) ||
+        !aligned16(d_pooled) || (reinterpret_cast<uintptr_t>(pool_idx) & 3) != 0 ||
+        (partial != nullptr && (!aligned16(mean) || !aligned16(invstd))))
+      return UNETPP_EINVAL;
+    const long img_rows = static_cast<long>(N) * H;
+    const long grid = img_rows < rows_buf ? img_rows : rows_buf;
+    if (partial != nullptr && grid < rows_buf) zero_rows(partial + grid * C * 2, (rows_buf - grid) * C * 2, ST(stream));
+    note_kernel(partial != nullptr ? "bn_frozen_bwd_pool/sums" : "bn_frozen_bwd_pool");
+#define UNETPP_FROZEN_POOL(SUMS)                                                                                       \
+  hipLaunchKernelGGL(bn_frozen_bwd_pool_kernel<SUMS>, dim3(static_cast<unsigned>(grid)), dim3(kThreads), 0, ST(stream),  \
+                     reinterpret_cast<const f32x4*>(d_act), reinterpret_cast<const f32x4*>(y),                         \
+                     reinterpret_cast<const f32x4*>(scale), reinterpret_cast<const f32x4*>(shift),                     \
+                     reinterpret_cast<const f32x4*>(mean), reinterpret_cast<const f32x4*>(invstd),                     \
+                     reinterpret_cast<const f32x4*>(d_pooled), reinterpret_cast<const uint32_t*>(pool_idx),            \
+                     static_cast<unsigned>(img_rows), static_cast<unsigned>(W), ilog2(static_cast<unsigned>(C >> 2)),  \
+                     reinterpret_cast<f32x4*>(dy), partial)
+    if (partial != nullptr)
+      UNETPP_FROZEN_POOL(true);
+    else
+      UNETPP_FROZEN_POOL(false);
+#undef UNETPP_FROZEN_POOL
+    return launch_status();
+  }
+  const bool vec = (C % 4 == 0) && aligned16(d_act) && aligned16(y) && aligned16(dy);
+  const long blocks = bn_frozen_blocks_for(pixels, C, vec);
+  if (partial != nullptr && blocks < rows_buf)
+    zero_rows(partial + blocks * C * 2, (rows_buf - blocks) * C * 2, ST(stream));
+  note_kernel(vec ? (partial != nullptr ? "bn_frozen_bwd<4>/sums" : "bn_frozen_bwd<4>")
+                  : (partial != nullptr ? "bn_frozen_bwd<1>/sums" : "bn_frozen_bwd<1>"));
+  const int CG = vec ? C / 4 : C;
+  const long items = pixels * CG;
+#define UNETPP_FROZEN(VEC, SUMS)                                                                                       \
+  hipLaunchKernelGGL((bn_frozen_bwd_kernel<VEC, SUMS>), dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0,         \
+                     ST(stream), d_act, y, scale, shift, mean, invstd, items, CG, dy, partial)
+  if (vec) {
+    if (partial != nullptr)
+      UNETPP_FROZEN(4, true);
+    else
+      UNETPP_FROZEN(4, false);
+  } else {
+    if (partial != nullptr)
+      UNETPP_FROZEN(1, true);
+    else
+      UNETPP_FROZEN(1, false);
+  }
+#undef UNETPP_FROZEN
   return launch_status();
 }
 

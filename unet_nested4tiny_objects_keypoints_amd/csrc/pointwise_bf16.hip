@@ -197,6 +197,64 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_apply_bf16_kernel(const bf16_
   }
 }
 
+// BatchNorm backward of a FROZEN layer (running statistics): one pass -- gg = (fma(y, scale, shift) > 0) ? g : 0,
+// dy = bf16(gg * scale) -- with the fp32 (sum gg, sum gg * xhat) rows as a by-product (SUMS).  dy may alias d_act.
+template <bool SUMS>
+__global__ __launch_bounds__(kThreads) void bn_frozen_bwd_bf16_kernel(const bf16_t* d_act, const bf16_t* __restrict__ y,
+                                                                      const float* scale, const float* shift,
+                                                                      const float* mean, const float* invstd,
+                                                                      const bf16_t* d_pooled, const uint8_t* pool_idx,
+                                                                      long items, int CG, int H, int W, bf16_t* dy,
+                                                                      float* __restrict__ partial) {
+  __shared__ float sm[SUMS ? kThreads : 1][17];
+  const long first = blockIdx.x * static_cast<long>(kThreads) + threadIdx.x;
+  const int c = static_cast<int>(first % CG) * 8;  // the grid stride is a multiple of CG (a power of two <= 256)
+  float sc[8], sh[8], mu[8], is[8], s1[8], s2[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    sc[e] = scale[c + e];
+    sh[e] = shift[c + e];
+    mu[e] = SUMS ? mean[c + e] : 0.f;
+    is[e] = SUMS ? invstd[c + e] : 0.f;
+    s1[e] = 0.f;
+    s2[e] = 0.f;
+  }
+  for (long i = first; i < items; i += static_cast<long>(gridDim.x) * kThreads) {
+    float g[8], v[8], out[8];
+    load_grad8(d_act, d_pooled, pool_idx, i, CG, H, W, g);
+    unpack8(reinterpret_cast<const u32x4*>(y)[i], v);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float gg = (fmaf(v[e], sc[e], sh[e]) > 0.f) ? g[e] : 0.f;
+      if constexpr (SUMS) {
+        s1[e] += gg;
+        s2[e] += gg * (v[e] - mu[e]) * is[e];
+      }
+      out[e] = gg * sc[e];
+    }
+    reinterpret_cast<u32x4*>(dy)[i] = pack8(out);  // may alias d_act: the item was read by this thread above
+  }
+  if constexpr (SUMS) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      sm[threadIdx.x][2 * e] = s1[e];
+      sm[threadIdx.x][2 * e + 1] = s2[e];
+    }
+    __syncthreads();
+    const int C = CG * 8;
+    for (int cc = threadIdx.x; cc < C; cc += kThreads) {  // kThreads % CG == 0: thread t holds octet t % CG
+      const int cg = cc >> 3, e = cc & 7;
+      float a = 0.f, b = 0.f;
+      for (int t = cg; t < kThreads; t += CG) {  // fixed order
+        a += sm[t][2 * e];
+        b += sm[t][2 * e + 1];
+      }
+      partial[(static_cast<long>(blockIdx.x) * C + cc) * 2 + 0] = a;
+      partial[(static_cast<long>(blockIdx.x) * C + cc) * 2 + 1] = b;
+    }
+  }
+}
+
 // ---- heads.  Forward: CG = C/8 lanes share a pixel (CG = 2^LOG2CG <= 16): every lane loads one octet, applies the
 // dropout keep mask, multiplies it with the n_cls weight octets and the CG partial sums are folded across the lanes by
 // DPP / ds_swizzle moves (xor_lane: the ds_bpermute shuffles of __shfl_xor made this kernel, like its fp32 twin,
@@ -671,6 +729,43 @@ extern "C" int unetpp_bn_bwd_apply_bf16(const void* d_act, const void* y, const 
                      static_cast<const bf16_t*>(d_act), static_cast<const bf16_t*>(y), scale, shift, mean, invstd, gamma,
                      dgamma, dbeta, static_cast<const bf16_t*>(d_pooled), pool_idx, 1.0f / static_cast<float>(pixels), items,
                      C >> 3, H, W, static_cast<bf16_t*>(dy));
+  return launch_status();
+}
+
+extern "C" int64_t unetpp_bn_frozen_bwd_blocks_bf16(int64_t pixels, int32_t C) {
+  if (pixels < 1 || !octets_ok(C)) return 0;
+  const long items = pixels * (C >> 3);
+  long b = (items + kThreads - 1) / kThreads;  // one item per thread up to the cap, then a grid-stride loop
+  if (b > 2048) b = 2048;
+  return b < 1 ? 1 : b;
+}
+
+extern "C" int unetpp_bn_frozen_bwd_bf16(const void* d_act, const void* y, const float* scale, const float* shift,
+                                         const float* mean, const float* invstd, const void* d_pooled,
+                                         const uint8_t* pool_idx, int32_t N, int32_t H, int32_t W, int32_t C, void* dy,
+                                         float* partial, void* stream) {
+  if (!d_act || !y || !scale || !shift || !dy || N < 1 || H < 1 || W < 1 || !octets_ok(C)) return UNETPP_EINVAL;
+  if (partial != nullptr && (!mean || !invstd)) return UNETPP_EINVAL;
+  if ((d_pooled == nullptr) != (pool_idx == nullptr) || (d_pooled != nullptr && ((H | W) & 1))) return UNETPP_EINVAL;
+  if (!a16(d_act) || !a16(y) || !a16(dy) || (d_pooled && !a16(d_pooled)) || (reinterpret_cast<uintptr_t>(pool_idx) & 7))
+    return UNETPP_EINVAL;
+  const long pixels = static_cast<long>(N) * H * W;
+  const long items = pixels * (C >> 3);
+  if (items >= 0x7fffffffL) return UNETPP_EINVAL;
+  const unsigned blocks = static_cast<unsigned>(unetpp_bn_frozen_bwd_blocks_bf16(pixels, C));
+  if (partial != nullptr) {
+    note_kernel(d_pooled != nullptr ? "bn_frozen_bwd_bf16/pool/sums" : "bn_frozen_bwd_bf16/sums");
+    hipLaunchKernelGGL(bn_frozen_bwd_bf16_kernel<true>, dim3(blocks), dim3(kThreads), 0, ST(stream),
+                       static_cast<const bf16_t*>(d_act), static_cast<const bf16_t*>(y), scale, shift, mean, invstd,
+                       static_cast<const bf16_t*>(d_pooled), pool_idx, items, C >> 3, H, W, static_cast<bf16_t*>(dy),
+                       partial);
+  } else {
+    note_kernel(d_pooled != nullptr ? "bn_frozen_bwd_bf16/pool" : "bn_frozen_bwd_bf16");
+    hipLaunchKernelGGL(bn_frozen_bwd_bf16_kernel<false>, dim3(blocks), dim3(kThreads), 0, ST(stream),
+                       static_cast<const bf16_t*>(d_act), static_cast<const bf16_t*>(y), scale, shift, mean, invstd,
+                       static_cast<const bf16_t*>(d_pooled), pool_idx, items, C >> 3, H, W, static_cast<bf16_t*>(dy),
+                       partial);
+  }
   return launch_status();
 }
 

@@ -113,7 +113,9 @@ def _phase_views(t, **kw):
 
 # ----------------------------------------------------------------------------- records kept for backward
 class _PairRec:
-    __slots__ = ("ins", "y1", "a1", "y2", "out", "pooled", "pool_idx", "bn1", "bn2", "h", "w")
+    # bn1 / bn2 = (mean, invstd, scale, shift) of the stage; frozen1 / frozen2: the layer normalised with its running
+    # statistics (mean is then the snapshot of running_mean; mean / invstd are None when nothing is kept for backward)
+    __slots__ = ("ins", "y1", "a1", "y2", "out", "pooled", "pool_idx", "bn1", "bn2", "frozen1", "frozen2", "h", "w")
 
     def __init__(self):
         for s in self.__slots__:
@@ -143,8 +145,10 @@ def flush_batch_counters():
         _PENDING_COUNTERS.clear()
 
 
-def _conv_bn_fwd(ins, conv, bn, y, b, h, w, training):
-    """conv3x3 + bias -> y, with the BatchNorm partial sums taken in the GEMM epilogue (training)."""
+def _conv_bn_fwd(ins, conv, bn, y, b, h, w, training, stats=False):
+    """conv3x3 + bias -> y, with the BatchNorm partial sums taken in the GEMM epilogue (training).  training: the mode of
+    THIS layer (BatchNormParams.training).  A frozen layer (training False) uses its running statistics and updates
+    nothing; stats: also keep what its backward needs (invstd and a snapshot of running_mean)."""
     co = conv.out_channels
     wp = pack_conv_fwd(conv.weight.detach())
     if training:
@@ -157,13 +161,17 @@ def _conv_bn_fwd(ins, conv, bn, y, b, h, w, training):
         _PENDING_COUNTERS.append(bn.num_batches_tracked)
         return (fin.mean, fin.invstd, fin.scale, fin.shift)
     ops.gemm_fwd(b, h, w, 9, ins, [V(y)], wp, conv.bias.detach(), None)
+    if stats:
+        return ops.bn_eval_coeffs_stats(bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bn.eps)
     scale, shift = ops.bn_eval_coeffs(bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bn.eps)
     return (None, None, scale, shift)
 
 
-def _pair_fwd(blk, ins: List[V], b, h, w, training, pool, adt=torch.float32) -> _PairRec:
+def _pair_fwd(blk, ins: List[V], b, h, w, training, pool, adt=torch.float32, stats=False) -> _PairRec:
     """models/unet.py:150-156: two [conv3x3 (+BN) + ReLU] stages; optional fused 2x2 max-pool of the result.
-    adt = storage type of the activations written (fp32, or bf16 for the UNETPP_GEMM_BF16 kernels)."""
+    adt = storage type of the activations written (fp32, or bf16 for the UNETPP_GEMM_BF16 kernels).
+    Every BatchNorm layer takes its mode from its OWN ``training`` flag, as an nn.BatchNorm2d does (`training` only
+    stands in for a holder without the flag); stats: the pass is kept for backward (see _conv_bn_fwd)."""
     conv1, conv2 = getattr(blk.conv1, "0"), getattr(blk.conv2, "0")
     co = conv1.out_channels
     like = ins[0].t
@@ -175,8 +183,10 @@ def _pair_fwd(blk, ins: List[V], b, h, w, training, pool, adt=torch.float32) -> 
         r.pool_idx = torch.empty((b, h // 2, w // 2, co), dtype=torch.uint8, device=like.device)
     if blk.is_batchnorm:
         bn1, bn2 = getattr(blk.conv1, "1"), getattr(blk.conv2, "1")
+        t1, t2 = bool(getattr(bn1, "training", training)), bool(getattr(bn2, "training", training))
+        r.frozen1, r.frozen2 = not t1, not t2
         r.y1 = new()
-        r.bn1 = _conv_bn_fwd(ins, conv1, bn1, r.y1, b, h, w, training)
+        r.bn1 = _conv_bn_fwd(ins, conv1, bn1, r.y1, b, h, w, t1, stats)
         # BatchNorm-apply + ReLU of the first stage is folded into the second convolution's operand load: the
         # normalised activation a1 = relu(y1*scale + shift) is never written (r.a1 stays None).  bf16 storage, small
         # tensors (round 4): a1 IS written -- the same fma and the same rounding the load transform applies, so the
@@ -187,9 +197,9 @@ def _pair_fwd(blk, ins: List[V], b, h, w, training, pool, adt=torch.float32) -> 
                 (adt == torch.float32 and r.y1.numel() * 4 <= _A1_MATERIALIZE_BYTES_F32)):
             r.a1 = new()
             ops.affine_relu_pool(r.y1, r.bn1[2], r.bn1[3], True, r.a1, None, None)
-            r.bn2 = _conv_bn_fwd([V(r.a1)], conv2, bn2, r.y2, b, h, w, training)
+            r.bn2 = _conv_bn_fwd([V(r.a1)], conv2, bn2, r.y2, b, h, w, t2, stats)
         else:
-            r.bn2 = _conv_bn_fwd([V(r.y1, scale=r.bn1[2], shift=r.bn1[3], relu=True)], conv2, bn2, r.y2, b, h, w, training)
+            r.bn2 = _conv_bn_fwd([V(r.y1, scale=r.bn1[2], shift=r.bn1[3], relu=True)], conv2, bn2, r.y2, b, h, w, t2, stats)
         r.out = new()
         ops.affine_relu_pool(r.y2, r.bn2[2], r.bn2[3], True, r.out, r.pooled, r.pool_idx)
     else:
@@ -320,6 +330,12 @@ def infer(model, x, head=None, ensemble: bool = False):
     if pruned_to is not None and top > pruned_to:
         raise RuntimeError("this model holds a checkpoint pruned to head %d: the nodes head %d needs were never loaded"
                            % (pruned_to, top))
+    if model.is_batchnorm:   # infer() is the eval forward of every layer: a layer left in training mode is an error, not ignored
+        for i in range(top + 1):
+            for stage in ("conv1", "conv2"):
+                if getattr(getattr(getattr(model, "conv%d0" % i), stage), "1").training:
+                    raise RuntimeError("UNet_Nested.infer is the eval forward, but BatchNorm layer conv%d0.%s.1 is in training "
+                                       "mode: call model.eval() (or .eval() on that layer) first" % (i, stage))
     with torch.no_grad():
         outs, _ = forward_impl(model, x, False, save=False, head=top, ensemble=bool(ensemble))
     return outs[0]
@@ -346,7 +362,8 @@ def _forward_impl(model, x, training: bool, save: bool, head: Optional[int] = No
     for (i, j) in needed_nodes(d, top):
         if j == 0:  # encoder column (:257-265)
             with ops.region("X%d0.fwd" % i):
-                r = _pair_fwd(getattr(model, "conv%d0" % i), [V(inp)], b, h, w, training, pool=(i < top), adt=adt)
+                r = _pair_fwd(getattr(model, "conv%d0" % i), [V(inp)], b, h, w, training, pool=(i < top), adt=adt,
+                              stats=save)
             pairs[(i, 0)], X[(i, 0)] = r, r.out
             if i < top:
                 inp, h, w = r.pooled, h // 2, w // 2
@@ -355,7 +372,7 @@ def _forward_impl(model, x, training: bool, save: bool, head: Optional[int] = No
             hi, wi = h0 >> i, w0 >> i
             u = _up_fwd(mod.up, model.is_deconv, X[(i + 1, j - 1)], b, hi // 2, wi // 2, adt)
             ins = [V(u.up)] + [V(X[(i, jj)]) for jj in range(j)]  # up first, then X_i0.. (:198-202)
-            r = _pair_fwd(mod.conv, ins, b, hi, wi, training, pool=False, adt=adt)
+            r = _pair_fwd(mod.conv, ins, b, hi, wi, training, pool=False, adt=adt, stats=save)
             ups[(i, j)], pairs[(i, j)], X[(i, j)] = u, r, r.out
     p_drop, seeds, masks, seed_dev = _dropout_config(model, training)
     outs = []
@@ -438,6 +455,21 @@ def _conv_wgrad(conv, xs, dys, b, h, w, grads):
     grads[conv.bias] = db
 
 
+def _bn_bwd(bn, coeffs, frozen, d_act, y, pool_grad):
+    """BatchNorm + ReLU backward of one stage, in place in d_act.  Returns (dgamma, dbeta).  A frozen layer (running
+    statistics in the forward) takes the one-pass kernel; when neither its gamma nor its beta requires grad the sums are
+    skipped too and both gradients are None -- the parameters are still reported as done (data-parallel frontier), but
+    nobody receives a gradient for them."""
+    mean, invstd, scale, shift = coeffs
+    if not frozen:
+        return ops.bn_backward(d_act, y, scale, shift, mean, invstd, bn.weight.detach(), d_act,
+                               _new_grad(bn.weight), _new_grad(bn.bias), pool=pool_grad)
+    if not (bn.weight.requires_grad or bn.bias.requires_grad):
+        return ops.bn_frozen_backward(d_act, y, scale, shift, None, None, d_act, pool=pool_grad, want_sums=False)
+    return ops.bn_frozen_backward(d_act, y, scale, shift, mean, invstd, d_act, _new_grad(bn.weight), _new_grad(bn.bias),
+                                  pool=pool_grad)
+
+
 def _pair_bwd(blk, r: _PairRec, d_out, in_targets: Optional[List[V]], b, grads, pre_gated=False, pool_grad=None,
               flush=None, in_slice: Optional[Tuple[int, int]] = None):
     """Backward of models/unet.py:150-156.  d_out (gradient of r.out) is consumed.  in_targets: output views
@@ -452,10 +484,7 @@ def _pair_bwd(blk, r: _PairRec, d_out, in_targets: Optional[List[V]], b, grads, 
     h, w = r.h, r.w
     if blk.is_batchnorm:
         bn1, bn2 = getattr(blk.conv1, "1"), getattr(blk.conv2, "1")
-        mean, invstd, scale, shift = r.bn2
-        dg, dbt = ops.bn_backward(d_out, r.y2, scale, shift, mean, invstd, bn2.weight.detach(), d_out,
-                                  _new_grad(bn2.weight), _new_grad(bn2.bias), pool=pool_grad)
-        grads[bn2.weight], grads[bn2.bias] = dg, dbt
+        grads[bn2.weight], grads[bn2.bias] = _bn_bwd(bn2, r.bn2, r.frozen2, d_out, r.y2, pool_grad)
         dy2 = V(d_out)
         mean, invstd, scale, shift = r.bn1
         if r.a1 is not None:   # bf16 storage, small tensors: a1 was materialised in the forward pass
@@ -466,9 +495,7 @@ def _pair_bwd(blk, r: _PairRec, d_out, in_targets: Optional[List[V]], b, grads, 
             flush()
         d_a1 = torch.empty_like(r.y1)
         ops.gemm_fwd(b, h, w, 9, [dy2], [V(d_a1)], pack_conv_dgrad(conv2.weight.detach()))
-        dg, dbt = ops.bn_backward(d_a1, r.y1, scale, shift, mean, invstd, bn1.weight.detach(), d_a1,
-                                  _new_grad(bn1.weight), _new_grad(bn1.bias))
-        grads[bn1.weight], grads[bn1.bias] = dg, dbt
+        grads[bn1.weight], grads[bn1.bias] = _bn_bwd(bn1, r.bn1, r.frozen1, d_a1, r.y1, None)
         dy1 = V(d_a1)
     else:
         # ReLU backward: already applied by the last contributor's epilogue, else folded into the operand load

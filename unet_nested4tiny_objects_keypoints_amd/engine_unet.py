@@ -70,7 +70,7 @@ def _forward(model, x, training: bool, save: bool):
     enc: List[_PairRec] = []
     inp, h, w = x_nhwc, h0, w0
     for i, name in enumerate(_ENC):  # models/unet.py:106-110
-        r = _pair_fwd(_enc_pair(model, name), [V(inp)], b, h, w, training, pool=(i < 4))
+        r = _pair_fwd(_enc_pair(model, name), [V(inp)], b, h, w, training, pool=(i < 4), stats=save)
         enc.append(r)
         if i < 4:
             inp, h, w = r.pooled, h // 2, w // 2
@@ -93,7 +93,8 @@ def _forward(model, x, training: bool, save: bool):
             interp = torch.zeros((b, hs, ws, low.shape[3]), dtype=torch.float32, device=x.device)
             oy, ox = (hs - 2 * hl) // 2, (ws - 2 * wl) // 2
             interp[:, oy:oy + 2 * hl, ox:ox + 2 * wl].copy_(tmp)
-        r = _pair_fwd(pair_of(getattr(model, name).conv), [V(skip.out), V(interp)], b, hs, ws, training, pool=False)
+        r = _pair_fwd(pair_of(getattr(model, name).conv), [V(skip.out), V(interp)], b, hs, ws, training, pool=False,
+                      stats=save)
         dec.append(r)
         interps.append(interp)
         low = r.out

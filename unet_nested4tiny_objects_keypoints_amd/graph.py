@@ -120,7 +120,10 @@ class GraphedTrainStep:
 
     ``outputs`` / ``loss`` are the graph's static tensors (detached): the next call overwrites them (clone what must
     live longer).  capture_optimizer=True puts ``optimizer.step()`` into the graph; it needs an optimizer whose step
-    makes no host decision that depends on device data (torch.optim.Adam / AdamW with ``capturable=True``, SGD)."""
+    makes no host decision that depends on device data (torch.optim.Adam / AdamW with ``capturable=True``, SGD).
+    The graph holds the BatchNorm modes it was captured with: a layer that was frozen (``BatchNormParams.eval()``,
+    ``model.freeze_batchnorm()``) at capture stays frozen in every replay, whatever its flag says later -- build a new
+    GraphedTrainStep after changing modes or ``requires_grad``."""
 
     def __init__(self, model, optimizer, criterion, inputs: torch.Tensor, target: torch.Tensor, warmup: int = 3,
                  capture_optimizer: bool = False, restore_state: bool = True, check_topology: bool = False,

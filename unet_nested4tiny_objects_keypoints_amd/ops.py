@@ -555,6 +555,17 @@ def bn_eval_coeffs(gamma, beta, running_mean, running_var, eps):
     return scale, shift
 
 
+def bn_eval_coeffs_stats(gamma, beta, running_mean, running_var, eps):
+    """(mean, invstd, scale, shift) of a frozen layer: bn_eval_coeffs' scale / shift (same kernel, same bits) plus the
+    snapshot of running_mean and 1/sqrt(running_var + eps) that bn_frozen_backward's sums read."""
+    c = gamma.numel()
+    mean, invstd, scale, shift = (torch.empty(c, dtype=torch.float32, device=gamma.device) for _ in range(4))
+    check(_lib.lib().unetpp_bn_eval_coeffs_stats(_ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var), eps, c,
+                                                 _ptr(scale), _ptr(shift), _ptr(mean), _ptr(invstd), _stream()),
+          "unetpp_bn_eval_coeffs_stats")
+    return mean, invstd, scale, shift
+
+
 def _is_bf16(t):
     return t.dtype == torch.bfloat16
 
@@ -637,6 +648,47 @@ def bn_backward(d_act, y, scale, shift, mean, invstd, gamma, dy_out, dgamma=None
         check(lib.unetpp_bn_bwd_apply_pool(_ptr(d_act), _ptr(y), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(invstd),
                                            _ptr(gamma), _ptr(dgamma), _ptr(dbeta), _ptr(pool[0]), _ptr(pool[1]), n, h,
                                            w, c, _ptr(dy_out), st), "unetpp_bn_bwd_apply_pool")
+    return dgamma, dbeta
+
+
+def bn_frozen_backward(d_act, y, scale, shift, mean, invstd, dy_out, dgamma=None, dbeta=None, pool=None, want_sums=True):
+    """BatchNorm+ReLU backward of a layer that normalised with its running statistics: dy = (y*scale+shift > 0) * g * scale
+    in ONE streaming launch (g = d_act plus the routed pool gradient); dy_out may alias d_act.  want_sums: also dgamma =
+    sum gg*xhat and dbeta = sum gg (per-workgroup rows + bn_bwd_finalize); returns (dgamma, dbeta), or (None, None) without
+    sums (gamma and beta frozen too: mean / invstd may then be None).  pool = (d_pooled, pool_idx) as in bn_backward."""
+    lib = _lib.lib()
+    n, h, w, c = y.shape
+    pixels = n * h * w
+    bf16 = _is_bf16(y)
+    adt = torch.bfloat16 if bf16 else torch.float32
+    _need(d_act, "d_act", adt), _need(y, "y", adt), _need(dy_out, "dy", adt)
+    if tuple(d_act.shape) != tuple(y.shape) or tuple(dy_out.shape) != tuple(y.shape):
+        raise ValueError("d_act, y and dy must have one shape")
+    if want_sums and (mean is None or invstd is None):
+        raise ValueError("the gamma / beta sums need the running mean snapshot and invstd")
+    blocks_fn = lib.unetpp_bn_frozen_bwd_blocks_bf16 if bf16 else lib.unetpp_bn_frozen_bwd_blocks
+    blocks = int(blocks_fn(pixels, c))
+    if blocks < 1:
+        raise ValueError("bf16 BatchNorm backward needs C = 8 * 2^k channels, got %d" % c)
+    if pool is not None and not bf16 and not (lib.unetpp_bn_bwd_pool_ok(n, h, w, c) and scale.data_ptr() % 16 == 0
+                                              and shift.data_ptr() % 16 == 0 and pool[1].data_ptr() % 4 == 0):
+        maxpool_bwd(pool[0], pool[1], d_act)
+        pool = None
+    dp, pi = (None, None) if pool is None else (_need(pool[0], "d_pooled", adt), _need(pool[1], "pool_idx", torch.uint8))
+    partial = torch.empty(blocks * c * 2, dtype=torch.float32, device=y.device) if want_sums else None
+    st = _stream()
+    fn = lib.unetpp_bn_frozen_bwd_bf16 if bf16 else lib.unetpp_bn_frozen_bwd
+    _timed_call(None, 0.0, lambda: check(fn(_ptr(d_act), _ptr(y), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(invstd),
+                                             _ptr(dp), _ptr(pi), n, h, w, c, _ptr(dy_out), _ptr(partial), st),
+                                          "unetpp_bn_frozen_bwd"),
+                (2.0 if bf16 else 4.0) * pixels * c * 3)
+    if not want_sums:
+        return None, None
+    if dgamma is None:
+        dgamma = torch.empty(c, dtype=torch.float32, device=y.device)
+    if dbeta is None:
+        dbeta = torch.empty(c, dtype=torch.float32, device=y.device)
+    check(lib.unetpp_bn_bwd_finalize(_ptr(partial), blocks, c, _ptr(dgamma), _ptr(dbeta), st), "unetpp_bn_bwd_finalize")
     return dgamma, dbeta
 
 

@@ -20,7 +20,9 @@ class GraphedForward:
 
     The returned tensors are the graph's static outputs: they are overwritten by the next call (clone what must live
     longer).  ``head=J`` (UNet_Nested only) captures ``model.infer(example, J, ensemble)`` instead -- the network cut at
-    head J, or the mean of heads 1 .. J -- and returns that single static tensor; ``head=None`` is the full forward."""
+    head J, or the mean of heads 1 .. J -- and returns that single static tensor; ``head=None`` is the full forward.
+    The graph holds the BatchNorm modes it was captured with (every layer on its running statistics after ``model.eval()``;
+    a layer put back into training mode before the capture would replay its batch-statistics launches)."""
 
     def __init__(self, model: torch.nn.Module, example: torch.Tensor, warmup: int = 3, head=None, ensemble: bool = False):
         if not example.is_cuda:

@@ -177,6 +177,24 @@ class UNet_Nested(nn.Module):
         ``validate_step(model, ..., forward=lambda x: (model.infer(x, 1),))`` validates a pruned network."""
         return engine.infer(self, inputs, head, ensemble)
 
+    def freeze_batchnorm(self, frozen: bool = True, affine: bool = True):
+        """The fine-tuning idiom ``for bn in batchnorms: bn.eval()`` in one call: puts every ``BatchNormParams`` into eval
+        mode (``frozen=True``) or back into training mode, whatever the mode of the model around them.  A frozen layer
+        normalises with its running statistics, updates neither them nor ``num_batches_tracked``, and its backward is one
+        streaming launch.  With ``affine=True`` gamma and beta get ``requires_grad = not frozen``; while neither requires
+        grad the layer's backward skips their sums and they receive no gradient (``p.grad`` stays ``None``).
+
+        Semantics are torch's: the flags are ordinary ``nn.Module.training`` flags, so a later ``model.train()`` (or
+        ``model.eval()``) sets every layer again and un-does the mode part of this call -- call it after ``train()``.  It
+        takes effect at the next forward; a captured graph keeps the modes it was captured with.  Returns ``self``."""
+        for m in self.modules():
+            if isinstance(m, BatchNormParams):
+                nn.Module.train(m, not frozen)
+                if affine:
+                    m.weight.requires_grad_(not frozen)
+                    m.bias.requires_grad_(not frozen)
+        return self
+
     # ---- weight-image cache control (ops.PackPlan) ------------------------------------------------
     def freeze_weight_images(self, frozen: bool = True):
         """Serving opt-in: keep the kernels' LDS weight images between passes instead of rebuilding them from the
@@ -288,6 +306,7 @@ class UNet(nn.Module):
         from . import engine_unet
         return engine_unet.run(self, x)
 
+    freeze_batchnorm = UNet_Nested.freeze_batchnorm
     freeze_weight_images = UNet_Nested.freeze_weight_images
     invalidate_weight_images = UNet_Nested.invalidate_weight_images
 
