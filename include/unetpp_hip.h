@@ -545,6 +545,40 @@ int unetpp_match_points(const float* points, const int32_t* found, int32_t heads
                         const float* labels, int32_t S, const int32_t* map_points, const int32_t* map_begin,
                         float* matched, uint8_t* mask, float* loss, int32_t* count, void* stream);
 
+/* ---- Weight averaging (csrc/average.hip): the reference trainer's "average" save strategy (trainer/trainer.py:243-252,
+ * not implemented there) as one multi-tensor launch per update.  Added within ABI version 12 without changing anything
+ * that was there before. ---- */
+#define UNETPP_AVG_MEAN 0         /* equal-weight running mean (SWA): w = 1 / (n + 1) */
+#define UNETPP_AVG_EMA 1          /* exponential moving average: w = 1 - decay */
+#define UNETPP_AVG_SWAP 2         /* exchange avg and src element by element */
+#define UNETPP_AVG_CAPTURABLE 1   /* flags: the update count and the decay live on the device; the launch advances the count */
+
+/* One tensor (fp32, contiguous) and its average.  avg and src do not overlap.  Segments are in chunk order: segment i
+ * owns chunks [chunk_begin, chunk_begin + ceil(numel / unetpp_optim_chunk_elems())). */
+typedef struct unetpp_avg_segment {
+  float* avg;
+  float* src;           /* written by UNETPP_AVG_SWAP only */
+  int64_t numel;
+  int64_t chunk_begin;
+  int32_t vec;          /* 1 when avg and src are both 16-byte aligned */
+  int32_t copy;         /* mean / ema: avg = src at every update (a buffer that is carried, not averaged) */
+} unetpp_avg_segment;
+
+/* unetpp_avg_update: one launch over every segment (device table `segments`, n_segments rows; chunk_segment [n_chunks]:
+ * the segment of each chunk; build and upload them as for unetpp_optim_step).  With n = the number of updates made before
+ * this one, UNETPP_AVG_MEAN / _EMA set avg = src bit for bit when n == 0 or segment.copy, else d = src - avg,
+ * avg = avg + w * d (each operation rounded once; w formed in double, rounded to float once).  UNETPP_AVG_SWAP exchanges
+ * avg and src, copy segments included.
+ * Eager (flags 0): n = count (>= 0) and decay (in [0, 1), EMA only) are arguments; count_dev = hyper_dev = done = NULL.
+ * UNETPP_AVG_CAPTURABLE (not with SWAP): n = *count_dev (device float32), decay = hyper_dev[0] (device double; may be
+ * NULL for MEAN); the launch leaves *count_dev = n + 1; done is a device int32, zero before the first launch, that the
+ * launch leaves zero.  count and decay are ignored.  SWAP takes flags 0 and NULL for all three device pointers.
+ * UNETPP_EINVAL without touching the device for a null table, zero segments or chunks, an unknown kind or flag, or a
+ * pointer combination that does not fit the mode. */
+int unetpp_avg_update(int32_t kind, int32_t flags, const unetpp_avg_segment* segments, int32_t n_segments,
+                      const int32_t* chunk_segment, int64_t n_chunks, int64_t count, double decay, float* count_dev,
+                      const double* hyper_dev, int32_t* done, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,7 +19,8 @@ from .serving import GraphedForward  # noqa: F401
 from .graph import GraphedTrainStep  # noqa: F401
 from .optim import AdamW, AdaBound, SGDW  # noqa: F401
 from .validate import validate_outputs, validate_step  # noqa: F401
+from .averaging import WeightAverager  # noqa: F401
 
 __all__ = ["UNet_Nested", "UNet", "count_param", "FocalLoss_BCE_2d", "train_step", "create_heatmap", "Heatmap",
            "GraphedForward", "GraphedTrainStep", "AdamW", "AdaBound", "SGDW", "validate_step",
-           "validate_outputs"]
+           "validate_outputs", "WeightAverager"]

@@ -15,7 +15,7 @@ _REPO = os.path.dirname(_PKG_DIR)
 LIB_PATH = os.environ.get("UNETPP_LIB", os.path.join(_PKG_DIR, "libunetpp_hip.so"))  # override: kernel A/B runs
 CSRC = os.path.join(_PKG_DIR, "csrc")
 INCLUDE = os.path.join(_REPO, "include")
-SOURCES = ("gemm_pix.hip", "gemm_fast.hip", "gemm_pw.hip", "gemm_pw_bf16.hip", "gemm_wino.hip", "gemm_bf16.hip", "gemm_bf16_dma.hip", "wgrad_bf16.hip", "pointwise_bf16.hip", "keypoints.hip", "weight_image.hip", "wgrad.hip", "wgrad_fast.hip", "wgrad_dma.hip", "wgrad_pw.hip", "wgrad_wino.hip", "first_layer.hip", "pointwise.hip", "caller.hip", "optim.hip", "validate.hip")
+SOURCES = ("gemm_pix.hip", "gemm_fast.hip", "gemm_pw.hip", "gemm_pw_bf16.hip", "gemm_wino.hip", "gemm_bf16.hip", "gemm_bf16_dma.hip", "wgrad_bf16.hip", "pointwise_bf16.hip", "keypoints.hip", "weight_image.hip", "wgrad.hip", "wgrad_fast.hip", "wgrad_dma.hip", "wgrad_pw.hip", "wgrad_wino.hip", "first_layer.hip", "pointwise.hip", "caller.hip", "optim.hip", "validate.hip", "average.hip")
 HEADERS = ("common.h", "gemm_units.h", "wgrad_reduce.h", "lds_asm.h", "bf16_common.h", "dropout.h", "bn_fused.h",
            "wino_experiments.h", "dma_experiments.h", "heads_mean.h")
 MAX_VIEWS = 8
@@ -137,9 +137,19 @@ class OptimSegment(C.Structure):
     ]
 
 
+class AvgSegment(C.Structure):
+    """mirror of struct unetpp_avg_segment"""
+    _fields_ = [
+        ("avg", C.c_void_p), ("src", C.c_void_p),
+        ("numel", C.c_int64), ("chunk_begin", C.c_int64), ("vec", C.c_int32), ("copy", C.c_int32),
+    ]
+
+
 OPTIM_ADAMW, OPTIM_ADABOUND, OPTIM_SGDW = 0, 1, 2   # unetpp_optim_step kinds
 OPTIM_AMS, OPTIM_CAPTURABLE = 1, 2                 # unetpp_optim_step flags
 OPTIM_HYPER = 8                                    # doubles per group of the hyper-parameter block
+AVG_MEAN, AVG_EMA, AVG_SWAP = 0, 1, 2                # unetpp_avg_update kinds
+AVG_CAPTURABLE = 1                                 # unetpp_avg_update flags
 MATCH_MAX = 64                                     # UNETPP_MATCH_MAX: labels / predictions per map of the matcher
 
 _P, _I32, _I64, _F, _U64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_uint64
@@ -220,6 +230,8 @@ SIGNATURES = {
     "unetpp_optim_upload": (C.c_int, [_P, _P, _I64, _P]),
     # validation matcher (validate.hip)
     "unetpp_match_points": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _P, _I32, _P, _P, _P, _P, _P, _P, _P]),
+    # weight averaging (average.hip; added within ABI 12)
+    "unetpp_avg_update": (C.c_int, [_I32, _I32, _P, _I32, _P, _I64, _I64, C.c_double, _P, _P, _P, _P]),
 }
 
 _LIB = None

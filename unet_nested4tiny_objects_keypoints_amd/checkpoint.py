@@ -44,17 +44,36 @@ def save_best(model, save_dir: str, epoch, heatmap_loss, landmark_loss) -> str:
     return path
 
 
-def save_checkpoint(model, optimizer, epoch: int, path: str) -> str:
-    """The .tar layout trainer.py:403-413 resumes from."""
-    torch.save({"model_state_dict": _unwrap(model).state_dict(),
-                "optimizer_state_dict": None if optimizer is None else optimizer.state_dict(),
-                "epoch": int(epoch)}, path)
+def average_model_name(epoch, heatmap_loss, landmark_loss) -> str:
+    return "average_epoch_{}_heatmaploss_{}_landmarkloss_{}.pth".format(epoch, heatmap_loss, landmark_loss)
+
+
+def save_average(avg, save_dir: str, epoch, heatmap_loss, landmark_loss) -> str:
+    """The ``model_save == "average"`` strategy trainer.py:243-252 names and does not implement: the averaged weights of
+    a ``WeightAverager`` as a bare state_dict under the model's key names -- a plain .pth like ``save_best``'s, which the
+    reference's model loads."""
+    path = os.path.join(save_dir, average_model_name(epoch, heatmap_loss, landmark_loss))
+    torch.save(avg.averaged_state_dict(), path)
     return path
 
 
-def resume(model, path: str, optimizer=None, resume_opt: bool = False, map_location: Optional[str] = "cpu") -> int:
+def save_checkpoint(model, optimizer, epoch: int, path: str, averager=None) -> str:
+    """The .tar layout trainer.py:403-413 resumes from.  With a ``WeightAverager`` its state travels along under
+    ``average_state_dict`` (the reference ignores keys it does not know); without one the file is what it always was."""
+    ckpt = {"model_state_dict": _unwrap(model).state_dict(),
+            "optimizer_state_dict": None if optimizer is None else optimizer.state_dict(),
+            "epoch": int(epoch)}
+    if averager is not None:
+        ckpt["average_state_dict"] = averager.state_dict()
+    torch.save(ckpt, path)
+    return path
+
+
+def resume(model, path: str, optimizer=None, resume_opt: bool = False, map_location: Optional[str] = "cpu",
+           averager=None) -> int:
     """trainer.py:399-419.  Loads `path` (suffix .tar or .pth) into `model` (and the optimizer when `resume_opt`);
-    returns the epoch to start from (0 unless a .tar is resumed together with its optimizer state)."""
+    returns the epoch to start from (0 unless a .tar is resumed together with its optimizer state).  `averager`: a
+    ``WeightAverager`` that takes the file's ``average_state_dict`` together with the optimizer state."""
     suf = path.rsplit(".", 1)[-1]
     start_epoch = 0
     target = _unwrap(model)
@@ -65,6 +84,10 @@ def resume(model, path: str, optimizer=None, resume_opt: bool = False, map_locat
             if optimizer is None:
                 raise ValueError("resume_opt needs the optimizer")
             optimizer.load_state_dict(ckpt["optimizer_state_dict"])
+            if averager is not None:
+                if "average_state_dict" not in ckpt:
+                    raise KeyError("%s was saved without an averager: it has no average_state_dict" % path)
+                averager.load_state_dict(ckpt["average_state_dict"])
             start_epoch = int(ckpt["epoch"]) + 1
     elif suf == "pth":
         target.load_state_dict(_strip_module_prefix(torch.load(path, map_location=map_location)))

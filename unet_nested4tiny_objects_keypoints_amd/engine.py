@@ -301,6 +301,53 @@ def plan_phase(depth: int, head=None) -> str:
     return "fwd" if head == depth - 1 else "fwd/%d" % head
 
 
+STATS_PHASE = "stats"   # weight-image plan phase of stats_pass: its own images, as a pruned pass has (ops.phase_tag)
+
+
+def stats_nodes(depth: int) -> List[Tuple[int, int]]:
+    """The nodes a BatchNorm statistics pass runs: the encoder column X_00 .. X_{depth-1,0}, top down.  Only these hold
+    BatchNorm layers (the decoder pairs are built without them, models/unet.py:182-202), and none of them reads a
+    decoder node."""
+    if isinstance(depth, bool) or not isinstance(depth, int) or depth < 1:
+        raise ValueError("depth must be a positive int, got %r" % (depth,))
+    return [(i, 0) for i in range(depth)]
+
+
+def stats_pass(model, x) -> None:
+    """Feeds one batch through the encoder column only, under no_grad, every BatchNorm layer in the mode of its own
+    ``training`` flag and with its own ``momentum``: the running statistics (and ``num_batches_tracked``) of the layers in
+    training mode move exactly as a whole training-mode forward would move them, and nothing else is computed -- no
+    decoder node, no head, no dropout seed, nothing kept for backward.  WeightAverager.update_bn is the caller.  A model
+    without BatchNorm runs nothing."""
+    _check_input(model, x)
+    if not model.is_batchnorm:
+        return
+    _PENDING_COUNTERS.clear()
+    try:
+        with torch.no_grad():
+            plan = None
+            if USE_PACK_PLAN:
+                plan = _plan_of(model)
+                plan.begin(STATS_PHASE)
+                ops.set_pack_plan(plan)
+            try:
+                b, _, h, w = x.shape
+                d = model.depth
+                adt = _activation_dtype(model)
+                inp = ops.nchw_to_nhwc(x.detach().contiguous())
+                for (i, _) in stats_nodes(d):
+                    with ops.region("X%d0.stats" % i):
+                        r = _pair_fwd(getattr(model, "conv%d0" % i), [V(inp)], b, h, w, True, pool=(i < d - 1), adt=adt,
+                                      stats=False)
+                    if i < d - 1:
+                        inp, h, w = r.pooled, h // 2, w // 2
+            finally:
+                if plan is not None:
+                    ops.set_pack_plan(None)
+    finally:
+        flush_batch_counters()
+
+
 def forward_impl(model, x, training: bool, save: bool, head: Optional[int] = None, ensemble: bool = False):
     """Runs the forward DAG of models/unet.py:255-300.  Returns (outputs, saved-for-backward or None).
     head = None: the whole graph and every head (``forward``).  head = J (``infer``): only needed_nodes(depth, J), and one
