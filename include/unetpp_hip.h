@@ -494,7 +494,11 @@ int unetpp_keypoints_extract(int32_t stage, const float* heat, int32_t maps, int
 #define UNETPP_OPTIM_CAPTURABLE 2   /* flags: step counters live on the device (segment.step), advanced by the launch */
 #define UNETPP_OPTIM_HYPER 8        /* doubles per parameter group in the hyper-parameter block: lr, beta1 (SGDW:
                                        momentum), beta2 (SGDW: dampening), eps, weight_decay, AdaBound's final_lr * lr /
-                                       base_lr, gamma, unused */
+                                       base_lr, gamma, and in slot 7 of ROW 0 only (unused in the other rows)
+                                       max_norm of unetpp_optim_step_clip: <= 0 = no clipping */
+#define UNETPP_OPTIM_H_MAX_NORM 7   /* index of max_norm in row 0 of the hyper-parameter block */
+#define UNETPP_OPTIM_SKIP_NONFINITE 4   /* flags of unetpp_optim_step_clip (with _CAPTURABLE only): a non-finite sum of
+                                           squared gradients leaves everything but skipped_steps unchanged */
 
 /* One parameter tensor (fp32, contiguous) of the step.  Segments are in chunk order: segment i owns chunks
  * [chunk_begin, chunk_begin + ceil(numel / unetpp_optim_chunk_elems())). */
@@ -526,6 +530,39 @@ int unetpp_optim_step(int32_t kind, int32_t flags, const unetpp_optim_segment* s
 /* unetpp_optim_upload: hipMemcpyAsync host -> device on `stream` (the segment table of a step; with page-locked
  * `host_src` it is a memcpy node when the stream is being captured, and host_src must then outlive the graph). */
 int unetpp_optim_upload(void* dst, const void* host_src, int64_t bytes, void* stream);
+
+/* ---- Global gradient norm, clipping and non-finite skip over the optimizer's table (csrc/optim.hip).  Added within ABI
+ * version 12 without changing anything that was there before. ---- */
+/* What the consuming launch publishes (device memory owned by the caller, stable address; zero it once). */
+typedef struct unetpp_clip_state {
+  float total_norm;        /* float(sqrt(sum of squares)): the norm BEFORE clipping */
+  float coef;              /* c = max_norm / (total_norm + 1e-6f); coef = c > 1 ? 1 : c (NaN norm: NaN; infinite: 0);
+                              1 when there is no max_norm */
+  int32_t skipped_steps;   /* advanced by one by every skipped unetpp_optim_step_clip */
+  int32_t reserved;
+} unetpp_clip_state;
+
+/* unetpp_grad_norm: partials [n_chunks] (device doubles) = per chunk the sum of double(grad)^2 in a fixed order; reads
+ * segment.grad, numel, chunk_begin and vec only.  The bits depend neither on the grid nor on segment.vec.  The table
+ * is unetpp_optim_step's.  UNETPP_EINVAL without touching the device for a null pointer, zero segments or chunks. */
+int unetpp_grad_norm(const unetpp_optim_segment* segments, int32_t n_segments, const int32_t* chunk_segment,
+                     int64_t n_chunks, double* partials, void* stream);
+/* unetpp_optim_step_clip: unetpp_optim_step with every gradient multiplied by coef as it is read (one rounded fp32
+ * multiply; segment.grad is not written).  partials: what unetpp_grad_norm left for the SAME table on the same stream;
+ * every workgroup sums it in one fixed order (double) before its first chunk and workgroup 0 writes *state.
+ * max_norm = float(hyper[UNETPP_OPTIM_H_MAX_NORM]); <= 0: coef = 1.  flags as unetpp_optim_step, plus
+ * UNETPP_OPTIM_SKIP_NONFINITE (UNETPP_EINVAL without _CAPTURABLE): when the sum of squares is not finite the launch
+ * stores nothing -- parameters, moments, aux, segment.step and done unchanged -- but state->skipped_steps + 1 (and the
+ * norm and coefficient).  Argument checks as unetpp_optim_step; partials and state must not be NULL. */
+int unetpp_optim_step_clip(int32_t kind, int32_t flags, const unetpp_optim_segment* segments, int32_t n_segments,
+                           const int32_t* chunk_segment, int64_t n_chunks, const double* hyper, const double* steps,
+                           int32_t* done, const double* partials, unetpp_clip_state* state, void* stream);
+/* unetpp_grad_scale: grad[i] = grad[i] * coef in place over the table (segment.grad is written, whatever its const
+ * says; nothing is stored when coef == 1), coef from partials and max_norm (> 0, else UNETPP_EINVAL) as above;
+ * state->total_norm and state->coef are written, skipped_steps is not touched.  Uses segment.grad, numel, chunk_begin
+ * and vec (1: grad is 16-byte aligned) only. */
+int unetpp_grad_scale(const unetpp_optim_segment* segments, int32_t n_segments, const int32_t* chunk_segment,
+                      int64_t n_chunks, const double* partials, float max_norm, unetpp_clip_state* state, void* stream);
 
 /* ---- Validation matcher (csrc/validate.hip): HeatmapPattern.match_distmin (tools/misc/heatmap.py:57-79, unfinished
  * there) and the landmark loss of the validation loop (trainer/trainer.py:220-221) for every head in one launch.  Added

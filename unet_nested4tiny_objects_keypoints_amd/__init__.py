@@ -17,10 +17,10 @@ from .targets import create_heatmap  # noqa: F401
 from .keypoints import Heatmap  # noqa: F401
 from .serving import GraphedForward  # noqa: F401
 from .graph import GraphedTrainStep  # noqa: F401
-from .optim import AdamW, AdaBound, SGDW  # noqa: F401
+from .optim import AdamW, AdaBound, SGDW, clip_grad_norm_  # noqa: F401
 from .validate import validate_outputs, validate_step  # noqa: F401
 from .averaging import WeightAverager  # noqa: F401
 
 __all__ = ["UNet_Nested", "UNet", "count_param", "FocalLoss_BCE_2d", "train_step", "create_heatmap", "Heatmap",
            "GraphedForward", "GraphedTrainStep", "AdamW", "AdaBound", "SGDW", "validate_step",
-           "validate_outputs", "WeightAverager"]
+           "validate_outputs", "WeightAverager", "clip_grad_norm_"]

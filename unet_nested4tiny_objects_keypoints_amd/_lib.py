@@ -137,6 +137,11 @@ class OptimSegment(C.Structure):
     ]
 
 
+class ClipState(C.Structure):
+    """mirror of struct unetpp_clip_state"""
+    _fields_ = [("total_norm", C.c_float), ("coef", C.c_float), ("skipped_steps", C.c_int32), ("reserved", C.c_int32)]
+
+
 class AvgSegment(C.Structure):
     """mirror of struct unetpp_avg_segment"""
     _fields_ = [
@@ -147,7 +152,9 @@ class AvgSegment(C.Structure):
 
 OPTIM_ADAMW, OPTIM_ADABOUND, OPTIM_SGDW = 0, 1, 2   # unetpp_optim_step kinds
 OPTIM_AMS, OPTIM_CAPTURABLE = 1, 2                 # unetpp_optim_step flags
+OPTIM_SKIP_NONFINITE = 4                           # unetpp_optim_step_clip only
 OPTIM_HYPER = 8                                    # doubles per group of the hyper-parameter block
+OPTIM_H_MAX_NORM = 7                               # row 0 of that block: max_norm of unetpp_optim_step_clip
 AVG_MEAN, AVG_EMA, AVG_SWAP = 0, 1, 2                # unetpp_avg_update kinds
 AVG_CAPTURABLE = 1                                 # unetpp_avg_update flags
 MATCH_MAX = 64                                     # UNETPP_MATCH_MAX: labels / predictions per map of the matcher
@@ -232,6 +239,10 @@ SIGNATURES = {
     "unetpp_match_points": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _P, _I32, _P, _P, _P, _P, _P, _P, _P]),
     # weight averaging (average.hip; added within ABI 12)
     "unetpp_avg_update": (C.c_int, [_I32, _I32, _P, _I32, _P, _I64, _I64, C.c_double, _P, _P, _P, _P]),
+    # gradient norm, clipped step, in-place scale (optim.hip; added within ABI 12)
+    "unetpp_grad_norm": (C.c_int, [_P, _I32, _P, _I64, _P, _P]),
+    "unetpp_optim_step_clip": (C.c_int, [_I32, _I32, _P, _I32, _P, _I64, _P, _P, _P, _P, _P, _P]),
+    "unetpp_grad_scale": (C.c_int, [_P, _I32, _P, _I64, _P, _F, _P, _P]),
 }
 
 _LIB = None

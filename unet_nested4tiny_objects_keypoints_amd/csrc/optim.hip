@@ -14,6 +14,16 @@
 // Scalars (bias corrections, step size, AdaBound's bounds) are formed in double from the segment's own step count and
 // rounded to float once, as the reference forms them in Python floats and hands them to aten as float scalars.
 // No floating-point atomics, no cross-workgroup order: every element's result depends on that element alone.
+//
+// Gradient clipping / non-finite skip (unetpp_grad_norm, unetpp_optim_step_clip, unetpp_grad_scale) over the same table:
+//   norm pass   one double per CHUNK: sum of double(g)^2 (the product of two floats is exact in double), per thread in
+//               element order, a fixed tree across the wave, the four waves through LDS; plain stores to partials[c].
+//               The element -> thread map is the float4 one on every path, so the bits do not depend on the alignment,
+//               on the grid size or on which workgroup took which chunk.
+//   combine     launch-boundary reduce: every workgroup of the consuming launch sums partials[0..n_chunks) itself, in
+//               one fixed order, before its first chunk; workgroup 0 publishes {total_norm, coef, skipped_steps}.
+//   consume     total = float(sqrt(sum)); c = max_norm / (total + 1e-6f); coef = c > 1 ? 1 : c (torch's
+//               clip_grad_norm_ in fp32: NaN stays NaN, an infinite norm gives 0); g = g * coef as it is read.
 #include "common.h"
 
 #include <math.h>
@@ -90,11 +100,12 @@ __device__ __forceinline__ void update(float& p, float g, float& m, float& v, fl
   }
 }
 
-template <int KIND, bool AMS>
-__global__ void __launch_bounds__(kOptThreads) optim_kernel(const unetpp_optim_segment* __restrict__ segs,
-                                                            int32_t n_segments, const int32_t* __restrict__ chunk_seg,
-                                                            int64_t n_chunks, const double* __restrict__ hyper,
-                                                            const double* __restrict__ steps, int32_t* done) {
+// the step itself; CLIP: every gradient is multiplied by coef (one rounded multiply) as it is read
+template <int KIND, bool AMS, bool CLIP>
+__device__ __forceinline__ void optim_body(const unetpp_optim_segment* __restrict__ segs, int32_t n_segments,
+                                           const int32_t* __restrict__ chunk_seg, int64_t n_chunks,
+                                           const double* __restrict__ hyper, const double* __restrict__ steps,
+                                           int32_t* done, float coef) {
   for (int64_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
     const int si = chunk_seg[c];
     const unetpp_optim_segment sg = segs[si];
@@ -118,7 +129,8 @@ __global__ void __launch_bounds__(kOptThreads) optim_kernel(const unetpp_optim_s
         const int64_t i = begin + (int64_t(k) * kOptThreads + threadIdx.x) * 4;
         if (i >= vend) break;
         f32x4 p = *reinterpret_cast<const f32x4*>(P + i);
-        const f32x4 g = *reinterpret_cast<const f32x4*>(G + i);
+        f32x4 g = *reinterpret_cast<const f32x4*>(G + i);
+        if (CLIP) g = g * coef;
         f32x4 m = {0.f, 0.f, 0.f, 0.f}, v = m, a = m;
         if (moments) {
           m = *reinterpret_cast<const f32x4*>(M + i);
@@ -140,7 +152,7 @@ __global__ void __launch_bounds__(kOptThreads) optim_kernel(const unetpp_optim_s
       }
       for (int64_t i = vend + threadIdx.x; i < end; i += kOptThreads) {   // < 4 elements: the segment's tail
         float pe = P[i], me = moments ? M[i] : 0.f, ve = moments ? V[i] : 0.f, ae = has_aux ? A[i] : 0.f;
-        update<KIND, AMS>(pe, G[i], me, ve, ae, s, decay, has_aux);
+        update<KIND, AMS>(pe, CLIP ? G[i] * coef : G[i], me, ve, ae, s, decay, has_aux);
         P[i] = pe;
         if (moments) M[i] = me, V[i] = ve;
         if (has_aux) A[i] = ae;
@@ -148,7 +160,7 @@ __global__ void __launch_bounds__(kOptThreads) optim_kernel(const unetpp_optim_s
     } else {
       for (int64_t i = begin + threadIdx.x; i < end; i += kOptThreads) {
         float pe = P[i], me = moments ? M[i] : 0.f, ve = moments ? V[i] : 0.f, ae = has_aux ? A[i] : 0.f;
-        update<KIND, AMS>(pe, G[i], me, ve, ae, s, decay, has_aux);
+        update<KIND, AMS>(pe, CLIP ? G[i] * coef : G[i], me, ve, ae, s, decay, has_aux);
         P[i] = pe;
         if (moments) M[i] = me, V[i] = ve;
         if (has_aux) A[i] = ae;
@@ -172,13 +184,156 @@ __global__ void __launch_bounds__(kOptThreads) optim_kernel(const unetpp_optim_s
 }
 
 template <int KIND, bool AMS>
-void launch(const unetpp_optim_segment* segs, int32_t n, const int32_t* chunk_seg, int64_t n_chunks,
-            const double* hyper, const double* steps, int32_t* done, hipStream_t st) {
+__global__ void __launch_bounds__(kOptThreads) optim_kernel(const unetpp_optim_segment* __restrict__ segs,
+                                                            int32_t n_segments, const int32_t* __restrict__ chunk_seg,
+                                                            int64_t n_chunks, const double* __restrict__ hyper,
+                                                            const double* __restrict__ steps, int32_t* done) {
+  optim_body<KIND, AMS, false>(segs, n_segments, chunk_seg, n_chunks, hyper, steps, done, 1.f);
+}
+
+// ---- gradient norm, clip coefficient, non-finite skip ---------------------------------------------------------------
+constexpr int kOptWaves = kOptThreads / 64;
+
+// sum over the workgroup in one fixed order: a tree across each wave, then ((w0 + w1) + (w2 + w3)); every thread gets it.
+// `red` must not be in use by a sum that some wave may still be reading (callers in a loop alternate two buffers).
+__device__ __forceinline__ double block_sum(double v, double* red) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = v + __shfl_down(v, off, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  static_assert(kOptWaves == 4, "the cross-wave order below is written out for four waves");
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+__global__ void __launch_bounds__(kOptThreads) grad_norm_kernel(const unetpp_optim_segment* __restrict__ segs,
+                                                                const int32_t* __restrict__ chunk_seg,
+                                                                int64_t n_chunks, double* __restrict__ partials) {
+  __shared__ double red[2][kOptWaves];
+  int slot = 0;
+  for (int64_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+    const unetpp_optim_segment sg = segs[chunk_seg[c]];
+    const int64_t begin = (c - sg.chunk_begin) * kOptChunk;
+    const int64_t end = begin + kOptChunk < sg.numel ? begin + kOptChunk : sg.numel;
+    const float* __restrict__ G = sg.grad;
+    double acc = 0.0;
+    // thread t owns elements (k*256 + t)*4 + e of the chunk, added in (k, e) order -- float4 loads where the segment is
+    // aligned and the four are inside it, scalar loads of the same elements otherwise: the same sum either way
+#pragma unroll
+    for (int k = 0; k < kOptVecPerThread; ++k) {
+      const int64_t i = begin + (int64_t(k) * kOptThreads + threadIdx.x) * 4;
+      if (i >= end) break;
+      if (sg.vec && i + 4 <= end) {
+        const f32x4 g = *reinterpret_cast<const f32x4*>(G + i);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const double d = static_cast<double>(g[e]);
+          acc = acc + d * d;
+        }
+      } else {
+        for (int e = 0; e < 4 && i + e < end; ++e) {
+          const double d = static_cast<double>(G[i + e]);
+          acc = acc + d * d;
+        }
+      }
+    }
+    const double sum = block_sum(acc, red[slot]);
+    slot ^= 1;
+    if (threadIdx.x == 0) partials[c] = sum;
+  }
+}
+
+struct Clip {
+  float coef;
+  bool skip;
+};
+
+// The launch-boundary reduce: EVERY workgroup sums the norm pass's per-chunk partials in the same fixed order, so all of
+// them hold the same bits without exchanging anything inside the launch; workgroup 0 publishes.  max_norm <= 0: no
+// clipping (coef = 1), the norm is formed for the skip decision and for the caller.
+__device__ __forceinline__ Clip clip_prologue(const double* __restrict__ partials, int64_t n_chunks, float max_norm,
+                                              bool skip_nonfinite, unetpp_clip_state* state, double* red) {
+  double acc = 0.0;
+  for (int64_t j = threadIdx.x; j < n_chunks; j += kOptThreads) acc = acc + partials[j];
+  const double sum = block_sum(acc, red);
+  const float total = static_cast<float>(sqrt(sum));   // the one fp32 rounding
+  Clip cl;
+  cl.coef = 1.f;
+  if (max_norm > 0.f) {
+    const float c = max_norm / (total + 1e-6f);
+    cl.coef = c > 1.f ? 1.f : c;                       // NaN stays NaN, as torch.clamp keeps it
+  }
+  cl.skip = skip_nonfinite && !isfinite(sum);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    state->total_norm = total;
+    state->coef = cl.coef;
+    if (cl.skip) state->skipped_steps = state->skipped_steps + 1;
+  }
+  return cl;
+}
+
+template <int KIND, bool AMS>
+__global__ void __launch_bounds__(kOptThreads) optim_clip_kernel(const unetpp_optim_segment* __restrict__ segs,
+                                                                 int32_t n_segments,
+                                                                 const int32_t* __restrict__ chunk_seg,
+                                                                 int64_t n_chunks, const double* __restrict__ hyper,
+                                                                 const double* __restrict__ steps, int32_t* done,
+                                                                 const double* __restrict__ partials,
+                                                                 unetpp_clip_state* state, int32_t skip_nonfinite) {
+  __shared__ double red[kOptWaves];
+  const Clip cl = clip_prologue(partials, n_chunks, static_cast<float>(hyper[UNETPP_OPTIM_H_MAX_NORM]),
+                                skip_nonfinite != 0, state, red);
+  if (cl.skip) return;   // every workgroup decides alike: nothing is stored, the arrival counter stays zero
+  optim_body<KIND, AMS, true>(segs, n_segments, chunk_seg, n_chunks, hyper, steps, done, cl.coef);
+}
+
+__global__ void __launch_bounds__(kOptThreads) grad_scale_kernel(const unetpp_optim_segment* __restrict__ segs,
+                                                                 const int32_t* __restrict__ chunk_seg,
+                                                                 int64_t n_chunks, const double* __restrict__ partials,
+                                                                 float max_norm, unetpp_clip_state* state) {
+  __shared__ double red[kOptWaves];
+  const Clip cl = clip_prologue(partials, n_chunks, max_norm, false, state, red);
+  if (cl.coef == 1.f) return;   // g * 1 = g bit for bit: nothing to write
+  const float coef = cl.coef;
+  for (int64_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+    const unetpp_optim_segment sg = segs[chunk_seg[c]];
+    const int64_t begin = (c - sg.chunk_begin) * kOptChunk;
+    const int64_t end = begin + kOptChunk < sg.numel ? begin + kOptChunk : sg.numel;
+    float* __restrict__ G = const_cast<float*>(sg.grad);
+    int64_t tail = begin;   // where the scalar loop starts
+    if (sg.vec) {
+      const int64_t vend = begin + ((end - begin) & ~int64_t(3));
+#pragma unroll
+      for (int k = 0; k < kOptVecPerThread; ++k) {
+        const int64_t i = begin + (int64_t(k) * kOptThreads + threadIdx.x) * 4;
+        if (i >= vend) break;
+        const f32x4 g = *reinterpret_cast<const f32x4*>(G + i);
+        *reinterpret_cast<f32x4*>(G + i) = g * coef;
+      }
+      tail = vend;   // < 4 elements: the segment's tail
+    }
+    for (int64_t i = tail + threadIdx.x; i < end; i += kOptThreads) G[i] = G[i] * coef;
+  }
+}
+
+inline unsigned persistent_grid(int64_t n_chunks) {
   const int cus = device_cu_count();
   const int64_t cap = int64_t(cus > 0 ? cus : 256) * 8;
-  const unsigned grid = static_cast<unsigned>(n_chunks < cap ? n_chunks : cap);
-  hipLaunchKernelGGL((optim_kernel<KIND, AMS>), dim3(grid), dim3(kOptThreads), 0, st, segs, n, chunk_seg, n_chunks,
-                     hyper, steps, done);
+  return static_cast<unsigned>(n_chunks < cap ? n_chunks : cap);
+}
+
+template <int KIND, bool AMS>
+void launch(const unetpp_optim_segment* segs, int32_t n, const int32_t* chunk_seg, int64_t n_chunks,
+            const double* hyper, const double* steps, int32_t* done, hipStream_t st) {
+  hipLaunchKernelGGL((optim_kernel<KIND, AMS>), dim3(persistent_grid(n_chunks)), dim3(kOptThreads), 0, st, segs, n,
+                     chunk_seg, n_chunks, hyper, steps, done);
+}
+
+template <int KIND, bool AMS>
+void launch_clip(const unetpp_optim_segment* segs, int32_t n, const int32_t* chunk_seg, int64_t n_chunks,
+                 const double* hyper, const double* steps, int32_t* done, const double* partials,
+                 unetpp_clip_state* state, int32_t skip, hipStream_t st) {
+  hipLaunchKernelGGL((optim_clip_kernel<KIND, AMS>), dim3(persistent_grid(n_chunks)), dim3(kOptThreads), 0, st, segs, n,
+                     chunk_seg, n_chunks, hyper, steps, done, partials, state, skip);
 }
 
 }  // namespace
@@ -206,6 +361,54 @@ extern "C" int unetpp_optim_step(int32_t kind, int32_t flags, const unetpp_optim
     case UNETPP_OPTIM_ADABOUND * 2 + 1: launch<UNETPP_OPTIM_ADABOUND, true>(segments, n_segments, chunk_segment, n_chunks, hyper, steps, done, st); note_kernel("optim_adabound_amsbound"); break;
     default: launch<UNETPP_OPTIM_SGDW, false>(segments, n_segments, chunk_segment, n_chunks, hyper, steps, done, st); note_kernel("optim_sgdw"); break;
   }
+  return launch_status();
+}
+
+extern "C" int unetpp_grad_norm(const unetpp_optim_segment* segments, int32_t n_segments, const int32_t* chunk_segment,
+                               int64_t n_chunks, double* partials, void* stream) {
+  if (segments == nullptr || n_segments <= 0 || chunk_segment == nullptr || n_chunks <= 0 || partials == nullptr)
+    return UNETPP_EINVAL;
+  hipLaunchKernelGGL(grad_norm_kernel, dim3(persistent_grid(n_chunks)), dim3(kOptThreads), 0,
+                     static_cast<hipStream_t>(stream), segments, chunk_segment, n_chunks, partials);
+  note_kernel("grad_norm");
+  return launch_status();
+}
+
+extern "C" int unetpp_optim_step_clip(int32_t kind, int32_t flags, const unetpp_optim_segment* segments,
+                                      int32_t n_segments, const int32_t* chunk_segment, int64_t n_chunks,
+                                      const double* hyper, const double* steps, int32_t* done, const double* partials,
+                                      unetpp_clip_state* state, void* stream) {
+  if (segments == nullptr || n_segments <= 0 || chunk_segment == nullptr || n_chunks <= 0 || hyper == nullptr ||
+      partials == nullptr || state == nullptr)
+    return UNETPP_EINVAL;
+  if (kind < UNETPP_OPTIM_ADAMW || kind > UNETPP_OPTIM_SGDW) return UNETPP_EINVAL;
+  if ((flags & ~(UNETPP_OPTIM_AMS | UNETPP_OPTIM_CAPTURABLE | UNETPP_OPTIM_SKIP_NONFINITE)) != 0) return UNETPP_EINVAL;
+  const bool ams = (flags & UNETPP_OPTIM_AMS) != 0, capturable = (flags & UNETPP_OPTIM_CAPTURABLE) != 0;
+  const int32_t skip = (flags & UNETPP_OPTIM_SKIP_NONFINITE) != 0;
+  if (ams && kind == UNETPP_OPTIM_SGDW) return UNETPP_EINVAL;
+  if (skip && !capturable) return UNETPP_EINVAL;   // an eager caller has advanced its step counts already
+  if (capturable ? (done == nullptr || steps != nullptr) : (steps == nullptr || done != nullptr)) return UNETPP_EINVAL;
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  switch (kind * 2 + (ams ? 1 : 0)) {
+    case UNETPP_OPTIM_ADAMW * 2: launch_clip<UNETPP_OPTIM_ADAMW, false>(segments, n_segments, chunk_segment, n_chunks, hyper, steps, done, partials, state, skip, st); note_kernel("optim_clip_adamw"); break;
+    case UNETPP_OPTIM_ADAMW * 2 + 1: launch_clip<UNETPP_OPTIM_ADAMW, true>(segments, n_segments, chunk_segment, n_chunks, hyper, steps, done, partials, state, skip, st); note_kernel("optim_clip_adamw_amsgrad"); break;
+    case UNETPP_OPTIM_ADABOUND * 2: launch_clip<UNETPP_OPTIM_ADABOUND, false>(segments, n_segments, chunk_segment, n_chunks, hyper, steps, done, partials, state, skip, st); note_kernel("optim_clip_adabound"); break;
+    case UNETPP_OPTIM_ADABOUND * 2 + 1: launch_clip<UNETPP_OPTIM_ADABOUND, true>(segments, n_segments, chunk_segment, n_chunks, hyper, steps, done, partials, state, skip, st); note_kernel("optim_clip_adabound_amsbound"); break;
+    default: launch_clip<UNETPP_OPTIM_SGDW, false>(segments, n_segments, chunk_segment, n_chunks, hyper, steps, done, partials, state, skip, st); note_kernel("optim_clip_sgdw"); break;
+  }
+  return launch_status();
+}
+
+extern "C" int unetpp_grad_scale(const unetpp_optim_segment* segments, int32_t n_segments, const int32_t* chunk_segment,
+                                int64_t n_chunks, const double* partials, float max_norm, unetpp_clip_state* state,
+                                void* stream) {
+  if (segments == nullptr || n_segments <= 0 || chunk_segment == nullptr || n_chunks <= 0 || partials == nullptr ||
+      state == nullptr)
+    return UNETPP_EINVAL;
+  if (!(max_norm > 0.f)) return UNETPP_EINVAL;
+  hipLaunchKernelGGL(grad_scale_kernel, dim3(persistent_grid(n_chunks)), dim3(kOptThreads), 0,
+                     static_cast<hipStream_t>(stream), segments, chunk_segment, n_chunks, partials, max_norm, state);
+  note_kernel("grad_scale");
   return launch_status();
 }
 

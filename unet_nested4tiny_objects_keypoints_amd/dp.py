@@ -28,6 +28,12 @@ autograd would leave them); a handed-out ``p.grad`` is a view into one of two al
 until the backward AFTER the next one (clone it to keep it longer); tensor hooks / post-accumulate hooks on parameters
 never fire on this path (delivery does not go through AccumulateGrad), so registering them is refused, and
 ``torch.autograd.grad(loss, params)`` is not supported with an attached averager (use ``loss.backward()``).
+
+Gradient clipping (optim.py: ``max_grad_norm`` / ``skip_nonfinite`` of the fused optimizers, ``clip_grad_norm_``) needs
+nothing here: ``optimizer.step()`` runs after the averager has delivered the all-reduced gradients into ``p.grad``, so
+the global norm it forms is that of the AVERAGED gradients, and since its summation order is fixed it comes out
+bit-identical on every rank -- every rank clips by the same coefficient and skips the same steps without another
+collective.  This is reasoned from the code, not run: the project has had no hardware run with more than one GPU.
 """
 from __future__ import annotations
 

@@ -153,7 +153,9 @@ class GraphedTrainStep:
         saved = None
         if restore_state:
             saved = ([p.detach().clone() for p in params], [b.detach().clone() for b in model.buffers()],
-                     copy.deepcopy(optimizer.state_dict()), {id(p) for p in optimizer.state})
+                     copy.deepcopy(optimizer.state_dict()), {id(p) for p in optimizer.state},
+                     # the fused optimizers' clip block (last_grad_norm, skipped_steps): not part of optimizer.state
+                     None if getattr(optimizer, "_clip_dev", None) is None else optimizer._clip_dev.clone())
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         check_topology = check_topology or debug_dot is not None
@@ -222,6 +224,9 @@ class GraphedTrainStep:
                         st[k] = copy.deepcopy(old[k])
                     elif isinstance(v, (int, float)):
                         st[k] = type(v)(0)
+            clip = getattr(self.optimizer, "_clip_dev", None)
+            if clip is not None:                              # made by the warm-up when there was none: zeros are fresh
+                clip.copy_(saved[4]) if saved[4] is not None else clip.zero_()
         if self._plan is not None:
             self._plan.invalidate()
 

@@ -25,6 +25,22 @@ data, so ``GraphedTrainStep(..., capture_optimizer=True)`` captures the step.  T
 small device block: an eager ``step()`` refreshes it, a captured one does not, so after changing ``group['lr']`` (an LR
 scheduler) call ``refresh_hyperparameters()`` before the next replay.
 
+Gradient clipping and the non-finite skip (keyword-only ``max_grad_norm=None``, ``skip_nonfinite=False``; optimizer
+attributes, not param-group keys, so ``state_dict()`` keeps the reference's format): with either set, ``step()`` is two
+launches over the same table.  ``unetpp_grad_norm`` leaves one float64 sum of squares per 4096-element chunk; the update
+launch (``unetpp_optim_step_clip``) sums them in a fixed order in every workgroup's prologue, forms torch's
+``clip_grad_norm_`` coefficient in fp32 (``c = max_norm / (norm + 1e-6)``, ``min(c, 1)``) over ALL groups' gradients and
+multiplies each gradient by it as it is read -- ``p.grad`` is not written.  ``skip_nonfinite=True`` (capturable mode only:
+eager mode has advanced ``state['step']`` on the host before the launch) makes a step whose gradients hold an inf or a NaN
+store nothing: parameters, moments and step counters stay, ``skipped_steps`` advances.  ``last_grad_norm`` (0-dim float32,
+the norm before clipping, overwritten by every step: clone it to keep it) and ``skipped_steps`` (0-dim int32) are device
+tensors; reading them is the caller's sync, ``step()`` makes none.  ``opt.max_grad_norm = x`` holds from the next eager
+step; a captured step reads it from the device hyper block (``refresh_hyperparameters()``, as for lr).  The defaults
+leave the code path, the launch and the results exactly as they were.
+
+``clip_grad_norm_(parameters, max_norm)`` is ``torch.nn.utils.clip_grad_norm_`` for fp32 CUDA gradients as two launches
+(norm, in-place scale), for optimizers that are not the three above or for code that wants the clipped gradients.
+
 fp32 CUDA tensors only: anything else raises (this path has no CPU fallback).
 """
 from __future__ import annotations
@@ -44,7 +60,8 @@ _MAX_TABLES = 8     # cached device tables (the data-parallel averager alternate
 
 class _Table:
     """One cached device table: segments, chunk -> segment map, the arrival counter of capturable launches."""
-    __slots__ = ("dev", "host", "n_seg", "n_chunks", "chunk_off", "done_off", "block", "pinned", "rows_used")
+    __slots__ = ("dev", "host", "n_seg", "n_chunks", "chunk_off", "done_off", "block", "pinned", "rows_used",
+                 "partials")     # partials: float64 [n_chunks] of the norm pass, made when a clipped step first needs it
 
 
 class _FusedOptimizer(Optimizer):
@@ -53,8 +70,14 @@ class _FusedOptimizer(Optimizer):
     _AMS_KEY = None          # group key that selects max_exp_avg_sq
     _MOMENTS = True          # exp_avg / exp_avg_sq (AdamW, AdaBound)
 
-    def _init_fused(self, capturable: bool):
+    def _init_fused(self, capturable: bool, max_grad_norm=None, skip_nonfinite: bool = False):
         self.capturable = bool(capturable)
+        self.max_grad_norm = max_grad_norm
+        self.skip_nonfinite = bool(skip_nonfinite)
+        if self.skip_nonfinite and not self.capturable:
+            raise ValueError("skip_nonfinite=True needs capturable=True: eager mode advances state['step'] on the host "
+                             "before the launch, and a skip decided on the device cannot take that back without a sync")
+        self._clip_dev = None      # device mirror of unetpp_clip_state: total_norm, coef, skipped_steps, reserved
         self._tables = collections.OrderedDict()
         self._state_epoch = 0
         self._hyper_dev = None
@@ -66,7 +89,44 @@ class _FusedOptimizer(Optimizer):
 
     def _hyper(self) -> np.ndarray:
         rows = [self._hyper_row(gi, g) for gi, g in enumerate(self.param_groups)]
-        return np.asarray(rows, dtype=np.float64).reshape(-1)
+        h = np.asarray(rows, dtype=np.float64).reshape(-1)
+        if self._max_grad_norm is not None:
+            h[_lib.OPTIM_H_MAX_NORM] = self._max_grad_norm      # row 0; 0 = no clipping
+        return h
+
+    # ---- clipping --------------------------------------------------------------------------------------------------
+    @property
+    def max_grad_norm(self):
+        """Largest global 2-norm of all gradients a step applies (None: no clipping)."""
+        return self._max_grad_norm
+
+    @max_grad_norm.setter
+    def max_grad_norm(self, value):
+        if value is not None:
+            value = float(value)
+            if not value > 0.0:
+                raise ValueError("Invalid max_grad_norm: {}".format(value))
+        self._max_grad_norm = value
+
+    def _clip_block(self) -> torch.Tensor:
+        if self._clip_dev is None:
+            dev = self._device()
+            if dev is None or dev.type != "cuda":
+                raise RuntimeError("%s parameters must live on the GPU: this path has no CPU fallback" % type(self).__name__)
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("capturable %s: run one eager step() before capturing it" % type(self).__name__)
+            self._clip_dev = torch.zeros(4, dtype=torch.float32, device=dev)
+        return self._clip_dev
+
+    @property
+    def last_grad_norm(self) -> torch.Tensor:
+        """0-dim float32 device tensor: the global gradient norm the last clipped step saw, before clipping."""
+        return self._clip_block()[0]
+
+    @property
+    def skipped_steps(self) -> torch.Tensor:
+        """0-dim int32 device tensor: steps that skip_nonfinite left undone."""
+        return self._clip_block()[2:3].view(torch.int32)[0]
 
     def refresh_hyperparameters(self):
         """capturable mode: copy the groups' current hyper-parameters (lr, betas, ...) to the device block the captured
@@ -152,22 +212,35 @@ class _FusedOptimizer(Optimizer):
                 self.refresh_hyperparameters()
             elif self._hyper_dev is None:
                 raise RuntimeError("capturable %s: run one eager step() before capturing it" % type(self).__name__)
-            status = L.unetpp_optim_step(self._KIND, self._flags() | _lib.OPTIM_CAPTURABLE, C.c_void_p(base), table.n_seg,
-                                         C.c_void_p(base + table.chunk_off), table.n_chunks,
-                                         C.c_void_p(self._hyper_dev.data_ptr()), None, C.c_void_p(base + table.done_off),
-                                         stream)
+            args = (C.c_void_p(base), table.n_seg, C.c_void_p(base + table.chunk_off), table.n_chunks,
+                    C.c_void_p(self._hyper_dev.data_ptr()), None, C.c_void_p(base + table.done_off))
+            flags = self._flags() | _lib.OPTIM_CAPTURABLE
         else:
             h = self._hyper()
+            if table.rows_used is not None:      # zero-element parameters have no segment, so no count in the block
+                steps = [steps[i] for i in table.rows_used]
             host = torch.empty(h.size + len(steps), dtype=torch.float64, pin_memory=True)
             arr = host.numpy()
             arr[:h.size] = h
-            arr[h.size:] = [steps[i] for i in table.rows_used] if table.rows_used is not None else steps
+            arr[h.size:] = steps
             table.block.copy_(host, non_blocking=True)
             blk = table.block.data_ptr()
-            status = L.unetpp_optim_step(self._KIND, self._flags(), C.c_void_p(base), table.n_seg,
-                                         C.c_void_p(base + table.chunk_off), table.n_chunks, C.c_void_p(blk),
-                                         C.c_void_p(blk + 8 * h.size), None, stream)
-        _lib.check(status, "unetpp_optim_step")
+            args = (C.c_void_p(base), table.n_seg, C.c_void_p(base + table.chunk_off), table.n_chunks, C.c_void_p(blk),
+                    C.c_void_p(blk + 8 * h.size), None)
+            flags = self._flags()
+        if self._max_grad_norm is None and not self.skip_nonfinite:
+            _lib.check(L.unetpp_optim_step(self._KIND, flags, *args, stream), "unetpp_optim_step")
+            return loss
+        # clipped: the norm pass over the same table, then the update that combines its partials in its prologue
+        state = self._clip_block()
+        if table.partials is None:
+            table.partials = torch.empty(table.n_chunks, dtype=torch.float64, device=table.dev.device)
+        partials = C.c_void_p(table.partials.data_ptr())
+        _lib.check(L.unetpp_grad_norm(args[0], args[1], args[2], args[3], partials, stream), "unetpp_grad_norm")
+        if self.skip_nonfinite:
+            flags |= _lib.OPTIM_SKIP_NONFINITE
+        _lib.check(L.unetpp_optim_step_clip(self._KIND, flags, *args, partials, C.c_void_p(state.data_ptr()), stream),
+                   "unetpp_optim_step_clip")
         return loss
 
     def _flags(self) -> int:
@@ -239,6 +312,7 @@ class _FusedOptimizer(Optimizer):
         t.dev = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         t.host, t.n_seg, t.n_chunks, t.chunk_off, t.done_off = host, n_seg, n_chunks, chunk_off, done_off
         t.pinned = capturing
+        t.partials = None
         t.rows_used = None if len(used) == len(rows) else used
         t.block = None if self.capturable else torch.empty(len(self.param_groups) * _lib.OPTIM_HYPER + len(used),
                                                           dtype=torch.float64, device=dev)
@@ -258,19 +332,20 @@ class AdamW(_FusedOptimizer):
     """AdamW of the reference (tools/optimizers/adamw.py): decoupled weight decay taken from the parameter BEFORE the
     update (``d = p*wd; p = p - step_size*m/denom; p = p - d``), ``step_size = lr*sqrt(1-beta2^t)/(1-beta1^t)``.
 
-    Arguments as the reference's, plus ``capturable`` (keyword; see the module docstring)."""
+    Arguments as the reference's, plus ``capturable``, ``max_grad_norm`` and ``skip_nonfinite`` (keywords; see the module
+    docstring)."""
     _KIND = _lib.OPTIM_ADAMW
     _AMS_KEY = "amsgrad"
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *,
-                 capturable=False):
+                 capturable=False, max_grad_norm=None, skip_nonfinite=False):
         if not 0.0 <= betas[0] < 1.0:
             raise ValueError("Invalid beta parameter at index 0: {}".format(betas[0]))
         if not 0.0 <= betas[1] < 1.0:
             raise ValueError("Invalid beta parameter at index 1: {}".format(betas[1]))
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad)
         super().__init__(params, defaults)
-        self._init_fused(capturable)
+        self._init_fused(capturable, max_grad_norm, skip_nonfinite)
         self._check_ams()
 
     def _check_ams(self):
@@ -310,7 +385,7 @@ class AdaBound(AdamW):
     _AMS_KEY = "amsbound"
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), final_lr=0.1, gamma=1e-3, eps=1e-8, weight_decay=0,
-                 amsbound=False, *, capturable=False):
+                 amsbound=False, *, capturable=False, max_grad_norm=None, skip_nonfinite=False):
         if not 0.0 <= lr:
             raise ValueError("Invalid learning rate: {}".format(lr))
         if not 0.0 <= eps:
@@ -326,7 +401,7 @@ class AdaBound(AdamW):
         defaults = dict(lr=lr, betas=betas, final_lr=final_lr, gamma=gamma, eps=eps, weight_decay=weight_decay,
                         amsbound=amsbound)
         Optimizer.__init__(self, params, defaults)
-        self._init_fused(capturable)
+        self._init_fused(capturable, max_grad_norm, skip_nonfinite)
         self._check_ams()
         self.base_lrs = list(map(lambda group: group["lr"], self.param_groups))
 
@@ -347,17 +422,18 @@ class SGDW(_FusedOptimizer):
     (1-dampening)*grad``; none with momentum 0) and then only decays the weights, ``p = p - weight_decay*p``; ``lr``
     and ``nesterov`` change nothing.  The trainer's call (momentum 0) is therefore a pure weight decay.
 
-    Arguments as the reference's, plus ``capturable`` (keyword; see the module docstring)."""
+    Arguments as the reference's, plus ``capturable``, ``max_grad_norm`` and ``skip_nonfinite`` (keywords; see the module
+    docstring)."""
     _KIND = _lib.OPTIM_SGDW
     _MOMENTS = False
 
     def __init__(self, params, lr=required, momentum=0, dampening=0, weight_decay=0, nesterov=False, *,
-                 capturable=False):
+                 capturable=False, max_grad_norm=None, skip_nonfinite=False):
         defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov)
         if nesterov and (momentum <= 0 or dampening != 0):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
         super().__init__(params, defaults)
-        self._init_fused(capturable)
+        self._init_fused(capturable, max_grad_norm, skip_nonfinite)
 
     def __setstate__(self, state):
         super().__setstate__(state)
@@ -382,4 +458,87 @@ class SGDW(_FusedOptimizer):
         return state["momentum_buffer"] if group["momentum"] != 0 else None
 
 
-__all__ = ["AdamW", "AdaBound", "SGDW"]
+# ---- stand-alone clipping -------------------------------------------------------------------------------------------
+_CLIP_TABLES = collections.OrderedDict()     # (device index, gradient data pointers and sizes) -> _Table
+
+
+def _clip_table(grads) -> _Table:
+    """The cached device table of a set of gradients: segments with grad / numel / chunk_begin / vec only."""
+    dev = grads[0].device
+    key = (dev.index, tuple((g.data_ptr(), g.numel()) for g in grads))
+    t = _CLIP_TABLES.get(key)
+    if t is not None:
+        _CLIP_TABLES.move_to_end(key)
+        return t
+    L = _lib.lib()
+    chunk = int(L.unetpp_optim_chunk_elems())
+    segs, n_chunks_of = [], []
+    n_chunks = 0
+    for g in grads:
+        s = _lib.OptimSegment()
+        s.grad, s.numel, s.chunk_begin, s.group = g.data_ptr(), g.numel(), n_chunks, 0
+        s.vec = int(g.data_ptr() % 16 == 0)
+        segs.append(s)
+        n_chunks_of.append((g.numel() + chunk - 1) // chunk)
+        n_chunks += n_chunks_of[-1]
+    n_seg = len(segs)
+    chunk_off = n_seg * _SEG_BYTES
+    nbytes = chunk_off + 4 * n_chunks
+    host = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+    C.memmove(host.data_ptr(), (_lib.OptimSegment * n_seg)(*segs), chunk_off)
+    host.numpy()[chunk_off:] = np.repeat(np.arange(n_seg, dtype=np.int32), n_chunks_of).view(np.uint8)
+    t = _Table()
+    t.dev = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    t.host, t.n_seg, t.n_chunks, t.chunk_off = host, n_seg, n_chunks, chunk_off
+    t.partials = torch.empty(n_chunks, dtype=torch.float64, device=dev)
+    _lib.check(L.unetpp_optim_upload(C.c_void_p(t.dev.data_ptr()), C.c_void_p(host.data_ptr()), nbytes,
+                                     C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "unetpp_optim_upload")
+    _CLIP_TABLES[key] = t
+    while len(_CLIP_TABLES) > _MAX_TABLES:
+        _CLIP_TABLES.popitem(last=False)
+    return t
+
+
+@torch.no_grad()
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False) -> torch.Tensor:
+    """``torch.nn.utils.clip_grad_norm_`` for fp32 CUDA gradients as two launches: the norm pass over a cached table of
+    the gradients (float64 sums, one fp32 rounding), then ``grad *= min(max_norm / (norm + 1e-6), 1)`` in place (nothing
+    is written when the coefficient is 1).  Returns the norm before clipping as a 0-dim device tensor without a host
+    sync; ``error_if_nonfinite=True`` reads it on the host before anything is scaled.  Parameters whose ``grad`` is None
+    are skipped.  2-norm only; CPU tensors and other dtypes raise (no fallback)."""
+    from .ops import _need
+    if torch.is_tensor(parameters):
+        parameters = [parameters]
+    if float(norm_type) != 2.0:
+        raise ValueError("clip_grad_norm_: only norm_type=2 is implemented, got %r" % (norm_type,))
+    max_norm = float(max_norm)
+    if not max_norm > 0.0:
+        raise ValueError("Invalid max_norm: {}".format(max_norm))
+    grads = [_need(p.grad, "clip_grad_norm_ gradient") for p in parameters if p.grad is not None]
+    if not grads:
+        return torch.tensor(0.0)
+    if any(g.device != grads[0].device for g in grads):
+        raise ValueError("clip_grad_norm_: all gradients must live on one device")
+    dev = grads[0].device
+    grads = [g for g in grads if g.numel() > 0]
+    if not grads:
+        return torch.zeros((), dtype=torch.float32, device=dev)
+    table = _clip_table(grads)
+    L = _lib.lib()
+    state = torch.empty(4, dtype=torch.float32, device=dev)      # this call's own: the returned norm is not overwritten
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    base = table.dev.data_ptr()
+    args = (C.c_void_p(base), table.n_seg, C.c_void_p(base + table.chunk_off), table.n_chunks,
+            C.c_void_p(table.partials.data_ptr()))
+    _lib.check(L.unetpp_grad_norm(*args, stream), "unetpp_grad_norm")
+    if error_if_nonfinite:
+        total = torch.sqrt(table.partials.sum())
+        if not bool(torch.isfinite(total)):
+            raise RuntimeError("The total norm of order 2.0 for gradients from `parameters` is non-finite, so it cannot "
+                               "be clipped. To disable this error and scale the gradients by the non-finite norm "
+                               "anyway, set `error_if_nonfinite=False`")
+    _lib.check(L.unetpp_grad_scale(*args, max_norm, C.c_void_p(state.data_ptr()), stream), "unetpp_grad_scale")
+    return state[0]
+
+
+__all__ = ["AdamW", "AdaBound", "SGDW", "clip_grad_norm_"]
