@@ -616,6 +616,61 @@ int unetpp_avg_update(int32_t kind, int32_t flags, const unetpp_avg_segment* seg
                       const int32_t* chunk_segment, int64_t n_chunks, int64_t count, double decay, float* count_dev,
                       const double* hyper_dev, int32_t* done, void* stream);
 
+/* ---- Device-resident input pipeline (csrc/loader.hip): the part of the training loop the reference leaves on the host
+ * (DatasetsBase.__getitem__ decodes an image and applies an empty transforms.Compose).  The decoded data set stays on the
+ * device; one launch gathers a batch from it, warps it, normalises it and carries the key-point labels through the same
+ * transform.  Added within ABI version 12 without changing anything that was there before. ---- */
+#define UNETPP_WARP_PARAMS 16     /* floats per sample of the parameter table */
+#define UNETPP_WARP_MAX_C 8
+#define UNETPP_STORE_U8 0         /* store uint8 [M, Hs, Ws, C]: decoded images, channels last */
+#define UNETPP_STORE_F32 1        /* store float32 [M, C, Hs, Ws] */
+
+/* One sample's row of the parameter table, 16 floats.  Coordinates are pixel indices, a pixel centre is an integer
+ * (align_corners = True):
+ *   [0..5]   inverse map, output pixel -> source position:  xs = m0*xo + m1*yo + m2,  ys = m3*xo + m4*yo + m5
+ *   [6..11]  forward map, source position -> output position, same form (labels)
+ *   [12]     gain     [13] bias     [14..15] zero
+ *
+ * unetpp_warp_batch: out[n, c, yo, xo] = gain * (v * mul[c] + add[c]) + bias, out float32 [N, C, Ho, Wo] contiguous, v =
+ * the bilinear sample of sample index[n] of the store at (xs, ys): the four neighbours of the position weighted
+ * (1-fx)(1-fy), fx(1-fy), (1-fx)fy, fx fy, a neighbour outside the source frame contributing `fill` (source units) -- so v
+ * is continuous in the position everywhere, and a map with whole entries copies pixels bit for bit.  Every operation is
+ * rounded once (no contraction).  index int64 [N], params float32 [N][16], mul / add float32 [C], all on the device.
+ * An index outside [0, M) gives an all-fill sample by the same arithmetic; nothing outside the store is read.
+ * labels (may be NULL, then S = 0 and labels_out = inside = NULL): float32 [M, S, 2] as (x, y) -> labels_out [N, S, 2] by
+ * the forward map and inside [N, S] uint8 = 1 iff 0 <= x <= Wo-1 and 0 <= y <= Ho-1.  A source label with a negative
+ * coordinate (the "none" sentinel (-1, -1)) and every label of an out-of-range index come out (-1, -1) with inside = 0.
+ * UNETPP_EINVAL without touching the device for a null pointer, a size <= 0, C > UNETPP_WARP_MAX_C, an image side above
+ * 2^24 or an unknown store type. */
+int unetpp_warp_batch(const void* store, int32_t store_type, int64_t M, int32_t Hs, int32_t Ws, int32_t C,
+                      const int64_t* index, int32_t N, const float* params, const float* mul, const float* add,
+                      float fill, float* out, int32_t Ho, int32_t Wo, const float* labels, int32_t S,
+                      float* labels_out, uint8_t* inside, void* stream);
+
+/* What unetpp_augment_draw draws from.  The defaults of the Python Augment are the blur-free family: flips, quarter
+ * turns and whole-pixel shifts are pixel permutations under the bilinear kernel. */
+typedef struct unetpp_augment {
+  float p_flip_h, p_flip_v;   /* probability of a flip in x / in y */
+  int32_t rot90;              /* non-zero: 0..3 quarter turns, applied as an exact integer matrix */
+  float max_deg;              /* rotation in [-max_deg, max_deg] degrees */
+  float scale_lo, scale_hi;   /* log-uniform scale, both > 0 */
+  float max_tx, max_ty;       /* shift in [-max, max] source pixels, rounded to whole pixels */
+  float gain_lo, gain_hi;     /* contrast */
+  float max_bias;             /* brightness in [-max_bias, max_bias] */
+  int32_t reserved;
+} unetpp_augment;
+
+/* unetpp_augment_draw: params [N][16] (device) for N samples, one thread per sample.  Uniform k of sample n is
+ * u = (mix64(seed + 0x9E3779B97F4A7C15 * (16 n + k + 1)) >> 40) * 2^-24 (splitmix64's finaliser, as the heads' dropout):
+ *   k = 0: flip x iff u < p_flip_h     1: flip y iff u < p_flip_v     2: q = floor(4 u) quarter turns (rot90)
+ *   3: theta = (2u - 1) max_deg        4: s = exp(ln lo + u (ln hi - ln lo))
+ *   5, 6: tx, ty = floor((2u - 1) max_t + 0.5)     7: gain = lo + u (hi - lo)     8: bias = (2u - 1) max_bias
+ * forward  p_o = c_o + D R(theta) Q^q s (p_s - c_s - t),  inverse  p_s = c_s + t + (1/s) Q^-q R(-theta) D (p_o - c_o),
+ * c = ((W - 1) / 2, (H - 1) / 2) of the source / output frame, D = diag(+-1, +-1), Q = [[0, -1], [1, 0]].  All in
+ * float64, rounded to float32 once.  UNETPP_EINVAL for a null pointer, a size <= 0 or a scale bound <= 0. */
+int unetpp_augment_draw(float* params, int32_t N, uint64_t seed, int32_t Hs, int32_t Ws, int32_t Ho, int32_t Wo,
+                        const unetpp_augment* augment, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

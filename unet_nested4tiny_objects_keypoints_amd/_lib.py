@@ -15,7 +15,7 @@ _REPO = os.path.dirname(_PKG_DIR)
 LIB_PATH = os.environ.get("UNETPP_LIB", os.path.join(_PKG_DIR, "libunetpp_hip.so"))  # override: kernel A/B runs
 CSRC = os.path.join(_PKG_DIR, "csrc")
 INCLUDE = os.path.join(_REPO, "include")
-SOURCES = ("gemm_pix.hip", "gemm_fast.hip", "gemm_pw.hip", "gemm_pw_bf16.hip", "gemm_wino.hip", "gemm_bf16.hip", "gemm_bf16_dma.hip", "wgrad_bf16.hip", "pointwise_bf16.hip", "keypoints.hip", "weight_image.hip", "wgrad.hip", "wgrad_fast.hip", "wgrad_dma.hip", "wgrad_pw.hip", "wgrad_wino.hip", "first_layer.hip", "pointwise.hip", "caller.hip", "optim.hip", "validate.hip", "average.hip")
+SOURCES = ("gemm_pix.hip", "gemm_fast.hip", "gemm_pw.hip", "gemm_pw_bf16.hip", "gemm_wino.hip", "gemm_bf16.hip", "gemm_bf16_dma.hip", "wgrad_bf16.hip", "pointwise_bf16.hip", "keypoints.hip", "weight_image.hip", "wgrad.hip", "wgrad_fast.hip", "wgrad_dma.hip", "wgrad_pw.hip", "wgrad_wino.hip", "first_layer.hip", "pointwise.hip", "caller.hip", "optim.hip", "validate.hip", "average.hip", "loader.hip")
 HEADERS = ("common.h", "gemm_units.h", "wgrad_reduce.h", "lds_asm.h", "bf16_common.h", "dropout.h", "bn_fused.h",
            "wino_experiments.h", "dma_experiments.h", "heads_mean.h")
 MAX_VIEWS = 8
@@ -150,6 +150,15 @@ class AvgSegment(C.Structure):
     ]
 
 
+class AugmentDesc(C.Structure):
+    """mirror of struct unetpp_augment"""
+    _fields_ = [
+        ("p_flip_h", C.c_float), ("p_flip_v", C.c_float), ("rot90", C.c_int32), ("max_deg", C.c_float),
+        ("scale_lo", C.c_float), ("scale_hi", C.c_float), ("max_tx", C.c_float), ("max_ty", C.c_float),
+        ("gain_lo", C.c_float), ("gain_hi", C.c_float), ("max_bias", C.c_float), ("reserved", C.c_int32),
+    ]
+
+
 OPTIM_ADAMW, OPTIM_ADABOUND, OPTIM_SGDW = 0, 1, 2   # unetpp_optim_step kinds
 OPTIM_AMS, OPTIM_CAPTURABLE = 1, 2                 # unetpp_optim_step flags
 OPTIM_SKIP_NONFINITE = 4                           # unetpp_optim_step_clip only
@@ -157,6 +166,8 @@ OPTIM_HYPER = 8                                    # doubles per group of the hy
 OPTIM_H_MAX_NORM = 7                               # row 0 of that block: max_norm of unetpp_optim_step_clip
 AVG_MEAN, AVG_EMA, AVG_SWAP = 0, 1, 2                # unetpp_avg_update kinds
 AVG_CAPTURABLE = 1                                 # unetpp_avg_update flags
+WARP_PARAMS, WARP_MAX_C = 16, 8                    # floats per row of a warp parameter table; channels of a store
+STORE_U8, STORE_F32 = 0, 1                         # unetpp_warp_batch store types
 MATCH_MAX = 64                                     # UNETPP_MATCH_MAX: labels / predictions per map of the matcher
 
 _P, _I32, _I64, _F, _U64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_uint64
@@ -243,6 +254,10 @@ SIGNATURES = {
     "unetpp_grad_norm": (C.c_int, [_P, _I32, _P, _I64, _P, _P]),
     "unetpp_optim_step_clip": (C.c_int, [_I32, _I32, _P, _I32, _P, _I64, _P, _P, _P, _P, _P, _P]),
     "unetpp_grad_scale": (C.c_int, [_P, _I32, _P, _I64, _P, _F, _P, _P]),
+    # device-resident input pipeline (loader.hip; added within ABI 12)
+    "unetpp_warp_batch": (C.c_int, [_P, _I32, _I64, _I32, _I32, _I32, _P, _I32, _P, _P, _P, _F, _P, _I32, _I32, _P, _I32,
+                                    _P, _P, _P]),
+    "unetpp_augment_draw": (C.c_int, [_P, _I32, _U64, _I32, _I32, _I32, _I32, C.POINTER(AugmentDesc), _P]),
 }
 
 _LIB = None

@@ -1025,3 +1025,63 @@ def match_points(points: torch.Tensor, found: torch.Tensor, labels: torch.Tensor
     check(lib.unetpp_match_points(_ptr(points), _ptr(found), heads, n, c, k, _ptr(labels), s, _ptr(mp), _ptr(mb),
                                   _ptr(matched), _ptr(mask), _ptr(loss), _ptr(count), _stream()), "unetpp_match_points")
     return matched, mask, loss, count
+
+
+def warp_batch(store: torch.Tensor, index: torch.Tensor, params: torch.Tensor, out_size, mul: torch.Tensor,
+               add: torch.Tensor, fill: float = 0.0, labels: Optional[torch.Tensor] = None,
+               out: Optional[torch.Tensor] = None):
+    """One launch: gather index [N] from the store (uint8 [M, Hs, Ws, C] or float32 [M, C, Hs, Ws]), warp by params
+    [N, 16], normalise by mul / add [C] -> float32 [N, C, Ho, Wo]; with labels [M, S, 2] also (labels_out [N, S, 2],
+    inside [N, S] uint8) (include/unetpp_hip.h: unetpp_warp_batch).  out: a contiguous float32 [N, C, Ho, Wo] to write."""
+    if not store.is_cuda:
+        raise RuntimeError("store must live on the GPU: this path has no CPU fallback")
+    if store.dtype not in (torch.uint8, torch.float32):
+        raise TypeError("store must be uint8 [M, Hs, Ws, C] or float32 [M, C, Hs, Ws], got %s" % store.dtype)
+    if store.dim() != 4 or not store.is_contiguous():
+        raise ValueError("store must be a contiguous 4-d tensor")
+    u8 = store.dtype == torch.uint8
+    m, (hs, ws, c) = int(store.shape[0]), (store.shape[1:] if u8 else (store.shape[2], store.shape[3], store.shape[1]))
+    hs, ws, c = int(hs), int(ws), int(c)
+    if not 1 <= c <= _lib.WARP_MAX_C:
+        raise ValueError("a store has 1 to %d channels, got %d" % (_lib.WARP_MAX_C, c))
+    _need(index, "index", torch.int64)
+    _need(params, "params")
+    _need(mul, "mul")
+    _need(add, "add")
+    n = int(index.numel())
+    if index.dim() != 1 or tuple(params.shape) != (n, _lib.WARP_PARAMS):
+        raise ValueError("index [N] and params [N, %d]" % _lib.WARP_PARAMS)
+    if tuple(mul.shape) != (c,) or tuple(add.shape) != (c,):
+        raise ValueError("mul and add must be [%d]" % c)
+    ho, wo = int(out_size[0]), int(out_size[1])
+    dev = store.device
+    if out is None:
+        out = torch.empty(n, c, ho, wo, dtype=torch.float32, device=dev)
+    elif tuple(_need(out, "out").shape) != (n, c, ho, wo):
+        raise ValueError("out must be [%d, %d, %d, %d]" % (n, c, ho, wo))
+    s, labels_out, inside = 0, None, None
+    if labels is not None:
+        _need(labels, "labels")
+        if labels.dim() != 3 or labels.shape[0] != m or labels.shape[2] != 2:
+            raise ValueError("labels must be [M, S, 2] with the store's M")
+        s = int(labels.shape[1])
+        labels_out = torch.empty(n, s, 2, dtype=torch.float32, device=dev)
+        inside = torch.empty(n, s, dtype=torch.uint8, device=dev)
+    nbytes = 4.0 * n * c * ho * wo + (1 if u8 else 4) * float(n) * c * min(hs * ws, ho * wo) + 17.0 * n * s
+    _timed_call("warp_batch", 0.0, lambda: check(_lib.lib().unetpp_warp_batch(
+        _ptr(store), _lib.STORE_U8 if u8 else _lib.STORE_F32, m, hs, ws, c, _ptr(index), n, _ptr(params), _ptr(mul),
+        _ptr(add), float(fill), _ptr(out), ho, wo, _ptr(labels), s, _ptr(labels_out), _ptr(inside), _stream()),
+        "unetpp_warp_batch"), nbytes)
+    return out if labels is None else (out, labels_out, inside)
+
+
+def augment_draw(n: int, seed: int, src_size, out_size, desc: "_lib.AugmentDesc", device) -> torch.Tensor:
+    """params [n, 16] drawn on the device from a 64-bit seed (include/unetpp_hip.h: unetpp_augment_draw)."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("the parameter table is drawn on the GPU: this path has no CPU fallback")
+    params = torch.empty(int(n), _lib.WARP_PARAMS, dtype=torch.float32, device=device)
+    check(_lib.lib().unetpp_augment_draw(_ptr(params), int(n), int(seed) & 0xFFFFFFFFFFFFFFFF, int(src_size[0]),
+                                         int(src_size[1]), int(out_size[0]), int(out_size[1]), C.byref(desc), _stream()),
+          "unetpp_augment_draw")
+    return params
