@@ -671,6 +671,41 @@ typedef struct unetpp_augment {
 int unetpp_augment_draw(float* params, int32_t N, uint64_t seed, int32_t Hs, int32_t Ws, int32_t Ho, int32_t Wo,
                         const unetpp_augment* augment, void* stream);
 
+/* ---- Scene inference (csrc/scene.hip): a frame far larger than the geometry the kernels are tuned for is cut into
+ * overlapping tiles, the tiles run through the eval forward as a batch, and this launch puts each tile's owned interior
+ * back into the frame maps -- averaging the dihedral variants of a tile (test-time augmentation) on the way.  The
+ * reference has no counterpart (its validation loop feeds whole 256x256 images).  Added within ABI version 12 without
+ * changing anything that was there before. ---- */
+#define UNETPP_SCENE_MAX_VARIANTS 8
+#define UNETPP_SCENE_FLIP_X 1     /* variant code bits: the variant is flip_y(flip_x(transpose(tile))), each step */
+#define UNETPP_SCENE_FLIP_Y 2     /* taken only when its bit is set -- tile pixel (y, x) sits at variant pixel (a, b): */
+#define UNETPP_SCENE_TRANSPOSE 4  /* (a, b) = (y, x), swapped by TRANSPOSE; then b = Tw-1-b (FLIP_X), a = Th-1-a (FLIP_Y) */
+
+/* One tile of a chunk.  The tile covers frame pixels [oy, oy + Th) x [ox, ox + Tw) and OWNS the half-open rectangle
+ * [y_lo, y_hi) x [x_lo, x_hi) (frame coordinates) inside it: only that part of its maps is read, and only that part of
+ * the frame is written. */
+typedef struct unetpp_scene_rect {
+  int32_t frame;               /* index on out's leading axis; negative: a padding tile, skipped */
+  int32_t oy, ox;
+  int32_t y_lo, y_hi, x_lo, x_hi;
+  int32_t reserved;
+} unetpp_scene_rect;
+
+/* unetpp_scene_stitch: tiles float32 [n_tiles, K, C, Th, Tw] (device): the head maps of K dihedral variants of every
+ * tile, variant k made with code variants[k] (host array of K codes, bits above).  For every owned frame pixel (y, x)
+ * of tile t and every class c:  out[frame, c, y, x] = (((v_0 + v_1) + ...) + v_{K-1}) / float(K), v_k = the value of
+ * variant k at the pixel (y - oy, x - ox) lands on (the inverse of the variant's transform); K = 1 stores v_0.  The same
+ * expression, with a true division, as unetpp_heads_mean_fwd; every operation rounded once.  out float32 [S, C, H, W]
+ * (device), offsets into it are 64-bit.  rects / rects_dev: the same n_tiles rows on the host (checked here; they size
+ * the grid) and on the device (read by the kernel).  Owned rectangles of one call must not overlap: every owned pixel is
+ * written exactly once, by one thread; no atomics, no LDS.
+ * UNETPP_EINVAL without touching the device for a null pointer, a size <= 0, K outside 1..8, an unknown variant bit, a
+ * transposing variant with Th != Tw, n_tiles or C above 65535, or a live row whose frame is >= S, whose tile leaves the
+ * frame, or whose owned rectangle is empty or leaves the tile. */
+int unetpp_scene_stitch(const float* tiles, int32_t n_tiles, int32_t K, int32_t C, int32_t Th, int32_t Tw,
+                        const int32_t* variants, const unetpp_scene_rect* rects, const unetpp_scene_rect* rects_dev,
+                        float* out, int32_t S, int32_t H, int32_t W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,7 +15,7 @@ _REPO = os.path.dirname(_PKG_DIR)
 LIB_PATH = os.environ.get("UNETPP_LIB", os.path.join(_PKG_DIR, "libunetpp_hip.so"))  # override: kernel A/B runs
 CSRC = os.path.join(_PKG_DIR, "csrc")
 INCLUDE = os.path.join(_REPO, "include")
-SOURCES = ("gemm_pix.hip", "gemm_fast.hip", "gemm_pw.hip", "gemm_pw_bf16.hip", "gemm_wino.hip", "gemm_bf16.hip", "gemm_bf16_dma.hip", "wgrad_bf16.hip", "pointwise_bf16.hip", "keypoints.hip", "weight_image.hip", "wgrad.hip", "wgrad_fast.hip", "wgrad_dma.hip", "wgrad_pw.hip", "wgrad_wino.hip", "first_layer.hip", "pointwise.hip", "caller.hip", "optim.hip", "validate.hip", "average.hip", "loader.hip")
+SOURCES = ("gemm_pix.hip", "gemm_fast.hip", "gemm_pw.hip", "gemm_pw_bf16.hip", "gemm_wino.hip", "gemm_bf16.hip", "gemm_bf16_dma.hip", "wgrad_bf16.hip", "pointwise_bf16.hip", "keypoints.hip", "weight_image.hip", "wgrad.hip", "wgrad_fast.hip", "wgrad_dma.hip", "wgrad_pw.hip", "wgrad_wino.hip", "first_layer.hip", "pointwise.hip", "caller.hip", "optim.hip", "validate.hip", "average.hip", "loader.hip", "scene.hip")
 HEADERS = ("common.h", "gemm_units.h", "wgrad_reduce.h", "lds_asm.h", "bf16_common.h", "dropout.h", "bn_fused.h",
            "wino_experiments.h", "dma_experiments.h", "heads_mean.h")
 MAX_VIEWS = 8
@@ -159,6 +159,14 @@ class AugmentDesc(C.Structure):
     ]
 
 
+class SceneRect(C.Structure):
+    """mirror of struct unetpp_scene_rect"""
+    _fields_ = [
+        ("frame", C.c_int32), ("oy", C.c_int32), ("ox", C.c_int32),
+        ("y_lo", C.c_int32), ("y_hi", C.c_int32), ("x_lo", C.c_int32), ("x_hi", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
 OPTIM_ADAMW, OPTIM_ADABOUND, OPTIM_SGDW = 0, 1, 2   # unetpp_optim_step kinds
 OPTIM_AMS, OPTIM_CAPTURABLE = 1, 2                 # unetpp_optim_step flags
 OPTIM_SKIP_NONFINITE = 4                           # unetpp_optim_step_clip only
@@ -168,6 +176,8 @@ AVG_MEAN, AVG_EMA, AVG_SWAP = 0, 1, 2                # unetpp_avg_update kinds
 AVG_CAPTURABLE = 1                                 # unetpp_avg_update flags
 WARP_PARAMS, WARP_MAX_C = 16, 8                    # floats per row of a warp parameter table; channels of a store
 STORE_U8, STORE_F32 = 0, 1                         # unetpp_warp_batch store types
+SCENE_MAX_VARIANTS = 8                             # variants of a tile unetpp_scene_stitch averages
+SCENE_FLIP_X, SCENE_FLIP_Y, SCENE_TRANSPOSE = 1, 2, 4   # bits of a variant code
 MATCH_MAX = 64                                     # UNETPP_MATCH_MAX: labels / predictions per map of the matcher
 
 _P, _I32, _I64, _F, _U64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_uint64
@@ -258,6 +268,9 @@ SIGNATURES = {
     "unetpp_warp_batch": (C.c_int, [_P, _I32, _I64, _I32, _I32, _I32, _P, _I32, _P, _P, _P, _F, _P, _I32, _I32, _P, _I32,
                                     _P, _P, _P]),
     "unetpp_augment_draw": (C.c_int, [_P, _I32, _U64, _I32, _I32, _I32, _I32, C.POINTER(AugmentDesc), _P]),
+    # scene inference: tile maps back into the frame maps (scene.hip; added within ABI 12)
+    "unetpp_scene_stitch": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, C.POINTER(C.c_int32), C.POINTER(SceneRect), _P, _P,
+                                      _I32, _I32, _I32, _P]),
 }
 
 _LIB = None

@@ -270,10 +270,15 @@ class PackPlan:
         self.phase = phase
         self.pass_id += 1
         if not self.pinned:
+            # an evicted entry takes its phase's job table with it: the table's rows hold the address of the entry's
+            # image (of the copy's destination), and a pass that records the same launches again gets the same keys --
+            # a table kept by key alone would make the batched launch write into the freed buffers
             stale = [k for k, e in self.entries.items() if self.pass_id - e.used > 16]
             for k in stale:
+                self._tables.pop(self.entries[k].phase, None)
                 del self.entries[k]
             for k in [k for k, c in self.copies.items() if self.pass_id - c.used > 16]:
+                self._copy_tables.pop(self.copies[k].phase, None)
                 del self.copies[k]
         self._begin_copies(phase)   # (first: weight images of this pass may be packed FROM a copied buffer)
         sigs = tuple(k for k, e in self.entries.items() if e.phase == phase)
@@ -1085,3 +1090,41 @@ def augment_draw(n: int, seed: int, src_size, out_size, desc: "_lib.AugmentDesc"
                                          int(src_size[1]), int(out_size[0]), int(out_size[1]), C.byref(desc), _stream()),
           "unetpp_augment_draw")
     return params
+
+
+def scene_rects(rows) -> torch.Tensor:
+    """Host table for scene_stitch: rows of (frame, oy, ox, y_lo, y_hi, x_lo, x_hi) -> int32 [n, 8] (CPU, the layout of
+    struct unetpp_scene_rect); frame < 0 marks a padding tile."""
+    t = torch.zeros(len(rows), 8, dtype=torch.int32)
+    if len(rows):
+        t[:, :7] = torch.tensor([[int(v) for v in r] for r in rows], dtype=torch.int32).reshape(len(rows), 7)
+    return t
+
+
+def scene_stitch(tiles: torch.Tensor, rects: torch.Tensor, rects_dev: torch.Tensor, variants, out: torch.Tensor) -> None:
+    """One launch: out [S, C, H, W] fp32 gets, on every tile's owned rectangle, the mean over the K dihedral variants of
+    tiles [n, K, C, Th, Tw] fp32, each read at the inverse-transformed position (include/unetpp_hip.h:
+    unetpp_scene_stitch).  rects: the int32 [n, 8] table of scene_rects on the host, rects_dev the same rows on the
+    device; variants: the K variant codes.  Pixels no tile of the call owns are left as they are."""
+    _need(tiles, "tiles")
+    _need(out, "out")
+    if tiles.dim() != 5 or out.dim() != 4 or out.shape[1] != tiles.shape[2]:
+        raise ValueError("tiles must be [n, K, C, Th, Tw] and out [S, C, H, W] with the same C")
+    n, k, c, th, tw = (int(v) for v in tiles.shape)
+    codes = [int(v) for v in variants]
+    if len(codes) != k or not 1 <= k <= _lib.SCENE_MAX_VARIANTS:
+        raise ValueError("one variant code per variant, 1 to %d variants; got %d codes for K = %d"
+                         % (_lib.SCENE_MAX_VARIANTS, len(codes), k))
+    if rects.is_cuda or rects.dtype != torch.int32 or tuple(rects.shape) != (n, 8) or not rects.is_contiguous():
+        raise ValueError("rects must be a contiguous CPU int32 [%d, 8] table (ops.scene_rects)" % n)
+    _need(rects_dev, "rects_dev", torch.int32)
+    if tuple(rects_dev.shape) != (n, 8) or rects_dev.device != tiles.device or out.device != tiles.device:
+        raise ValueError("rects_dev must be int32 [%d, 8] on the device of tiles and out" % n)
+    s, _, h, w = (int(v) for v in out.shape)
+    host = C.cast(C.c_void_p(rects.data_ptr()), C.POINTER(_lib.SceneRect))
+    nbytes = 0.0
+    if _TIMER is not None:   # K reads and one write per owned pixel and class
+        nbytes = 4.0 * (k + 1) * c * float((rects[:, 4] - rects[:, 3]).clamp_min(0).mul(rects[:, 6] - rects[:, 5]).sum())
+    _timed_call("scene_stitch", 0.0, lambda: check(_lib.lib().unetpp_scene_stitch(
+        _ptr(tiles), n, k, c, th, tw, (C.c_int32 * k)(*codes), host, _ptr(rects_dev), _ptr(out), s, h, w, _stream()),
+        "unetpp_scene_stitch"), nbytes)

@@ -1,0 +1,243 @@
+"""Scene inference: the eval forward of UNet_Nested over frames far larger than the geometry the kernels are tuned for,
+exact rather than blended, with dihedral test-time augmentation folded into the stitch (csrc/scene.hip).
+
+    scene = SceneInference(model.eval(), head=3, tile=512, tta="dihedral")
+    maps = scene(frames)                      # uint8 [S, H, W, C] or float32 [S, C, H, W] on the GPU -> [S, n_classes, H, W]
+    points, counts = scene.points(maps, heatmap)
+
+The frame is cut into overlapping tiles of one fixed shape; chunks of tiles run through ``model.infer`` (or one captured
+``GraphedForward``) and ``unetpp_scene_stitch`` puts each tile's OWNED interior back.  Why the result equals the
+whole-frame forward: in eval mode with the transposed-convolution up path head J has a finite receptive
+field of radius r_J = 7 * 2^J - 5 pixels; a pixel at least that far from every cut edge of its tile sees exactly the
+inputs it would see in the frame, and a tile edge that IS a frame edge sees the same zero padding.  Tile origins are
+multiples of A = 2^(depth-1), so pooling windows and transposed-convolution phases line up with the frame's.
+
+The reference has no counterpart: its validation loop feeds whole 256x256 images (trainer/trainer.py:141-180).
+"""
+from __future__ import annotations
+
+from typing import List, Tuple
+
+import torch
+
+from . import _lib, engine, ops
+from .loader import _per_channel, affine_params
+from .serving import GraphedForward
+
+__all__ = ["required_halo", "plan_tiles", "SceneInference", "TTA_VARIANTS"]
+
+_FX, _FY, _T = _lib.SCENE_FLIP_X, _lib.SCENE_FLIP_Y, _lib.SCENE_TRANSPOSE
+# variant codes (include/unetpp_hip.h): the variant is flip_y(flip_x(transpose(tile))), each step only if its bit is set
+TTA_VARIANTS = {None: (0,), "flips": (0, _FX, _FY, _FX | _FY), "dihedral": tuple(range(8))}
+_MAX_SIDE = 1 << 24   # pixel indices are exact in fp32 below this (the warp's parameter rows are fp32)
+
+
+def required_halo(depth: int, head: int) -> int:
+    """The least halo at which a tiled forward of head `head` is exact: the head's receptive-field radius
+    r_J = 7 * 2^J - 5 (9, 23, 51, 107 for heads 1 to 4; measured on the float64 oracle as the support of the input
+    gradient of one head pixel, whatever the depth, the widths or the BatchNorm setting), rounded up to a multiple of
+    A = 2^(depth-1), the divisibility the engine demands of H and W."""
+    head = engine.check_head(depth, head)
+    a = 1 << (depth - 1)
+    r = 7 * (1 << head) - 5
+    return -(-r // a) * a
+
+
+def _plan_axis(L: int, tile: int, halo: int) -> List[Tuple[int, int, int]]:
+    T = min(tile, L)
+    if T == L:
+        return [(0, 0, L)]
+    s = T - 2 * halo
+    if s <= 0:
+        raise ValueError("tile %d leaves no interior beside a halo of %d: tile must exceed 2 * halo" % (tile, halo))
+    out, k, own_lo = [], 0, 0
+    while True:
+        o = min(k * s, L - T)
+        last = o == L - T
+        own_hi = L if last else o + T - halo
+        out.append((o, own_lo, own_hi))
+        if last:
+            return out
+        own_lo, k = own_hi, k + 1
+
+
+def plan_tiles(H: int, W: int, tile: int, halo: int, align: int):
+    """(rows, cols): per axis, a list of (origin, own_lo, own_hi) in frame coordinates.  Along an axis of length L the
+    tile length is T = min(tile, L); T == L is one tile that owns [0, L).  Otherwise tile k starts at
+    min(k * (T - 2 halo), L - T) and owns from where the previous tile's ownership ended (0 for the first) up to
+    origin + T - halo, the tile that reaches L - T being the last and owning up to L.  So origins are multiples of
+    `align`, the owned intervals partition [0, L), and an owned pixel is at least `halo` from every tile edge that is not
+    a frame edge.  H, W, tile and halo must be positive multiples of `align` (halo may be 0)."""
+    for name, v in (("H", H), ("W", W), ("tile", tile), ("halo", halo), ("align", align)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError("%s must be an int, got %r" % (name, v))
+    if align < 1 or H < 1 or W < 1 or tile < 1 or halo < 0:
+        raise ValueError("H, W, tile and align must be positive and halo non-negative")
+    for name, v in (("H", H), ("W", W), ("tile", tile), ("halo", halo)):
+        if v % align:
+            raise ValueError("%s = %d is not a multiple of %d" % (name, v, align))
+    return _plan_axis(H, tile, halo), _plan_axis(W, tile, halo)
+
+
+def _variant_forward(code: int, oy: int, ox: int, th: int, tw: int):
+    """Forward map (frame pixel -> variant pixel) of the variant `code` of the tile at (oy, ox), as the [2, 3] rows of
+    affine_params: whole numbers throughout, so the warp copies pixels bit for bit."""
+    sx, cx = (-1, tw - 1) if code & _FX else (1, 0)
+    sy, cy = (-1, th - 1) if code & _FY else (1, 0)
+    if code & _T:   # variant (row, column) = (x - ox, y - oy), then the flips
+        return [[0, sx, cx - sx * oy], [sy, 0, cy - sy * ox]]
+    return [[sx, 0, cx - sx * ox], [0, sy, cy - sy * oy]]
+
+
+class _Chunk:
+    __slots__ = ("n", "index", "params", "rects", "rects_dev")
+
+
+class SceneInference:
+    """scene(frames) -> float32 [S, n_classes, H, W] on the device: head `head` of ``model`` (``None`` = the last; with
+    ``ensemble`` the mean of heads 1 .. head) over whole frames, computed tile by tile and equal to what the whole-frame
+    forward computes wherever the same kernels are selected (bit for bit equal to per-tile ``model.infer`` outputs placed
+    by ownership).
+
+    tile: side of the square tile (a frame side below it becomes the tile's side).  halo: pixels of context around the
+    owned interior, default and minimum ``required_halo(depth, head)``.  tta: ``None``, ``"flips"`` (identity, h, v, hv)
+    or ``"dihedral"`` (all eight; square tiles only) -- the variants' maps are averaged at the inverse-transformed
+    position inside the stitch launch, ``(((v_0 + v_1) + ...) + v_{K-1}) / K``.  chunk: tiles per forward (``chunk * K``
+    samples).  mul / add: the DeviceLoader's normalisation, ``pixel * mul[c] + add[c]``, for uint8 and float32 frames
+    alike.  graphed: one ``GraphedForward`` captured for the chunk shape serves frames of any size; the last chunk is
+    padded with the loader's all-fill samples, which the stitch skips.
+
+    Per chunk: one warp launch (gather, flips and turns, normalisation), the forward, one stitch launch; at most one
+    chunk of tile maps is alive.  Tile tables are built once per (S, H, W) and cached."""
+
+    def __init__(self, model, head=None, ensemble: bool = False, tile: int = 512, halo=None, tta=None, chunk: int = 8,
+                 mul=1.0 / 255.0, add=0.0, graphed: bool = False):
+        depth = getattr(model, "depth", None)
+        if depth is None or not hasattr(model, "infer"):
+            raise TypeError("SceneInference drives UNet_Nested.infer")
+        self.head = engine.check_head(depth, head)
+        if model.training:
+            raise RuntimeError("SceneInference runs the eval forward: call model.eval() first")
+        if not model.is_deconv:
+            raise ValueError(
+                "no halo makes a tile exact with the bilinear up path (is_deconv=False): UpsamplingBilinear2d is "
+                "align_corners=True, so every output pixel's source position depends on the size of the whole frame")
+        self.align = 1 << (depth - 1)
+        need = required_halo(depth, self.head)
+        halo = need if halo is None else halo
+        for name, v in (("tile", tile), ("halo", halo), ("chunk", chunk)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+                raise ValueError("%s must be a positive int, got %r" % (name, v))
+        if tile % self.align or halo % self.align:
+            raise ValueError("tile and halo must be multiples of %d for a depth-%d network, got %d and %d"
+                             % (self.align, depth, tile, halo))
+        if halo < need:
+            raise ValueError("head %d of a depth-%d network needs a halo of %d (receptive-field radius %d), got %d"
+                             % (self.head, depth, need, 7 * (1 << self.head) - 5, halo))
+        if tile <= 2 * halo:
+            raise ValueError("tile %d leaves no interior beside a halo of %d: tile must exceed 2 * halo" % (tile, halo))
+        if tta not in TTA_VARIANTS:
+            raise ValueError("tta is None, 'flips' or 'dihedral', got %r" % (tta,))
+        self.model, self.ensemble, self.tile, self.halo, self.chunk = model, bool(ensemble), tile, halo, chunk
+        self.tta, self.variants, self.graphed = tta, TTA_VARIANTS[tta], bool(graphed)
+        self.mul, self.add = mul, add
+        self._plans, self._graphs, self._norm = {}, {}, {}
+
+    # ---- host side ---------------------------------------------------------------------------------
+    def tile_shape(self, H: int, W: int) -> Tuple[int, int]:
+        return min(self.tile, H), min(self.tile, W)
+
+    def efficiency(self, H: int, W: int) -> float:
+        """Owned pixels over computed pixels of one frame (per variant): (400 / 512)^2 = 0.61 for a large frame at tile
+        512 and halo 56."""
+        rows, cols = plan_tiles(H, W, self.tile, self.halo, self.align)
+        th, tw = self.tile_shape(H, W)
+        return float(H * W) / float(len(rows) * len(cols) * th * tw)
+
+    def _check_size(self, H: int, W: int) -> None:
+        if H >= _MAX_SIDE or W >= _MAX_SIDE:
+            raise ValueError("frame sides must be below 2^24 (pixel indices are carried in fp32), got %dx%d" % (H, W))
+        if H % self.align or W % self.align:
+            raise ValueError("H and W must be divisible by %d, got %dx%d" % (self.align, H, W))
+        if self.tta == "dihedral" and (H < self.tile or W < self.tile):
+            raise ValueError("tta='dihedral' needs square tiles: both frame sides must reach tile = %d, got %dx%d"
+                             % (self.tile, H, W))
+
+    def _plan(self, S: int, H: int, W: int, device) -> List[_Chunk]:
+        key = (S, H, W, str(device))
+        plan = self._plans.get(key)
+        if plan is not None:
+            return plan
+        rows, cols = plan_tiles(H, W, self.tile, self.halo, self.align)
+        th, tw = self.tile_shape(H, W)
+        tiles = [(s, oy, ox, y0, y1, x0, x1) for s in range(S) for (oy, y0, y1) in rows for (ox, x0, x1) in cols]
+        identity = _variant_forward(0, 0, 0, th, tw)
+        plan = []
+        for i in range(0, len(tiles), self.chunk):
+            part = tiles[i:i + self.chunk]
+            live = len(part)
+            if self.graphed:   # the captured shape: pad with all-fill samples that the stitch skips
+                part = part + [(-1, 0, 0, 0, 0, 0, 0)] * (self.chunk - live)
+            c = _Chunk()
+            c.n = len(part)
+            c.index = torch.tensor([t[0] for t in part for _ in self.variants], dtype=torch.int64).to(device)
+            fwd = [_variant_forward(code, t[1], t[2], th, tw) if t[0] >= 0 else identity
+                   for t in part for code in self.variants]
+            c.params = affine_params(fwd).to(device)
+            c.rects = ops.scene_rects(part)
+            c.rects_dev = c.rects.to(device)
+            plan.append(c)
+        self._plans[key] = plan
+        return plan
+
+    # ---- device side -------------------------------------------------------------------------------
+    def __call__(self, frames: torch.Tensor) -> torch.Tensor:
+        if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
+            raise RuntimeError("frames must live on the GPU: this path has no CPU fallback")
+        if frames.dtype not in (torch.uint8, torch.float32):
+            raise TypeError("frames must be uint8 [S, H, W, C] or float32 [S, C, H, W], got %s" % frames.dtype)
+        if frames.dim() == 3:
+            frames = frames.unsqueeze(0)
+        if frames.dim() != 4:
+            raise ValueError("frames must be uint8 [S, H, W, C] or float32 [S, C, H, W] (or one frame without S)")
+        u8 = frames.dtype == torch.uint8
+        S = int(frames.shape[0])
+        H, W, cin = (int(v) for v in (frames.shape[1:] if u8 else (frames.shape[2], frames.shape[3], frames.shape[1])))
+        model = self.model
+        if cin != model.in_channels:
+            raise ValueError("expected %d input channels, got %d" % (model.in_channels, cin))
+        if model.training:
+            raise RuntimeError("SceneInference runs the eval forward: call model.eval() first")
+        self._check_size(H, W)
+        dev = frames.device
+        frames = frames.contiguous()
+        norm = self._norm.get(str(dev))
+        if norm is None:
+            norm = self._norm[str(dev)] = (_per_channel(self.mul, cin, dev), _per_channel(self.add, cin, dev))
+        th, tw = self.tile_shape(H, W)
+        K = len(self.variants)
+        out = torch.empty(S, model.n_classes, H, W, dtype=torch.float32, device=dev)
+        graph = self._graph(cin, th, tw, dev) if self.graphed else None
+        for c in self._plan(S, H, W, dev):
+            if graph is not None:
+                x = ops.warp_batch(frames, c.index, c.params, (th, tw), norm[0], norm[1], 0.0, out=graph.static_input)
+                maps = graph(x)
+            else:
+                x = ops.warp_batch(frames, c.index, c.params, (th, tw), norm[0], norm[1], 0.0)
+                maps = model.infer(x, self.head, self.ensemble)
+            ops.scene_stitch(maps.view(c.n, K, model.n_classes, th, tw), c.rects, c.rects_dev, self.variants, out)
+        return out
+
+    def _graph(self, cin: int, th: int, tw: int, dev) -> GraphedForward:
+        key = (cin, th, tw, str(dev))
+        g = self._graphs.get(key)
+        if g is None:
+            example = torch.zeros(self.chunk * len(self.variants), cin, th, tw, dtype=torch.float32, device=dev)
+            g = self._graphs[key] = GraphedForward(self.model, example, head=self.head, ensemble=self.ensemble)
+        return g
+
+    def points(self, maps: torch.Tensor, heatmap, threshold: float = 0.5):
+        """``heatmap.transfer_points`` on the stitched maps.  The extraction works per map and its core threshold is a
+        per-map maximum (cores are what lies above a tenth of the map's largest distance value), so it must see the whole
+        frame: run on tiles it would judge each tile by its own maximum and find other points."""
+        return heatmap.transfer_points(maps, None, threshold)

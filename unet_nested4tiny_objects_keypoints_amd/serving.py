@@ -64,6 +64,12 @@ class GraphedForward:
         self._outs: Tuple[torch.Tensor, ...] = tuple(outs) if isinstance(outs, (tuple, list)) else (outs,)
         self._single = not isinstance(outs, (tuple, list))
 
+    @property
+    def static_input(self) -> torch.Tensor:
+        """The graph's own input tensor.  A producer may write it in place (a kernel's ``out=``) and then call the object
+        with it: the copy into the static input is skipped for that tensor."""
+        return self._x
+
     def __call__(self, x: torch.Tensor):
         if x.shape != self._x.shape or x.dtype != self._x.dtype or x.device != self._x.device:
             raise ValueError("GraphedForward was captured for %s %s on %s, got %s %s on %s" % (
@@ -73,7 +79,8 @@ class GraphedForward:
         if [p.data_ptr() for p in self.model.parameters()] != self._param_ptrs:
             raise RuntimeError("the model's parameters moved (.to() / load with assign) since the graph was captured: "
                                "build a new GraphedForward")
-        self._x.copy_(x)
+        if x is not self._x:
+            self._x.copy_(x)
         self._graph.replay()
         return self._outs[0] if self._single else self._outs
 
