@@ -706,6 +706,48 @@ int unetpp_scene_stitch(const float* tiles, int32_t n_tiles, int32_t K, int32_t 
                         const int32_t* variants, const unetpp_scene_rect* rects, const unetpp_scene_rect* rects_dev,
                         float* out, int32_t S, int32_t H, int32_t W, void* stream);
 
+/* ---- Detection (csrc/detect.hip): from the maps of a scene to a list of points per map, and from such lists to
+ * true / false positives against labelled points.  The reference has no counterpart: its extraction returns a fixed
+ * number of points per map (tools/misc/heatmap.py:148-200) and its matcher is unfinished.  Added within ABI version 12
+ * without changing anything that was there before. ---- */
+
+/* unetpp_peaks_detect: maps float32 [M, H, W] (device) -> the peaks of every map in raster order.  Pixel p is a peak
+ * when v_p >= threshold and no other pixel q of the (2 radius + 1)^2 window around p, clipped to the map (there is no
+ * padding value), beats it: q beats p when v_q > v_p, or v_q == v_p and q comes earlier in raster order.  Plain
+ * comparisons, so a NaN is never a peak and never beats anything; a plateau gives one peak, its first pixel; equal
+ * maxima more than `radius` apart (Chebyshev) are both peaks.
+ * score [M, cap] = v_p.  xy [M, cap, 2] = (x, y), a pixel centre being an integer: the integer peak, plus -- with
+ * refine != 0 -- a per-axis parabola offset computed in float64 from the float32 values a, b, c at x-1, x, x+1:
+ * den = (a - 2*b) + c; den < 0: off = (0.5 * (a - c)) / den, limited to [-0.5, 0.5] by comparisons; else (den >= 0 or
+ * NaN, or a neighbour beyond the map's edge) off = 0; x_out = float32(double(x) + off), rounded once.  Likewise y.
+ * count [M] int32 = the number of peaks of the map, which may exceed cap: the first cap in raster order are kept.  Rows
+ * k >= min(count, cap) are xy = -1, score = -inf.  Ranks come from per-workgroup counts and a prefix sum: the order is
+ * the raster order on any grid, the same bits on every run, no atomics, no host read-back (three launches on `stream`).
+ * workspace: unetpp_peaks_workspace_bytes(M, H, W) bytes on the device, 8-byte aligned (0 for sizes the call refuses).
+ * Offsets into the maps and raster indices are 64-bit.
+ * UNETPP_EINVAL without touching the device for a null pointer, a size <= 0, radius outside 1..8, cap <= 0, a NaN
+ * threshold, H or W >= 2^24 (coordinates are carried in fp32), M > 65535, H * W above 2^42, or a misaligned workspace. */
+int64_t unetpp_peaks_workspace_bytes(int32_t M, int32_t H, int32_t W);
+int unetpp_peaks_detect(const float* maps, int32_t M, int32_t H, int32_t W, float threshold, int32_t radius,
+                        int32_t refine, int32_t cap, float* xy, float* score, int32_t* count, void* workspace,
+                        void* stream);
+
+/* unetpp_detect_match: detections against labels, per group g = s * C + c (frame s, class c), G = S * C groups.
+ * xy float32 [G, cap, 2]; n_pred int32 [G] (clipped to 0..cap here); order int32 [G, cap]: the first n_pred[g] entries
+ * are the slots of group g's predictions in the order they are served (an entry outside 0..cap-1 is skipped).  labels
+ * float32 [S, L, 2], label_class int32 [S, L]: label l of frame s belongs to group (s, label_class[s, l]); a class
+ * outside 0..C-1 (-1 by convention) is padding.  Each prediction in turn takes the nearest label of its group that no
+ * earlier prediction took, d = (double)dx*dx + (double)dy*dy of the float32 differences, provided
+ * d <= (double)tolerance * tolerance; ties go to the lowest label index.
+ * Out (all written here): pred_label int32 [G, cap] = the label index or -1; label_pred int32 [S, L] = the slot of the
+ * matched prediction or -1; stats int32 [G, 3] = true positives, false positives (served and unmatched), false
+ * negatives (labels of the group left over).  One workgroup per group, integer bookkeeping, deterministic.
+ * UNETPP_EINVAL without touching the device for a null pointer, a size <= 0, S * C above 2^31 - 1, or a negative or NaN
+ * tolerance. */
+int unetpp_detect_match(const float* xy, const int32_t* n_pred, const int32_t* order, int32_t S, int32_t C, int32_t cap,
+                        const float* labels, const int32_t* label_class, int32_t L, float tolerance, int32_t* pred_label,
+                        int32_t* label_pred, int32_t* stats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,7 +15,8 @@ _REPO = os.path.dirname(_PKG_DIR)
 LIB_PATH = os.environ.get("UNETPP_LIB", os.path.join(_PKG_DIR, "libunetpp_hip.so"))  # override: kernel A/B runs
 CSRC = os.path.join(_PKG_DIR, "csrc")
 INCLUDE = os.path.join(_REPO, "include")
-SOURCES = ("gemm_pix.hip", "gemm_fast.hip", "gemm_pw.hip", "gemm_pw_bf16.hip", "gemm_wino.hip", "gemm_bf16.hip", "gemm_bf16_dma.hip", "wgrad_bf16.hip", "pointwise_bf16.hip", "keypoints.hip", "weight_image.hip", "wgrad.hip", "wgrad_fast.hip", "wgrad_dma.hip", "wgrad_pw.hip", "wgrad_wino.hip", "first_layer.hip", "pointwise.hip", "caller.hip", "optim.hip", "validate.hip", "average.hip", "loader.hip", "scene.hip")
+SOURCES = ("gemm_pix.hip", "gemm_fast.hip", "gemm_pw.hip", "gemm_pw_bf16.hip", "gemm_wino.hip", "gemm_bf16.hip", "gemm_bf16_dma.hip", "wgrad_bf16.hip", "pointwise_bf16.hip", "keypoints.hip", "weight_image.hip", "wgrad.hip", "wgrad_fast.hip", "wgrad_dma.hip", "wgrad_pw.hip", "wgrad_wino.hip", "first_layer.hip", "pointwise.hip", "caller.hip", "optim.hip", "validate.hip", "average.hip", "loader.hip", "scene.hip",
+           "detect.hip")
 HEADERS = ("common.h", "gemm_units.h", "wgrad_reduce.h", "lds_asm.h", "bf16_common.h", "dropout.h", "bn_fused.h",
            "wino_experiments.h", "dma_experiments.h", "heads_mean.h")
 MAX_VIEWS = 8
@@ -178,6 +179,7 @@ WARP_PARAMS, WARP_MAX_C = 16, 8                    # floats per row of a warp pa
 STORE_U8, STORE_F32 = 0, 1                         # unetpp_warp_batch store types
 SCENE_MAX_VARIANTS = 8                             # variants of a tile unetpp_scene_stitch averages
 SCENE_FLIP_X, SCENE_FLIP_Y, SCENE_TRANSPOSE = 1, 2, 4   # bits of a variant code
+PEAKS_MAX_RADIUS, PEAKS_MAX_MAPS = 8, 65535         # unetpp_peaks_detect: window radius 1..8, maps per call
 MATCH_MAX = 64                                     # UNETPP_MATCH_MAX: labels / predictions per map of the matcher
 
 _P, _I32, _I64, _F, _U64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_uint64
@@ -271,6 +273,10 @@ SIGNATURES = {
     # scene inference: tile maps back into the frame maps (scene.hip; added within ABI 12)
     "unetpp_scene_stitch": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, C.POINTER(C.c_int32), C.POINTER(SceneRect), _P, _P,
                                       _I32, _I32, _I32, _P]),
+    # detection: peaks of scene maps in raster order, detections against labels (detect.hip; added within ABI 12)
+    "unetpp_peaks_workspace_bytes": (_I64, [_I32, _I32, _I32]),
+    "unetpp_peaks_detect": (C.c_int, [_P, _I32, _I32, _I32, _F, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
+    "unetpp_detect_match": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _P, _P, _I32, _F, _P, _P, _P, _P]),
 }
 
 _LIB = None

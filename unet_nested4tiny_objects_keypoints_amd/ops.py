@@ -1128,3 +1128,77 @@ def scene_stitch(tiles: torch.Tensor, rects: torch.Tensor, rects_dev: torch.Tens
     _timed_call("scene_stitch", 0.0, lambda: check(_lib.lib().unetpp_scene_stitch(
         _ptr(tiles), n, k, c, th, tw, (C.c_int32 * k)(*codes), host, _ptr(rects_dev), _ptr(out), s, h, w, _stream()),
         "unetpp_scene_stitch"), nbytes)
+
+
+def peaks_detect(maps: torch.Tensor, threshold: float, radius: int, cap: int, refine: bool = True):
+    """maps [M, H, W] fp32 on the GPU -> (xy [M, cap, 2] as (x, y), score [M, cap], count [M] int32): the local maxima of
+    every map that reach `threshold`, in raster order (include/unetpp_hip.h: unetpp_peaks_detect; rule, sub-pixel
+    offset and order guarantee in csrc/detect.hip).  count may exceed cap: the first cap peaks in raster order are
+    kept; rows k >= min(count, cap) are xy = -1, score = -inf.  Three launches, nothing is read back."""
+    _need(maps, "maps")
+    if maps.dim() != 3:
+        raise ValueError("maps must be [M, H, W]")
+    m, h, w = (int(v) for v in maps.shape)
+    if isinstance(radius, bool) or not isinstance(radius, int) or not 1 <= radius <= _lib.PEAKS_MAX_RADIUS:
+        raise ValueError("radius must be an int in 1..%d, got %r" % (_lib.PEAKS_MAX_RADIUS, radius))
+    if isinstance(cap, bool) or not isinstance(cap, int) or cap < 1:
+        raise ValueError("cap must be a positive int, got %r" % (cap,))
+    threshold = float(threshold)
+    if threshold != threshold:
+        raise ValueError("threshold must not be NaN")
+    if m < 1 or h < 1 or w < 1 or m > _lib.PEAKS_MAX_MAPS or h >= (1 << 24) or w >= (1 << 24):
+        raise ValueError("1 to %d non-empty maps with sides below 2^24 (coordinates are carried in fp32), got %dx%dx%d"
+                         % (_lib.PEAKS_MAX_MAPS, m, h, w))
+    lib = _lib.lib()
+    dev = maps.device
+    nbytes = int(lib.unetpp_peaks_workspace_bytes(m, h, w))
+    if nbytes <= 0:
+        raise ValueError("maps of %dx%dx%d are beyond what one call takes" % (m, h, w))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    xy = torch.empty(m, cap, 2, dtype=torch.float32, device=dev)
+    score = torch.empty(m, cap, dtype=torch.float32, device=dev)
+    count = torch.empty(m, dtype=torch.int32, device=dev)
+    _timed_call("peaks_detect", 0.0, lambda: check(lib.unetpp_peaks_detect(
+        _ptr(maps), m, h, w, threshold, radius, 1 if refine else 0, cap, _ptr(xy), _ptr(score), _ptr(count), _ptr(ws),
+        _stream()), "unetpp_peaks_detect"), 4.0 * m * h * w)
+    return xy, score, count
+
+
+def detect_match(xy: torch.Tensor, n_pred: torch.Tensor, order: torch.Tensor, labels: torch.Tensor,
+                 label_class: torch.Tensor, tolerance: float):
+    """Detections against labels, one launch (include/unetpp_hip.h: unetpp_detect_match).  xy [S, C, cap, 2] fp32,
+    n_pred [S, C] int32 (predictions of the group), order [S, C, cap] int32 (the slots in the order they are served),
+    labels [S, L, 2] fp32, label_class [S, L] int32 (-1: padding) -> (pred_label [S, C, cap] int32: the label a
+    prediction took or -1; label_pred [S, L] int32: the slot that took the label or -1; stats [S, C, 3] int32: true
+    positives, false positives, false negatives).  Each prediction in turn takes the nearest unspent label of its
+    (frame, class) within `tolerance`, ties to the lowest label index."""
+    _need(xy, "xy")
+    _need(n_pred, "n_pred", torch.int32)
+    _need(order, "order", torch.int32)
+    _need(labels, "labels")
+    _need(label_class, "label_class", torch.int32)
+    if xy.dim() != 4 or xy.shape[3] != 2:
+        raise ValueError("xy must be [S, C, cap, 2]")
+    s, c, cap = (int(v) for v in xy.shape[:3])
+    if tuple(n_pred.shape) != (s, c) or tuple(order.shape) != (s, c, cap):
+        raise ValueError("n_pred must be [%d, %d] and order [%d, %d, %d]" % (s, c, s, c, cap))
+    if labels.dim() != 3 or labels.shape[0] != s or labels.shape[2] != 2:
+        raise ValueError("labels must be [%d, L, 2]" % s)
+    n_labels = int(labels.shape[1])
+    if tuple(label_class.shape) != (s, n_labels):
+        raise ValueError("label_class must be [%d, %d]" % (s, n_labels))
+    if min(s, c, cap, n_labels) < 1:
+        raise ValueError("S, C, cap and L must be positive (pad an empty label list with one label of class -1)")
+    tolerance = float(tolerance)
+    if not tolerance >= 0.0:
+        raise ValueError("tolerance must be a non-negative number, got %r" % (tolerance,))
+    dev = xy.device
+    if any(t.device != dev for t in (n_pred, order, labels, label_class)):
+        raise ValueError("all tensors must live on one device")
+    pred_label = torch.empty(s, c, cap, dtype=torch.int32, device=dev)
+    label_pred = torch.empty(s, n_labels, dtype=torch.int32, device=dev)
+    stats = torch.empty(s, c, 3, dtype=torch.int32, device=dev)
+    _timed_call("detect_match", 0.0, lambda: check(_lib.lib().unetpp_detect_match(
+        _ptr(xy), _ptr(n_pred), _ptr(order), s, c, cap, _ptr(labels), _ptr(label_class), n_labels, tolerance,
+        _ptr(pred_label), _ptr(label_pred), _ptr(stats), _stream()), "unetpp_detect_match"))
+    return pred_label, label_pred, stats

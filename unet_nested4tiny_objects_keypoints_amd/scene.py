@@ -4,6 +4,7 @@ exact rather than blended, with dihedral test-time augmentation folded into the 
     scene = SceneInference(model.eval(), head=3, tile=512, tta="dihedral")
     maps = scene(frames)                      # uint8 [S, H, W, C] or float32 [S, C, H, W] on the GPU -> [S, n_classes, H, W]
     points, counts = scene.points(maps, heatmap)
+    dets = scene.detect(frames, PeakDetector())   # any number of objects per map (detect.py)
 
 The frame is cut into overlapping tiles of one fixed shape; chunks of tiles run through ``model.infer`` (or one captured
 ``GraphedForward``) and ``unetpp_scene_stitch`` puts each tile's OWNED interior back.  Why the result equals the
@@ -239,5 +240,10 @@ class SceneInference:
     def points(self, maps: torch.Tensor, heatmap, threshold: float = 0.5):
         """``heatmap.transfer_points`` on the stitched maps.  The extraction works per map and its core threshold is a
         per-map maximum (cores are what lies above a tenth of the map's largest distance value), so it must see the whole
-        frame: run on tiles it would judge each tile by its own maximum and find other points."""
+        frame: run on tiles it would judge each tile by its own maximum and find other points.  This is the reference's
+        fixed-count extraction (at most ``len(pattern[c])`` points per map); ``detect()`` is the one for scenes."""
         return heatmap.transfer_points(maps, None, threshold)
+
+    def detect(self, frames: torch.Tensor, detector):
+        """``detector(self(frames))``: the frames' maps through a ``detect.PeakDetector`` -> ``Detections``."""
+        return detector(self(frames))
