@@ -17,6 +17,10 @@ constexpr int kLossPerThread = 8;  // elements per thread: 2 x float4
 // The elements of one thread (2 x float4 at `base`): the gradient (times `scale`: 1 for a single head, 1 / heads under
 // the trainer's mean over heads -- a second float32 product, as autograd forms it) and the thread's part of the loss sum.
 // t[2][4]: the thread's targets, read once for all heads.
+// kLow: gamma < 1, where u^(gamma-1) is inf at u == 0 (an exact hit, or |p - t| below float32 rounding of 1): there
+// u^gamma is 0^0 = 1 for gamma == 0 (torch's value) and 0 otherwise, and gamma u^(gamma-1) log e is taken at its limit 0,
+// so the loss stays finite and the gradient at an exact hit is 0.  gamma >= 1 runs the instantiation without the test.
+template <bool kLow>
 __device__ __forceinline__ float focal_thread(const float* __restrict__ pred, float* __restrict__ grad,
                                               const float (&t)[kLossPerThread / 4][4], long base, long n, float gamma,
                                               float inv_rows, float scale) {
@@ -44,8 +48,14 @@ __device__ __forceinline__ float focal_thread(const float* __restrict__ pred, fl
       const float lg = logf(err);
       const float ug1 = cube ? u * u : powf(u, gamma - 1.f);  // u^(gamma-1)
       const float ug = ug1 * u;
-      const float le = -ug * lg;
-      const float dl_de = gamma * ug1 * lg - ug / err;
+      float le = -ug * lg;
+      float dl_de = gamma * ug1 * lg - ug / err;
+      if constexpr (kLow) {
+        if (u == 0.f) {
+          le = 0.f;
+          dl_de = (gamma == 0.f) ? -1.f / err : 0.f;
+        }
+      }
       const float sgn = (d > 0.f) ? 1.f : ((d < 0.f) ? -1.f : 0.f);
       g[e] = (-dl_de * sgn * inv_rows) * scale;
       if (i + e < n) sum += le;
@@ -79,6 +89,7 @@ __device__ __forceinline__ void focal_read_target(const float* __restrict__ targ
   }
 }
 
+template <bool kLow>
 __global__ __launch_bounds__(kLossThreads) void focal_bce_kernel(const float* __restrict__ pred,
                                                                 const float* __restrict__ target, long n, float gamma,
                                                                 float inv_rows, float* __restrict__ grad,
@@ -87,7 +98,7 @@ __global__ __launch_bounds__(kLossThreads) void focal_bce_kernel(const float* __
   const long base = (blockIdx.x * static_cast<long>(kLossThreads) + threadIdx.x) * kLossPerThread;
   float t[kLossPerThread / 4][4];
   focal_read_target(target, base, n, t);
-  float sum = focal_thread(pred, grad, t, base, n, gamma, inv_rows, 1.f);
+  float sum = focal_thread<kLow>(pred, grad, t, base, n, gamma, inv_rows, 1.f);
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
@@ -97,6 +108,7 @@ __global__ __launch_bounds__(kLossThreads) void focal_bce_kernel(const float* __
 
 // All deep-supervision heads against one target: the target is read once, partial[h * gridDim.x + block] as
 // focal_bce_kernel writes partial[block] for head h (same per-thread order, same wave and block sums).
+template <bool kLow>
 __global__ __launch_bounds__(kLossThreads) void focal_bce_heads_kernel(const unetpp_focal_heads hd,
                                                                       const float* __restrict__ target, long n, float gamma,
                                                                       float inv_rows, float scale,
@@ -106,7 +118,7 @@ __global__ __launch_bounds__(kLossThreads) void focal_bce_heads_kernel(const une
   float t[kLossPerThread / 4][4];
   focal_read_target(target, base, n, t);
   for (int h = 0; h < hd.n_heads; ++h) {
-    float sum = focal_thread(hd.pred[h], hd.grad[h], t, base, n, gamma, inv_rows, scale);
+    float sum = focal_thread<kLow>(hd.pred[h], hd.grad[h], t, base, n, gamma, inv_rows, scale);
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off);
     if ((threadIdx.x & 63) == 0) red[h][threadIdx.x >> 6] = sum;
@@ -250,8 +262,8 @@ extern "C" int unetpp_focal_bce(const float* pred, const float* target, int64_t 
     return UNETPP_EINVAL;
   const int64_t blocks = unetpp_focal_bce_blocks(n);
   if (blocks > 0x7fffffffLL) return UNETPP_EINVAL;
-  hipLaunchKernelGGL(focal_bce_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kLossThreads), 0,
-                     static_cast<hipStream_t>(stream), pred, target, static_cast<long>(n), gamma,
+  hipLaunchKernelGGL(gamma < 1.f ? focal_bce_kernel<true> : focal_bce_kernel<false>, dim3(static_cast<unsigned>(blocks)),
+                     dim3(kLossThreads), 0, static_cast<hipStream_t>(stream), pred, target, static_cast<long>(n), gamma,
                      1.f / static_cast<float>(rows), grad, partial);
   hipLaunchKernelGGL(focal_bce_finish_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), partial,
                      static_cast<long>(blocks), loss);
@@ -273,9 +285,9 @@ extern "C" int unetpp_focal_bce_heads(const unetpp_focal_heads* heads, const flo
   unetpp_focal_heads hd = *heads;
   for (int h = hd.n_heads; h < UNETPP_MAX_HEADS; ++h) hd.pred[h] = nullptr, hd.grad[h] = nullptr;
   const float inv_heads = 1.0f / static_cast<float>(hd.n_heads);
-  hipLaunchKernelGGL(focal_bce_heads_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kLossThreads), 0,
-                     static_cast<hipStream_t>(stream), hd, target, static_cast<long>(n), gamma,
-                     1.f / static_cast<float>(rows), inv_heads, partial);
+  hipLaunchKernelGGL(gamma < 1.f ? focal_bce_heads_kernel<true> : focal_bce_heads_kernel<false>,
+                     dim3(static_cast<unsigned>(blocks)), dim3(kLossThreads), 0, static_cast<hipStream_t>(stream), hd, target,
+                     static_cast<long>(n), gamma, 1.f / static_cast<float>(rows), inv_heads, partial);
   hipLaunchKernelGGL(focal_bce_heads_finish_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), partial,
                      static_cast<long>(blocks), hd.n_heads, inv_heads, loss);
   return launch_status();

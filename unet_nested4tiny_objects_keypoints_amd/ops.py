@@ -789,6 +789,12 @@ def nhwc_to_nchw(src):
     return dst
 
 
+def _aligned16(t: torch.Tensor) -> torch.Tensor:
+    """The loss kernels read float4: a contiguous view whose storage offset leaves it off a 16-byte boundary is copied
+    (the C ABI's alignment contract stays)."""
+    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
+
+
 def focal_bce(pred: torch.Tensor, target: torch.Tensor, rows: int, gamma: float, want_grad: bool = True):
     """FocalLoss_BCE_2d value (0-dim tensor) and d loss / d pred in one pass over (pred, target)."""
     lib = _lib.lib()
@@ -796,6 +802,7 @@ def focal_bce(pred: torch.Tensor, target: torch.Tensor, rows: int, gamma: float,
     _need(target, "target")
     if pred.shape != target.shape:
         raise ValueError("pred and target must have the same shape")
+    pred, target = _aligned16(pred), _aligned16(target)
     n = pred.numel()
     blocks = int(lib.unetpp_focal_bce_blocks(n))
     partial = torch.empty(blocks, dtype=torch.float32, device=pred.device)
@@ -818,6 +825,7 @@ def focal_bce_heads(preds, target: torch.Tensor, rows: int, gamma: float, want_g
         _need(p, "pred")
         if p.shape != target.shape:
             raise ValueError("pred and target must have the same shape")
+    preds, target = [_aligned16(p) for p in preds], _aligned16(target)
     n = target.numel()
     blocks = int(lib.unetpp_focal_bce_blocks(n))
     partial = torch.empty(len(preds) * blocks, dtype=torch.float32, device=target.device)
