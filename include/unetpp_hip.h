@@ -748,6 +748,48 @@ int unetpp_detect_match(const float* xy, const int32_t* n_pred, const int32_t* o
                         const float* labels, const int32_t* label_class, int32_t L, float tolerance, int32_t* pred_label,
                         int32_t* label_pred, int32_t* stats, void* stream);
 
+/* ---- Training on scenes (csrc/crops.hip): windows drawn where the objects are, and the target maps of such windows from
+ * label lists of any length.  The reference has no counterpart: its targets come from a fixed pattern of points per
+ * image (tools/misc/heatmap.py:203-230).  Added within ABI version 12 without changing anything that was there
+ * before. ---- */
+
+/* unetpp_points_target: out float32 [N, C, Ho, Wo] (device) = the target maps of N warped windows.  labels float32
+ * [M, L, 2] as (x, y), label_class int32 [M, L], index int64 [N], params float32 [N][16] (the rows of unetpp_warp_batch).
+ * Label l of sample n is valid when index[n] lies in [0, M), its class lies in 0..C-1 and neither source coordinate is
+ * negative (!(x < 0) && !(y < 0), the loader's sentinel test).  Its position in the window is the forward map in the
+ * warp's own float32 expression, xo = (P[0]*x + P[1]*y) + P[2], yo = (P[3]*x + P[4]*y) + P[5], P = params[n] + 6 -- the
+ * labels_out of unetpp_warp_batch.  Every valid label of the frame counts, inside the window or not.
+ *   m = min over the valid labels of class c of dx*dx + dy*dy,  dx = (double)x - (double)xo,  dy likewise
+ *   out[n, c, y, x] = (float)exp(-0.5 * sqrt(m) / (double)radius),  exactly 0 where class c has no valid label.
+ * The search is exact: a workgroup keeps, per pixel tile and class, the labels whose least squared distance to the tile
+ * does not exceed the least over the labels of the greatest one, and takes the minimum over those (csrc/crops.hip).
+ * No atomics, no contraction, 64-bit offsets into out; the same bits on any grid and on every run.
+ * UNETPP_EINVAL without touching the device for a null pointer, a size <= 0, C > 65535, a window side above 2^24, or a
+ * radius that is not > 0 (a NaN included). */
+int unetpp_points_target(const float* labels, const int32_t* label_class, int64_t M, int32_t L, const int64_t* index,
+                         int32_t N, const float* params, int32_t C, int32_t Ho, int32_t Wo, float radius, float* out,
+                         void* stream);
+
+/* unetpp_crops_draw: N windows of Ho x Wo pixels in M frames of Hs x Ws, one thread per sample: params [N][16], index
+ * int64 [N] (the frame), origin int32 [N, 2] as (ox, oy), all on the device.  Uniforms u_k and the meaning of
+ * k = 0, 1, 2, 3, 4, 7, 8 are unetpp_augment_draw's; k = 5, 6 are unused (max_tx and max_ty must be 0).  centre_frame
+ * int32 [V], centre_xy float32 [V, 2] (device; V may be 0, the tables then unread):
+ *   k = 9:   an object window iff V > 0 and u < p_object, a uniform window otherwise
+ *   k = 10:  object: j = min(floor(u V), V - 1), frame = centre_frame[j], (cx, cy) = floor(centre_xy[j] + 0.5)
+ *            uniform: frame = min(floor(u M), M - 1)
+ *   k = 11:  object: cx += floor((2u - 1) jitter_x + 0.5)      uniform: cx = min(floor(u Ws), Ws - 1)
+ *   k = 12:  object: cy += floor((2u - 1) jitter_y + 0.5)      uniform: cy = min(floor(u Hs), Hs - 1)
+ * ox = cx - Wo / 2 limited to [0, Ws - Wo] when Ws >= Wo, else -((Wo - Ws) / 2), a centred pad (whole-number
+ * divisions); oy likewise.  The row is unetpp_augment_draw's forward / inverse pair with c_s + t replaced by the
+ * window's centre (ox + (Wo - 1) / 2, oy + (Ho - 1) / 2): with no rotation and unit scale every entry is a whole number.
+ * A table row whose frame lies outside [0, M) gives index = -1, the all-fill sample of unetpp_warp_batch, for which
+ * unetpp_points_target writes zeros.
+ * UNETPP_EINVAL for a null pointer (the tables when V > 0), a size <= 0, V < 0, a side above 2^24, a scale bound <= 0,
+ * a non-zero max_tx or max_ty, quarter turns with Ho != Wo, or a negative or NaN p_object or jitter. */
+int unetpp_crops_draw(float* params, int64_t* index, int32_t* origin, int32_t N, uint64_t seed, int32_t M, int32_t Hs,
+                      int32_t Ws, int32_t Ho, int32_t Wo, const int32_t* centre_frame, const float* centre_xy, int32_t V,
+                      float p_object, float jitter_x, float jitter_y, const unetpp_augment* augment, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,9 +23,10 @@ from .averaging import WeightAverager  # noqa: F401
 from .loader import Augment, DeviceLoader, affine_params, warp_batch  # noqa: F401
 from .scene import SceneInference  # noqa: F401
 from .detect import DetectionScore, Detections, PeakDetector, classes_from_pattern, evaluate  # noqa: F401
+from .crops import SceneCrops, false_positive_centres  # noqa: F401
 
 __all__ = ["UNet_Nested", "UNet", "count_param", "FocalLoss_BCE_2d", "train_step", "create_heatmap", "Heatmap",
            "GraphedForward", "GraphedTrainStep", "AdamW", "AdaBound", "SGDW", "validate_step",
            "validate_outputs", "WeightAverager", "clip_grad_norm_", "DeviceLoader", "Augment", "affine_params",
            "warp_batch", "SceneInference", "PeakDetector", "Detections", "DetectionScore", "evaluate",
-           "classes_from_pattern"]
+           "classes_from_pattern", "SceneCrops", "false_positive_centres"]

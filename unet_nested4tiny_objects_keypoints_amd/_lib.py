@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("UNETPP_LIB", os.path.join(_PKG_DIR, "libunetpp_hip.so
 CSRC = os.path.join(_PKG_DIR, "csrc")
 INCLUDE = os.path.join(_REPO, "include")
 SOURCES = ("gemm_pix.hip", "gemm_fast.hip", "gemm_pw.hip", "gemm_pw_bf16.hip", "gemm_wino.hip", "gemm_bf16.hip", "gemm_bf16_dma.hip", "wgrad_bf16.hip", "pointwise_bf16.hip", "keypoints.hip", "weight_image.hip", "wgrad.hip", "wgrad_fast.hip", "wgrad_dma.hip", "wgrad_pw.hip", "wgrad_wino.hip", "first_layer.hip", "pointwise.hip", "caller.hip", "optim.hip", "validate.hip", "average.hip", "loader.hip", "scene.hip",
-           "detect.hip")
+           "detect.hip", "crops.hip")
 HEADERS = ("common.h", "gemm_units.h", "wgrad_reduce.h", "lds_asm.h", "bf16_common.h", "dropout.h", "bn_fused.h",
            "wino_experiments.h", "dma_experiments.h", "heads_mean.h")
 MAX_VIEWS = 8
@@ -277,6 +277,10 @@ SIGNATURES = {
     "unetpp_peaks_workspace_bytes": (_I64, [_I32, _I32, _I32]),
     "unetpp_peaks_detect": (C.c_int, [_P, _I32, _I32, _I32, _F, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
     "unetpp_detect_match": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _P, _P, _I32, _F, _P, _P, _P, _P]),
+    # training on scenes: target maps of warped windows, where the windows are (crops.hip; added within ABI 12)
+    "unetpp_points_target": (C.c_int, [_P, _P, _I64, _I32, _P, _I32, _P, _I32, _I32, _I32, _F, _P, _P]),
+    "unetpp_crops_draw": (C.c_int, [_P, _P, _P, _I32, _U64, _I32, _I32, _I32, _I32, _I32, _P, _P, _I32, _F, _F, _F,
+                                    C.POINTER(AugmentDesc), _P]),
 }
 
 _LIB = None

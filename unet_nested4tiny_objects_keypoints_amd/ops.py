@@ -1210,3 +1210,69 @@ def detect_match(xy: torch.Tensor, n_pred: torch.Tensor, order: torch.Tensor, la
         _ptr(xy), _ptr(n_pred), _ptr(order), s, c, cap, _ptr(labels), _ptr(label_class), n_labels, tolerance,
         _ptr(pred_label), _ptr(label_pred), _ptr(stats), _stream()), "unetpp_detect_match"))
     return pred_label, label_pred, stats
+
+
+def points_target(labels: torch.Tensor, label_class: torch.Tensor, index: torch.Tensor, params: torch.Tensor,
+                  n_classes: int, out_size, radius: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One launch: the target maps [N, n_classes, Ho, Wo] fp32 of N warped windows from labels [M, L, 2] fp32 as (x, y),
+    label_class [M, L] int32, index [N] int64 and the warp's params [N, 16]: per class exp(-0.5 d / radius) of the distance
+    d to the nearest valid label under the sample's forward map, 0 where the class has none (include/unetpp_hip.h:
+    unetpp_points_target).  out: a contiguous float32 [N, n_classes, Ho, Wo] to write."""
+    _need(labels, "labels")
+    _need(label_class, "label_class", torch.int32)
+    _need(index, "index", torch.int64)
+    _need(params, "params")
+    if labels.dim() != 3 or labels.shape[2] != 2 or tuple(label_class.shape) != tuple(labels.shape[:2]):
+        raise ValueError("labels must be [M, L, 2] and label_class [M, L]")
+    m, n_labels = int(labels.shape[0]), int(labels.shape[1])
+    n = int(index.numel())
+    if index.dim() != 1 or tuple(params.shape) != (n, _lib.WARP_PARAMS):
+        raise ValueError("index [N] and params [N, %d]" % _lib.WARP_PARAMS)
+    c, (ho, wo) = int(n_classes), (int(out_size[0]), int(out_size[1]))
+    radius = float(radius)
+    if not radius > 0.0:
+        raise ValueError("radius must be a positive number, got %r" % (radius,))
+    if min(m, n_labels, n, ho, wo) < 1 or not 1 <= c <= 65535:
+        raise ValueError("M, L, N and the window must be positive and n_classes in 1..65535 (pad an empty label list "
+                         "with one label of class -1)")
+    dev = labels.device
+    if any(t.device != dev for t in (label_class, index, params)):
+        raise ValueError("all tensors must live on one device")
+    if out is None:
+        out = torch.empty(n, c, ho, wo, dtype=torch.float32, device=dev)
+    elif tuple(_need(out, "out").shape) != (n, c, ho, wo) or out.device != dev:
+        raise ValueError("out must be [%d, %d, %d, %d] on the labels' device" % (n, c, ho, wo))
+    _timed_call("points_target", 0.0, lambda: check(_lib.lib().unetpp_points_target(
+        _ptr(labels), _ptr(label_class), m, n_labels, _ptr(index), n, _ptr(params), c, ho, wo, radius, _ptr(out),
+        _stream()), "unetpp_points_target"), 4.0 * n * c * ho * wo)
+    return out
+
+
+def crops_draw(n: int, seed: int, n_frames: int, src_size, out_size, centre_frame: Optional[torch.Tensor],
+               centre_xy: Optional[torch.Tensor], p_object: float, jitter, desc: "_lib.AugmentDesc", device):
+    """One launch: n windows of out_size in n_frames frames of src_size drawn from a 64-bit seed -> (params [n, 16] fp32,
+    index [n] int64, origin [n, 2] int32 as (ox, oy)) on the device.  centre_frame [V] int32 / centre_xy [V, 2] fp32: the
+    table object windows are centred on (None or V = 0: every window is uniform) (include/unetpp_hip.h:
+    unetpp_crops_draw)."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("windows are drawn on the GPU: this path has no CPU fallback")
+    v = 0
+    if centre_frame is not None and centre_frame.numel() > 0:
+        _need(centre_frame, "centre_frame", torch.int32)
+        _need(centre_xy, "centre_xy")
+        v = int(centre_frame.numel())
+        if centre_frame.dim() != 1 or tuple(centre_xy.shape) != (v, 2):
+            raise ValueError("centre_frame must be [V] and centre_xy [V, 2]")
+        if centre_frame.device != device or centre_xy.device != device:
+            raise ValueError("the centre table must live on %s" % device)
+    n = int(n)
+    params = torch.empty(n, _lib.WARP_PARAMS, dtype=torch.float32, device=device)
+    index = torch.empty(n, dtype=torch.int64, device=device)
+    origin = torch.empty(n, 2, dtype=torch.int32, device=device)
+    check(_lib.lib().unetpp_crops_draw(
+        _ptr(params), _ptr(index), _ptr(origin), n, int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_frames), int(src_size[0]),
+        int(src_size[1]), int(out_size[0]), int(out_size[1]), _ptr(centre_frame) if v else None,
+        _ptr(centre_xy) if v else None, v, float(p_object), float(jitter[0]), float(jitter[1]), C.byref(desc), _stream()),
+        "unetpp_crops_draw")
+    return params, index, origin
