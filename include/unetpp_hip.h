@@ -374,6 +374,23 @@ typedef struct unetpp_focal_heads {
 } unetpp_focal_heads;
 int unetpp_focal_bce_heads(const unetpp_focal_heads* heads, const float* target, int64_t n, int64_t rows, float gamma,
                            float* partial, float* loss, void* stream);
+/* ---- top-k focal loss: hard-pixel mining per map (added within v12: new entry points only) ----
+ * Heads and target are [rows, P] (rows = N*C maps of P = H*W pixels).  Per head and row only the k_eff = min(k, P)
+ * elements with the largest |pred - target| (one float32 subtraction; ranked by the bits of its absolute value, so a
+ * NaN ranks first) enter the loss; among elements equal to the k-th largest the lowest indices are taken.
+ *   loss[1 + h] = sum over the selected elements of head h of the FocalLoss_BCE_2d term / denom,
+ *   loss[0]     = (0 + loss[1] + ... + loss[n_heads]) * (1 / n_heads) as unetpp_focal_bce_heads forms it,
+ *   grad[h]     = d loss[0] / d pred[h]: unetpp_focal_bce_heads' bits (same denom) on the selected elements, +0.0
+ *                 on every other (and on a selected element with pred == target, where those write -0.0); grad[h]
+ *                 may be NULL,
+ *   kth[h * rows + r] = the k_eff-th largest |pred - target| of that head and row (exact).
+ * denom: rows for the sum convention of FocalLoss_BCE_2d, rows * k_eff for the mean over the selected pixels.
+ * k >= P is unetpp_focal_bce_heads itself (same bits).  workspace: unetpp_topk_focal_workspace_bytes(n_heads, rows, P)
+ * bytes (0 for arguments the call would refuse).  target and every pred[h] / grad[h] 16-byte aligned (rows need not
+ * be); 1 <= P < 2^31, 1 <= rows < 2^31, k >= 1, denom >= 1, 1 <= n_heads <= UNETPP_MAX_HEADS. */
+int64_t unetpp_topk_focal_workspace_bytes(int32_t n_heads, int64_t rows, int64_t P);
+int unetpp_topk_focal_heads(const unetpp_focal_heads* heads, const float* target, int64_t rows, int64_t P, int64_t k,
+                            int64_t denom, float gamma, void* workspace, float* kth, float* loss, void* stream);
 /* ---- ensemble head of an eval forward (added within v12: new entry points only, nothing existing changes) ----
  * The output selection the UNet++ authors left as comments in models/unet.py:293-298: the mean of the first n_heads
  * deep-supervision heads, out = (((s_1 + s_2) + ...) + s_n) / (float)n with s_h = 1 / (1 + exp(-(bias_h + x_h . w_h)))

@@ -7,6 +7,7 @@
 //     key points, channels 1 and 3 divided by their per-image maximum.  Each map is evaluated in fp64; the sums of channels 1 and 3
 //     are float32 running sums and the quotient is float32, as in the reference's numpy code.
 #include "common.h"
+#include "focal_element.h"
 
 namespace unetpp {
 namespace {
@@ -16,10 +17,7 @@ constexpr int kLossPerThread = 8;  // elements per thread: 2 x float4
 
 // The elements of one thread (2 x float4 at `base`): the gradient (times `scale`: 1 for a single head, 1 / heads under
 // the trainer's mean over heads -- a second float32 product, as autograd forms it) and the thread's part of the loss sum.
-// t[2][4]: the thread's targets, read once for all heads.
-// kLow: gamma < 1, where u^(gamma-1) is inf at u == 0 (an exact hit, or |p - t| below float32 rounding of 1): there
-// u^gamma is 0^0 = 1 for gamma == 0 (torch's value) and 0 otherwise, and gamma u^(gamma-1) log e is taken at its limit 0,
-// so the loss stays finite and the gradient at an exact hit is 0.  gamma >= 1 runs the instantiation without the test.
+// t[2][4]: the thread's targets, read once for all heads.  The element arithmetic (and kLow) is focal_element.h.
 template <bool kLow>
 __device__ __forceinline__ float focal_thread(const float* __restrict__ pred, float* __restrict__ grad,
                                               const float (&t)[kLossPerThread / 4][4], long base, long n, float gamma,
@@ -42,22 +40,7 @@ __device__ __forceinline__ float focal_thread(const float* __restrict__ pred, fl
     }
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      const float d = p[e] - t[h][e];
-      const float err = (1.f - fabsf(d)) + 1e-20f;
-      const float u = 1.f - err;
-      const float lg = logf(err);
-      const float ug1 = cube ? u * u : powf(u, gamma - 1.f);  // u^(gamma-1)
-      const float ug = ug1 * u;
-      float le = -ug * lg;
-      float dl_de = gamma * ug1 * lg - ug / err;
-      if constexpr (kLow) {
-        if (u == 0.f) {
-          le = 0.f;
-          dl_de = (gamma == 0.f) ? -1.f / err : 0.f;
-        }
-      }
-      const float sgn = (d > 0.f) ? 1.f : ((d < 0.f) ? -1.f : 0.f);
-      g[e] = (-dl_de * sgn * inv_rows) * scale;
+      const float le = focal_element<kLow>(p[e], t[h][e], gamma, cube, inv_rows, scale, g[e]);
       if (i + e < n) sum += le;
     }
     if (grad != nullptr) {

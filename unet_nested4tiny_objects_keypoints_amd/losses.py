@@ -65,3 +65,103 @@ class FocalLoss_BCE_2d(nn.Module):
         rows = t.numel() if self.size_average else t.shape[0] * t.shape[1]
         loss, grads = ops.focal_bce_heads([o.detach() for o in outputs], t, rows, float(self.gamma))
         return loss[0], grads
+
+
+class _TopKFocalBCEFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, target, k, denom, gamma):
+        from . import ops
+        loss, grads, kth = ops.topk_focal_heads([pred.contiguous()], target.contiguous(), k, denom, gamma,
+                                                want_grad=ctx.needs_input_grad[0])
+        ctx.save_for_backward(grads[0] if grads is not None else None)
+        kth = kth[0]
+        ctx.mark_non_differentiable(kth)
+        return loss[0], kth
+
+    @staticmethod
+    def backward(ctx, g, _g_kth):
+        (grad,) = ctx.saved_tensors
+        return (grad * g if grad is not None else None), None, None, None, None
+
+
+class TopKFocalLoss_BCE_2d(nn.Module):
+    """Hard-pixel mining for ``FocalLoss_BCE_2d``: of every (n, c) map only the ``k`` pixels with the largest
+    ``|input - target|`` -- the largest loss terms, the ranking of the reference's ``BCE_loss(results, labels, topk)``
+    (tools/losses/bce_loss.py:14-35) -- enter the loss; pixels equal to the k-th largest are taken in index order, so a
+    step stays bit-reproducible.  Exactly one of ``k`` (pixels per map, >= 1) and ``fraction`` (of the map's P = H*W
+    pixels, in (0, 1]: k = max(1, ceil(fraction * P))) is given; k >= P is ``FocalLoss_BCE_2d`` itself.
+    ``size_average=False`` divides the sum by the N*C maps (the ``FocalLoss_BCE_2d`` convention), ``True`` by the number
+    of selected pixels as well.  GPU fp32 tensors take one fused HIP launch (csrc/topk_loss.hip: an exact radix select,
+    value and gradient together); CPU tensors the same rule as plain torch ops.  After a call ``last_threshold`` holds the
+    k-th largest ``|input - target|`` of every map: [N*C] after ``forward``, [heads, N*C] after ``mean_over_heads``.
+
+    Deliberately not a subclass of ``FocalLoss_BCE_2d``: code that tests for that class computes the unselected loss."""
+
+    def __init__(self, k=None, fraction=None, gamma=3, size_average=False):
+        super().__init__()
+        if (k is None) == (fraction is None):
+            raise ValueError("give exactly one of k and fraction")
+        if k is not None:
+            if isinstance(k, bool) or int(k) != k or int(k) < 1:
+                raise ValueError("k must be an integer >= 1, got %r" % (k,))
+            k = int(k)
+        else:
+            fraction = float(fraction)
+            if not 0.0 < fraction <= 1.0:
+                raise ValueError("fraction must be in (0, 1], got %r" % (fraction,))
+        self.k = k
+        self.fraction = fraction
+        self.gamma = gamma
+        self.size_average = size_average
+        self.last_threshold = None
+
+    def k_for(self, pixels: int) -> int:
+        """the pixels selected of a map of `pixels` pixels"""
+        import math
+        k = self.k if self.k is not None else max(1, math.ceil(self.fraction * pixels))
+        return min(k, pixels)
+
+    def _denom(self, rows, k_eff):
+        return rows * k_eff if self.size_average else rows
+
+    def forward(self, input, target):
+        if input.dim() > 2:
+            input = input.reshape(-1, input.size(-2), input.size(-1))
+        target = target.reshape(-1, target.size(-2), target.size(-1))
+        rows, pixels = target.shape[0], target.shape[1] * target.shape[2]
+        k_eff = self.k_for(pixels)
+        denom = self._denom(rows, k_eff)
+        if (input.is_cuda and target.is_cuda and input.dtype == torch.float32 and target.dtype == torch.float32
+                and not target.requires_grad):
+            loss, kth = _TopKFocalBCEFn.apply(input, target, k_eff, denom, float(self.gamma))
+            self.last_threshold = kth
+            return loss
+        d = (input - target).reshape(rows, pixels)
+        # descending and stable: the lowest index first among equals (a NaN sorts first, as in the kernel)
+        ranked, order = torch.sort(d.detach().abs(), dim=1, descending=True, stable=True)
+        selected = torch.zeros(rows, pixels, dtype=torch.bool).scatter_(1, order[:, :k_eff], True)
+        self.last_threshold = ranked[:, k_eff - 1]
+        error = 1 - torch.abs(d) + 1e-20
+        loss = -1 * (1 - error) ** self.gamma * torch.log(error)
+        return torch.where(selected, loss, torch.zeros_like(loss)).sum() / denom
+
+    def mean_over_heads(self, outputs, target):
+        """``FocalLoss_BCE_2d.mean_over_heads`` for this criterion: the trainer's loop over the deep-supervision heads in
+        ONE launch, the selection taken per head -> (avg: 0-dim tensor without a graph, [d avg / d output]) or None when
+        the heads do not qualify; the caller then runs the loop.  Same bits as the loop (tests/test_gpu_topk.py)."""
+        from . import _lib, ops
+        if not (isinstance(outputs, (tuple, list)) and 2 <= len(outputs) <= _lib.MAX_HEADS):
+            return None
+        if not (target.is_cuda and target.dtype == torch.float32 and not target.requires_grad and target.dim() == 4):
+            return None
+        for o in outputs:
+            if not (o.is_cuda and o.dtype == torch.float32 and o.shape == target.shape and o.is_contiguous()
+                    and o.device == target.device):
+                return None
+        t = target.contiguous()
+        rows, pixels = t.shape[0] * t.shape[1], t.shape[2] * t.shape[3]
+        k_eff = self.k_for(pixels)
+        loss, grads, kth = ops.topk_focal_heads([o.detach() for o in outputs], t, k_eff, self._denom(rows, k_eff),
+                                                float(self.gamma))
+        self.last_threshold = kth
+        return loss[0], grads

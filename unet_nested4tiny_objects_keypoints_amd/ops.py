@@ -841,6 +841,44 @@ def focal_bce_heads(preds, target: torch.Tensor, rows: int, gamma: float, want_g
     return loss, grads
 
 
+def topk_focal_heads(preds, target: torch.Tensor, k: int, denom: int, gamma: float, want_grad: bool = True):
+    """Top-k focal loss of every head against one target [..., H, W] (a row is one map of P = H*W pixels): per head and
+    row only the min(k, P) pixels with the largest |pred - target| enter FocalLoss_BCE_2d, ties at the threshold taken in
+    index order (csrc/topk_loss.hip: an exact radix select, one launch for all heads).
+    -> (losses [1 + heads]: the mean over heads, then every head's value; d mean / d pred per head (+0.0 on every pixel
+    that is not selected) or None; kth [heads, rows]: the k-th largest |pred - target| of every head and row)."""
+    lib = _lib.lib()
+    if not 1 <= len(preds) <= _lib.MAX_HEADS:
+        raise ValueError("1 to %d heads" % _lib.MAX_HEADS)
+    _need(target, "target")
+    if target.dim() < 3:
+        raise ValueError("target must be [..., H, W]")
+    for p in preds:
+        _need(p, "pred")
+        if p.shape != target.shape:
+            raise ValueError("pred and target must have the same shape")
+    if int(k) < 1 or int(denom) < 1:
+        raise ValueError("k and denom must be at least 1")
+    preds, target = [_aligned16(p) for p in preds], _aligned16(target)
+    pixels = target.shape[-2] * target.shape[-1]
+    rows = target.numel() // max(pixels, 1)
+    nbytes = int(lib.unetpp_topk_focal_workspace_bytes(len(preds), rows, pixels))
+    if nbytes <= 0:
+        raise ValueError("topk_focal_heads: %d rows of %d pixels are outside what the kernel takes" % (rows, pixels))
+    workspace = torch.empty(nbytes // 4, dtype=torch.float32, device=target.device)
+    grads = [torch.empty_like(p) for p in preds] if want_grad else None
+    loss = torch.empty(1 + len(preds), dtype=torch.float32, device=target.device)
+    kth = torch.empty(len(preds), rows, dtype=torch.float32, device=target.device)
+    hd = _lib.FocalHeads()
+    hd.n_heads = len(preds)
+    for i, p in enumerate(preds):
+        hd.pred[i] = p.data_ptr()
+        hd.grad[i] = grads[i].data_ptr() if want_grad else None
+    check(lib.unetpp_topk_focal_heads(C.byref(hd), _ptr(target), rows, pixels, int(k), int(denom), float(gamma),
+                                      _ptr(workspace), _ptr(kth), _ptr(loss), _stream()), "unetpp_topk_focal_heads")
+    return loss, grads, kth
+
+
 def create_heatmap(points: torch.Tensor, height: int, width: int, radius: float = 3.0) -> torch.Tensor:
     """points [N, P, 2] (x, y) fp32 on the GPU -> target heat maps [N, 4, H, W] (tools/misc/helper.py:87-172)."""
     lib = _lib.lib()
