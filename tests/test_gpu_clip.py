@@ -8,7 +8,10 @@ for 8 CUs (64 workgroups) walks several of the 81 chunks; two parameter groups. 
 tensor by 1e-3 ... 1e3.
 
 The oracle of the clipped step is the EXISTING unclipped kernel (pinned by the reference's fixtures in
-tests/test_gpu_optim.py) on gradients that torch scaled beforehand; the oracle of the norm is numpy float64."""
+tests/test_gpu_optim.py) on gradients that torch scaled beforehand; the oracle of the norm is numpy float64.  That
+compares kernel with kernel (the unaligned segment included); the clipped step also has an oracle that shares no code
+with the kernel: tests/test_gpu_optim_elementwise.py takes the norm a clipped step published, recomputes the coefficient
+and the update in numpy float32 (tests/optim_oracle.py) and holds every element of every step to it, bit for bit."""
 import copy
 
 import numpy as np

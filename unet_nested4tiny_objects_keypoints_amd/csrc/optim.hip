@@ -3,10 +3,14 @@
 // fixed-size chunks of the segments (chunk -> segment map built by the caller), float4 where all five streams of a
 // segment are 16-byte aligned, scalar in the tail.
 //
-// Per element the op sequence of the reference's torch calls is restated in their order, each aten op rounded once as
-// aten's CPU kernels round it (the golden fixtures are CPU runs of the reference): add(a, b, alpha) = fma(alpha, b, a),
-// addcmul(a, b, c, s) = fma(s*b, c, a), addcdiv(a, b, c, s) = a + (s*b)/c.  Implicit contraction is off; every fma
-// below is one aten op.
+// Per element the op sequence of the reference's torch calls is restated in their order, each aten op as ONE float32 op
+// rounded once as IEEE-754 rounds it: add(a, b, alpha) = fma(alpha, b, a), addcmul(a, b, c, s) = fma(s*b, c, a),
+// addcdiv(a, b, c, s) = a + (s*b)/c, sqrt = the correctly rounded sqrtf (NOT __fsqrt_rn: without
+// OCML_BASIC_ROUNDED_OPERATIONS the HIP headers map that to the native 1-ulp v_sqrt_f32).  Implicit contraction is off;
+// every fma below is one aten op.  aten's CPU kernels (the golden fixtures are CPU runs of the reference) round + - * /
+// and fma the same way; their vectorised sqrt is not correctly rounded in the build that made the fixtures, and that is
+// the whole of the rounding allowance of tests/test_gpu_optim.py.  tests/test_gpu_optim_elementwise.py holds every
+// element of every step to tests/optim_oracle.py, a numpy restatement of this contract, bit for bit.
 //   AdamW     m = fma(1-b1, g, m*b1);  v = fma((1-b2)*g, g, v*b2);  [vmax = max(vmax, v)];  denom = sqrt(v|vmax) + eps;
 //             [d = p*wd];  p = p + (-step_size*m)/denom;  [p = p - d]
 //   AdaBound  [g = fma(wd, p, g)];  m, v, vmax, denom as above;  s = clamp(step_size/denom, lo, hi)*m;  p = p - s
@@ -84,9 +88,9 @@ __device__ __forceinline__ void update(float& p, float g, float& m, float& v, fl
   float denom;
   if (AMS) {
     a = fmaxf(a, v);
-    denom = __fsqrt_rn(a) + s.eps;
+    denom = sqrtf(a) + s.eps;
   } else {
-    denom = __fsqrt_rn(v) + s.eps;
+    denom = sqrtf(v) + s.eps;
   }
   if (KIND == UNETPP_OPTIM_ADAMW) {
     const float d = decay ? p * s.wd : 0.f;
