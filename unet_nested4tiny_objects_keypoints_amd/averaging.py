@@ -20,7 +20,8 @@ launch in and one out, so nothing is allocated and the model's own weights survi
 write through raw pointers: ``p._version`` does not move (the weight-image pack plan is rebuilt every pass, DESIGN.md
 section 4; a model with frozen weight images is invalidated by every swap).
 
-The segment table is built once per set of data pointers and cached, as optim.py does.
+The segment table (multi_tensor.py; the format and the chunk walk are described in csrc/multi_tensor.h) is built once per
+set of data pointers and cached.
 
 ``capturable=True``: ``n_averaged`` is a float32 device scalar, the decay lives in a one-double device block, ``w`` and the
 first-update decision are formed on the device and the launch itself advances the count -- no host sync, no host decision
@@ -31,31 +32,26 @@ fp32 CUDA tensors only: anything else raises (this path has no CPU fallback).
 """
 from __future__ import annotations
 
-import collections
 import contextlib
 import ctypes as C
 
-import numpy as np
 import torch
 
 from . import _lib
 from .checkpoint import _unwrap
+from .multi_tensor import Table, TableCache, aligned16
 
 _KINDS = {"mean": _lib.AVG_MEAN, "ema": _lib.AVG_EMA}
-_SEG_BYTES = C.sizeof(_lib.AvgSegment)
-_MAX_TABLES = 8
 _ALIGN = 4          # floats: every shadow entry starts on a 16-byte boundary
 
 
-class SegmentTable:
-    """A device table of {avg, src} segments with its chunk -> segment map and the arrival counter of capturable launches.
+class SegmentTable(Table):
+    """A device table of {avg, src} segments with the arrival counter of capturable launches.
     pairs: (avg tensor, src tensor, copy flag) -- fp32, contiguous, on one GPU, the same number of elements each."""
 
     def __init__(self, pairs):
         from .ops import _need
-        L = _lib.lib()
-        chunk = int(L.unetpp_optim_chunk_elems())
-        segs, chunk_seg, dev = [], [], None
+        segs, dev = [], None
         for avg, src, copy in pairs:
             _need(avg, "average")
             _need(src, "averaged tensor")
@@ -72,36 +68,22 @@ class SegmentTable:
             if a0 < s0 + 4 * n and s0 < a0 + 4 * n:
                 raise ValueError("an average overlaps its tensor")
             s = _lib.AvgSegment()
-            s.avg, s.src, s.numel, s.chunk_begin = a0, s0, n, len(chunk_seg)
-            s.vec, s.copy = int(a0 % 16 == 0 and s0 % 16 == 0), int(bool(copy))
-            chunk_seg += [len(segs)] * ((n + chunk - 1) // chunk)
+            s.avg, s.src, s.numel = a0, s0, n
+            s.vec, s.copy = aligned16(avg, src), int(bool(copy))
             segs.append(s)
         if not segs:
             raise ValueError("no tensor with elements to average")
-        self.n_seg, self.n_chunks = len(segs), len(chunk_seg)
-        self.chunk_off = self.n_seg * _SEG_BYTES
-        self.done_off = self.chunk_off + 4 * self.n_chunks
-        nbytes = self.done_off + 8
-        self.host = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)   # kept: the upload below is asynchronous
-        arr = self.host.numpy()
-        C.memmove(self.host.data_ptr(), (_lib.AvgSegment * self.n_seg)(*segs), self.chunk_off)
-        arr[self.chunk_off:self.done_off] = np.asarray(chunk_seg, dtype=np.int32).view(np.uint8)
-        arr[self.done_off:nbytes] = 0
-        self.dev = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        _lib.check(L.unetpp_optim_upload(C.c_void_p(self.dev.data_ptr()), C.c_void_p(self.host.data_ptr()), nbytes,
-                                         C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "unetpp_optim_upload")
+        super().__init__(segs, dev, True)
 
     def launch(self, kind: int, count: int = 0, decay: float = 0.0, count_dev=None, hyper_dev=None) -> None:
         """One unetpp_avg_update over the table on the current stream.  count_dev (float32 device scalar) selects the
         capturable form; hyper_dev is its one-double decay block."""
-        base = self.dev.data_ptr()
         capturable = count_dev is not None
         status = _lib.lib().unetpp_avg_update(
-            kind, _lib.AVG_CAPTURABLE if capturable else 0, C.c_void_p(base), self.n_seg,
-            C.c_void_p(base + self.chunk_off), self.n_chunks, int(count), float(decay),
+            kind, _lib.AVG_CAPTURABLE if capturable else 0, *self.args, int(count), float(decay),
             C.c_void_p(count_dev.data_ptr()) if capturable else None,
             C.c_void_p(hyper_dev.data_ptr()) if (capturable and hyper_dev is not None) else None,
-            C.c_void_p(base + self.done_off) if capturable else None,
+            self.done if capturable else None,
             C.c_void_p(torch.cuda.current_stream(self.dev.device).cuda_stream))
         _lib.check(status, "unetpp_avg_update")
 
@@ -165,7 +147,7 @@ class WeightAverager:
             if held.get(leaf) is None:
                 raise ValueError("WeightAverager: cannot find %s on the model" % k)
             self._slots[k] = (held, leaf)
-        self._tables = collections.OrderedDict()
+        self._tables = TableCache()
         self._applied = False
         self._n = 0
         self._count_dev = torch.zeros((), dtype=torch.float32, device=dev) if self.capturable else None
@@ -202,10 +184,7 @@ class WeightAverager:
                     raise RuntimeError("WeightAverager: %s must be a float32 tensor on the GPU: this path has no CPU "
                                        "fallback" % k)
                 pairs.append((self._view(k, t).view(-1), t, not (self._is_param[k] or self.average_buffers)))
-            table = SegmentTable(pairs)
-            self._tables[key] = table
-            while len(self._tables) > _MAX_TABLES:
-                self._tables.popitem(last=False)
+            table = self._tables.add(key, SegmentTable(pairs))
         else:
             self._tables.move_to_end(key)
         return table

@@ -1,8 +1,7 @@
 // Weight averaging: the reference trainer's `model_save == "average"` strategy (trainer/trainer.py:243-252, left
 // unimplemented there) as ONE multi-tensor streaming launch per update.  Every floating state-dict entry of the model
-// is a segment {avg, src} of a device table; a persistent grid walks fixed-size chunks of the segments (chunk -> segment
-// map built by the caller, the chunk size is the optimizer's: unetpp_optim_chunk_elems), float4 where both streams of a
-// segment are 16-byte aligned, scalar otherwise and in a segment's last < 4 elements.
+// is a segment {avg, src} (two streams) of a device table; the table, the persistent grid, the chunk walk and the
+// arrival counter of capturable launches are multi_tensor.h's and are described there.
 //
 // Per element, n = the number of updates made before this one:
 //   mean / ema   n == 0 or segment.copy:  avg = src                       (bit for bit)
@@ -12,17 +11,14 @@
 // Implicit contraction is off: w*d and the add are two roundings on every path, so the vector and the scalar path give
 // the same bits.  No floating-point atomics, no cross-workgroup order: every element's result depends on that element
 // alone.  Capturable launches read n (float32) and decay (double) from the device, and the last workgroup to arrive
-// (integer arrival counter, reset for the next launch) advances n -- as optim_kernel advances its step counters.
+// advances n -- as optim_kernel advances its step counters.
 #include "common.h"
+#include "multi_tensor.h"
 
 #pragma clang fp contract(off)
 
 namespace unetpp {
 namespace {
-
-constexpr int kAvgThreads = 256;
-constexpr int kAvgVecPerThread = 4;                                        // float4 per thread and stream
-constexpr int64_t kAvgChunk = int64_t(kAvgThreads) * kAvgVecPerThread * 4;   // 4096 elements, = optim.hip's kOptChunk
 
 template <int KIND>
 __device__ __forceinline__ void apply(float& a, float& s, float w, bool copy) {
@@ -40,10 +36,10 @@ __device__ __forceinline__ void apply(float& a, float& s, float w, bool copy) {
 }
 
 template <int KIND>
-__global__ void __launch_bounds__(kAvgThreads) avg_kernel(const unetpp_avg_segment* __restrict__ segs,
-                                                          const int32_t* __restrict__ chunk_seg, int64_t n_chunks,
-                                                          float w_host, int32_t first_host, float* count_dev,
-                                                          const double* __restrict__ hyper_dev, int32_t* done) {
+__global__ void __launch_bounds__(kMtThreads) avg_kernel(const unetpp_avg_segment* __restrict__ segs,
+                                                         const int32_t* __restrict__ chunk_seg, int64_t n_chunks,
+                                                         float w_host, int32_t first_host, float* count_dev,
+                                                         const double* __restrict__ hyper_dev, int32_t* done) {
   constexpr bool kSwap = KIND == UNETPP_AVG_SWAP;
   float w = w_host;
   bool first = first_host != 0;
@@ -57,48 +53,32 @@ __global__ void __launch_bounds__(kAvgThreads) avg_kernel(const unetpp_avg_segme
   for (int64_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
     const unetpp_avg_segment sg = segs[chunk_seg[c]];
     const bool copy = first || sg.copy != 0;
-    const int64_t begin = (c - sg.chunk_begin) * kAvgChunk;
-    const int64_t end = begin + kAvgChunk < sg.numel ? begin + kAvgChunk : sg.numel;
     float* __restrict__ A = sg.avg;
     float* __restrict__ S = sg.src;
-    int64_t tail = begin;   // where the scalar loop starts
-    if (sg.vec) {
-      const int64_t vend = begin + ((end - begin) & ~int64_t(3));
+    walk_chunk(
+        chunk_span(sg.numel, sg.chunk_begin, c), sg.vec != 0,
+        [&](int64_t i) __attribute__((always_inline)) {
+          f32x4 a = *reinterpret_cast<const f32x4*>(A + i);
+          f32x4 s = *reinterpret_cast<const f32x4*>(S + i);
 #pragma unroll
-      for (int k = 0; k < kAvgVecPerThread; ++k) {
-        const int64_t i = begin + (int64_t(k) * kAvgThreads + threadIdx.x) * 4;
-        if (i >= vend) break;
-        f32x4 a = *reinterpret_cast<const f32x4*>(A + i);
-        f32x4 s = *reinterpret_cast<const f32x4*>(S + i);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          float ae = a[e], se = s[e];
+          for (int e = 0; e < 4; ++e) {
+            float ae = a[e], se = s[e];
+            apply<KIND>(ae, se, w, copy);
+            a[e] = ae, s[e] = se;
+          }
+          *reinterpret_cast<f32x4*>(A + i) = a;
+          if (kSwap) *reinterpret_cast<f32x4*>(S + i) = s;
+        },
+        [&](int64_t i) __attribute__((always_inline)) {
+          float ae = A[i], se = S[i];
           apply<KIND>(ae, se, w, copy);
-          a[e] = ae, s[e] = se;
-        }
-        *reinterpret_cast<f32x4*>(A + i) = a;
-        if (kSwap) *reinterpret_cast<f32x4*>(S + i) = s;
-      }
-      tail = vend;   // < 4 elements: the segment's tail
-    }
-    for (int64_t i = tail + threadIdx.x; i < end; i += kAvgThreads) {
-      float ae = A[i], se = S[i];
-      apply<KIND>(ae, se, w, copy);
-      A[i] = ae;
-      if (kSwap) S[i] = se;
-    }
+          A[i] = ae;
+          if (kSwap) S[i] = se;
+        });
   }
   if (kSwap || done == nullptr) return;
-  // capturable: the device count advances once every workgroup has read it -- the last workgroup to arrive does it;
-  // nothing floating-point depends on the order
-  __shared__ int last;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __threadfence();
-    last = atomicAdd(done, 1) == static_cast<int>(gridDim.x) - 1;
-  }
-  __syncthreads();
-  if (!last) return;
+  // capturable: the device count advances once every workgroup has read it
+  if (!last_workgroup(done)) return;
   if (threadIdx.x == 0) {
     *count_dev = n_before + 1.f;
     *done = 0;
@@ -108,11 +88,8 @@ __global__ void __launch_bounds__(kAvgThreads) avg_kernel(const unetpp_avg_segme
 template <int KIND>
 void launch(const unetpp_avg_segment* segs, const int32_t* chunk_seg, int64_t n_chunks, float w, int32_t first,
             float* count_dev, const double* hyper_dev, int32_t* done, hipStream_t st) {
-  const int cus = device_cu_count();
-  const int64_t cap = int64_t(cus > 0 ? cus : 256) * 8;
-  const unsigned grid = static_cast<unsigned>(n_chunks < cap ? n_chunks : cap);
-  hipLaunchKernelGGL((avg_kernel<KIND>), dim3(grid), dim3(kAvgThreads), 0, st, segs, chunk_seg, n_chunks, w, first,
-                     count_dev, hyper_dev, done);
+  hipLaunchKernelGGL((avg_kernel<KIND>), dim3(persistent_grid(n_chunks)), dim3(kMtThreads), 0, st, segs, chunk_seg,
+                     n_chunks, w, first, count_dev, hyper_dev, done);
 }
 
 }  // namespace
@@ -123,7 +100,7 @@ using namespace unetpp;
 extern "C" int unetpp_avg_update(int32_t kind, int32_t flags, const unetpp_avg_segment* segments, int32_t n_segments,
                                  const int32_t* chunk_segment, int64_t n_chunks, int64_t count, double decay,
                                  float* count_dev, const double* hyper_dev, int32_t* done, void* stream) {
-  if (segments == nullptr || n_segments <= 0 || chunk_segment == nullptr || n_chunks <= 0) return UNETPP_EINVAL;
+  if (!table_args_ok(segments, n_segments, chunk_segment, n_chunks)) return UNETPP_EINVAL;
   if (kind < UNETPP_AVG_MEAN || kind > UNETPP_AVG_SWAP) return UNETPP_EINVAL;
   if ((flags & ~UNETPP_AVG_CAPTURABLE) != 0) return UNETPP_EINVAL;
   const bool capturable = (flags & UNETPP_AVG_CAPTURABLE) != 0;

@@ -1,7 +1,7 @@
 // Fused optimizer step: the reference trainer's own optimizers (tools/optimizers/{adamw,adabound,sgdw}.py) as ONE
-// multi-tensor launch per step.  Every parameter of every group is a segment of a device table; a persistent grid walks
-// fixed-size chunks of the segments (chunk -> segment map built by the caller), float4 where all five streams of a
-// segment are 16-byte aligned, scalar in the tail.
+// multi-tensor launch per step.  Every parameter of every group is a segment of a device table (param, grad, exp_avg,
+// exp_avg_sq, aux: five streams); the table, the persistent grid, the chunk walk and the arrival counter of capturable
+// launches are multi_tensor.h's and are described there.
 //
 // Per element the op sequence of the reference's torch calls is restated in their order, each aten op as ONE float32 op
 // rounded once as IEEE-754 rounds it: add(a, b, alpha) = fma(alpha, b, a), addcmul(a, b, c, s) = fma(s*b, c, a),
@@ -29,6 +29,7 @@
 //   consume     total = float(sqrt(sum)); c = max_norm / (total + 1e-6f); coef = c > 1 ? 1 : c (torch's
 //               clip_grad_norm_ in fp32: NaN stays NaN, an infinite norm gives 0); g = g * coef as it is read.
 #include "common.h"
+#include "multi_tensor.h"
 
 #include <math.h>
 
@@ -36,10 +37,6 @@
 
 namespace unetpp {
 namespace {
-
-constexpr int kOptThreads = 256;
-constexpr int kOptVecPerThread = 4;                                      // float4 per thread and stream
-constexpr int64_t kOptChunk = int64_t(kOptThreads) * kOptVecPerThread * 4;   // 4096 elements
 
 enum { H_LR = 0, H_B1 = 1, H_B2 = 2, H_EPS = 3, H_WD = 4, H_FINAL_LR = 5, H_GAMMA = 6 };
 
@@ -118,85 +115,63 @@ __device__ __forceinline__ void optim_body(const unetpp_optim_segment* __restric
     const Scalars s = make_scalars(KIND, hyper + int64_t(sg.group) * UNETPP_OPTIM_HYPER, t);
     const bool decay = s.wd != 0.f;
     const bool has_aux = sg.aux != nullptr;
-    const int64_t begin = (c - sg.chunk_begin) * kOptChunk;
-    const int64_t end = begin + kOptChunk < sg.numel ? begin + kOptChunk : sg.numel;
     float* __restrict__ P = sg.param;
     const float* __restrict__ G = sg.grad;
     float* __restrict__ M = sg.exp_avg;
     float* __restrict__ V = sg.exp_avg_sq;
     float* __restrict__ A = sg.aux;
     const bool moments = KIND != UNETPP_OPTIM_SGDW;
-    if (sg.vec) {
-      const int64_t vend = begin + ((end - begin) & ~int64_t(3));
+    walk_chunk(
+        chunk_span(sg.numel, sg.chunk_begin, c), sg.vec != 0,
+        [&](int64_t i) __attribute__((always_inline)) {
+          f32x4 p = *reinterpret_cast<const f32x4*>(P + i);
+          f32x4 g = *reinterpret_cast<const f32x4*>(G + i);
+          if (CLIP) g = g * coef;
+          f32x4 m = {0.f, 0.f, 0.f, 0.f}, v = m, a = m;
+          if (moments) {
+            m = *reinterpret_cast<const f32x4*>(M + i);
+            v = *reinterpret_cast<const f32x4*>(V + i);
+          }
+          if (has_aux && (AMS || KIND == UNETPP_OPTIM_SGDW)) a = *reinterpret_cast<const f32x4*>(A + i);
 #pragma unroll
-      for (int k = 0; k < kOptVecPerThread; ++k) {
-        const int64_t i = begin + (int64_t(k) * kOptThreads + threadIdx.x) * 4;
-        if (i >= vend) break;
-        f32x4 p = *reinterpret_cast<const f32x4*>(P + i);
-        f32x4 g = *reinterpret_cast<const f32x4*>(G + i);
-        if (CLIP) g = g * coef;
-        f32x4 m = {0.f, 0.f, 0.f, 0.f}, v = m, a = m;
-        if (moments) {
-          m = *reinterpret_cast<const f32x4*>(M + i);
-          v = *reinterpret_cast<const f32x4*>(V + i);
-        }
-        if (has_aux && (AMS || KIND == UNETPP_OPTIM_SGDW)) a = *reinterpret_cast<const f32x4*>(A + i);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          float pe = p[e], me = m[e], ve = v[e], ae = a[e];
-          update<KIND, AMS>(pe, g[e], me, ve, ae, s, decay, has_aux);
-          p[e] = pe, m[e] = me, v[e] = ve, a[e] = ae;
-        }
-        if (KIND != UNETPP_OPTIM_SGDW || decay) *reinterpret_cast<f32x4*>(P + i) = p;
-        if (moments) {
-          *reinterpret_cast<f32x4*>(M + i) = m;
-          *reinterpret_cast<f32x4*>(V + i) = v;
-        }
-        if (has_aux && (AMS || KIND == UNETPP_OPTIM_SGDW)) *reinterpret_cast<f32x4*>(A + i) = a;
-      }
-      for (int64_t i = vend + threadIdx.x; i < end; i += kOptThreads) {   // < 4 elements: the segment's tail
-        float pe = P[i], me = moments ? M[i] : 0.f, ve = moments ? V[i] : 0.f, ae = has_aux ? A[i] : 0.f;
-        update<KIND, AMS>(pe, CLIP ? G[i] * coef : G[i], me, ve, ae, s, decay, has_aux);
-        P[i] = pe;
-        if (moments) M[i] = me, V[i] = ve;
-        if (has_aux) A[i] = ae;
-      }
-    } else {
-      for (int64_t i = begin + threadIdx.x; i < end; i += kOptThreads) {
-        float pe = P[i], me = moments ? M[i] : 0.f, ve = moments ? V[i] : 0.f, ae = has_aux ? A[i] : 0.f;
-        update<KIND, AMS>(pe, CLIP ? G[i] * coef : G[i], me, ve, ae, s, decay, has_aux);
-        P[i] = pe;
-        if (moments) M[i] = me, V[i] = ve;
-        if (has_aux) A[i] = ae;
-      }
-    }
+          for (int e = 0; e < 4; ++e) {
+            float pe = p[e], me = m[e], ve = v[e], ae = a[e];
+            update<KIND, AMS>(pe, g[e], me, ve, ae, s, decay, has_aux);
+            p[e] = pe, m[e] = me, v[e] = ve, a[e] = ae;
+          }
+          if (KIND != UNETPP_OPTIM_SGDW || decay) *reinterpret_cast<f32x4*>(P + i) = p;
+          if (moments) {
+            *reinterpret_cast<f32x4*>(M + i) = m;
+            *reinterpret_cast<f32x4*>(V + i) = v;
+          }
+          if (has_aux && (AMS || KIND == UNETPP_OPTIM_SGDW)) *reinterpret_cast<f32x4*>(A + i) = a;
+        },
+        [&](int64_t i) __attribute__((always_inline)) {
+          float pe = P[i], me = moments ? M[i] : 0.f, ve = moments ? V[i] : 0.f, ae = has_aux ? A[i] : 0.f;
+          update<KIND, AMS>(pe, CLIP ? G[i] * coef : G[i], me, ve, ae, s, decay, has_aux);
+          P[i] = pe;
+          if (moments) M[i] = me, V[i] = ve;
+          if (has_aux) A[i] = ae;
+        });
   }
   if (done == nullptr) return;
-  // capturable: the device step counters advance once every workgroup has read them -- the last workgroup to arrive
-  // (integer arrival counter, reset for the next launch) does it; nothing floating-point depends on the order
-  __shared__ int last;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __threadfence();
-    last = atomicAdd(done, 1) == static_cast<int>(gridDim.x) - 1;
-  }
-  __syncthreads();
-  if (!last) return;
-  for (int i = threadIdx.x; i < n_segments; i += kOptThreads)
+  // capturable: the device step counters advance once every workgroup has read them
+  if (!last_workgroup(done)) return;
+  for (int i = threadIdx.x; i < n_segments; i += kMtThreads)
     if (segs[i].step != nullptr) segs[i].step[0] = segs[i].step[0] + 1.f;
   if (threadIdx.x == 0) *done = 0;
 }
 
 template <int KIND, bool AMS>
-__global__ void __launch_bounds__(kOptThreads) optim_kernel(const unetpp_optim_segment* __restrict__ segs,
-                                                            int32_t n_segments, const int32_t* __restrict__ chunk_seg,
-                                                            int64_t n_chunks, const double* __restrict__ hyper,
-                                                            const double* __restrict__ steps, int32_t* done) {
+__global__ void __launch_bounds__(kMtThreads) optim_kernel(const unetpp_optim_segment* __restrict__ segs,
+                                                           int32_t n_segments, const int32_t* __restrict__ chunk_seg,
+                                                           int64_t n_chunks, const double* __restrict__ hyper,
+                                                           const double* __restrict__ steps, int32_t* done) {
   optim_body<KIND, AMS, false>(segs, n_segments, chunk_seg, n_chunks, hyper, steps, done, 1.f);
 }
 
 // ---- gradient norm, clip coefficient, non-finite skip ---------------------------------------------------------------
-constexpr int kOptWaves = kOptThreads / 64;
+constexpr int kOptWaves = kMtThreads / 64;
 
 // sum over the workgroup in one fixed order: a tree across each wave, then ((w0 + w1) + (w2 + w3)); every thread gets it.
 // `red` must not be in use by a sum that some wave may still be reading (callers in a loop alternate two buffers).
@@ -209,22 +184,22 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
   return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-__global__ void __launch_bounds__(kOptThreads) grad_norm_kernel(const unetpp_optim_segment* __restrict__ segs,
-                                                                const int32_t* __restrict__ chunk_seg,
-                                                                int64_t n_chunks, double* __restrict__ partials) {
+__global__ void __launch_bounds__(kMtThreads) grad_norm_kernel(const unetpp_optim_segment* __restrict__ segs,
+                                                               const int32_t* __restrict__ chunk_seg,
+                                                               int64_t n_chunks, double* __restrict__ partials) {
   __shared__ double red[2][kOptWaves];
   int slot = 0;
   for (int64_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
     const unetpp_optim_segment sg = segs[chunk_seg[c]];
-    const int64_t begin = (c - sg.chunk_begin) * kOptChunk;
-    const int64_t end = begin + kOptChunk < sg.numel ? begin + kOptChunk : sg.numel;
+    const ChunkSpan sp = chunk_span(sg.numel, sg.chunk_begin, c);
+    const int64_t end = sp.end;
     const float* __restrict__ G = sg.grad;
     double acc = 0.0;
     // thread t owns elements (k*256 + t)*4 + e of the chunk, added in (k, e) order -- float4 loads where the segment is
     // aligned and the four are inside it, scalar loads of the same elements otherwise: the same sum either way
 #pragma unroll
-    for (int k = 0; k < kOptVecPerThread; ++k) {
-      const int64_t i = begin + (int64_t(k) * kOptThreads + threadIdx.x) * 4;
+    for (int k = 0; k < kMtVecPerThread; ++k) {
+      const int64_t i = sp.begin + vec_slot_offset(k, threadIdx.x);
       if (i >= end) break;
       if (sg.vec && i + 4 <= end) {
         const f32x4 g = *reinterpret_cast<const f32x4*>(G + i);
@@ -257,7 +232,7 @@ struct Clip {
 __device__ __forceinline__ Clip clip_prologue(const double* __restrict__ partials, int64_t n_chunks, float max_norm,
                                               bool skip_nonfinite, unetpp_clip_state* state, double* red) {
   double acc = 0.0;
-  for (int64_t j = threadIdx.x; j < n_chunks; j += kOptThreads) acc = acc + partials[j];
+  for (int64_t j = threadIdx.x; j < n_chunks; j += kMtThreads) acc = acc + partials[j];
   const double sum = block_sum(acc, red);
   const float total = static_cast<float>(sqrt(sum));   // the one fp32 rounding
   Clip cl;
@@ -276,13 +251,13 @@ __device__ __forceinline__ Clip clip_prologue(const double* __restrict__ partial
 }
 
 template <int KIND, bool AMS>
-__global__ void __launch_bounds__(kOptThreads) optim_clip_kernel(const unetpp_optim_segment* __restrict__ segs,
-                                                                 int32_t n_segments,
-                                                                 const int32_t* __restrict__ chunk_seg,
-                                                                 int64_t n_chunks, const double* __restrict__ hyper,
-                                                                 const double* __restrict__ steps, int32_t* done,
-                                                                 const double* __restrict__ partials,
-                                                                 unetpp_clip_state* state, int32_t skip_nonfinite) {
+__global__ void __launch_bounds__(kMtThreads) optim_clip_kernel(const unetpp_optim_segment* __restrict__ segs,
+                                                                int32_t n_segments,
+                                                                const int32_t* __restrict__ chunk_seg,
+                                                                int64_t n_chunks, const double* __restrict__ hyper,
+                                                                const double* __restrict__ steps, int32_t* done,
+                                                                const double* __restrict__ partials,
+                                                                unetpp_clip_state* state, int32_t skip_nonfinite) {
   __shared__ double red[kOptWaves];
   const Clip cl = clip_prologue(partials, n_chunks, static_cast<float>(hyper[UNETPP_OPTIM_H_MAX_NORM]),
                                 skip_nonfinite != 0, state, red);
@@ -290,54 +265,50 @@ __global__ void __launch_bounds__(kOptThreads) optim_clip_kernel(const unetpp_op
   optim_body<KIND, AMS, true>(segs, n_segments, chunk_seg, n_chunks, hyper, steps, done, cl.coef);
 }
 
-__global__ void __launch_bounds__(kOptThreads) grad_scale_kernel(const unetpp_optim_segment* __restrict__ segs,
-                                                                 const int32_t* __restrict__ chunk_seg,
-                                                                 int64_t n_chunks, const double* __restrict__ partials,
-                                                                 float max_norm, unetpp_clip_state* state) {
+__global__ void __launch_bounds__(kMtThreads) grad_scale_kernel(const unetpp_optim_segment* __restrict__ segs,
+                                                                const int32_t* __restrict__ chunk_seg,
+                                                                int64_t n_chunks, const double* __restrict__ partials,
+                                                                float max_norm, unetpp_clip_state* state) {
   __shared__ double red[kOptWaves];
   const Clip cl = clip_prologue(partials, n_chunks, max_norm, false, state, red);
   if (cl.coef == 1.f) return;   // g * 1 = g bit for bit: nothing to write
   const float coef = cl.coef;
   for (int64_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
     const unetpp_optim_segment sg = segs[chunk_seg[c]];
-    const int64_t begin = (c - sg.chunk_begin) * kOptChunk;
-    const int64_t end = begin + kOptChunk < sg.numel ? begin + kOptChunk : sg.numel;
     float* __restrict__ G = const_cast<float*>(sg.grad);
-    int64_t tail = begin;   // where the scalar loop starts
-    if (sg.vec) {
-      const int64_t vend = begin + ((end - begin) & ~int64_t(3));
-#pragma unroll
-      for (int k = 0; k < kOptVecPerThread; ++k) {
-        const int64_t i = begin + (int64_t(k) * kOptThreads + threadIdx.x) * 4;
-        if (i >= vend) break;
-        const f32x4 g = *reinterpret_cast<const f32x4*>(G + i);
-        *reinterpret_cast<f32x4*>(G + i) = g * coef;
-      }
-      tail = vend;   // < 4 elements: the segment's tail
-    }
-    for (int64_t i = tail + threadIdx.x; i < end; i += kOptThreads) G[i] = G[i] * coef;
+    walk_chunk(
+        chunk_span(sg.numel, sg.chunk_begin, c), sg.vec != 0,
+        [&](int64_t i) __attribute__((always_inline)) {
+          const f32x4 g = *reinterpret_cast<const f32x4*>(G + i);
+          *reinterpret_cast<f32x4*>(G + i) = g * coef;
+        },
+        [&](int64_t i) __attribute__((always_inline)) { G[i] = G[i] * coef; });
   }
 }
 
-inline unsigned persistent_grid(int64_t n_chunks) {
-  const int cus = device_cu_count();
-  const int64_t cap = int64_t(cus > 0 ? cus : 256) * 8;
-  return static_cast<unsigned>(n_chunks < cap ? n_chunks : cap);
-}
-
+// (kind, AMS flag) -> the template arguments and the kernel labels of the plain and of the clipped step
 template <int KIND, bool AMS>
-void launch(const unetpp_optim_segment* segs, int32_t n, const int32_t* chunk_seg, int64_t n_chunks,
-            const double* hyper, const double* steps, int32_t* done, hipStream_t st) {
-  hipLaunchKernelGGL((optim_kernel<KIND, AMS>), dim3(persistent_grid(n_chunks)), dim3(kOptThreads), 0, st, segs, n,
-                     chunk_seg, n_chunks, hyper, steps, done);
-}
+struct Variant {
+  static constexpr int kind = KIND;
+  static constexpr bool ams = AMS;
+  const char *label, *clip_label;
+};
 
-template <int KIND, bool AMS>
-void launch_clip(const unetpp_optim_segment* segs, int32_t n, const int32_t* chunk_seg, int64_t n_chunks,
-                 const double* hyper, const double* steps, int32_t* done, const double* partials,
-                 unetpp_clip_state* state, int32_t skip, hipStream_t st) {
-  hipLaunchKernelGGL((optim_clip_kernel<KIND, AMS>), dim3(persistent_grid(n_chunks)), dim3(kOptThreads), 0, st, segs, n,
-                     chunk_seg, n_chunks, hyper, steps, done, partials, state, skip);
+template <class F>
+void with_variant(int32_t kind, bool ams, F&& f) {
+  switch (kind * 2 + (ams ? 1 : 0)) {
+    case UNETPP_OPTIM_ADAMW * 2: f(Variant<UNETPP_OPTIM_ADAMW, false>{"optim_adamw", "optim_clip_adamw"}); break;
+    case UNETPP_OPTIM_ADAMW * 2 + 1:
+      f(Variant<UNETPP_OPTIM_ADAMW, true>{"optim_adamw_amsgrad", "optim_clip_adamw_amsgrad"});
+      break;
+    case UNETPP_OPTIM_ADABOUND * 2:
+      f(Variant<UNETPP_OPTIM_ADABOUND, false>{"optim_adabound", "optim_clip_adabound"});
+      break;
+    case UNETPP_OPTIM_ADABOUND * 2 + 1:
+      f(Variant<UNETPP_OPTIM_ADABOUND, true>{"optim_adabound_amsbound", "optim_clip_adabound_amsbound"});
+      break;
+    default: f(Variant<UNETPP_OPTIM_SGDW, false>{"optim_sgdw", "optim_clip_sgdw"}); break;
+  }
 }
 
 }  // namespace
@@ -345,34 +316,30 @@ void launch_clip(const unetpp_optim_segment* segs, int32_t n, const int32_t* chu
 
 using namespace unetpp;
 
-extern "C" int64_t unetpp_optim_chunk_elems(void) { return kOptChunk; }
+extern "C" int64_t unetpp_optim_chunk_elems(void) { return kMtChunk; }
 
 extern "C" int unetpp_optim_step(int32_t kind, int32_t flags, const unetpp_optim_segment* segments, int32_t n_segments,
                                  const int32_t* chunk_segment, int64_t n_chunks, const double* hyper,
                                  const double* steps, int32_t* done, void* stream) {
-  if (segments == nullptr || n_segments <= 0 || chunk_segment == nullptr || n_chunks <= 0 || hyper == nullptr)
-    return UNETPP_EINVAL;
+  if (!table_args_ok(segments, n_segments, chunk_segment, n_chunks) || hyper == nullptr) return UNETPP_EINVAL;
   if (kind < UNETPP_OPTIM_ADAMW || kind > UNETPP_OPTIM_SGDW) return UNETPP_EINVAL;
   if ((flags & ~(UNETPP_OPTIM_AMS | UNETPP_OPTIM_CAPTURABLE)) != 0) return UNETPP_EINVAL;
   const bool ams = (flags & UNETPP_OPTIM_AMS) != 0, capturable = (flags & UNETPP_OPTIM_CAPTURABLE) != 0;
   if (ams && kind == UNETPP_OPTIM_SGDW) return UNETPP_EINVAL;
   if (capturable ? (done == nullptr || steps != nullptr) : (steps == nullptr || done != nullptr)) return UNETPP_EINVAL;
   const hipStream_t st = static_cast<hipStream_t>(stream);
-  switch (kind * 2 + (ams ? 1 : 0)) {
-    case UNETPP_OPTIM_ADAMW * 2: launch<UNETPP_OPTIM_ADAMW, false>(segments, n_segments, chunk_segment, n_chunks, hyper, steps, done, st); note_kernel("optim_adamw"); break;
-    case UNETPP_OPTIM_ADAMW * 2 + 1: launch<UNETPP_OPTIM_ADAMW, true>(segments, n_segments, chunk_segment, n_chunks, hyper, steps, done, st); note_kernel("optim_adamw_amsgrad"); break;
-    case UNETPP_OPTIM_ADABOUND * 2: launch<UNETPP_OPTIM_ADABOUND, false>(segments, n_segments, chunk_segment, n_chunks, hyper, steps, done, st); note_kernel("optim_adabound"); break;
-    case UNETPP_OPTIM_ADABOUND * 2 + 1: launch<UNETPP_OPTIM_ADABOUND, true>(segments, n_segments, chunk_segment, n_chunks, hyper, steps, done, st); note_kernel("optim_adabound_amsbound"); break;
-    default: launch<UNETPP_OPTIM_SGDW, false>(segments, n_segments, chunk_segment, n_chunks, hyper, steps, done, st); note_kernel("optim_sgdw"); break;
-  }
+  with_variant(kind, ams, [&](auto v) {
+    hipLaunchKernelGGL((optim_kernel<decltype(v)::kind, decltype(v)::ams>), dim3(persistent_grid(n_chunks)),
+                       dim3(kMtThreads), 0, st, segments, n_segments, chunk_segment, n_chunks, hyper, steps, done);
+    note_kernel(v.label);
+  });
   return launch_status();
 }
 
 extern "C" int unetpp_grad_norm(const unetpp_optim_segment* segments, int32_t n_segments, const int32_t* chunk_segment,
                                int64_t n_chunks, double* partials, void* stream) {
-  if (segments == nullptr || n_segments <= 0 || chunk_segment == nullptr || n_chunks <= 0 || partials == nullptr)
-    return UNETPP_EINVAL;
-  hipLaunchKernelGGL(grad_norm_kernel, dim3(persistent_grid(n_chunks)), dim3(kOptThreads), 0,
+  if (!table_args_ok(segments, n_segments, chunk_segment, n_chunks) || partials == nullptr) return UNETPP_EINVAL;
+  hipLaunchKernelGGL(grad_norm_kernel, dim3(persistent_grid(n_chunks)), dim3(kMtThreads), 0,
                      static_cast<hipStream_t>(stream), segments, chunk_segment, n_chunks, partials);
   note_kernel("grad_norm");
   return launch_status();
@@ -382,8 +349,8 @@ extern "C" int unetpp_optim_step_clip(int32_t kind, int32_t flags, const unetpp_
                                       int32_t n_segments, const int32_t* chunk_segment, int64_t n_chunks,
                                       const double* hyper, const double* steps, int32_t* done, const double* partials,
                                       unetpp_clip_state* state, void* stream) {
-  if (segments == nullptr || n_segments <= 0 || chunk_segment == nullptr || n_chunks <= 0 || hyper == nullptr ||
-      partials == nullptr || state == nullptr)
+  if (!table_args_ok(segments, n_segments, chunk_segment, n_chunks) || hyper == nullptr || partials == nullptr ||
+      state == nullptr)
     return UNETPP_EINVAL;
   if (kind < UNETPP_OPTIM_ADAMW || kind > UNETPP_OPTIM_SGDW) return UNETPP_EINVAL;
   if ((flags & ~(UNETPP_OPTIM_AMS | UNETPP_OPTIM_CAPTURABLE | UNETPP_OPTIM_SKIP_NONFINITE)) != 0) return UNETPP_EINVAL;
@@ -393,24 +360,22 @@ extern "C" int unetpp_optim_step_clip(int32_t kind, int32_t flags, const unetpp_
   if (skip && !capturable) return UNETPP_EINVAL;   // an eager caller has advanced its step counts already
   if (capturable ? (done == nullptr || steps != nullptr) : (steps == nullptr || done != nullptr)) return UNETPP_EINVAL;
   const hipStream_t st = static_cast<hipStream_t>(stream);
-  switch (kind * 2 + (ams ? 1 : 0)) {
-    case UNETPP_OPTIM_ADAMW * 2: launch_clip<UNETPP_OPTIM_ADAMW, false>(segments, n_segments, chunk_segment, n_chunks, hyper, steps, done, partials, state, skip, st); note_kernel("optim_clip_adamw"); break;
-    case UNETPP_OPTIM_ADAMW * 2 + 1: launch_clip<UNETPP_OPTIM_ADAMW, true>(segments, n_segments, chunk_segment, n_chunks, hyper, steps, done, partials, state, skip, st); note_kernel("optim_clip_adamw_amsgrad"); break;
-    case UNETPP_OPTIM_ADABOUND * 2: launch_clip<UNETPP_OPTIM_ADABOUND, false>(segments, n_segments, chunk_segment, n_chunks, hyper, steps, done, partials, state, skip, st); note_kernel("optim_clip_adabound"); break;
-    case UNETPP_OPTIM_ADABOUND * 2 + 1: launch_clip<UNETPP_OPTIM_ADABOUND, true>(segments, n_segments, chunk_segment, n_chunks, hyper, steps, done, partials, state, skip, st); note_kernel("optim_clip_adabound_amsbound"); break;
-    default: launch_clip<UNETPP_OPTIM_SGDW, false>(segments, n_segments, chunk_segment, n_chunks, hyper, steps, done, partials, state, skip, st); note_kernel("optim_clip_sgdw"); break;
-  }
+  with_variant(kind, ams, [&](auto v) {
+    hipLaunchKernelGGL((optim_clip_kernel<decltype(v)::kind, decltype(v)::ams>), dim3(persistent_grid(n_chunks)),
+                       dim3(kMtThreads), 0, st, segments, n_segments, chunk_segment, n_chunks, hyper, steps, done,
+                       partials, state, skip);
+    note_kernel(v.clip_label);
+  });
   return launch_status();
 }
 
 extern "C" int unetpp_grad_scale(const unetpp_optim_segment* segments, int32_t n_segments, const int32_t* chunk_segment,
                                 int64_t n_chunks, const double* partials, float max_norm, unetpp_clip_state* state,
                                 void* stream) {
-  if (segments == nullptr || n_segments <= 0 || chunk_segment == nullptr || n_chunks <= 0 || partials == nullptr ||
-      state == nullptr)
+  if (!table_args_ok(segments, n_segments, chunk_segment, n_chunks) || partials == nullptr || state == nullptr)
     return UNETPP_EINVAL;
   if (!(max_norm > 0.f)) return UNETPP_EINVAL;
-  hipLaunchKernelGGL(grad_scale_kernel, dim3(persistent_grid(n_chunks)), dim3(kOptThreads), 0,
+  hipLaunchKernelGGL(grad_scale_kernel, dim3(persistent_grid(n_chunks)), dim3(kMtThreads), 0,
                      static_cast<hipStream_t>(stream), segments, chunk_segment, n_chunks, partials, max_norm, state);
   note_kernel("grad_scale");
   return launch_status();

@@ -12,9 +12,10 @@ reference's in both directions.  Steps are counted per parameter: a parameter wh
 count does not advance.  ``group['lr']`` is read at every step (LR schedulers work unchanged).
 
 What ``step()`` does on the device (csrc/optim.hip, ``unetpp_optim_step``): every parameter with a gradient is a segment
-of one device table, and one launch updates them all, element by element in the reference's op order.  The table is
-built once per set of data pointers (parameters, their CURRENT gradients, state tensors) and cached, so a gradient
-buffer that moves (the data-parallel averager swaps ``p.grad`` between two flat buffers, dp.py) gets its own table.
+of one device table (multi_tensor.py; the format and the chunk walk are described in csrc/multi_tensor.h), and one
+launch updates them all, element by element in the reference's op order.  The table is built once per set of data
+pointers (parameters, their CURRENT gradients, state tensors) and cached, so a gradient buffer that moves (the
+data-parallel averager swaps ``p.grad`` between two flat buffers, dp.py) gets its own table.
 Eager mode: per step one small host -> device copy (the hyper-parameters and each segment's step count) and one
 launch.  The update writes through raw pointers, as the reference writes through ``p.data``: ``p._version`` does not
 move (the weight-image pack plan is rebuilt every pass).
@@ -45,7 +46,6 @@ fp32 CUDA tensors only: anything else raises (this path has no CPU fallback).
 """
 from __future__ import annotations
 
-import collections
 import ctypes as C
 
 import numpy as np
@@ -53,15 +53,7 @@ import torch
 from torch.optim.optimizer import Optimizer, required
 
 from . import _lib
-
-_SEG_BYTES = C.sizeof(_lib.OptimSegment)
-_MAX_TABLES = 8     # cached device tables (the data-parallel averager alternates between two)
-
-
-class _Table:
-    """One cached device table: segments, chunk -> segment map, the arrival counter of capturable launches."""
-    __slots__ = ("dev", "host", "n_seg", "n_chunks", "chunk_off", "done_off", "block", "pinned", "rows_used",
-                 "partials")     # partials: float64 [n_chunks] of the norm pass, made when a clipped step first needs it
+from .multi_tensor import Table, TableCache, aligned16
 
 
 class _FusedOptimizer(Optimizer):
@@ -78,7 +70,7 @@ class _FusedOptimizer(Optimizer):
             raise ValueError("skip_nonfinite=True needs capturable=True: eager mode advances state['step'] on the host "
                              "before the launch, and a skip decided on the device cannot take that back without a sync")
         self._clip_dev = None      # device mirror of unetpp_clip_state: total_norm, coef, skipped_steps, reserved
-        self._tables = collections.OrderedDict()
+        self._tables = TableCache()
         self._state_epoch = 0
         self._hyper_dev = None
         self._spare_host = None
@@ -197,23 +189,17 @@ class _FusedOptimizer(Optimizer):
         key = (self._state_epoch, tuple(ptrs))
         table = self._tables.get(key)
         if table is None:
-            table = self._build_table(rows)
-            self._tables[key] = table
-            while len(self._tables) > _MAX_TABLES:
-                old = next(k for k, v in self._tables.items() if not v.pinned)   # captured tables stay alive
-                del self._tables[old]
+            table = self._tables.add(key, self._build_table(rows))
         else:
             self._tables.move_to_end(key)
         L = _lib.lib()
         stream = C.c_void_p(torch.cuda.current_stream(table.dev.device).cuda_stream)
-        base = table.dev.data_ptr()
         if capturable:
             if not torch.cuda.is_current_stream_capturing():
                 self.refresh_hyperparameters()
             elif self._hyper_dev is None:
                 raise RuntimeError("capturable %s: run one eager step() before capturing it" % type(self).__name__)
-            args = (C.c_void_p(base), table.n_seg, C.c_void_p(base + table.chunk_off), table.n_chunks,
-                    C.c_void_p(self._hyper_dev.data_ptr()), None, C.c_void_p(base + table.done_off))
+            args = table.args + (C.c_void_p(self._hyper_dev.data_ptr()), None, table.done)
             flags = self._flags() | _lib.OPTIM_CAPTURABLE
         else:
             h = self._hyper()
@@ -225,8 +211,7 @@ class _FusedOptimizer(Optimizer):
             arr[h.size:] = steps
             table.block.copy_(host, non_blocking=True)
             blk = table.block.data_ptr()
-            args = (C.c_void_p(base), table.n_seg, C.c_void_p(base + table.chunk_off), table.n_chunks, C.c_void_p(blk),
-                    C.c_void_p(blk + 8 * h.size), None)
+            args = table.args + (C.c_void_p(blk), C.c_void_p(blk + 8 * h.size), None)
             flags = self._flags()
         if self._max_grad_norm is None and not self.skip_nonfinite:
             _lib.check(L.unetpp_optim_step(self._KIND, flags, *args, stream), "unetpp_optim_step")
@@ -236,7 +221,7 @@ class _FusedOptimizer(Optimizer):
         if table.partials is None:
             table.partials = torch.empty(table.n_chunks, dtype=torch.float64, device=table.dev.device)
         partials = C.c_void_p(table.partials.data_ptr())
-        _lib.check(L.unetpp_grad_norm(args[0], args[1], args[2], args[3], partials, stream), "unetpp_grad_norm")
+        _lib.check(L.unetpp_grad_norm(*table.args, partials, stream), "unetpp_grad_norm")
         if self.skip_nonfinite:
             flags |= _lib.OPTIM_SKIP_NONFINITE
         _lib.check(L.unetpp_optim_step_clip(self._KIND, flags, *args, partials, C.c_void_p(state.data_ptr()), stream),
@@ -250,11 +235,12 @@ class _FusedOptimizer(Optimizer):
         """Creates missing state and advances the count of this parameter; returns the eager count of this update."""
         raise NotImplementedError
 
-    def _build_table(self, rows) -> _Table:
+    def _build_table(self, rows) -> Table:
+        """The table of this set of tensors, with what a step needs beside it: block (eager: the device block of the
+        hyper-parameters and step counts), rows_used (the rows that have a segment, when some have no elements) and
+        partials (float64 [n_chunks] of the norm pass, made when a clipped step first needs it)."""
         from .ops import _need
-        L = _lib.lib()
-        chunk = int(L.unetpp_optim_chunk_elems())
-        segs, chunk_seg, used = [], [], []
+        segs, used = [], []
         for i, (p, g, state, gi) in enumerate(rows):
             _need(p, "%s parameter" % type(self).__name__)
             _need(g, "%s gradient" % type(self).__name__)
@@ -281,44 +267,32 @@ class _FusedOptimizer(Optimizer):
             for t in tensors:
                 if t.numel() != n or t.device != p.device:
                     raise ValueError("optimizer state does not match its parameter's shape or device")
-            s.numel, s.chunk_begin, s.group = n, len(chunk_seg), gi
-            s.vec = int(all(t.data_ptr() % 16 == 0 for t in tensors))
-            chunk_seg += [len(segs)] * ((n + chunk - 1) // chunk)
+            s.numel, s.group, s.vec = n, gi, aligned16(*tensors)
             segs.append(s)
             used.append(i)
         if not segs:
             raise ValueError("no parameter with elements to update")
-        n_seg, n_chunks = len(segs), len(chunk_seg)
-        chunk_off = n_seg * _SEG_BYTES
-        done_off = chunk_off + 4 * n_chunks
-        nbytes = done_off + 8
         dev = rows[0][0].device
-        capturing = torch.cuda.is_current_stream_capturing()
-        if capturing:
-            # no page-locked allocation inside a capture: the staging buffer reserved by the last eager build is used
-            # (the captured copy reads it at every replay: it stays with the table, unchanged, as long as the optimizer)
-            host = self._spare_host
-            if host is None or host.numel() < nbytes:
-                raise RuntimeError("capturable %s: run one eager step() before capturing it" % type(self).__name__)
-            self._spare_host = None
-        else:
-            host = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
-            self._spare_host = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
-        arr = host.numpy()
-        C.memmove(host.data_ptr(), (_lib.OptimSegment * n_seg)(*segs), chunk_off)
-        arr[chunk_off:done_off] = np.asarray(chunk_seg, dtype=np.int32).view(np.uint8)
-        arr[done_off:nbytes] = 0
-        t = _Table()
-        t.dev = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        t.host, t.n_seg, t.n_chunks, t.chunk_off, t.done_off = host, n_seg, n_chunks, chunk_off, done_off
-        t.pinned = capturing
+        t = Table(segs, dev, True, self._staging)
+        t.pinned = torch.cuda.is_current_stream_capturing()
         t.partials = None
         t.rows_used = None if len(used) == len(rows) else used
         t.block = None if self.capturable else torch.empty(len(self.param_groups) * _lib.OPTIM_HYPER + len(used),
                                                           dtype=torch.float64, device=dev)
-        _lib.check(L.unetpp_optim_upload(C.c_void_p(t.dev.data_ptr()), C.c_void_p(host.data_ptr()), nbytes,
-                                         C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "unetpp_optim_upload")
         return t
+
+    def _staging(self, nbytes: int) -> torch.Tensor:
+        """The page-locked staging buffer of a new table.  No page-locked allocation inside a capture: the buffer that
+        the last eager build reserved is used (the captured copy reads it at every replay: it stays with the table,
+        unchanged, as long as the optimizer)."""
+        if torch.cuda.is_current_stream_capturing():
+            host = self._spare_host
+            if host is None or host.numel() < nbytes:
+                raise RuntimeError("capturable %s: run one eager step() before capturing it" % type(self).__name__)
+            self._spare_host = None
+            return host
+        self._spare_host = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+        return torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
 
     def _aux(self, state, group):
         return None
@@ -459,44 +433,25 @@ class SGDW(_FusedOptimizer):
 
 
 # ---- stand-alone clipping -------------------------------------------------------------------------------------------
-_CLIP_TABLES = collections.OrderedDict()     # (device index, gradient data pointers and sizes) -> _Table
+_CLIP_TABLES = TableCache()     # (device index, gradient data pointers and sizes) -> Table
 
 
-def _clip_table(grads) -> _Table:
-    """The cached device table of a set of gradients: segments with grad / numel / chunk_begin / vec only."""
+def _clip_table(grads) -> Table:
+    """The cached device table of a set of gradients: segments with grad / numel / vec only, no arrival counter."""
     dev = grads[0].device
     key = (dev.index, tuple((g.data_ptr(), g.numel()) for g in grads))
     t = _CLIP_TABLES.get(key)
     if t is not None:
         _CLIP_TABLES.move_to_end(key)
         return t
-    L = _lib.lib()
-    chunk = int(L.unetpp_optim_chunk_elems())
-    segs, n_chunks_of = [], []
-    n_chunks = 0
+    segs = []
     for g in grads:
         s = _lib.OptimSegment()
-        s.grad, s.numel, s.chunk_begin, s.group = g.data_ptr(), g.numel(), n_chunks, 0
-        s.vec = int(g.data_ptr() % 16 == 0)
+        s.grad, s.numel, s.group, s.vec = g.data_ptr(), g.numel(), 0, aligned16(g)
         segs.append(s)
-        n_chunks_of.append((g.numel() + chunk - 1) // chunk)
-        n_chunks += n_chunks_of[-1]
-    n_seg = len(segs)
-    chunk_off = n_seg * _SEG_BYTES
-    nbytes = chunk_off + 4 * n_chunks
-    host = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
-    C.memmove(host.data_ptr(), (_lib.OptimSegment * n_seg)(*segs), chunk_off)
-    host.numpy()[chunk_off:] = np.repeat(np.arange(n_seg, dtype=np.int32), n_chunks_of).view(np.uint8)
-    t = _Table()
-    t.dev = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    t.host, t.n_seg, t.n_chunks, t.chunk_off = host, n_seg, n_chunks, chunk_off
-    t.partials = torch.empty(n_chunks, dtype=torch.float64, device=dev)
-    _lib.check(L.unetpp_optim_upload(C.c_void_p(t.dev.data_ptr()), C.c_void_p(host.data_ptr()), nbytes,
-                                     C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "unetpp_optim_upload")
-    _CLIP_TABLES[key] = t
-    while len(_CLIP_TABLES) > _MAX_TABLES:
-        _CLIP_TABLES.popitem(last=False)
-    return t
+    t = Table(segs, dev, False)
+    t.partials = torch.empty(t.n_chunks, dtype=torch.float64, device=dev)
+    return _CLIP_TABLES.add(key, t)
 
 
 @torch.no_grad()
@@ -527,9 +482,7 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=Fals
     L = _lib.lib()
     state = torch.empty(4, dtype=torch.float32, device=dev)      # this call's own: the returned norm is not overwritten
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    base = table.dev.data_ptr()
-    args = (C.c_void_p(base), table.n_seg, C.c_void_p(base + table.chunk_off), table.n_chunks,
-            C.c_void_p(table.partials.data_ptr()))
+    args = table.args + (C.c_void_p(table.partials.data_ptr()),)
     _lib.check(L.unetpp_grad_norm(*args, stream), "unetpp_grad_norm")
     if error_if_nonfinite:
         total = torch.sqrt(table.partials.sum())
