@@ -496,6 +496,35 @@ def test_pointwise_wgrad_direct_kernel(dev, case):
     assert (db - db2).abs().max().item() <= 2e-5 * bias.grad.abs().max().item()
 
 
+@pytest.mark.parametrize("form", ["folded", "gated"])
+def test_conv1x1_wgrad_folded_and_gated_views(dev, form):
+    """The two pointwise weight-gradient kernels behind the LDS-DMA one: a folded x view takes wgrad_fast_kernel<1>, a
+    ReLU gate on dy the generic wgrad_kernel<1> (exact per-element cases: tests/test_gpu_wgrad_exact.py)."""
+    from unet_nested4tiny_objects_keypoints_amd import _lib, ops
+    from unet_nested4tiny_objects_keypoints_amd.ops import V
+    b, h, w, ci, co = 2, 8, 12, 8, 8
+    g = torch.Generator().manual_seed(19)
+    y1 = torch.randn(b, ci, h, w, generator=g, dtype=torch.float64)
+    scale, shift = torch.randn(ci, generator=g, dtype=torch.float64), torch.randn(ci, generator=g, dtype=torch.float64)
+    act = torch.randn(b, co, h, w, generator=g, dtype=torch.float64)
+    dy = torch.randn(b, co, h, w, generator=g, dtype=torch.float64)
+    wt = torch.randn(co, ci, 1, 1, generator=g, dtype=torch.float64, requires_grad=True)
+    bias = torch.zeros(co, dtype=torch.float64, requires_grad=True)
+    if form == "folded":
+        F.conv2d(F.relu(y1 * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1)), wt, bias).backward(dy)
+        xv, dv = V(nhwc(y1.float()), scale=scale.float().cuda(), shift=shift.float().cuda(), relu=True), V(nhwc(dy.float()))
+    else:
+        F.conv2d(y1, wt, bias).backward(dy * (act > 0))
+        xv, dv = V(nhwc(y1.float())), V(nhwc(dy.float()), gate=nhwc(act.float()))
+    dw = torch.full((co, ci, 1, 1), float("nan"), device=dev)
+    db = torch.full((co,), float("nan"), device=dev)
+    plan = ops.wgrad(b, h, w, 1, [xv], [dv], dw, (0, 1, ci, 0), db)
+    name = _lib.lib().unetpp_last_kernel_name().decode()
+    assert plan.kernel.decode() == name == ("wgrad_fast_kernel<1>" if form == "folded" else "wgrad_kernel<1>")
+    assert rel_err(dw.cpu(), wt.grad.float()) < TOL
+    assert rel_err(db.cpu(), bias.grad.float()) < TOL
+
+
 @pytest.mark.parametrize("shape", [(2, 16, 16, [8], 8), (1, 32, 32, [32, 32, 32], 32), (2, 24, 40, [3], 4),
                                    (1, 8, 8, [40, 5], 33), (3, 64, 64, [16], 16), (2, 32, 64, [1], 32),
                                    (1, 24, 40, [3], 8)])
