@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define UNETPP_ABI_VERSION 12
+#define UNETPP_ABI_VERSION 13
 #define UNETPP_MAX_VIEWS 8
 
 #define UNETPP_OK 0
@@ -177,6 +177,26 @@ int32_t unetpp_usable_cus(int32_t* physical);
 int64_t unetpp_gemm_pixel_blocks(int32_t N, int32_t H, int32_t W);
 /* rows of [Ncols][2] floats stats_partial must hold when the finalize is fused (d->bn.scale != NULL) */
 int64_t unetpp_gemm_stats_rows(int32_t N, int32_t H, int32_t W);
+/* What a forward / input-gradient GEMM launch needs settled before it runs (v13).  The library looks at the descriptor
+ * once and decides which of its kernels takes it; the size of the weight image, the grid, the rows of an attached
+ * BatchNorm finalize and the label all follow from that one decision, and unetpp_gemm_fwd launches the same kernel for the
+ * same descriptor on a device with that many usable CUs. */
+typedef struct unetpp_gemm_sizes {
+  int64_t image_floats;   /* what d->weight_image must hold for this descriptor; 0: no image kernel applies */
+  int64_t bn_rows;        /* rows the attached finalize reads; 0: one per 256-pixel block */
+  int32_t workgroups, threads; /* grid and workgroup size of the (first) launch */
+  const char* kernel;     /* label unetpp_last_kernel_name() reports after unetpp_gemm_fwd(d) (static string) */
+} unetpp_gemm_sizes;
+/* Everything in the descriptor, pointers included (their alignment selects kernels), must be what unetpp_gemm_fwd will
+ * get, with ONE exception: only whether d->weight_image is NULL counts, not where it points -- NULL plans the kernels
+ * that read d->weight (first layer, generic), anything else the image kernels, so a caller that has not allocated the
+ * image yet passes any non-NULL value and allocates image_floats.  image_floats itself does not depend on
+ * d->weight_image (it is unetpp_gemm_weight_image_floats(d)).  cus = usable CUs to plan for (the 8-wave LDS-DMA form
+ * and every persistent grid depend on it), <= 0: those of the current device (unetpp_usable_cus).  Touches no device
+ * memory and launches nothing.  UNETPP_EINVAL for a NULL argument or a descriptor unetpp_gemm_fwd would refuse (a bf16
+ * descriptor without an image that is not a first layer; an image on a descriptor no image kernel can read; ...);
+ * UNETPP_ELAUNCH when cus <= 0 and there is no device to ask. */
+int unetpp_gemm_plan(const unetpp_gemm_desc* d, int32_t cus, unetpp_gemm_sizes* out);
 int unetpp_gemm_fwd(const unetpp_gemm_desc* d, void* stream);
 /* Fast path (register-prefetched LDS-image kernels; Winograd F(2x2,3x3) for taps = 9 unless UNETPP_GEMM_DIRECT):
  * applies when every input view is a 16-byte aligned slice without a ReLU gate on load (C, c_off and c_len

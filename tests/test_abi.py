@@ -41,7 +41,7 @@ def test_exported_symbols_are_plain_c(built_lib):
     out = subprocess.run(["nm", "-D", "--defined-only", built_lib.LIB_PATH], capture_output=True, text=True).stdout
     exported = {ln.split()[-1] for ln in out.splitlines() if " T " in ln}
     assert set(_declared_functions()) <= exported
-    assert built_lib.lib().unetpp_abi_version() == built_lib.ABI_VERSION == 12
+    assert built_lib.lib().unetpp_abi_version() == built_lib.ABI_VERSION == 13
     assert built_lib.lib().unetpp_build_arch() == b"gfx950"
 
 
@@ -49,14 +49,15 @@ def test_struct_layout_matches_header(built_lib, tmp_path):
     """sizeof/offsetof from a C compile of the header vs the ctypes mirrors."""
     src = tmp_path / "layout.c"
     src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "unetpp_hip.h"\nint main(void){'
-                   'printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(unetpp_view), offsetof(unetpp_view, gate),'
+                   'printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(unetpp_view), offsetof(unetpp_view, gate),'
                    'offsetof(unetpp_view, gate_sum), sizeof(unetpp_gemm_desc), offsetof(unetpp_gemm_desc, out),'
                    'offsetof(unetpp_gemm_desc, weight_image), sizeof(unetpp_wgrad_desc), offsetof(unetpp_wgrad_desc, dy),'
                    'offsetof(unetpp_wgrad_desc, slabs), sizeof(unetpp_weight_src), offsetof(unetpp_weight_src, k_inner),'
                    'sizeof(unetpp_pack_job), offsetof(unetpp_pack_job, image), offsetof(unetpp_pack_job, out_len),'
                    'sizeof(unetpp_bn_fused), offsetof(unetpp_bn_fused, count), offsetof(unetpp_bn_fused, momentum),'
                    'offsetof(unetpp_gemm_desc, bn), sizeof(unetpp_wgrad_sizes), offsetof(unetpp_wgrad_sizes, slab_floats),'
-                   'offsetof(unetpp_wgrad_sizes, kernel));return 0;}')
+                   'offsetof(unetpp_wgrad_sizes, kernel), sizeof(unetpp_gemm_sizes), offsetof(unetpp_gemm_sizes, bn_rows),'
+                   'offsetof(unetpp_gemm_sizes, threads), offsetof(unetpp_gemm_sizes, kernel));return 0;}')
     exe = tmp_path / "layout"
     subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
     got = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
@@ -66,7 +67,8 @@ def test_struct_layout_matches_header(built_lib, tmp_path):
             L.WgradDesc.slabs.offset, ctypes.sizeof(L.WeightSrc), L.WeightSrc.k_inner.offset, ctypes.sizeof(L.PackJob),
             L.PackJob.image.offset, L.PackJob.out_len.offset, ctypes.sizeof(L.BnFused), L.BnFused.count.offset,
             L.BnFused.momentum.offset, L.GemmDesc.bn.offset, ctypes.sizeof(L.WgradSizes), L.WgradSizes.slab_floats.offset,
-            L.WgradSizes.kernel.offset]
+            L.WgradSizes.kernel.offset, ctypes.sizeof(L.GemmSizes), L.GemmSizes.bn_rows.offset, L.GemmSizes.threads.offset,
+            L.GemmSizes.kernel.offset]
     assert got == want
 
 
@@ -106,6 +108,7 @@ def test_argument_validation_without_gpu(built_lib):
     assert lib.unetpp_gemm_weight_image_floats(ctypes.byref(d)) == 0
     d.N, d.H, d.W, d.taps, d.n_in, d.n_out = 1, 8, 8, 5, 1, 1
     assert lib.unetpp_gemm_fwd(ctypes.byref(d), None) == -1          # taps must be 1 or 9
+    assert lib.unetpp_gemm_plan(ctypes.byref(d), 256, ctypes.byref(built_lib.GemmSizes())) == -1   # (tests/test_gemm_plan.py)
     w = built_lib.WgradDesc()
     assert lib.unetpp_wgrad(ctypes.byref(w), None) == -1
     assert lib.unetpp_pack_weight(None, None, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0, None) == -1

@@ -20,7 +20,7 @@ SOURCES = ("gemm_pix.hip", "gemm_fast.hip", "gemm_pw.hip", "gemm_pw_bf16.hip", "
 HEADERS = ("common.h", "gemm_units.h", "wgrad_reduce.h", "lds_asm.h", "bf16_common.h", "dropout.h", "bn_fused.h",
            "wino_experiments.h", "dma_experiments.h", "heads_mean.h", "focal_element.h", "multi_tensor.h")
 MAX_VIEWS = 8
-ABI_VERSION = 12
+ABI_VERSION = 13
 # packed-f32 VALU (SLP-vectorised add pairs) costs issue slots beside MFMAs: keep the Winograd transforms scalar
 EXTRA_FLAGS = {"gemm_wino.hip": ("-fno-slp-vectorize",), "wgrad_wino.hip": ("-fno-slp-vectorize",)}
 GEMM_DIRECT = 1  # unetpp_gemm_desc.flags: direct summation only (no Winograd)
@@ -129,6 +129,15 @@ class WgradSizes(C.Structure):
     ]
 
 
+class GemmSizes(C.Structure):
+    """mirror of struct unetpp_gemm_sizes"""
+    _fields_ = [
+        ("image_floats", C.c_int64), ("bn_rows", C.c_int64),
+        ("workgroups", C.c_int32), ("threads", C.c_int32),
+        ("kernel", C.c_char_p),
+    ]
+
+
 class OptimSegment(C.Structure):
     """mirror of struct unetpp_optim_segment"""
     _fields_ = [
@@ -195,6 +204,7 @@ SIGNATURES = {
     "unetpp_usable_cus": (_I32, [C.POINTER(C.c_int32)]),
     "unetpp_gemm_pixel_blocks": (_I64, [_I32, _I32, _I32]),
     "unetpp_gemm_stats_rows": (_I64, [_I32, _I32, _I32]),
+    "unetpp_gemm_plan": (C.c_int, [C.POINTER(GemmDesc), _I32, C.POINTER(GemmSizes)]),
     "unetpp_gemm_fwd": (C.c_int, [C.POINTER(GemmDesc), _P]),
     "unetpp_gemm_weight_image_floats": (_I64, [C.POINTER(GemmDesc)]),
     "unetpp_gemm_pack_weight_image": (C.c_int, [C.POINTER(GemmDesc), _P, _P]),

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+
 #include "unetpp_hip.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -116,6 +118,19 @@ __device__ __forceinline__ f32x4 view_load4(const unetpp_view& v, long off, int 
 
 inline int launch_status() { return hipGetLastError() == hipSuccess ? UNETPP_OK : UNETPP_ELAUNCH; }
 
+// Dynamic LDS above 64 KB has to be allowed once per kernel function and device.  A launcher calls this immediately
+// before its launch with flags of its own (one static array per kernel instantiation, zero-initialised); false: the
+// device cannot be told or the runtime refuses.
+constexpr int kMaxDevices = 64;
+inline bool allow_dynamic_lds(const void* func, int bytes, std::atomic<bool> (&raised)[kMaxDevices]) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return false;
+  if (raised[dev].load(std::memory_order_acquire)) return true;
+  if (hipFuncSetAttribute(func, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return false;
+  raised[dev].store(true, std::memory_order_release);
+  return true;
+}
+
 // CUs of the current device, queried once per device (every persistent-grid launcher sizes its grid from it: ~100
 // launches per step); 0 when the runtime cannot tell
 int reserved_cus();  // unetpp_set_reserved_cus (gemm_pix.hip): CUs the persistent grids leave to a concurrent collective
@@ -165,22 +180,41 @@ enum Opt {
 bool opt_is_set(Opt o);
 long opt_value(Opt o, long dflt);   // dflt when unset
 
-// gemm_fast.hip: register-prefetched kernel for plain aligned views (needs d->weight_image)
-int launch_gemm_fast(const unetpp_gemm_desc* d, hipStream_t st);
-// gemm_pw.hip: fp32 pointwise GEMM with the weights resident in LDS and the activations loaded straight into the MFMA
-// operand registers (fa = the descriptor's fast_args); returns 1 when the descriptor is not one it takes
-int launch_gemm_pw(const unetpp_gemm_desc* d, const struct FastArgs& fa, hipStream_t st);
-// gemm_pw_bf16.hip: the bf16-storage twin of gemm_pw.hip (fa = bf16_gemm_args of the descriptor)
-int launch_gemm_pw_bf16(const unetpp_gemm_desc* d, const struct FastArgs& fa, hipStream_t st);
-// gemm_wino.hip: Winograd F(2x2,3x3) kernel for taps == 9 without UNETPP_GEMM_DIRECT (needs its own weight image)
+// ---- forward / input-gradient GEMM: gemm_select (gemm_pix.hip) decides ONCE, from the descriptor and a CU count, which
+// kernel takes it and what follows from that (GemmSel, gemm_units.h); unetpp_gemm_plan reports the decision,
+// unetpp_gemm_fwd launches what it says.  Each kernel file exports what only it knows -- `bool ..._applies(d, s)`:
+// EVERY reason its kernel cannot take a descriptor that reached it in gemm_select's order, and, when it can, its part of
+// s (kernel, label, grid, ...); `..._plan(d, s)` where the kernel takes whatever reaches it -- and a launcher that
+// fills its argument struct from s and launches (UNETPP_OK or UNETPP_ELAUNCH).
+struct FastArgs;
+struct GemmSel;
+int gemm_select(const unetpp_gemm_desc* d, int cus, GemmSel& s);  // UNETPP_OK, UNETPP_EINVAL, UNETPP_ELAUNCH (cus <= 0)
+// the weight image of d's fast kernels (s.image_*, s.fa), whether or not d->weight_image is set; false: none applies
+bool gemm_image_of(const unetpp_gemm_desc* d, GemmSel& s);
+// first_layer.hip: VALU kernel for the forward of the 1..4-channel first convolution (reads d->weight, no image)
+bool small_cin_fwd_applies(const unetpp_gemm_desc* d);
+void small_cin_fwd_plan(const unetpp_gemm_desc* d, GemmSel& s);
+int launch_small_cin_fwd(const unetpp_gemm_desc* d, const GemmSel& s, hipStream_t st);
+// gemm_pw_bf16.hip: bf16 pointwise GEMM, weights resident in LDS, activations loaded straight into the MFMA operands
+bool gemm_pw_bf16_applies(const unetpp_gemm_desc* d, GemmSel& s);
+int launch_gemm_pw_bf16(const unetpp_gemm_desc* d, const GemmSel& s, hipStream_t st);
+// gemm_bf16_dma.hip: bf16 GEMM with both operands staged by LDS-DMA (plain input views, 32-channel slices), 8- or 4-wave
+bool gemm_bf16_dma_applies(const unetpp_gemm_desc* d, GemmSel& s);
+int launch_gemm_bf16_dma(const unetpp_gemm_desc* d, const GemmSel& s, hipStream_t st);
+// gemm_bf16.hip: bf16-storage direct implicit GEMM (UNETPP_GEMM_BF16), register staging; bf16_gemm_args = its fast_args
+bool bf16_gemm_args(const unetpp_gemm_desc* d, FastArgs& a);
+void gemm_bf16_plan(const unetpp_gemm_desc* d, GemmSel& s);
+int launch_gemm_bf16(const unetpp_gemm_desc* d, const GemmSel& s, hipStream_t st);
+// gemm_wino.hip: Winograd F(2x2,3x3) kernel for fp32, taps == 9 without UNETPP_GEMM_DIRECT (its own weight image)
 bool wino_applies(const unetpp_gemm_desc* d);
-int launch_gemm_wino(const unetpp_gemm_desc* d, hipStream_t st, long* bn_rows);  // *bn_rows = rows of BatchNorm sums written, when per workgroup
-// gemm_bf16.hip: bf16-storage direct implicit GEMM (UNETPP_GEMM_BF16); needs its own weight image
-bool bf16_gemm_args(const unetpp_gemm_desc* d, struct FastArgs& a);
-int launch_gemm_bf16(const unetpp_gemm_desc* d, hipStream_t st);
-// gemm_bf16_dma.hip: the same GEMM with both operands staged by LDS-DMA (plain input views, 32-channel slices); returns 1
-// when the descriptor is not one it takes (same weight image as gemm_bf16.hip)
-int launch_gemm_bf16_dma(const unetpp_gemm_desc* d, hipStream_t st);
+void gemm_wino_plan(const unetpp_gemm_desc* d, GemmSel& s);
+int launch_gemm_wino(const unetpp_gemm_desc* d, const GemmSel& s, hipStream_t st);
+// gemm_pw.hip: fp32 pointwise GEMM, weights resident in LDS, activations loaded straight into the MFMA operands
+bool gemm_pw_applies(const unetpp_gemm_desc* d, GemmSel& s);
+int launch_gemm_pw(const unetpp_gemm_desc* d, const GemmSel& s, hipStream_t st);
+// gemm_fast.hip: register-prefetched direct kernel for plain aligned fp32 views
+void gemm_fast_plan(const unetpp_gemm_desc* d, GemmSel& s);
+int launch_gemm_fast(const unetpp_gemm_desc* d, const GemmSel& s, hipStream_t st);
 // ---- weight gradient: wgrad_select (wgrad.hip) decides ONCE, from the descriptor alone, which kernel takes it and what
 // follows from that; unetpp_wgrad_plan sizes n_split and the slabs from it, unetpp_wgrad launches what it says.
 enum WgradKernel {  // in the order of precedence
@@ -220,7 +254,5 @@ int launch_wgrad_dma(const unetpp_wgrad_desc* d, const WgradSel& s, hipStream_t 
 // wgrad_fast.hip: 8-wave double-buffered direct sum for aligned views (x may carry the folded BatchNorm)
 bool wgrad_fast_applies(const unetpp_wgrad_desc* d);
 int launch_wgrad_fast(const unetpp_wgrad_desc* d, const WgradSel& s, hipStream_t st);
-// first_layer.hip: VALU kernel for the forward of the 1..4-channel first convolution; returns 1 when it does not apply
-int launch_small_cin_fwd(const unetpp_gemm_desc* d, hipStream_t st, long* bn_rows);
 
 }  // namespace unetpp

@@ -10,6 +10,7 @@
 #include "bf16_common.h"
 #include "bn_fused.h"
 #include "common.h"
+#include "gemm_units.h"
 #include "lds_asm.h"
 
 namespace unetpp {
@@ -372,19 +373,41 @@ void fill_geom(SmallArgs& a, int N, int H, int W) {
 
 }  // namespace
 
-// 3x3 forward for <= 4 input channels.  Returns 1 when the descriptor does not fit this path.
-int launch_small_cin_fwd(const unetpp_gemm_desc* d, hipStream_t st, long* bn_rows) {
-  if (d->taps != 9 || d->n_in != 1 || d->n_out != 1) return 1;
+// 3x3 forward for <= 4 input channels: one plain x view that is its whole tensor, one plain output view, packed weights
+bool small_cin_fwd_applies(const unetpp_gemm_desc* d) {
+  if (d->taps != 9 || d->n_in != 1 || d->n_out != 1) return false;
   const unetpp_view& X = d->in[0];
   const unetpp_view& Y = d->out[0];
-  if (!small_shape_ok(X, Y, d->H, d->W) || Y.gate != nullptr || Y.accumulate) return 1;
-  if (d->bias != nullptr && (reinterpret_cast<uintptr_t>(d->bias) & 15)) return 1;
+  if (!small_shape_ok(X, Y, d->H, d->W) || Y.gate != nullptr || Y.accumulate) return false;
+  if (d->bias != nullptr && (reinterpret_cast<uintptr_t>(d->bias) & 15)) return false;
   SmallArgs a = {};
   fill_geom(a, d->N, d->H, d->W);
-  if (a.n_patches > 0x7fffffffL) return 1;
-  if ((16L * d->W + 64) * Y.C * 4 > 0x7fffffffL) return 1;  // 32-bit offsets inside a patch (at most 16 rows)
+  if (a.n_patches > 0x7fffffffL) return false;
+  if ((16L * d->W + 64) * Y.C * 4 > 0x7fffffffL) return false;  // 32-bit offsets inside a patch (at most 16 rows)
+  return d->weight != nullptr;
+}
+
+void small_cin_fwd_plan(const unetpp_gemm_desc* d, GemmSel& s) {
+  s.kernel = GEMM_SMALL_CIN;
+  s.label = "small_cin_fwd_kernel";
+  SmallArgs a = {};
+  fill_geom(a, d->N, d->H, d->W);
+  // persistent grid: as many workgroups as are resident at once (<= 128 registers up to three input channels, 156
+  // with four: four / three one-wave-per-SIMD workgroups per CU)
+  long workers = static_cast<long>(s.cus) * (d->in[0].C >= 3 ? 3 : 4);   // = the kernel's launch bounds
+  if (workers > kBnFusedRows) workers = kBnFusedRows;
+  s.grid_x = static_cast<unsigned>(a.n_patches < workers ? a.n_patches : workers);
+  s.grid_y = 1;
+  s.fa.bn_in_kernel = bn_rows_per_workgroup(d, d->out[0].c_len) ? 1 : 0;
+  s.bn_rows = s.fa.bn_in_kernel ? s.grid_x : 0;
+}
+
+int launch_small_cin_fwd(const unetpp_gemm_desc* d, const GemmSel& s, hipStream_t st) {
+  const unetpp_view& X = d->in[0];
+  const unetpp_view& Y = d->out[0];
+  SmallArgs a = {};
+  fill_geom(a, d->N, d->H, d->W);
   const bool bf = (d->flags & UNETPP_GEMM_BF16) != 0;
-  if (d->weight == nullptr) return 1;
   a.x = X.ptr;
   a.w = d->weight;
   a.bias = d->bias;
@@ -393,14 +416,8 @@ int launch_small_cin_fwd(const unetpp_gemm_desc* d, hipStream_t st, long* bn_row
   a.COUT = Y.c_len;
   a.yC = Y.C;
   a.relu = Y.relu;
-  const int cus = device_cu_count();
-  if (cus <= 0) return UNETPP_ELAUNCH;
-  // persistent grid: as many workgroups as are resident at once (<= 128 registers up to three input channels, 156
-  // with four: four / three one-wave-per-SIMD workgroups per CU)
-  long workers = static_cast<long>(cus) * (X.C >= 3 ? 3 : 4);   // = the kernel's launch bounds
-  if (workers > kBnFusedRows) workers = kBnFusedRows;
-  const dim3 grid(static_cast<unsigned>(a.n_patches < workers ? a.n_patches : workers)), block(kThreads);
-  a.bn_in_kernel = bn_rows_per_workgroup(d, a.COUT) ? 1 : 0;
+  a.bn_in_kernel = s.fa.bn_in_kernel;
+  const dim3 grid(s.grid_x), block(kThreads);
 #define UNETPP_SMALL_FWD(B)                                                                          \
   switch (X.C) {                                                                                     \
     case 1: hipLaunchKernelGGL((small_cin_fwd_kernel<1, B>), grid, block, 0, st, a); break;          \
@@ -414,8 +431,6 @@ int launch_small_cin_fwd(const unetpp_gemm_desc* d, hipStream_t st, long* bn_row
     UNETPP_SMALL_FWD(false)
   }
 #undef UNETPP_SMALL_FWD
-  note_kernel("small_cin_fwd_kernel");
-  if (a.bn_in_kernel && bn_rows != nullptr) *bn_rows = grid.x;
   return launch_status();
 }
 

@@ -571,17 +571,20 @@ bool bf16_gemm_args(const unetpp_gemm_desc* d, FastArgs& a) {
   return true;
 }
 
-int launch_gemm_bf16(const unetpp_gemm_desc* d, hipStream_t st) {
-  FastArgs a;
-  if (!bf16_gemm_args(d, a) || d->weight_image == nullptr) return UNETPP_EINVAL;
-  if (d->stats_partial != nullptr && d->n_out != 1) return UNETPP_EINVAL;
-  const int cus = device_cu_count();
-  if (cus <= 0) return UNETPP_ELAUNCH;
+// takes every descriptor with a bf16 image (gemm_image_of: s.fa is bf16_gemm_args)
+void gemm_bf16_plan(const unetpp_gemm_desc* d, GemmSel& s) {
+  s.kernel = GEMM_BF16;
+  s.label = d->taps == 9 ? "gemm_bf16_kernel<9>" : "gemm_bf16_kernel<1>";
   // = the kernels' launch bounds (four workgroups per CU for the pointwise GEMMs: 128 VGPRs, spills, 2x slower)
-  long workers = (static_cast<long>(UNETPP_BF16_WGS(d->taps, a.nt_unit)) * cus) & ~7L;
-  if (d->stats_partial != nullptr) workers = (static_cast<long>(UNETPP_BF16_STATS_WGS) * cus) & ~7L;
+  long workers = (static_cast<long>(UNETPP_BF16_WGS(d->taps, s.fa.nt_unit)) * s.cus) & ~7L;
+  if (d->stats_partial != nullptr) workers = (static_cast<long>(UNETPP_BF16_STATS_WGS) * s.cus) & ~7L;
   if (workers < 8) workers = 8;
-  const dim3 grid(static_cast<unsigned>(a.total_blocks <= workers ? a.total_blocks : workers)), block(kThreads);
+  s.grid_x = static_cast<unsigned>(s.fa.total_blocks <= workers ? s.fa.total_blocks : workers);
+}
+
+int launch_gemm_bf16(const unetpp_gemm_desc* d, const GemmSel& s, hipStream_t st) {
+  const FastArgs& a = s.fa;
+  const dim3 grid(s.grid_x), block(kThreads);
 #define UNETPP_LAUNCH_BF16(T, NTU, ST)                                                                    \
   do {                                                                                                    \
     if (a.log2tw == 5) hipLaunchKernelGGL((gemm_bf16_kernel<T, 5, NTU, ST>), grid, block, 0, st, a);      \
@@ -596,7 +599,6 @@ int launch_gemm_bf16(const unetpp_gemm_desc* d, hipStream_t st) {
   } else if (a.nt_unit == 2) UNETPP_LAUNCH_BF16(1, 2, false);
   else UNETPP_LAUNCH_BF16(1, 1, false);
 #undef UNETPP_LAUNCH_BF16
-  note_kernel(d->taps == 9 ? "gemm_bf16_kernel<9>" : "gemm_bf16_kernel<1>");
   return launch_status();
 }
 

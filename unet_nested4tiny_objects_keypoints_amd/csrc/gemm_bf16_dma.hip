@@ -642,13 +642,11 @@ bool dma_env_off() { return opt_value(OPT_BF16_NO_DMA, 0) != 0; }  // unetpp_deb
 
 }  // namespace
 
-// UNETPP_OK after launching; 1 when the descriptor is not one this kernel takes (the caller falls back to gemm_bf16.hip)
-int launch_gemm_bf16_dma(const unetpp_gemm_desc* d, hipStream_t st) {
-  if (dma_env_off()) return 1;
-  DmaArgs da;
-  FastArgs& a = da.f;
-  if (!bf16_gemm_args(d, a) || d->weight_image == nullptr) return 1;
-  if (d->stats_partial != nullptr && d->n_out != 1) return 1;
+// The form choice, the switches and the view checks (s.fa: the descriptor's bf16_gemm_args).  false: the register kernel
+// (gemm_bf16.hip) takes the launch.
+bool gemm_bf16_dma_applies(const unetpp_gemm_desc* d, GemmSel& s) {
+  if (dma_env_off()) return false;
+  FastArgs& a = s.fa;
   // Which form (tools/bench_kernels.py, 512 x 512 x 8; UNETPP_BF16_DMA_FORM = 0 / 4 / 8 forces none / one of them, and
   // UNETPP_BF16_DMA_ALL=1 lifts the restrictions: the tests run every shape class through both kernels):
   //   8 waves, 512-pixel patches   plain 3x3 launches on images at least 32 wide with more than one chunk or column tile
@@ -660,8 +658,7 @@ int launch_gemm_bf16_dma(const unetpp_gemm_desc* d, hipStream_t st) {
   const bool all = opt_value(OPT_BF16_DMA_ALL, 0) != 0;
   const bool stats = d->stats_partial != nullptr;
   int form = 4;
-  const int cus = device_cu_count();
-  if (cus <= 0) return UNETPP_ELAUNCH;
+  const int cus = s.cus;
   // (the 8-wave form only when its 512-pixel units still cover the chip: the deepest layers of a small image do not)
   const long units8 = static_cast<long>(d->N) * ((d->H + 15) / 16) * a.tiles_x * ((a.n_tiles % 2 == 0) ? a.n_tiles / 2 : a.n_tiles);
   const long min8 = opt_value(OPT_BF16_DMA_MIN8, 2);  // (A/B knob)
@@ -669,7 +666,7 @@ int launch_gemm_bf16_dma(const unetpp_gemm_desc* d, hipStream_t st) {
   if (d->taps == 9 && !stats && a.log2tw == 5 && (a.n_chunks > 1 || a.n_tiles > 1) && units8 >= min8 * cus) form = 8;
   if (opt_is_set(OPT_BF16_DMA_FORM)) {
     const int want = static_cast<int>(opt_value(OPT_BF16_DMA_FORM, 4));
-    if (want == 0) return 1;
+    if (want == 0) return false;
     if (want == 4 || (want == 8 && d->taps == 9 && !stats && a.log2tw == 5)) form = want;
   }
   // Round 4: plain 3x3 launches too small for the 8-wave form (the deep levels: 24 x 24 .. 96 x 96 images) take the 4-wave
@@ -685,33 +682,65 @@ int launch_gemm_bf16_dma(const unetpp_gemm_desc* d, hipStream_t st) {
   // the transposed-convolution GEMMs (pointwise, four phase views) through this kernel as well: +1 % on the configs[3]
   // step, nothing at configs[4] (same box, alternating); UNETPP_BF16_DMA_POINTWISE=0 keeps them on the register kernel
   const bool pointwise = opt_value(OPT_BF16_DMA_POINTWISE, 1) != 0 && d->taps == 1 && !stats;
-  if (!all && !small3x3 && !stats3x3 && !pointwise && form == 4 && (d->taps != 9 || a.n_tiles != 1 || stats)) return 1;
+  if (!all && !small3x3 && !stats3x3 && !pointwise && form == 4 && (d->taps != 9 || a.n_tiles != 1 || stats)) return false;
   const unetpp_view& V0 = d->in[0];
   for (int i = 0; i < d->n_in; ++i) {
     const unetpp_view& v = d->in[i];
-    if (v.scale != nullptr || v.relu != 0 || v.gate != nullptr) return 1;       // load transforms need VALU on the way
-    if ((v.c_len % DKC) != 0) return 1;                                          // whole 32-channel chunks
-    if (v.C != V0.C || v.Hs != V0.Hs || v.Ws != V0.Ws || v.sy != V0.sy || v.sx != V0.sx) return 1;  // one geometry
-    if (d->taps == 9 && (v.sy != 1 || v.sx != 1 || v.oy != 0 || v.ox != 0 || v.Hs != d->H || v.Ws != d->W)) return 1;
+    if (v.scale != nullptr || v.relu != 0 || v.gate != nullptr) return false;       // load transforms need VALU on the way
+    if ((v.c_len % DKC) != 0) return false;                                          // whole 32-channel chunks
+    if (v.C != V0.C || v.Hs != V0.Hs || v.Ws != V0.Ws || v.sy != V0.sy || v.sx != V0.sx) return false;  // one geometry
+    if (d->taps == 9 && (v.sy != 1 || v.sx != 1 || v.oy != 0 || v.ox != 0 || v.Hs != d->H || v.Ws != d->W)) return false;
   }
-  const long view_bytes = static_cast<long>(d->N) * V0.Hs * V0.Ws * V0.C * 2;
-  if (view_bytes > 0x7fffffffL) return 1;
+  if (static_cast<long>(d->N) * V0.Hs * V0.Ws * V0.C * 2 > 0x7fffffffL) return false;                   // view_bytes
+  if (static_cast<long>(a.n_tiles) * a.n_chunks * (d->taps * 2 * DSTEP) > 0x7fffffffL) return false;  // wimg_bytes
+  s.label = d->taps == 9 ? "gemm_bf16_dma_kernel<9>" : "gemm_bf16_dma_kernel<1>";
+  s.plain_out = 0;
+  long workers;
+  if (form == 8) {
+    s.kernel = GEMM_BF16_DMA8;
+    // 16 x 32 patches; two column tiles per unit when the launch has an even number of them
+    a.nt_unit = (a.n_tiles % 2 == 0) ? 2 : 1;
+    a.n_groups = a.n_tiles / a.nt_unit;
+    a.tiles_y = (d->H + 15) / 16;
+    a.total_blocks = static_cast<long>(d->N) * a.tiles_y * a.tiles_x * a.n_groups;
+    workers = static_cast<long>(cus) & ~7L;  // one 8-wave workgroup per CU
+    s.threads = 512;
+  } else {
+    s.kernel = GEMM_BF16_DMA4;
+    // 4 waves, 3x3: one column tile per unit (two weight buffers of 18 KB beside two input buffers of 22 KB: 80 KB, two
+    // workgroups per CU); pointwise: two tiles when the launch has an even number of them
+    if (d->taps == 9 && a.nt_unit == 2) {
+      a.nt_unit = 1;
+      a.n_groups = a.n_tiles;
+      a.total_blocks *= 2;
+    }
+    // pointwise launches whose output views carry no gate / accumulate flag (the forward of a transposed or 1x1 convolution):
+    // the three-per-CU instantiation (UNETPP_BF16_PW_PLAIN=0 / unetpp_debug_set keeps them on the two-per-CU one: A/B runs)
+    bool plain_out = d->taps == 1 && !stats && opt_value(OPT_BF16_PW_PLAIN, 1) != 0;
+    for (int i = 0; i < d->n_out; ++i) plain_out = plain_out && d->out[i].gate == nullptr && d->out[i].accumulate == 0;
+    s.plain_out = plain_out ? 1 : 0;
+    workers = ((plain_out ? 3L : 2L) * cus) & ~7L;
+  }
+  if (workers < 8) workers = 8;
+  s.grid_x = static_cast<unsigned>(a.total_blocks <= workers ? a.total_blocks : workers);
+  return true;
+}
+
+int launch_gemm_bf16_dma(const unetpp_gemm_desc* d, const GemmSel& s, hipStream_t st) {
+  DmaArgs da;
+  FastArgs& a = da.f;
+  a = s.fa;
+  const unetpp_view& V0 = d->in[0];
   da.pitch = V0.C * 2;
   da.row_pitch = V0.sy * V0.Ws * V0.C * 2;
   da.col_pitch = V0.sx * V0.C * 2;
   da.img_pitch = V0.Hs * V0.Ws * V0.C * 2;
-  da.view_bytes = static_cast<int>(view_bytes);
-  const long wimg_bytes = static_cast<long>(a.n_tiles) * a.n_chunks * (d->taps * 2 * DSTEP);
-  if (wimg_bytes > 0x7fffffffL) return 1;
-  da.wimg_bytes = static_cast<int>(wimg_bytes);
+  da.view_bytes = static_cast<int>(static_cast<long>(d->N) * V0.Hs * V0.Ws * V0.C * 2);
+  da.wimg_bytes = static_cast<int>(static_cast<long>(a.n_tiles) * a.n_chunks * (d->taps * 2 * DSTEP));
   da.unit_base = 0;
-  if (form == 8) {
-    // 16 x 32 patches; two column tiles per unit when the launch has an even number of them
-    const int nt = (a.n_tiles % 2 == 0) ? 2 : 1;
-    a.nt_unit = nt;
-    a.n_groups = a.n_tiles / nt;
-    a.tiles_y = (d->H + 15) / 16;
-    a.total_blocks = static_cast<long>(d->N) * a.tiles_y * a.tiles_x * a.n_groups;
+  const int cus = s.cus;
+  if (s.kernel == GEMM_BF16_DMA8) {
+    const int nt = a.nt_unit;
     long workers = static_cast<long>(cus) & ~7L;  // one 8-wave workgroup per CU
     if (workers < 8) workers = 8;
     // Round 4: the tail.  Units are equal, every workgroup walks ceil(units / workers) of them, so 1152 units on 256 CUs
@@ -759,23 +788,10 @@ int launch_gemm_bf16_dma(const unetpp_gemm_desc* d, hipStream_t st) {
       const dim3 grid(static_cast<unsigned>(a.total_blocks <= workers4 ? a.total_blocks : workers4)), block(kThreads);
       hipLaunchKernelGGL((gemm_bf16_dma_kernel<9, 5, 1, false>), grid, block, 0, st, da);
     }
-    note_kernel("gemm_bf16_dma_kernel<9>");
     return launch_status();
   }
-  // 4 waves, 3x3: one column tile per unit (two weight buffers of 18 KB beside two input buffers of 22 KB: 80 KB, two
-  // workgroups per CU); pointwise: two tiles when the launch has an even number of them
-  if (d->taps == 9 && a.nt_unit == 2) {
-    a.nt_unit = 1;
-    a.n_groups = a.n_tiles;
-    a.total_blocks *= 2;
-  }
-  // pointwise launches whose output views carry no gate / accumulate flag (the forward of a transposed or 1x1 convolution):
-  // the three-per-CU instantiation (UNETPP_BF16_PW_PLAIN=0 / unetpp_debug_set keeps them on the two-per-CU one: A/B runs)
-  bool plain_out = d->taps == 1 && !stats && opt_value(OPT_BF16_PW_PLAIN, 1) != 0;
-  for (int i = 0; i < d->n_out; ++i) plain_out = plain_out && d->out[i].gate == nullptr && d->out[i].accumulate == 0;
-  long workers = ((plain_out ? 3L : 2L) * cus) & ~7L;
-  if (workers < 8) workers = 8;
-  const dim3 grid(static_cast<unsigned>(a.total_blocks <= workers ? a.total_blocks : workers)), block(kThreads);
+  const dim3 grid(s.grid_x), block(kThreads);
+  const bool stats = d->stats_partial != nullptr, plain_out = s.plain_out != 0;
 #define UNETPP_LAUNCH_BF16_DMA(T, NTU, ST, RW)                                                                         \
   do {                                                                                                                 \
     if (a.log2tw == 5) hipLaunchKernelGGL((gemm_bf16_dma_kernel<T, 5, NTU, ST, 4, RW>), grid, block, 0, st, da);      \
@@ -793,7 +809,6 @@ int launch_gemm_bf16_dma(const unetpp_gemm_desc* d, hipStream_t st) {
     else UNETPP_LAUNCH_BF16_DMA(1, 1, false, true);
   }
 #undef UNETPP_LAUNCH_BF16_DMA
-  note_kernel(d->taps == 9 ? "gemm_bf16_dma_kernel<9>" : "gemm_bf16_dma_kernel<1>");
   return launch_status();
 }
 

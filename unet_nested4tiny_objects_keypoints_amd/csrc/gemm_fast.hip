@@ -402,21 +402,20 @@ __global__ __launch_bounds__(kThreads, (TAPS == 1 ? (NT == 1 ? 4 : UNETPP_FAST_P
 
 }  // namespace
 
-int launch_gemm_fast(const unetpp_gemm_desc* d, hipStream_t st) {
-  FastArgs a;
-  if (!fast_args(d, a, KC) || d->weight_image == nullptr) return UNETPP_EINVAL;
-  if (d->stats_partial != nullptr && d->n_out != 1) return UNETPP_EINVAL;
-  if (d->taps == 1) {  // plain aligned pointwise launches whose weights fit LDS: gemm_pw.hip
-    const int pw = launch_gemm_pw(d, a, st);
-    if (pw != 1) return pw;
-  }
+// takes every descriptor with a direct fp32 image (gemm_image_of: s.fa is fast_args with 16-channel chunks)
+void gemm_fast_plan(const unetpp_gemm_desc* d, GemmSel& s) {
+  s.kernel = GEMM_FAST;
+  s.label = d->taps == 9 ? "gemm_fast_kernel<9>" : "gemm_fast_kernel<1>";
   // persistent grid: at most 3 workgroups per CU (the kernel's LDS/VGPR budget), a multiple of 8
-  const int cus = device_cu_count();
-  if (cus <= 0) return UNETPP_ELAUNCH;
-  const long per_cu = (d->taps == 1 && a.nt_unit == 1) ? 4 : (d->taps == 1 ? UNETPP_FAST_PW_WGS : 3);  // = the kernel's launch bounds
-  long workers = (per_cu * cus) & ~7L;
+  const long per_cu = (d->taps == 1 && s.fa.nt_unit == 1) ? 4 : (d->taps == 1 ? UNETPP_FAST_PW_WGS : 3);  // = the kernel's launch bounds
+  long workers = (per_cu * s.cus) & ~7L;
   if (workers < 8) workers = 8;
-  const dim3 grid(static_cast<unsigned>(a.total_blocks <= workers ? a.total_blocks : workers)), block(kThreads);
+  s.grid_x = static_cast<unsigned>(s.fa.total_blocks <= workers ? s.fa.total_blocks : workers);
+}
+
+int launch_gemm_fast(const unetpp_gemm_desc* d, const GemmSel& s, hipStream_t st) {
+  const FastArgs& a = s.fa;
+  const dim3 grid(s.grid_x), block(kThreads);
 #define UNETPP_LAUNCH_FAST(T, NTU)                                                                      \
   do {                                                                                                  \
     if (a.log2tw == 5) hipLaunchKernelGGL((gemm_fast_kernel<T, 5, NTU>), grid, block, 0, st, a);        \
@@ -427,7 +426,6 @@ int launch_gemm_fast(const unetpp_gemm_desc* d, hipStream_t st) {
   else if (a.nt_unit == 2) UNETPP_LAUNCH_FAST(1, 2);
   else UNETPP_LAUNCH_FAST(1, 1);
 #undef UNETPP_LAUNCH_FAST
-  note_kernel(d->taps == 9 ? "gemm_fast_kernel<9>" : "gemm_fast_kernel<1>");
   return launch_status();
 }
 

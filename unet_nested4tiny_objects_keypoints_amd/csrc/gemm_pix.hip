@@ -301,89 +301,144 @@ extern "C" int64_t unetpp_gemm_stats_rows(int32_t N, int32_t H, int32_t W) {
   return blocks > kBnFusedRows ? blocks : kBnFusedRows;  // per-workgroup rows (bn_fused.h) or per-block rows
 }
 
-namespace {
-// *bn_rows: rows of BatchNorm partial sums the launched kernel writes when that is NOT one per 256-pixel block (the
-// persistent kernels of bn_fused.h write one per workgroup); left untouched otherwise
-int gemm_fwd_dispatch(const unetpp_gemm_desc* d, void* stream, long* bn_rows);
-}
-
-extern "C" int unetpp_gemm_fwd(const unetpp_gemm_desc* d, void* stream) {
-  if (d == nullptr || d->N <= 0 || d->H <= 0 || d->W <= 0) return UNETPP_EINVAL;
-  const unetpp_bn_fused& bn = d->bn;
-  long bn_rows = 0;
-  if (bn.scale == nullptr) return gemm_fwd_dispatch(d, stream, &bn_rows);
-  // BatchNorm finalize attached to this call: over the kernel's per-workgroup rows where it writes those (bn_fused.h),
-  // else over per-block rows
-  if (!d->stats_partial || !bn.gamma || !bn.beta || !bn.mean || !bn.invstd || !bn.shift || bn.count < 1 ||
-      (bn.running_mean == nullptr) != (bn.running_var == nullptr) || d->n_out != 1)
-    return UNETPP_EINVAL;
-  const int rc = gemm_fwd_dispatch(d, stream, &bn_rows);
-  if (rc != UNETPP_OK) return rc;
-  const int64_t rows = bn_rows > 0 ? bn_rows : unetpp_gemm_pixel_blocks(d->N, d->H, d->W);
-  const char* gemm_name = g_last_kernel;  // the call keeps the label of its GEMM, not that of the attached finalize
-  const int fin = unetpp_bn_finalize(d->stats_partial, rows, d->out[0].c_len, bn.count, bn.gamma, bn.beta, bn.eps,
-                                     bn.momentum, bn.running_mean, bn.running_var, bn.mean, bn.invstd, bn.scale, bn.shift,
-                                     stream);
-  note_kernel(gemm_name);
-  return fin;
+// The weight image of a descriptor's fast kernels: bf16 storage has one layout, fp32 3x3 without UNETPP_GEMM_DIRECT the
+// Winograd one, everything else the direct one.  Does not look at d->weight_image: the caller sizes the image by it.
+bool unetpp::gemm_image_of(const unetpp_gemm_desc* d, GemmSel& s) {
+  s.image_kind = s.image_kc = 0;
+  s.image_floats = 0;
+  if (d == nullptr) return false;
+  const bool bf = (d->flags & UNETPP_GEMM_BF16) != 0, wino = wino_applies(d);
+  const int kc = bf ? 32 : (wino ? 8 : 16);
+  if (bf ? !bf16_gemm_args(d, s.fa) : !fast_args(d, s.fa, kc, 32)) return false;
+  s.image_kind = bf ? kKindBf16 : (wino ? kKindWino : kKindFast);
+  s.image_kc = kc;
+  s.image_floats = static_cast<long>(s.fa.n_tiles) * s.fa.n_chunks * (wino ? 4096 : d->taps * 512L);
+  return true;
 }
 
 namespace {
-int gemm_fwd_dispatch(const unetpp_gemm_desc* d, void* stream, long* bn_rows) {
-  if (d == nullptr || d->N <= 0 || d->H <= 0 || d->W <= 0) return UNETPP_EINVAL;
-  if (d->taps != 9 && d->taps != 1) return UNETPP_EINVAL;
-  if (d->n_in < 1 || d->n_in > UNETPP_MAX_VIEWS || d->n_out < 1 || d->n_out > UNETPP_MAX_VIEWS) return UNETPP_EINVAL;
-  if (d->weight == nullptr && d->weight_image == nullptr) return UNETPP_EINVAL;
-  if (d->stats_partial != nullptr && d->n_out != 1) return UNETPP_EINVAL;
-  if (d->flags & UNETPP_GEMM_BF16) {  // bf16 storage: the MFMA kernel, or the VALU first layer (fp32 input, bf16 output)
-    if (d->weight_image != nullptr) {
-      if (d->taps == 1) {  // plain pointwise launches whose weights fit LDS: gemm_pw_bf16.hip
-        FastArgs fa;
-        if (bf16_gemm_args(d, fa)) {
-          const int pw = launch_gemm_pw_bf16(d, fa, static_cast<hipStream_t>(stream));
-          if (pw != 1) return pw;
-        }
-      }
-      const int dma = launch_gemm_bf16_dma(d, static_cast<hipStream_t>(stream));
-      return dma != 1 ? dma : launch_gemm_bf16(d, static_cast<hipStream_t>(stream));
-    }
-    const int small = launch_small_cin_fwd(d, static_cast<hipStream_t>(stream), bn_rows);
-    return small == 1 ? UNETPP_EINVAL : small;  // no generic bf16 kernel: unaligned views are refused
-  }
-  if (d->weight_image != nullptr)  // the image was packed for the algorithm the same descriptor selects
-    return wino_applies(d) ? launch_gemm_wino(d, static_cast<hipStream_t>(stream), bn_rows)
-                           : launch_gemm_fast(d, static_cast<hipStream_t>(stream));
-  GemmArgs a;
-  a.d = *d;
-  a.Ktot = 0;
-  a.Ncols = 0;
-  int n_tiles = 0;
+// the generic kernel takes any views that are views at all; one workgroup per (256-pixel block, 32-column tile)
+bool gemm_generic_applies(const unetpp_gemm_desc* d, GemmSel& s) {
+  FastArgs& a = s.fa;
+  a.Ktot = a.Ncols = a.n_tiles = 0;
   for (int i = 0; i < d->n_in; ++i) {
-    if (!view_ok(d->in[i]) || !view_covers(d->in[i], d->H, d->W)) return UNETPP_EINVAL;
+    if (!view_ok(d->in[i]) || !view_covers(d->in[i], d->H, d->W)) return false;
     a.Ktot += d->in[i].c_len;
   }
   for (int i = 0; i < d->n_out; ++i) {
-    if (!view_ok(d->out[i]) || !view_covers(d->out[i], d->H, d->W)) return UNETPP_EINVAL;
+    if (!view_ok(d->out[i]) || !view_covers(d->out[i], d->H, d->W)) return false;
     a.Ncols += d->out[i].c_len;
-    n_tiles += (d->out[i].c_len + 31) / 32;
+    a.n_tiles += (d->out[i].c_len + 31) / 32;
   }
   const TileGeom g = tile_geom(d->H, d->W);
   a.log2tw = g.log2tw;
   a.tiles_x = g.tiles_x;
   a.tiles_y = g.tiles_y;
   const int64_t pix_blocks = static_cast<int64_t>(d->N) * g.tiles_y * g.tiles_x;
-  if (pix_blocks > 0x7fffffffLL || n_tiles > 65535) return UNETPP_EINVAL;
-  {
-    const int small = launch_small_cin_fwd(d, static_cast<hipStream_t>(stream), bn_rows);  // 1..4-channel first layer
-    if (small != 1) return small;
-  }
-  const dim3 grid(static_cast<unsigned>(pix_blocks), static_cast<unsigned>(n_tiles));
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (pix_blocks > 0x7fffffffLL || a.n_tiles > 65535) return false;
+  s.kernel = GEMM_GENERIC;
+  s.label = d->taps == 9 ? "gemm_pix_kernel<9>" : "gemm_pix_kernel<1>";
+  s.grid_x = static_cast<unsigned>(pix_blocks);
+  s.grid_y = static_cast<unsigned>(a.n_tiles);
+  return true;
+}
+
+int launch_gemm_generic(const unetpp_gemm_desc* d, const GemmSel& s, hipStream_t st) {
+  GemmArgs a;
+  a.d = *d;
+  a.log2tw = s.fa.log2tw;
+  a.tiles_x = s.fa.tiles_x;
+  a.tiles_y = s.fa.tiles_y;
+  a.Ktot = s.fa.Ktot;
+  a.Ncols = s.fa.Ncols;
+  const dim3 grid(s.grid_x, s.grid_y);
   if (d->taps == 9)
     hipLaunchKernelGGL(gemm_pix_kernel<9>, grid, dim3(kThreads), 0, st, a);
   else
     hipLaunchKernelGGL(gemm_pix_kernel<1>, grid, dim3(kThreads), 0, st, a);
-  note_kernel(d->taps == 9 ? "gemm_pix_kernel<9>" : "gemm_pix_kernel<1>");
   return launch_status();
 }
 }  // namespace
+
+// The one place that decides which kernel takes a forward / input-gradient descriptor.  Precedence: without a weight
+// image the first-layer kernel, else the generic one (bf16 storage has no generic kernel: UNETPP_EINVAL); with one, bf16
+// storage: pointwise, LDS-DMA (8-wave, 4-wave), register kernel; fp32: Winograd, pointwise, fast.  A descriptor that
+// carries an image no image kernel can read is refused.
+int unetpp::gemm_select(const unetpp_gemm_desc* d, int cus, GemmSel& s) {
+  if (d == nullptr || d->N <= 0 || d->H <= 0 || d->W <= 0) return UNETPP_EINVAL;
+  if (d->taps != 9 && d->taps != 1) return UNETPP_EINVAL;
+  if (d->n_in < 1 || d->n_in > UNETPP_MAX_VIEWS || d->n_out < 1 || d->n_out > UNETPP_MAX_VIEWS) return UNETPP_EINVAL;
+  if (d->weight == nullptr && d->weight_image == nullptr) return UNETPP_EINVAL;
+  if (d->stats_partial != nullptr && d->n_out != 1) return UNETPP_EINVAL;
+  const unetpp_bn_fused& bn = d->bn;  // BatchNorm finalize attached to the call
+  if (bn.scale != nullptr &&
+      (!d->stats_partial || !bn.gamma || !bn.beta || !bn.mean || !bn.invstd || !bn.shift || bn.count < 1 ||
+       (bn.running_mean == nullptr) != (bn.running_var == nullptr) || d->n_out != 1))
+    return UNETPP_EINVAL;
+  const bool bf = (d->flags & UNETPP_GEMM_BF16) != 0;
+  const bool has_image = gemm_image_of(d, s);
+  s.cus = cus;
+  s.grid_y = 1;
+  s.threads = kThreads;
+  s.lds_bytes = 0;
+  s.bn_rows = 0;
+  if (d->weight_image == nullptr) {
+    const bool small = small_cin_fwd_applies(d);
+    if (bf ? !small : !gemm_generic_applies(d, s)) return UNETPP_EINVAL;  // (no generic bf16 kernel)
+    if (cus <= 0) return UNETPP_ELAUNCH;
+    if (small) small_cin_fwd_plan(d, s);
+    return UNETPP_OK;
+  }
+  if (!has_image) return UNETPP_EINVAL;
+  if (cus <= 0) return UNETPP_ELAUNCH;
+  if (bf) {
+    if (!gemm_pw_bf16_applies(d, s) && !gemm_bf16_dma_applies(d, s)) gemm_bf16_plan(d, s);
+  } else if (wino_applies(d)) {
+    gemm_wino_plan(d, s);
+  } else if (!gemm_pw_applies(d, s)) {
+    gemm_fast_plan(d, s);
+  }
+  return UNETPP_OK;
+}
+
+extern "C" int unetpp_gemm_plan(const unetpp_gemm_desc* d, int32_t cus, unetpp_gemm_sizes* out) {
+  GemmSel s;
+  if (out == nullptr) return UNETPP_EINVAL;
+  const int rc = gemm_select(d, cus > 0 ? cus : device_cu_count(), s);
+  if (rc != UNETPP_OK) return rc;
+  out->image_floats = s.image_floats;
+  out->bn_rows = s.bn_rows;
+  out->workgroups = static_cast<int32_t>(s.grid_x * s.grid_y);
+  out->threads = static_cast<int32_t>(s.threads);
+  out->kernel = s.label;
+  return UNETPP_OK;
+}
+
+extern "C" int unetpp_gemm_fwd(const unetpp_gemm_desc* d, void* stream) {
+  GemmSel s;
+  int rc = gemm_select(d, device_cu_count(), s);
+  if (rc != UNETPP_OK) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  note_kernel(s.label);
+  switch (s.kernel) {
+    case GEMM_SMALL_CIN: rc = launch_small_cin_fwd(d, s, st); break;
+    case GEMM_BF16_PW: rc = launch_gemm_pw_bf16(d, s, st); break;
+    case GEMM_BF16_DMA8:
+    case GEMM_BF16_DMA4: rc = launch_gemm_bf16_dma(d, s, st); break;
+    case GEMM_BF16: rc = launch_gemm_bf16(d, s, st); break;
+    case GEMM_PW: rc = launch_gemm_pw(d, s, st); break;
+    case GEMM_WINO: rc = launch_gemm_wino(d, s, st); break;
+    case GEMM_FAST: rc = launch_gemm_fast(d, s, st); break;
+    case GEMM_GENERIC: rc = launch_gemm_generic(d, s, st); break;
+  }
+  const unetpp_bn_fused& bn = d->bn;
+  if (rc != UNETPP_OK || bn.scale == nullptr) return rc;
+  // BatchNorm finalize attached to this call: over the kernel's per-workgroup rows where it writes those (bn_fused.h),
+  // else over per-block rows
+  const int64_t rows = s.bn_rows > 0 ? s.bn_rows : unetpp_gemm_pixel_blocks(d->N, d->H, d->W);
+  const int fin = unetpp_bn_finalize(d->stats_partial, rows, d->out[0].c_len, bn.count, bn.gamma, bn.beta, bn.eps,
+                                     bn.momentum, bn.running_mean, bn.running_var, bn.mean, bn.invstd, bn.scale, bn.shift,
+                                     stream);
+  note_kernel(s.label);  // the call keeps the label of its GEMM, not that of the attached finalize
+  return fin;
+}

@@ -215,15 +215,8 @@ int block_count(int units16) {  // 16-wide groups per chunk / blocks per pass: a
 
 template <int QC, int NCBP, int EPI>
 int launch_pw_epi(const PwArgs& a, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st) {
-  static bool raised[64] = {};  // per device: dynamic LDS above 64 KB has to be allowed once per function
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return UNETPP_ELAUNCH;
-  if (!raised[dev]) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_pw_kernel<QC, NCBP, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            160 * 1024) != hipSuccess)
-      return UNETPP_ELAUNCH;
-    raised[dev] = true;
-  }
+  static std::atomic<bool> raised[kMaxDevices];
+  if (!allow_dynamic_lds(reinterpret_cast<const void*>(&gemm_pw_kernel<QC, NCBP, EPI>), 160 * 1024, raised)) return UNETPP_ELAUNCH;
   hipLaunchKernelGGL((gemm_pw_kernel<QC, NCBP, EPI>), grid, block, lds_bytes, st, a);
   return launch_status();
 }
@@ -235,57 +228,67 @@ int launch_pw(const PwArgs& a, bool plain, dim3 grid, dim3 block, size_t lds_byt
 
 }  // namespace
 
-// returns UNETPP_OK after launching, 1 when the descriptor is not one this kernel takes (gemm_fast.hip then does)
-int launch_gemm_pw(const unetpp_gemm_desc* d, const FastArgs& fa, hipStream_t st) {
-  if (d->taps != 1 || (d->flags & UNETPP_GEMM_BF16) != 0 || d->weight_image == nullptr || d->stats_partial != nullptr) return 1;
-  if (opt_value(OPT_PW_DIRECT, 1) == 0 || (d->W & 15) != 0) return 1;
-  PwArgs a;
-  a.d = *d;
-  a.K = fa.Ktot;
-  a.N = fa.Ncols;
+// plain aligned pointwise launches without a statistics epilogue whose weights fit LDS (s.fa: the descriptor's fast_args);
+// gemm_fast_kernel<1> takes the others
+bool gemm_pw_applies(const unetpp_gemm_desc* d, GemmSel& s) {
+  if (d->taps != 1 || d->stats_partial != nullptr) return false;
+  if (opt_value(OPT_PW_DIRECT, 1) == 0 || (d->W & 15) != 0) return false;
   for (int i = 0; i < d->n_in; ++i)
-    if (!pw_in_view_ok(d->in[i])) return 1;
+    if (!pw_in_view_ok(d->in[i])) return false;
   for (int i = 0; i < d->n_out; ++i)
-    if (!pw_out_view_ok(d->out[i], d->n_out > 1)) return 1;
-  const int qc = block_count(a.K >> 4), ncbp = block_count(a.N >> 4);
-  if (qc == 0 || ncbp == 0) return 1;
-  const size_t lds_bytes = (static_cast<size_t>(a.K) * a.N + a.N) * sizeof(float);
+    if (!pw_out_view_ok(d->out[i], d->n_out > 1)) return false;
+  const int K = s.fa.Ktot, N = s.fa.Ncols;
+  const int qc = block_count(K >> 4), ncbp = block_count(N >> 4);
+  if (qc == 0 || ncbp == 0) return false;
+  const size_t lds_bytes = (static_cast<size_t>(K) * N + N) * sizeof(float);
   // (Weights beyond the LDS -- level 2 of the base-32 network: 512 KB -- were tried as column groups, one 128 KB group per
   // workgroup of sixteen waves: 139 / 147 us against gemm_fast_kernel<1>'s 112 / 122, profiles/r6/bench_pw_column_groups.txt:
   // two tiles per wave do not pay for staging the group.)
-  if (lds_bytes > 148 * 1024) return 1;
-  a.n_kchunk = (a.K >> 4) / qc;
-  a.n_pass = (a.N >> 4) / ncbp;
-  a.tiles_x = d->W >> 4;
-  a.tiles_shift = -1;
-  for (int s = 0; s < 16; ++s)
-    if ((1 << s) == a.tiles_x) a.tiles_shift = s;
-  a.n_tiles = static_cast<long>(d->N) * d->H * a.tiles_x;
-  if (a.n_tiles >= 0x7fffffffL) return 1;
+  if (lds_bytes > 148 * 1024) return false;
+  const long n_tiles = static_cast<long>(d->N) * d->H * (d->W >> 4);
+  if (n_tiles >= 0x7fffffffL) return false;
+  s.kernel = GEMM_PW;
+  s.label = "gemm_pw_kernel";
+  s.qc = qc;
+  s.ncbp = ncbp;
+  s.lds_bytes = static_cast<int>(lds_bytes);
   // outputs far beyond the L2 (4 MB per XCD) leave as non-temporal stores; OPT_PW_NT forces either form
   long out_bytes = 0;
   for (int i = 0; i < d->n_out; ++i) out_bytes += static_cast<long>(d->N) * d->H * d->W * d->out[i].c_len * 4;
-  a.nt_store = static_cast<int>(opt_value(OPT_PW_NT, out_bytes >= (64L << 20) ? 1 : 0));
-  const int cus = device_cu_count();
-  if (cus <= 0) return UNETPP_ELAUNCH;
+  s.nt_store = static_cast<int>(opt_value(OPT_PW_NT, out_bytes >= (64L << 20) ? 1 : 0));
   // 16 waves per CU: four workgroups of four waves while four weight images fit the LDS, else two of eight, else one of 16
-  const int threads = lds_bytes <= 38 * 1024 ? 256 : (lds_bytes <= 78 * 1024 ? 512 : 1024);
-  const int waves = threads >> 6;
-  long blocks = static_cast<long>(cus) * (16 / waves);
-  const long need = (a.n_tiles + waves - 1) / waves;
-  if (blocks > need) blocks = need;
-  const dim3 grid(static_cast<unsigned>(blocks)), block(threads);
-  bool plain = true;  // no output view asks for more than bias + store
+  s.threads = lds_bytes <= 38 * 1024 ? 256 : (lds_bytes <= 78 * 1024 ? 512 : 1024);
+  const int waves = s.threads >> 6;
+  long blocks = static_cast<long>(s.cus) * (16 / waves);
+  const long need = (n_tiles + waves - 1) / waves;
+  s.grid_x = static_cast<unsigned>(blocks > need ? need : blocks);
+  s.plain = 1;  // no output view asks for more than bias + store
   for (int i = 0; i < d->n_out; ++i)
-    plain = plain && d->out[i].relu == 0 && d->out[i].accumulate == 0 && d->out[i].gate == nullptr;
-  int rc = 1;
+    if (d->out[i].relu != 0 || d->out[i].accumulate != 0 || d->out[i].gate != nullptr) s.plain = 0;
+  return true;
+}
+
+int launch_gemm_pw(const unetpp_gemm_desc* d, const GemmSel& s, hipStream_t st) {
+  PwArgs a;
+  a.d = *d;
+  a.K = s.fa.Ktot;
+  a.N = s.fa.Ncols;
+  a.n_kchunk = (a.K >> 4) / s.qc;
+  a.n_pass = (a.N >> 4) / s.ncbp;
+  a.tiles_x = d->W >> 4;
+  a.tiles_shift = -1;
+  for (int t = 0; t < 16; ++t)
+    if ((1 << t) == a.tiles_x) a.tiles_shift = t;
+  a.n_tiles = static_cast<long>(d->N) * d->H * a.tiles_x;
+  a.nt_store = s.nt_store;
+  const dim3 grid(s.grid_x), block(s.threads);
+  int rc = UNETPP_ELAUNCH;
 #define UNETPP_PW_CASE(Q, C) \
-  if (qc == Q && ncbp == C) rc = launch_pw<Q, C>(a, plain, grid, block, lds_bytes, st);
+  if (s.qc == Q && s.ncbp == C) rc = launch_pw<Q, C>(a, s.plain != 0, grid, block, s.lds_bytes, st);
 #define UNETPP_PW_ROW(Q) UNETPP_PW_CASE(Q, 1) UNETPP_PW_CASE(Q, 2) UNETPP_PW_CASE(Q, 4) UNETPP_PW_CASE(Q, 8)
   UNETPP_PW_ROW(1) UNETPP_PW_ROW(2) UNETPP_PW_ROW(4) UNETPP_PW_ROW(8)
 #undef UNETPP_PW_ROW
 #undef UNETPP_PW_CASE
-  if (rc == UNETPP_OK) note_kernel("gemm_pw_kernel");
   return rc;
 }
 

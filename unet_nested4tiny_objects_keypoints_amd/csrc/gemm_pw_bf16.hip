@@ -201,15 +201,8 @@ int pwb_block_count(int units) {
 
 template <int QC, int NCBP, int EPI>
 int launch_pwb_epi(const PwBfArgs& a, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st) {
-  static bool raised[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return UNETPP_ELAUNCH;
-  if (!raised[dev]) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_pw_bf16_kernel<QC, NCBP, EPI>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      return UNETPP_ELAUNCH;
-    raised[dev] = true;
-  }
+  static std::atomic<bool> raised[kMaxDevices];
+  if (!allow_dynamic_lds(reinterpret_cast<const void*>(&gemm_pw_bf16_kernel<QC, NCBP, EPI>), 160 * 1024, raised)) return UNETPP_ELAUNCH;
   hipLaunchKernelGGL((gemm_pw_bf16_kernel<QC, NCBP, EPI>), grid, block, lds_bytes, st, a);
   return launch_status();
 }
@@ -217,55 +210,66 @@ template <int QC, int NCBP>
 int launch_pwb(const PwBfArgs& a, bool plain, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st) {
   if (plain) return launch_pwb_epi<QC, NCBP, 0>(a, grid, block, lds_bytes, st);
   if constexpr (NCBP <= 4) return launch_pwb_epi<QC, NCBP, 1>(a, grid, block, lds_bytes, st);
-  return 1;
+  return UNETPP_ELAUNCH;  // (gemm_pw_bf16_applies plans at most four blocks per pass for these)
 }
 
 }  // namespace
 
-// returns UNETPP_OK after launching, 1 when the descriptor is not one this kernel takes (fa = bf16_gemm_args of d)
-int launch_gemm_pw_bf16(const unetpp_gemm_desc* d, const FastArgs& fa, hipStream_t st) {
-  if (d->taps != 1 || (d->flags & UNETPP_GEMM_BF16) == 0 || d->weight_image == nullptr || d->stats_partial != nullptr) return 1;
-  if (opt_value(OPT_PW_DIRECT, 1) == 0 || (d->W & 15) != 0) return 1;
-  PwBfArgs a;
-  a.d = *d;
-  a.K = fa.Ktot;
-  a.N = fa.Ncols;
+// plain pointwise launches without a statistics epilogue whose weights fit LDS (s.fa: the descriptor's bf16_gemm_args);
+// the LDS-DMA and register kernels take the others
+bool gemm_pw_bf16_applies(const unetpp_gemm_desc* d, GemmSel& s) {
+  if (d->taps != 1 || d->stats_partial != nullptr) return false;
+  if (opt_value(OPT_PW_DIRECT, 1) == 0 || (d->W & 15) != 0) return false;
   for (int i = 0; i < d->n_in; ++i)
-    if (!pwb_in_ok(d->in[i])) return 1;
+    if (!pwb_in_ok(d->in[i])) return false;
   for (int i = 0; i < d->n_out; ++i)
-    if (!pwb_out_ok(d->out[i])) return 1;
+    if (!pwb_out_ok(d->out[i])) return false;
   bool plain = true;
   for (int i = 0; i < d->n_out; ++i)
     plain = plain && d->out[i].relu == 0 && d->out[i].accumulate == 0 && d->out[i].gate == nullptr;
-  int qc = pwb_block_count(a.K >> 5), ncbp = pwb_block_count(a.N >> 5);
-  if (qc == 0 || ncbp == 0) return 1;
+  const int K = s.fa.Ktot, N = s.fa.Ncols;
+  int qc = pwb_block_count(K >> 5), ncbp = pwb_block_count(N >> 5);
+  if (qc == 0 || ncbp == 0) return false;
   if (!plain && ncbp == 8) ncbp = 4;  // (the read-modify-write epilogue beside 64 accumulators does not fit 128 registers)
-  const size_t lds_bytes = static_cast<size_t>(a.K) * a.N * 2 + static_cast<size_t>(a.N) * 4;
-  if (lds_bytes > 148 * 1024) return 1;
-  a.n_kchunk = (a.K >> 5) / qc;
-  a.n_pass = (a.N >> 5) / ncbp;
+  const size_t lds_bytes = static_cast<size_t>(K) * N * 2 + static_cast<size_t>(N) * 4;
+  if (lds_bytes > 148 * 1024) return false;
+  const long n_tiles = static_cast<long>(d->N) * d->H * (d->W >> 4);
+  if (n_tiles >= 0x7fffffffL) return false;
+  s.kernel = GEMM_BF16_PW;
+  s.label = "gemm_pw_bf16_kernel";
+  s.qc = qc;
+  s.ncbp = ncbp;
+  s.plain = plain ? 1 : 0;
+  s.nt_store = 0;
+  s.lds_bytes = static_cast<int>(lds_bytes);
+  s.threads = lds_bytes <= 38 * 1024 ? 256 : (lds_bytes <= 78 * 1024 ? 512 : 1024);
+  const int waves = s.threads >> 6;
+  long blocks = static_cast<long>(s.cus) * (16 / waves);
+  const long need = (n_tiles + waves - 1) / waves;
+  s.grid_x = static_cast<unsigned>(blocks > need ? need : blocks);
+  return true;
+}
+
+int launch_gemm_pw_bf16(const unetpp_gemm_desc* d, const GemmSel& s, hipStream_t st) {
+  PwBfArgs a;
+  a.d = *d;
+  a.K = s.fa.Ktot;
+  a.N = s.fa.Ncols;
+  a.n_kchunk = (a.K >> 5) / s.qc;
+  a.n_pass = (a.N >> 5) / s.ncbp;
   a.tiles_x = d->W >> 4;
   a.tiles_shift = -1;
-  for (int s = 0; s < 16; ++s)
-    if ((1 << s) == a.tiles_x) a.tiles_shift = s;
+  for (int t = 0; t < 16; ++t)
+    if ((1 << t) == a.tiles_x) a.tiles_shift = t;
   a.n_tiles = static_cast<long>(d->N) * d->H * a.tiles_x;
-  if (a.n_tiles >= 0x7fffffffL) return 1;
-  const int cus = device_cu_count();
-  if (cus <= 0) return UNETPP_ELAUNCH;
-  const int threads = lds_bytes <= 38 * 1024 ? 256 : (lds_bytes <= 78 * 1024 ? 512 : 1024);
-  const int waves = threads >> 6;
-  long blocks = static_cast<long>(cus) * (16 / waves);
-  const long need = (a.n_tiles + waves - 1) / waves;
-  if (blocks > need) blocks = need;
-  const dim3 grid(static_cast<unsigned>(blocks)), block(threads);
-  int rc = 1;
+  const dim3 grid(s.grid_x), block(s.threads);
+  int rc = UNETPP_ELAUNCH;
 #define UNETPP_PWB_CASE(Q, C) \
-  if (qc == Q && ncbp == C) rc = launch_pwb<Q, C>(a, plain, grid, block, lds_bytes, st);
+  if (s.qc == Q && s.ncbp == C) rc = launch_pwb<Q, C>(a, s.plain != 0, grid, block, s.lds_bytes, st);
 #define UNETPP_PWB_ROW(Q) UNETPP_PWB_CASE(Q, 1) UNETPP_PWB_CASE(Q, 2) UNETPP_PWB_CASE(Q, 4) UNETPP_PWB_CASE(Q, 8)
   UNETPP_PWB_ROW(1) UNETPP_PWB_ROW(2) UNETPP_PWB_ROW(4) UNETPP_PWB_ROW(8)
 #undef UNETPP_PWB_ROW
 #undef UNETPP_PWB_CASE
-  if (rc == UNETPP_OK) note_kernel("gemm_pw_bf16_kernel");
   return rc;
 }
 

@@ -75,6 +75,28 @@ __device__ __forceinline__ UnitGeom decode_unit(const FastArgs& a, long lb) {
   return g;
 }
 
+// ---- forward / input-gradient GEMM: gemm_select (gemm_pix.hip) decides ONCE, from the descriptor and a CU count, which
+// kernel takes it and everything that follows from that; unetpp_gemm_plan reports it, unetpp_gemm_fwd launches what it says.
+constexpr int kKindFast = 0, kKindWino = 1, kKindBf16 = 2;  // weight image layouts (weight_image.hip)
+enum GemmKernel {
+  GEMM_SMALL_CIN, GEMM_BF16_PW, GEMM_BF16_DMA8, GEMM_BF16_DMA4, GEMM_BF16, GEMM_PW, GEMM_WINO, GEMM_FAST, GEMM_GENERIC
+};
+struct GemmSel {
+  GemmKernel kernel;
+  const char* label;   // what unetpp_last_kernel_name() reports after the launch
+  int cus;             // the CU count the choice was made for
+  // the weight image the descriptor's fast kernels read -- whether or not d->weight_image is set (gemm_image_of)
+  int image_kind, image_kc;  // kKind*, channels per K chunk; image_floats == 0: no image kernel applies
+  long image_floats;
+  FastArgs fa;         // the descriptor and its unit geometry, chunked and tiled for the chosen kernel
+  unsigned grid_x, grid_y, threads;
+  int lds_bytes;       // dynamic LDS
+  long bn_rows;        // rows the attached finalize reads: grid_x where the kernel writes one per workgroup, else 0
+  int qc, ncbp, plain, nt_store;  // pointwise kernels (gemm_pw.hip, gemm_pw_bf16.hip)
+  int mode, narrow;               // Winograd: 0 general / 1 lean / 2 lean with the fold on load; no view wider than 16
+  int plain_out;                  // 4-wave LDS-DMA form: the three-per-CU pointwise instantiation
+};
+
 // Host side: validates a descriptor for the fast kernels and fills the unit geometry; kc = channels per K chunk,
 // ncol = columns per tile.
 inline bool fast_args(const unetpp_gemm_desc* d, FastArgs& a, int kc, int ncol = 32) {

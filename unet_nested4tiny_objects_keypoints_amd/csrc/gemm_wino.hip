@@ -793,19 +793,17 @@ bool wino_applies(const unetpp_gemm_desc* d) {
   return d != nullptr && d->taps == 9 && (d->flags & (UNETPP_GEMM_DIRECT | UNETPP_GEMM_BF16)) == 0;
 }
 
-int launch_gemm_wino(const unetpp_gemm_desc* d, hipStream_t st, long* bn_rows) {
-  FastArgs a;
-  if (!wino_applies(d) || !fast_args(d, a, WKC, WNC) || d->weight_image == nullptr) return UNETPP_EINVAL;
-  if (d->stats_partial != nullptr && d->n_out != 1) return UNETPP_EINVAL;
-  const int cus = device_cu_count();
-  if (cus <= 0) return UNETPP_ELAUNCH;
-  long workers = (2L * cus) & ~7L;  // persistent grid: two workgroups per CU (= the kernel's launch bounds)
+// takes every descriptor with a Winograd image (gemm_image_of: s.fa is fast_args with 8-channel chunks)
+void gemm_wino_plan(const unetpp_gemm_desc* d, GemmSel& s) {
+  s.kernel = GEMM_WINO;
+  s.label = "gemm_wino_kernel";
+  long workers = (2L * s.cus) & ~7L;  // persistent grid: two workgroups per CU (= the kernel's launch bounds)
 #ifdef UNETPP_WINO_EXP
-  if (opt_value(OPT_WINO_ONE_PER_CU, 0) == 1) workers = cus & ~7L;  // waves alone on their SIMD
+  if (opt_value(OPT_WINO_ONE_PER_CU, 0) == 1) workers = s.cus & ~7L;  // waves alone on their SIMD
 #endif
   if (workers < 8) workers = 8;
   if (workers > kBnFusedRows) workers = kBnFusedRows;
-  const dim3 grid(static_cast<unsigned>(a.total_blocks <= workers ? a.total_blocks : workers)), block(kThreads);
+  s.grid_x = static_cast<unsigned>(s.fa.total_blocks <= workers ? s.fa.total_blocks : workers);
   bool narrow = true;  // no output view wider than 16 channels: the second column half is never used
   for (int i = 0; i < d->n_out; ++i) narrow = narrow && d->out[i].c_len <= 16;
   // lean staging: launch-sized fp32 tensors, whole 8-channel chunks, 2 GB at most; mode 1 = no transform on load
@@ -816,8 +814,17 @@ int launch_gemm_wino(const unetpp_gemm_desc* d, hipStream_t st, long* bn_rows) {
            v.ox == 0 && static_cast<long>(d->N) * v.Hs * v.Ws * v.C * 4 <= 0x7fffffffL;
     fold = fold || v.scale != nullptr || v.relu != 0;
   }
-  const int mode = !lean ? 0 : (fold ? 2 : 1);
-  a.bn_in_kernel = (mode != 0 && bn_rows_per_workgroup(d, a.Ncols)) ? 1 : 0;  // (the general kernel: per-block rows)
+  s.narrow = narrow ? 1 : 0;
+  s.mode = !lean ? 0 : (fold ? 2 : 1);
+  s.fa.bn_in_kernel = (s.mode != 0 && bn_rows_per_workgroup(d, s.fa.Ncols)) ? 1 : 0;  // (the general kernel: per-block rows)
+  s.bn_rows = s.fa.bn_in_kernel ? s.grid_x : 0;
+}
+
+int launch_gemm_wino(const unetpp_gemm_desc*, const GemmSel& s, hipStream_t st) {
+  const FastArgs& a = s.fa;
+  const int mode = s.mode;
+  const bool narrow = s.narrow != 0;
+  const dim3 grid(s.grid_x), block(kThreads);
 #define UNETPP_LAUNCH_WINO_M(L, NHV)                                                                    \
   do {                                                                                                  \
     if (mode == 0) hipLaunchKernelGGL((gemm_wino_kernel<L, NHV, 0>), grid, block, 0, st, a);            \
@@ -836,8 +843,6 @@ int launch_gemm_wino(const unetpp_gemm_desc* d, hipStream_t st, long* bn_rows) {
   else UNETPP_LAUNCH_WINO(3);
 #undef UNETPP_LAUNCH_WINO
 #undef UNETPP_LAUNCH_WINO_M
-  note_kernel("gemm_wino_kernel");
-  if (a.bn_in_kernel && bn_rows != nullptr) *bn_rows = grid.x;
   return launch_status();
 }
 

@@ -17,7 +17,7 @@
 namespace unetpp {
 namespace {
 
-constexpr int kKindFast = 0, kKindWino = 1, kKindBf16 = 2;  // bf16: gemm_bf16.hip, [tap][g 2][col 32][h 2][8 bf16], 32-channel chunks
+// image kinds (gemm_units.h): kKindFast, kKindWino, kKindBf16 = gemm_bf16.hip, [tap][g 2][col 32][h 2][8 bf16], 32-channel chunks
 
 struct PackGeom {  // what the image layout depends on: the channel structure of the launch
   int kind, taps, kc, ncol;  // kc = channels per K chunk, ncol = columns per tile
@@ -283,14 +283,13 @@ __global__ void pack_image_jobs_kernel(const unetpp_pack_job* __restrict__ jobs)
   for (long row = blockIdx.x; row < rows; row += gridDim.x) fill_image_row(g, j.src, row, j.image);
 }
 
+// the layout is the selection's (gemm_image_of): kind, chunk width, chunk and tile counts, size
 bool geom_of(const unetpp_gemm_desc* d, PackGeom& g) {
-  FastArgs a;
-  const bool bf = d != nullptr && (d->flags & UNETPP_GEMM_BF16) != 0;
-  const bool wino = wino_applies(d);
-  if (bf ? !bf16_gemm_args(d, a) : !fast_args(d, a, wino ? 8 : 16, 32)) return false;
-  g.kind = bf ? kKindBf16 : (wino ? kKindWino : kKindFast);
+  GemmSel s;
+  if (!gemm_image_of(d, s)) return false;
+  g.kind = s.image_kind;
   g.taps = d->taps;
-  g.kc = bf ? 32 : (wino ? 8 : 16);
+  g.kc = s.image_kc;
   g.ncol = 32;
   g.n_in = d->n_in;
   g.n_out = d->n_out;
@@ -298,8 +297,10 @@ bool geom_of(const unetpp_gemm_desc* d, PackGeom& g) {
     g.in_len[i] = i < d->n_in ? d->in[i].c_len : 0;
     g.out_len[i] = i < d->n_out ? d->out[i].c_len : 0;
   }
-  finish_geom(g);
-  return g.n_chunks == a.n_chunks && g.n_tiles == a.n_tiles;
+  g.n_chunks = s.fa.n_chunks;
+  g.n_tiles = s.fa.n_tiles;
+  g.floats = s.image_floats;
+  return true;
 }
 
 }  // namespace

@@ -227,16 +227,9 @@ int launch_wgrad_pw(const unetpp_wgrad_desc* d, hipStream_t st) {
   WPwArgs a;
   if (!wgrad_pw_shape(d, a)) return UNETPP_EINVAL;  // (the block structure; wgrad_select has asked wgrad_pw_applies)
   a.d = *d;
-  static bool raised[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return UNETPP_ELAUNCH;
+  static std::atomic<bool> raised[kMaxDevices];
   constexpr size_t lds_bytes = 4 * 34 * 256 * sizeof(float);  // four regions of 34 KB
-  if (!raised[dev]) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_pw_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            static_cast<int>(lds_bytes)) != hipSuccess)
-      return UNETPP_ELAUNCH;
-    raised[dev] = true;
-  }
+  if (!allow_dynamic_lds(reinterpret_cast<const void*>(&wgrad_pw_kernel), static_cast<int>(lds_bytes), raised)) return UNETPP_ELAUNCH;
   const dim3 grid(static_cast<unsigned>(d->n_split) * static_cast<unsigned>(a.kb_count * a.nb_count));
   hipLaunchKernelGGL(wgrad_pw_kernel, grid, dim3(kPwThreads), lds_bytes, st, a);
   return launch_status();

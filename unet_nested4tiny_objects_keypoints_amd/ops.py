@@ -377,6 +377,7 @@ class PackPlan:
 
 
 _PLAN: Optional[PackPlan] = None
+_NO_IMAGE_YET = 16  # d.weight_image while a launch is planned: "an image will be there" (never dereferenced)
 
 
 def set_pack_plan(plan: Optional[PackPlan]) -> None:
@@ -425,9 +426,10 @@ def gemm_stats_rows(n: int, h: int, w: int) -> int:
 
 def gemm_fwd(n: int, h: int, w: int, taps: int, ins: Sequence[V], outs: Sequence[V], weight: torch.Tensor,
              bias: Optional[torch.Tensor] = None, stats_partial: Optional[torch.Tensor] = None,
-             direct: bool = False, bn: Optional[BatchNormFinish] = None) -> None:
+             direct: bool = False, bn: Optional[BatchNormFinish] = None) -> _lib.GemmSizes:
     """direct=True forbids the Winograd form of the 3x3 fast path (bit-exact direct summation).
-    bn: finalize the BatchNorm statistics inside this call (stats_partial then is workspace of gemm_stats_rows() rows)."""
+    bn: finalize the BatchNorm statistics inside this call (stats_partial then is workspace of gemm_stats_rows() rows).
+    Returns the library's plan of the launch (kernel label, grid, image size, finalize rows: unetpp_gemm_plan)."""
     if len(ins) > MAX_VIEWS or len(outs) > MAX_VIEWS:
         raise ValueError("too many views")
     d = GemmDesc()
@@ -462,38 +464,46 @@ def gemm_fwd(n: int, h: int, w: int, taps: int, ins: Sequence[V], outs: Sequence
     d.weight = None if from_src else weight.data_ptr()
     d.bias = None if bias is None else bias.data_ptr()
     d.stats_partial = None if stats_partial is None else stats_partial.data_ptr()
-    d.weight_image = None
-    if USE_FAST_GEMM:
-        lib = _lib.lib()
-        n_img = int(lib.unetpp_gemm_weight_image_floats(C.byref(d)))
-        if n_img > 0:  # aligned views: a fast kernel applies; its weight image is built in one launch
-            ready = False
-            if from_src and _PLAN is not None and _PLAN.phase is not None:
-                sig = (weight.t.data_ptr(), weight.s_t, weight.s_k, weight.s_ko, weight.s_n, weight.s_no, weight.k_inner,
-                       weight.n_inner, weight.flip, taps, d.flags, tuple(v.c_len for v in d.inp[:d.n_in]),
-                       tuple(v.c_len for v in d.out[:d.n_out])) + phase_tag(_PLAN.phase)
-                image, ready = _PLAN.image_for(sig, n_img, weight, d)
-            else:
-                image = torch.empty(n_img, dtype=torch.float32, device=weight.device)
-            if ready:
-                pass  # packed by PackPlan.begin() together with the other images of this pass
-            elif from_src:
-                ws = WeightSrc()
-                weight.fill(ws)
-                check(lib.unetpp_gemm_pack_weight_image_from(C.byref(d), C.byref(ws), _ptr(image), _stream()),
-                      "unetpp_gemm_pack_weight_image_from")
-            else:
-                check(lib.unetpp_gemm_pack_weight_image(C.byref(d), _ptr(image), _stream()),
-                      "unetpp_gemm_pack_weight_image")
-            d.weight_image = image.data_ptr()
-    if d.weight_image is None and from_src:  # generic kernel: it reads the packed operand
-        packed = weight.packed()
-        d.weight = packed.data_ptr()
+    # One look at the descriptor (unetpp_gemm_plan) for the launch as it will run with a weight image: only whether
+    # d.weight_image is NULL counts for the plan, so the image is allocated from the plan's own image_floats.  A refusal
+    # means no image kernel takes these views: the launch then reads the packed operand and is planned as that.
+    lib = _lib.lib()
+    plan = _lib.GemmSizes()
+    d.weight_image = _NO_IMAGE_YET if USE_FAST_GEMM else None
+    if USE_FAST_GEMM and lib.unetpp_gemm_plan(C.byref(d), 0, C.byref(plan)) != 0:
+        d.weight_image = None
+    if d.weight_image is not None:  # aligned views: a fast kernel applies; its weight image is built in one launch
+        n_img = int(plan.image_floats)
+        ready = False
+        if from_src and _PLAN is not None and _PLAN.phase is not None:
+            sig = (weight.t.data_ptr(), weight.s_t, weight.s_k, weight.s_ko, weight.s_n, weight.s_no, weight.k_inner,
+                   weight.n_inner, weight.flip, taps, d.flags, tuple(v.c_len for v in d.inp[:d.n_in]),
+                   tuple(v.c_len for v in d.out[:d.n_out])) + phase_tag(_PLAN.phase)
+            image, ready = _PLAN.image_for(sig, n_img, weight, d)
+        else:
+            image = torch.empty(n_img, dtype=torch.float32, device=weight.device)
+        if ready:
+            pass  # packed by PackPlan.begin() together with the other images of this pass
+        elif from_src:
+            ws = WeightSrc()
+            weight.fill(ws)
+            check(lib.unetpp_gemm_pack_weight_image_from(C.byref(d), C.byref(ws), _ptr(image), _stream()),
+                  "unetpp_gemm_pack_weight_image_from")
+        else:
+            check(lib.unetpp_gemm_pack_weight_image(C.byref(d), _ptr(image), _stream()),
+                  "unetpp_gemm_pack_weight_image")
+        d.weight_image = image.data_ptr()
+    if d.weight_image is None:
+        if from_src:  # generic kernel: it reads the packed operand
+            packed = weight.packed()
+            d.weight = packed.data_ptr()
+        check(lib.unetpp_gemm_plan(C.byref(d), 0, C.byref(plan)), "unetpp_gemm_plan")
     # operands the launch has to read besides its inputs: accumulated outputs and ReLU gates of the output views
     acc = sum(v.c_len for v in d.out[:d.n_out] if v.accumulate) + sum(v.c_len for v in d.out[:d.n_out] if v.gate)
     _timed_call(None, 2.0 * n * h * w * taps * k * nc,
-                lambda: check(_lib.lib().unetpp_gemm_fwd(C.byref(d), _stream()), "unetpp_gemm_fwd"),
+                lambda: check(lib.unetpp_gemm_fwd(C.byref(d), _stream()), "unetpp_gemm_fwd"),
                 (2.0 if d.flags & _lib.GEMM_BF16 else 4.0) * n * h * w * (k + nc + acc))
+    return plan
 
 
 def first_layer_dgrad_bf16(dy: torch.Tensor, weight: torch.Tensor, dx: torch.Tensor) -> None:
