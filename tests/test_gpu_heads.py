@@ -1,7 +1,7 @@
 """The deep-supervision heads (dropout + 1x1 convolution + sigmoid, forward and backward) against float64.
 
-The four head launchers (pointwise.hip unetpp_head_fwd / unetpp_head_bwd, pointwise_bf16.hip unetpp_head_fwd_bf16 /
-unetpp_head_bwd_bf16) dispatch ~140 instantiations: the dropout mode D (0 none, 1 keep flags from the in-kernel
+The four head launchers (heads.hip: unetpp_head_fwd / unetpp_head_bwd, unetpp_head_fwd_bf16 / unetpp_head_bwd_bf16; the
+choice is head_select's, head_select.h) dispatch ~140 instantiations: the dropout mode D (0 none, 1 keep flags from the in-kernel
 counter hash, 2 keep flags from a mask tensor), the channel count as a power of two L and the padded class count PC,
 plus general fallbacks for other channel counts.  Each launcher names its choice (unetpp_last_kernel_name).
 
@@ -93,7 +93,7 @@ def _note(name, d):
 
 
 def spans(bf16, pixels, c, hw):
-    """(forward span, backward span) in pixels of the launchers' grids (pointwise.hip / pointwise_bf16.hip)."""
+    """(forward span, backward span) in pixels of the launchers' grids (head_select.h)."""
     if bf16:
         cg = c // 8
         ppb = 256 // cg

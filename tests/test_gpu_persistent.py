@@ -624,7 +624,7 @@ def test_bf16_gemm_multi_unit(dev, case, names, spec, form):
 
 def test_bf16_head_backward_several_rounds(dev):
     """The bf16 head backward: at most HEAD_WGS_PER_CU (4) workgroups per CU take 256-pixel tiles, so a reduced grid
-    walks several rounds of them (pointwise_bf16.hip); dx (accumulate + gate), dW and db against float64."""
+    walks several rounds of them (heads.hip); dx (accumulate + gate), dW and db against float64."""
     from tests.test_gpu_bf16 import close_bf16, close_f32
     from unet_nested4tiny_objects_keypoints_amd import ops
     b, h, w, c, n_cls = 4, 128, 100, 32, 4

@@ -1,5 +1,5 @@
 """The streaming kernels between the GEMMs (BatchNorm finalize / apply / backward, the pool passes, bilinear x2, the
-layout converters; pointwise.hip without the heads, and their bf16 twins in pointwise_bf16.hip) against float64.
+layout converters; pointwise.hip and their bf16 twins in pointwise_bf16.hip; the heads are heads.hip's) against float64.
 
 Every launcher names the form it chose (unetpp_last_kernel_name); each case restates the launcher's own conditions
 (C % 4, 16-byte alignment, even / odd H and W, (W/2)*(C/4) >= 64, bn_bwd_pool_ok, octets_ok) and asserts the label.

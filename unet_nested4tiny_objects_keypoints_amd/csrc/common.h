@@ -116,6 +116,16 @@ __device__ __forceinline__ f32x4 view_load4(const unetpp_view& v, long off, int 
   return val;
 }
 
+// launcher helpers of the streaming files (pointwise.hip, pointwise_bf16.hip, heads.hip)
+inline hipStream_t ST(void* s) { return static_cast<hipStream_t>(s); }
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+inline unsigned grid_for(long items, long cap = 2048 * 8) {  // one item per thread up to `cap` workgroups, then a grid stride
+  long b = (items + kThreads - 1) / kThreads;
+  if (b < 1) b = 1;
+  if (b > cap) b = cap;
+  return static_cast<unsigned>(b);
+}
+
 inline int launch_status() { return hipGetLastError() == hipSuccess ? UNETPP_OK : UNETPP_ELAUNCH; }
 
 // Dynamic LDS above 64 KB has to be allowed once per kernel function and device.  A launcher calls this immediately

@@ -20,9 +20,6 @@ __device__ __forceinline__ bool keep_one(uint64_t bits, int c_in_group, uint32_t
 }
 
 
-constexpr int kHeadMaxC = 128;
-constexpr int kHeadMaxCls = 8;
-
 inline uint32_t keep_threshold(float p_drop) {
   const double keep = 1.0 - static_cast<double>(p_drop);
   uint32_t t = static_cast<uint32_t>(keep * 65536.0 + 0.5);

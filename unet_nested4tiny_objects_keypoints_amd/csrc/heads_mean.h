@@ -2,7 +2,8 @@
 // storage types of the features.
 #pragma once
 #include "bf16_common.h"
-#include "dropout.h"
+#include "common.h"
+#include "head_select.h"
 
 namespace unetpp {
 

@@ -1,11 +1,9 @@
-// HBM-bound companions of the MFMA kernels: BatchNorm statistics / apply / backward, fused
-// affine+ReLU+2x2 max-pool, the 1x1 sigmoid heads with dropout, bilinear x2 (align_corners),
-// and the NCHW<->NHWC converters used at the network edge.  All NHWC fp32; 16-byte vector
-// accesses whenever the channel count is a multiple of 4, scalar fallback otherwise.
+// HBM-bound companions of the MFMA kernels: BatchNorm statistics / apply / backward (training and frozen), fused
+// affine+ReLU+2x2 max-pool and its backward, the sum over partial rows (unetpp_sum_partials), bilinear x2
+// (align_corners), and the NCHW<->NHWC converters used at the network edge.  All NHWC fp32; 16-byte vector
+// accesses whenever the channel count is a multiple of 4, scalar fallback otherwise.  (The heads: heads.hip.)
 #include "common.h"
 #include "lds_asm.h"
-#include "dropout.h"
-#include "heads_mean.h"
 
 namespace unetpp {
 namespace {
@@ -33,13 +31,6 @@ __device__ __forceinline__ float lane_of(const typename Pack<VEC>::T& v, int i) 
     return v[i];
   else
     return v;
-}
-
-inline unsigned grid_for(long items, int cap = 2048 * 8) {
-  long b = (items + kThreads - 1) / kThreads;
-  if (b < 1) b = 1;
-  if (b > cap) b = cap;
-  return static_cast<unsigned>(b);
 }
 
 // ------------------------------------------------------------------ BatchNorm statistics
@@ -595,618 +586,6 @@ __global__ __launch_bounds__(kThreads) void bn_frozen_bwd_pool_kernel(
 }
 
 
-__global__ __launch_bounds__(kThreads) void head_fwd_kernel(const float* __restrict__ x, const float* __restrict__ weight,
-                                                            const float* __restrict__ bias, long pixels, int HW, int C,
-                                                            int n_cls, float keep_scale, uint32_t thr16, uint64_t seed,
-                                                            const uint8_t* __restrict__ mask, const uint64_t* __restrict__ seed_dev, int use_drop,
-                                                            float* __restrict__ out) {
-  if (seed_dev != nullptr) seed += *seed_dev;  // graph-captured steps: the varying part of the seed lives in device memory
-  __shared__ float wsm[kHeadMaxCls * kHeadMaxC];
-  for (int i = threadIdx.x; i < n_cls * C; i += kThreads) wsm[i] = weight[i];
-  __syncthreads();
-  const int g4n = (C + 3) >> 2;
-  for (long p = blockIdx.x * static_cast<long>(kThreads) + threadIdx.x; p < pixels;
-       p += static_cast<long>(gridDim.x) * kThreads) {
-    float acc[kHeadMaxCls];
-#pragma unroll
-    for (int k = 0; k < kHeadMaxCls; ++k) acc[k] = (k < n_cls) ? bias[k] : 0.f;
-    const float* xp = x + p * C;
-    for (int g = 0; g < g4n; ++g) {
-      const uint64_t bits = (use_drop && mask == nullptr) ? keep_bits(seed, p, g4n, g) : 0;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int c = 4 * g + q;
-        if (c < C) {
-          float v = xp[c];
-          if (use_drop) {
-            const bool keep = (mask != nullptr) ? (mask[p * C + c] != 0) : keep_one(bits, q, thr16);
-            v = keep ? v * keep_scale : 0.f;
-          }
-#pragma unroll
-          for (int k = 0; k < kHeadMaxCls; ++k)
-            if (k < n_cls) acc[k] += v * wsm[k * C + c];
-        }
-      }
-    }
-    const long n = p / HW, hw = p - n * HW;
-#pragma unroll
-    for (int k = 0; k < kHeadMaxCls; ++k)
-      if (k < n_cls) out[(n * n_cls + k) * HW + hw] = 1.0f / (1.0f + expf(-acc[k]));
-  }
-}
-
-// Forward head, coalesced: one wave per workgroup stages 64 pixels x C channels through LDS with full-line
-// 16-byte loads (dropout applied on the way in), then lane = pixel reads its row (stride C+1: conflict-free)
-// and the class weights come through scalar loads (uniform index).  Output is NCHW, coalesced along pixels.
-__global__ __launch_bounds__(64) void head_fwd_tiled_kernel(const float* __restrict__ x, const float* __restrict__ weight,
-                                                            const float* __restrict__ bias, long pixels, int HW, int C,
-                                                            int n_cls, float keep_scale, uint32_t thr16, uint64_t seed,
-                                                            const uint8_t* __restrict__ mask, const uint64_t* __restrict__ seed_dev, int use_drop,
-                                                            float* __restrict__ out) {
-  if (seed_dev != nullptr) seed += *seed_dev;  // graph-captured steps: the varying part of the seed lives in device memory
-  extern __shared__ __attribute__((aligned(16))) float xs[];  // 64 * (C + 1) floats (sized by the launcher)
-  const int lane = threadIdx.x;
-  const int XS = C + 1, g4n = C >> 2;  // launcher guarantees C % 4 == 0
-  const long n_tiles = (pixels + 63) / 64;
-  for (long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    const long p0 = tile * 64;
-    __syncthreads();
-    for (int it = lane; it < 64 * g4n; it += 64) {
-      const int pl = it / g4n, gq = it - pl * g4n;
-      const long p = p0 + pl;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (p < pixels) {
-        v = *reinterpret_cast<const f32x4*>(x + p * C + 4 * gq);
-        if (use_drop) {
-          const uint64_t bits = (mask == nullptr) ? keep_bits(seed, p, g4n, gq) : 0;
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const bool keep = (mask != nullptr) ? (mask[p * C + 4 * gq + q] != 0) : keep_one(bits, q, thr16);
-            v[q] = keep ? v[q] * keep_scale : 0.f;
-          }
-        }
-      }
-      float* dst = &xs[pl * XS + 4 * gq];
-      dst[0] = v[0];
-      dst[1] = v[1];
-      dst[2] = v[2];
-      dst[3] = v[3];
-    }
-    __syncthreads();
-    const long p = p0 + lane;
-    float acc[kHeadMaxCls];
-#pragma unroll
-    for (int k = 0; k < kHeadMaxCls; ++k) acc[k] = (k < n_cls) ? bias[k] : 0.f;
-    for (int c = 0; c < C; ++c) {
-      const float v = xs[lane * XS + c];
-#pragma unroll
-      for (int k = 0; k < kHeadMaxCls; ++k)
-        if (k < n_cls) acc[k] += v * weight[k * C + c];
-    }
-    if (p < pixels) {
-      const long n = p / HW, hw = p - n * HW;
-#pragma unroll
-      for (int k = 0; k < kHeadMaxCls; ++k)
-        if (k < n_cls) out[(n * n_cls + k) * HW + hw] = 1.0f / (1.0f + expf(-acc[k]));
-    }
-  }
-}
-
-// One pixel's logits in the streaming layout (lane = (pixel, channel quad), G = 2^LOG2G lanes per pixel): the P per-class
-// partial dot products of the lane's quad, summed over the pixel's lanes by a reduce-scatter in a fixed order.  Returns
-// the total (without the bias) of class `cls`, the one this lane ends up with; G / P lanes (at least one) hold each class.
-// Shared by head_fwd_stream_kernel and heads_mean_stream_kernel: both produce the same bits for the same operands.
-template <int LOG2G, int P>
-__device__ __forceinline__ float head_pixel_logit(const f32x4& v, const f32x4 (&wq)[P], int gq, int& cls) {
-  constexpr int G = 1 << LOG2G;
-  float acc[P];
-#pragma unroll
-  for (int k = 0; k < P; ++k)
-    acc[k] = fmaf(v[0], wq[k][0], fmaf(v[1], wq[k][1], fmaf(v[2], wq[k][2], v[3] * wq[k][3])));
-  // reduce-scatter over the G lanes of the pixel: with `live` classes left, a lane keeps the half selected by its
-  // bit `off` and adds the partner's partials of that half; once one class is left, a plain butterfly sum
-  int c = 0;
-  static_for<LOG2G>([&](auto sc) {
-    constexpr int step = decltype(sc)::v, off = G >> (1 + step);
-    constexpr int live = (P >> step) > 1 ? (P >> step) : 1;  // classes a lane still carries before this step
-    if constexpr (live > 1) {
-      constexpr int half = live >> 1;
-      const bool upper = (gq & off) != 0;
-#pragma unroll
-      for (int i = 0; i < half; ++i) {
-        const float send = upper ? acc[i] : acc[half + i];
-        const float keep = upper ? acc[half + i] : acc[i];
-        acc[i] = keep + xor_lane<off>(send);
-      }
-      c += upper ? half : 0;
-    } else {
-      acc[0] += xor_lane<off>(acc[0]);
-    }
-  });
-  cls = c;
-  return acc[0];
-}
-
-// Forward head, streaming form for power-of-two channel-quad counts (C = 4 .. 128): lane = (pixel, channel quad), one
-// coalesced 16-byte load per item, the class weights of the quad in registers.  The P per-class partial dot products
-// of a lane are summed over the C/4 lanes of the pixel by a reduce-scatter (each exchange step halves the classes a
-// lane still carries: P-1 + log2(G/P) shuffles instead of P log2 G), fixed order.  No LDS tile, no transposition.
-// DROP: 0 = no dropout, 1 = keep flags from the counter hash, 2 = keep flags from a mask tensor -- three instantiations so
-// that the loop body is straight-line code (as one kernel it carried ~16 uniform branches per item).  32-bit element
-// offsets (the launcher takes this path for tensors below 2^31 elements); C = 4 G, so pixel -> element offset and
-// pixel -> hash counter are shifts; the (image, position) pair of the NCHW output is carried along instead of divided
-// out per item.
-template <int LOG2G, int P, int DROP>  // P = classes padded to a power of two (4 or 8), P <= G
-__global__ __launch_bounds__(kThreads) void head_fwd_stream_kernel(const float* __restrict__ x, const float* __restrict__ weight,
-                                                                   const float* __restrict__ bias, unsigned pixels, unsigned HW,
-                                                                   int n_cls, float keep_scale, uint32_t thr16, uint64_t seed,
-                                                                   const uint8_t* __restrict__ mask, const uint64_t* __restrict__ seed_dev, float* __restrict__ out) {
-  if (seed_dev != nullptr) seed += *seed_dev;  // graph-captured steps: the varying part of the seed lives in device memory
-  constexpr int G = 1 << LOG2G;  // lanes (channel quads) per pixel
-  const int gq = threadIdx.x & (G - 1);
-  f32x4 wq[P];
-#pragma unroll
-  for (int k = 0; k < P; ++k)
-    wq[k] = (k < n_cls) ? *reinterpret_cast<const f32x4*>(weight + k * 4 * G + 4 * gq) : f32x4{0.f, 0.f, 0.f, 0.f};
-  constexpr unsigned ppb = kThreads >> LOG2G;  // pixels per block and slot
-  constexpr int U = 4;                         // pixels per thread and iteration: 4 loads in flight
-  const unsigned span = gridDim.x * ppb, outer = U * span;
-  const unsigned pl = threadIdx.x >> LOG2G;
-  // (image, position) of this thread's first pixel and the step of one `span`, kept up to date by adds
-  const unsigned span_n = span / HW, span_hw = span - span_n * HW;
-  unsigned p0 = blockIdx.x * ppb + pl;
-  unsigned n0 = p0 / HW, hw0 = p0 - n0 * HW;
-  for (; p0 - pl < pixels; p0 += outer) {  // wave-uniform trip count
-    f32x4 v[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const unsigned p = p0 + u * span;
-      v[u] = (p < pixels) ? *reinterpret_cast<const f32x4*>(x + ((p << (LOG2G + 2)) + 4 * gq)) : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const unsigned p = p0 + u * span;
-      const bool valid = p < pixels;
-      if constexpr (DROP == 1) {
-        const uint64_t bits = keep_bits(seed, p, G, gq);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) v[u][q] = keep_one(bits, q, thr16) ? v[u][q] * keep_scale : 0.f;
-      } else if constexpr (DROP == 2) {
-        const uint32_t m4 = valid ? *reinterpret_cast<const uint32_t*>(mask + ((p << (LOG2G + 2)) + 4 * gq)) : 0u;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) v[u][q] = ((m4 >> (8 * q)) & 0xffu) != 0 ? v[u][q] * keep_scale : 0.f;
-      }
-      int cls;  // class this lane ends up with
-      const float logit = head_pixel_logit<LOG2G, P>(v[u], wq, gq, cls);
-      // this item's (image, position): u steps of `span` from the thread's first pixel of the iteration
-      unsigned n = n0 + u * span_n, hw = hw0 + u * span_hw;
-#pragma unroll
-      for (int c = 0; c < U - 1; ++c) {  // at most u carries
-        const bool carry = c < u && hw >= HW;
-        hw -= carry ? HW : 0u;
-        n += carry ? 1u : 0u;
-      }
-      constexpr int kDup = (G > P) ? G / P : 1;  // lanes that end with the same class total
-      if (valid && cls < n_cls && (gq & (kDup - 1)) == 0)
-        out[(static_cast<long>(n) * n_cls + cls) * HW + hw] = 1.0f / (1.0f + __expf(-(logit + bias[cls])));
-    }
-    // advance the carried position by U spans
-    n0 += U * span_n;
-    hw0 += U * span_hw;
-#pragma unroll
-    for (int c = 0; c < U; ++c) {
-      const bool carry = hw0 >= HW;
-      hw0 -= carry ? HW : 0u;
-      n0 += carry ? 1u : 0u;
-    }
-  }
-}
-
-// Ensemble head (unetpp_heads_mean_fwd), streaming form: the layout, the loop and the per-pixel logit of
-// head_fwd_stream_kernel without dropout, with the heads as an inner loop -- for every iteration's U pixels each head's
-// quad is loaded once (16 bytes), its class weights come from the L1-resident [n_cls, C] table (no LDS tile), and the
-// sigmoids are added in head order; the mean is stored once.  32-bit element offsets (launcher: < 2^31 elements).
-template <int LOG2G, int P>
-__global__ __launch_bounds__(kThreads) void heads_mean_stream_kernel(const unetpp_heads_mean hd, unsigned pixels, unsigned HW,
-                                                                     int n_cls, float* __restrict__ out) {
-  constexpr int G = 1 << LOG2G;
-  const int gq = threadIdx.x & (G - 1);
-  constexpr unsigned ppb = kThreads >> LOG2G;
-  constexpr int U = 4;
-  const unsigned span = gridDim.x * ppb, outer = U * span;
-  const unsigned pl = threadIdx.x >> LOG2G;
-  const unsigned span_n = span / HW, span_hw = span - span_n * HW;
-  const int n_heads = hd.n_heads;
-  const float count = static_cast<float>(n_heads);
-  unsigned p0 = blockIdx.x * ppb + pl;
-  unsigned n0 = p0 / HW, hw0 = p0 - n0 * HW;
-  for (; p0 - pl < pixels; p0 += outer) {  // wave-uniform trip count
-    float sum[U] = {0.f, 0.f, 0.f, 0.f};  // 0 + s_1 is s_1: the sum is ((s_1 + s_2) + ...) in head order
-    int cls = 0;
-    for (int h = 0; h < n_heads; ++h) {
-      const float* __restrict__ x = static_cast<const float*>(hd.head[h].x);
-      const float* __restrict__ weight = hd.head[h].weight;
-      f32x4 v[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const unsigned p = p0 + u * span;
-        v[u] = (p < pixels) ? *reinterpret_cast<const f32x4*>(x + ((p << (LOG2G + 2)) + 4 * gq)) : f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-      f32x4 wq[P];
-#pragma unroll
-      for (int k = 0; k < P; ++k)
-        wq[k] = (k < n_cls) ? *reinterpret_cast<const f32x4*>(weight + k * 4 * G + 4 * gq) : f32x4{0.f, 0.f, 0.f, 0.f};
-      float logit[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) logit[u] = head_pixel_logit<LOG2G, P>(v[u], wq, gq, cls);
-      const float b = cls < n_cls ? hd.head[h].bias[cls] : 0.f;
-#pragma unroll
-      for (int u = 0; u < U; ++u) sum[u] += 1.0f / (1.0f + __expf(-(logit[u] + b)));
-    }
-    constexpr int kDup = (G > P) ? G / P : 1;  // lanes that end with the same class total
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      unsigned n = n0 + u * span_n, hw = hw0 + u * span_hw;
-#pragma unroll
-      for (int c = 0; c < U - 1; ++c) {  // at most u carries
-        const bool carry = c < u && hw >= HW;
-        hw -= carry ? HW : 0u;
-        n += carry ? 1u : 0u;
-      }
-      if (p0 + u * span < pixels && cls < n_cls && (gq & (kDup - 1)) == 0)
-        out[(static_cast<long>(n) * n_cls + cls) * HW + hw] = sum[u] / count;
-    }
-    n0 += U * span_n;
-    hw0 += U * span_hw;
-#pragma unroll
-    for (int c = 0; c < U; ++c) {
-      const bool carry = hw0 >= HW;
-      hw0 -= carry ? HW : 0u;
-      n0 += carry ? 1u : 0u;
-    }
-  }
-}
-
-// tile = 64 consecutive pixels.  LDS: x*keep*scale [64][C+1], dlogit [64][8], W [8][C].
-__global__ __launch_bounds__(kThreads) void head_bwd_kernel(const float* __restrict__ d_out, const float* __restrict__ outp,
-                                                            const float* __restrict__ x, const float* __restrict__ weight,
-                                                            long pixels, int HW, int C, int n_cls, float keep_scale,
-                                                            uint32_t thr16, uint64_t seed, const uint8_t* __restrict__ mask, const uint64_t* __restrict__ seed_dev,
-                                                            int use_drop, float* __restrict__ dx, int accumulate, int gate_x,
-                                                            float* __restrict__ partial) {
-  if (seed_dev != nullptr) seed += *seed_dev;  // graph-captured steps: the varying part of the seed lives in device memory
-  __shared__ float xs[64 * (kHeadMaxC + 1)];
-  __shared__ float dl[64 * kHeadMaxCls];
-  __shared__ float wsm[kHeadMaxCls * kHeadMaxC];
-  const int tid = threadIdx.x;
-  const int XS = C + 1;
-  const int g4n = (C + 3) >> 2;
-  for (int i = tid; i < n_cls * C; i += kThreads) wsm[i] = weight[i];
-  float wacc[4] = {0.f, 0.f, 0.f, 0.f};  // dW entries tid, tid+256, ... (n_cls*C <= 1024)
-  float bacc = 0.f;                      // db entry tid (< n_cls)
-  const long n_tiles = (pixels + 63) / 64;
-  for (long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    const long p0 = tile * 64;
-    __syncthreads();
-    // dlogit = d_out * out * (1 - out)
-    for (int it = tid; it < 64 * n_cls; it += kThreads) {
-      const int pl = it & 63, k = it >> 6;
-      const long p = p0 + pl;
-      float v = 0.f;
-      if (p < pixels) {
-        const long n = p / HW, hw = p - n * HW;
-        const long o = (n * n_cls + k) * HW + hw;
-        const float pr = outp[o];
-        v = d_out[o] * pr * (1.f - pr);
-      }
-      dl[pl * kHeadMaxCls + k] = v;
-    }
-    // x * keep * scale
-    for (int it = tid; it < 64 * C; it += kThreads) {
-      const int pl = it / C, c = it - pl * C;
-      const long p = p0 + pl;
-      float v = 0.f;
-      if (p < pixels) {
-        v = x[p * C + c];
-        if (use_drop) {
-          const bool keep = (mask != nullptr) ? (mask[p * C + c] != 0)
-                                              : keep_one(keep_bits(seed, p, g4n, c >> 2), c & 3, thr16);
-          v = keep ? v * keep_scale : 0.f;
-        }
-      }
-      xs[pl * XS + c] = v;
-    }
-    __syncthreads();
-    // dx[p, c] = keep * scale * sum_k W[k, c] * dlogit[p, k]
-    for (int it = tid; it < 64 * C; it += kThreads) {
-      const int pl = it / C, c = it - pl * C;
-      const long p = p0 + pl;
-      if (p < pixels) {
-        float s = 0.f;
-#pragma unroll
-        for (int k = 0; k < kHeadMaxCls; ++k)
-          if (k < n_cls) s += wsm[k * C + c] * dl[pl * kHeadMaxCls + k];
-        if (use_drop) {
-          const bool keep = (mask != nullptr) ? (mask[p * C + c] != 0)
-                                              : keep_one(keep_bits(seed, p, g4n, c >> 2), c & 3, thr16);
-          s = keep ? s * keep_scale : 0.f;
-        }
-        if (accumulate) s += dx[p * C + c];
-        if (gate_x) s = (x[p * C + c] > 0.f) ? s : 0.f;
-        dx[p * C + c] = s;
-      }
-    }
-    // dW[k, c] += sum_p dlogit[p, k] * xs[p, c];  db[k] += sum_p dlogit[p, k]
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int idx = tid + q * kThreads;
-      if (idx < n_cls * C) {
-        const int k = idx / C, c = idx - k * C;
-        float s = 0.f;
-        for (int pl = 0; pl < 64; ++pl) s += dl[pl * kHeadMaxCls + k] * xs[pl * XS + c];
-        wacc[q] += s;
-      }
-    }
-    if (tid < n_cls) {
-      float s = 0.f;
-      for (int pl = 0; pl < 64; ++pl) s += dl[pl * kHeadMaxCls + tid];
-      bacc += s;
-    }
-  }
-  float* dst = partial + static_cast<long>(blockIdx.x) * (n_cls * C + n_cls);
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int idx = tid + q * kThreads;
-    if (idx < n_cls * C) dst[idx] = wacc[q];
-  }
-  if (tid < n_cls) dst[n_cls * C + tid] = bacc;
-}
-
-// Backward head, vectorised (C % 4 == 0): per 64-pixel tile
-//   1. dlogit = d_out * out * (1 - out)                    (NCHW reads, coalesced along pixels) -> LDS
-//   2. one pass over x in 16-byte pieces: dropout keep mask from ONE hash per piece, x*keep*scale -> LDS for
-//      the weight gradient, and dx = keep*scale * (W^T dlogit) (+ old dx, ReLU gate) written straight back
-//   3. dW[k, c] += sum_p dlogit[p, k] * xs[p, c]: all 256 threads, two pixel halves per (k, c)
-// Dynamic LDS: xs [64][C+1] | dlogit [64][8] | W [8][C] | scratch [2][n_cls*C].
-// (launch bound of 4 waves per SIMD: left alone hipcc unrolls the reduction loops into 256 VGPRs and the kernel
-// runs at 2 workgroups per CU, latency-bound at 1 TB/s)
-__global__ __launch_bounds__(kThreads, 4) void head_bwd_vec_kernel(const float* __restrict__ d_out,
-                                                                const float* __restrict__ outp,
-                                                                const float* __restrict__ x,
-                                                                const float* __restrict__ weight, long pixels, int HW,
-                                                                int C, int n_cls, float keep_scale, uint32_t thr16,
-                                                                uint64_t seed, const uint8_t* __restrict__ mask, const uint64_t* __restrict__ seed_dev,
-                                                                int use_drop, float* __restrict__ dx, int accumulate,
-                                                                int gate_x, float* __restrict__ partial) {
-  if (seed_dev != nullptr) seed += *seed_dev;  // graph-captured steps: the varying part of the seed lives in device memory
-  extern __shared__ __attribute__((aligned(16))) float hsm[];
-  const int XS = C + 1, g4n = C >> 2, NW = n_cls * C;
-  float* xs = hsm;
-  float* dl = xs + 64 * XS;
-  float* wsm = dl + 64 * kHeadMaxCls;
-  float* scratch = wsm + kHeadMaxCls * C;
-  const int tid = threadIdx.x;
-  for (int i = tid; i < NW; i += kThreads) wsm[i] = weight[i];
-  constexpr int kMaxPairs = (kHeadMaxCls * kHeadMaxC + 127) / 128;  // (k, c) pairs per thread
-  float wacc[kMaxPairs];
-#pragma unroll
-  for (int q = 0; q < kMaxPairs; ++q) wacc[q] = 0.f;
-  float bacc = 0.f;
-  const int pair0 = tid & 127, half = tid >> 7;
-  const long n_tiles = (pixels + 63) / 64;
-  for (long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    const long p0 = tile * 64;
-    __syncthreads();
-    for (int it = tid; it < 64 * n_cls; it += kThreads) {
-      const int pl = it & 63, k = it >> 6;
-      const long p = p0 + pl;
-      float v = 0.f;
-      if (p < pixels) {
-        const long n = p / HW, hw = p - n * HW;
-        const long o = (n * n_cls + k) * HW + hw;
-        const float pr = outp[o];
-        v = d_out[o] * pr * (1.f - pr);
-      }
-      dl[pl * kHeadMaxCls + k] = v;
-    }
-    __syncthreads();
-    for (int it = tid; it < 64 * g4n; it += kThreads) {
-      const int pl = it / g4n, gq = it - pl * g4n;
-      const long p = p0 + pl;
-      f32x4 xv = {0.f, 0.f, 0.f, 0.f};
-      float ms[4] = {1.f, 1.f, 1.f, 1.f};
-      if (p < pixels) {
-        xv = *reinterpret_cast<const f32x4*>(x + p * C + 4 * gq);
-        if (use_drop) {
-          const uint64_t bits = (mask == nullptr) ? keep_bits(seed, p, g4n, gq) : 0;
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const bool keep = (mask != nullptr) ? (mask[p * C + 4 * gq + q] != 0) : keep_one(bits, q, thr16);
-            ms[q] = keep ? keep_scale : 0.f;
-          }
-        }
-        f32x4 s = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int k = 0; k < kHeadMaxCls; ++k) {
-          if (k < n_cls) {
-            const float dk = dl[pl * kHeadMaxCls + k];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) s[q] += wsm[k * C + 4 * gq + q] * dk;
-          }
-        }
-        float* dst = dx + p * C + 4 * gq;
-        f32x4 old = {0.f, 0.f, 0.f, 0.f};
-        if (accumulate) old = *reinterpret_cast<const f32x4*>(dst);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          float v = s[q] * ms[q] + old[q];
-          if (gate_x) v = (xv[q] > 0.f) ? v : 0.f;
-          s[q] = v;
-        }
-        *reinterpret_cast<f32x4*>(dst) = s;
-      }
-      float* xd = &xs[pl * XS + 4 * gq];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) xd[q] = xv[q] * ms[q];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < kMaxPairs; ++q) {
-      const int idx = pair0 + q * 128;
-      if (idx < NW) {
-        const int k = idx / C, c = idx - k * C;
-        float s = 0.f;
-#pragma unroll 4
-        for (int pl = 32 * half; pl < 32 * half + 32; ++pl) s += dl[pl * kHeadMaxCls + k] * xs[pl * XS + c];
-        wacc[q] += s;
-      }
-    }
-    if (tid < n_cls) {
-      float s = 0.f;
-      for (int pl = 0; pl < 64; ++pl) s += dl[pl * kHeadMaxCls + tid];
-      bacc += s;
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < kMaxPairs; ++q) {
-    const int idx = pair0 + q * 128;
-    if (idx < NW) scratch[half * NW + idx] = wacc[q];
-  }
-  __syncthreads();
-  float* dst = partial + static_cast<long>(blockIdx.x) * (NW + n_cls);
-  for (int i = tid; i < NW; i += kThreads) dst[i] = scratch[i] + scratch[NW + i];
-  if (tid < n_cls) dst[NW + tid] = bacc;
-}
-
-// The same for C = 4 * 2^LOG2G channels and tensors below 2^31 elements (every configuration of the reference): the
-// index arithmetic is shifts and 32-bit, a thread's channel quad is the same for all its pieces so its class weights
-// live in registers (the general kernel re-reads them from LDS per piece: 16 + 4 LDS reads per 16 bytes of x), the
-// (class, channel) pairs of the weight-gradient pass are decoded once instead of once per tile, and the dropout mode is
-// a template parameter (0 none, 1 counter hash, 2 mask tensor) so that the piece loop is straight-line code.
-template <int LOG2G, int DROP, int PCLS>  // PCLS = classes padded to 4 or 8 (zero weights past n_cls: no class branches)
-__global__ __launch_bounds__(kThreads, 4) void head_bwd_pow2_kernel(const float* __restrict__ d_out,
-                                                                 const float* __restrict__ outp,
-                                                                 const float* __restrict__ x,
-                                                                 const float* __restrict__ weight, unsigned pixels,
-                                                                 unsigned HW, int n_cls, float keep_scale, uint32_t thr16,
-                                                                 uint64_t seed, const uint8_t* __restrict__ mask, const uint64_t* __restrict__ seed_dev,
-                                                                 float* __restrict__ dx, int accumulate, int gate_x,
-                                                                 float* __restrict__ partial) {
-  if (seed_dev != nullptr) seed += *seed_dev;  // graph-captured steps: the varying part of the seed lives in device memory
-  extern __shared__ __attribute__((aligned(16))) float hsm[];
-  constexpr int G = 1 << LOG2G, C = 4 * G, XS = C + 1;
-  constexpr int ITEMS = (64 * G + kThreads - 1) / kThreads;  // 16-byte pieces of a 64-pixel tile per thread
-  const int NW = n_cls * C;
-  float* xs = hsm;
-  float* dl = xs + 64 * XS;
-  float* scratch = dl + 64 * kHeadMaxCls;
-  const int tid = threadIdx.x;
-  const int gq = tid & (G - 1);  // channel quad of every piece of this thread (kThreads is a multiple of G)
-  f32x4 wq[PCLS];
-#pragma unroll
-  for (int k = 0; k < PCLS; ++k)
-    wq[k] = (k < n_cls) ? *reinterpret_cast<const f32x4*>(weight + k * C + 4 * gq) : f32x4{0.f, 0.f, 0.f, 0.f};
-  constexpr int kMaxPairs = (PCLS * C + 127) / 128;  // (k, c) pairs per thread
-  float wacc[kMaxPairs];
-  int pair_k[kMaxPairs], pair_c[kMaxPairs];
-  const int pair0 = tid & 127, half = tid >> 7;
-#pragma unroll
-  for (int q = 0; q < kMaxPairs; ++q) {
-    wacc[q] = 0.f;
-    const int idx = pair0 + q * 128;
-    pair_k[q] = idx >> (LOG2G + 2);
-    pair_c[q] = idx & (C - 1);
-  }
-  float bacc = 0.f;
-  for (int i = tid; i < 64 * kHeadMaxCls; i += kThreads) dl[i] = 0.f;  // classes past n_cls are never written again
-  const unsigned n_tiles = (pixels + 63) / 64;
-  for (unsigned tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    const unsigned p0 = tile * 64;
-    __syncthreads();
-    for (int it = tid; it < 64 * n_cls; it += kThreads) {
-      const int pl = it & 63, k = it >> 6;
-      const unsigned p = p0 + pl;
-      float v = 0.f;
-      if (p < pixels) {
-        const unsigned n = p / HW, hw = p - n * HW;
-        const long o = (static_cast<long>(n) * n_cls + k) * HW + hw;
-        const float pr = outp[o];
-        v = d_out[o] * pr * (1.f - pr);
-      }
-      dl[pl * kHeadMaxCls + k] = v;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < ITEMS; ++u) {
-      const int it = tid + u * kThreads;
-      if (ITEMS * kThreads != 64 * G && it >= 64 * G) break;
-      const int pl = it >> LOG2G;
-      const unsigned p = p0 + pl;
-      f32x4 xv = {0.f, 0.f, 0.f, 0.f};
-      float ms[4] = {1.f, 1.f, 1.f, 1.f};
-      if (p < pixels) {
-        const unsigned off = (p << (LOG2G + 2)) + 4 * gq;
-        xv = *reinterpret_cast<const f32x4*>(x + off);
-        if constexpr (DROP == 1) {
-          const uint64_t bits = keep_bits(seed, p, G, gq);
-#pragma unroll
-          for (int q = 0; q < 4; ++q) ms[q] = keep_one(bits, q, thr16) ? keep_scale : 0.f;
-        } else if constexpr (DROP == 2) {
-          const uint32_t m4 = *reinterpret_cast<const uint32_t*>(mask + off);
-#pragma unroll
-          for (int q = 0; q < 4; ++q) ms[q] = ((m4 >> (8 * q)) & 0xffu) != 0 ? keep_scale : 0.f;
-        }
-        f32x4 sacc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int k = 0; k < PCLS; ++k) {
-          const float dk = dl[pl * kHeadMaxCls + k];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) sacc[q] += wq[k][q] * dk;
-        }
-        f32x4 old = {0.f, 0.f, 0.f, 0.f};
-        if (accumulate) old = *reinterpret_cast<const f32x4*>(dx + off);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          float v = sacc[q] * ms[q] + old[q];
-          if (gate_x) v = (xv[q] > 0.f) ? v : 0.f;
-          sacc[q] = v;
-        }
-        *reinterpret_cast<f32x4*>(dx + off) = sacc;
-      }
-      float* xd = &xs[pl * XS + 4 * gq];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) xd[q] = xv[q] * ms[q];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < kMaxPairs; ++q) {
-      if (pair0 + q * 128 < NW) {
-        const int k = pair_k[q], c = pair_c[q];
-        float sum = 0.f;
-#pragma unroll 4
-        for (int pl = 32 * half; pl < 32 * half + 32; ++pl) sum += dl[pl * kHeadMaxCls + k] * xs[pl * XS + c];
-        wacc[q] += sum;
-      }
-    }
-    if (tid < n_cls) {
-      float sum = 0.f;
-      for (int pl = 0; pl < 64; ++pl) sum += dl[pl * kHeadMaxCls + tid];
-      bacc += sum;
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < kMaxPairs; ++q) {
-    const int idx = pair0 + q * 128;
-    if (idx < NW) scratch[half * NW + idx] = wacc[q];
-  }
-  __syncthreads();
-  float* dst = partial + static_cast<long>(blockIdx.x) * (NW + n_cls);
-  for (int i = tid; i < NW; i += kThreads) dst[i] = scratch[i] + scratch[NW + i];
-  if (tid < n_cls) dst[NW + tid] = bacc;
-}
-
 __global__ void sum_partials_kernel(const float* __restrict__ partial, long n_blocks, long len, float* __restrict__ out) {
   // 16 outputs x 64 row groups per workgroup (1024 threads): a thread adds n_blocks / 64 rows (4 loads in flight);
   // the groups are combined through LDS in fixed order.  fp64 sums: thousands of same-sign partials.
@@ -1343,13 +722,11 @@ inline const char* fin_label(long n_blocks, const char* l256, const char* l512, 
   const unsigned t = fin_threads(n_blocks);
   return t == 1024u ? l1024 : t == 512u ? l512 : l256;
 }
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 }  // namespace unetpp
 
 using namespace unetpp;
-#define ST(s) static_cast<hipStream_t>(s)
 
 extern "C" int unetpp_bn_finalize(const float* partial, int64_t n_blocks, int32_t C, int64_t count, const float* gamma,
                                   const float* beta, float eps, float momentum, float* running_mean,
@@ -1721,186 +1098,6 @@ extern "C" int unetpp_bn_frozen_bwd(const float* d_act, const float* y, const fl
       UNETPP_FROZEN(1, false);
   }
 #undef UNETPP_FROZEN
-  return launch_status();
-}
-
-namespace {
-inline bool head_args_ok(int N, int H, int W, int C, int n_cls, float p_drop) {
-  return N >= 1 && H >= 1 && W >= 1 && C >= 1 && C <= kHeadMaxC && n_cls >= 1 && n_cls <= kHeadMaxCls &&
-         p_drop >= 0.f && p_drop < 1.f;
-}
-}  // namespace
-
-extern "C" int unetpp_head_fwd(const float* x, const float* weight, const float* bias, int32_t N, int32_t H, int32_t W,
-                               int32_t C, int32_t n_cls, float p_drop, uint64_t seed, const uint8_t* mask, const uint64_t* seed_dev,
-                               float* out_nchw, void* stream) {
-  if (!x || !weight || !bias || !out_nchw || !head_args_ok(N, H, W, C, n_cls, p_drop)) return UNETPP_EINVAL;
-  const long pixels = static_cast<long>(N) * H * W;
-  const int use_drop = p_drop > 0.f;
-  const int g4 = C >> 2;
-  const int pcls = n_cls <= 4 ? 4 : 8;
-  if ((C & 3) == 0 && aligned16(x) && aligned16(weight) && (g4 & (g4 - 1)) == 0 && g4 <= 32 && pcls <= g4 && pixels * C < 0x7fffffffL &&
-      (mask == nullptr || (reinterpret_cast<uintptr_t>(mask) & 3) == 0)) {
-    const long ppb = kThreads / g4;
-    const long want = (pixels + ppb - 1) / ppb;
-    const dim3 grid(static_cast<unsigned>(want < 256 * 16 ? want : 256 * 16));
-#define UNETPP_HEAD_STREAM_D(L, PC, D)                                                                                \
-  do {                                                                                                              \
-    note_kernel("head_fwd_stream<" #L "," #PC "," #D ">");                                                          \
-    hipLaunchKernelGGL((head_fwd_stream_kernel<L, PC, D>), grid, dim3(kThreads), 0, ST(stream), x, weight, bias,     \
-                       static_cast<unsigned>(pixels), static_cast<unsigned>(H * W), n_cls, 1.0f / (1.0f - p_drop),    \
-                       keep_threshold(p_drop), seed, mask, seed_dev, out_nchw);                                     \
-  } while (0)
-#define UNETPP_HEAD_STREAM(L, PC)                              \
-  do {                                                         \
-    if (!use_drop) UNETPP_HEAD_STREAM_D(L, PC, 0);             \
-    else if (mask == nullptr) UNETPP_HEAD_STREAM_D(L, PC, 1);  \
-    else UNETPP_HEAD_STREAM_D(L, PC, 2);                       \
-  } while (0)
-    if (pcls == 4) {
-      switch (g4) {
-        case 4: UNETPP_HEAD_STREAM(2, 4); break;
-        case 8: UNETPP_HEAD_STREAM(3, 4); break;
-        case 16: UNETPP_HEAD_STREAM(4, 4); break;
-        default: UNETPP_HEAD_STREAM(5, 4); break;
-      }
-    } else {
-      switch (g4) {
-        case 8: UNETPP_HEAD_STREAM(3, 8); break;
-        case 16: UNETPP_HEAD_STREAM(4, 8); break;
-        default: UNETPP_HEAD_STREAM(5, 8); break;
-      }
-    }
-#undef UNETPP_HEAD_STREAM
-#undef UNETPP_HEAD_STREAM_D
-    return launch_status();
-  }
-  if ((C & 3) == 0 && aligned16(x)) {
-    const long tiles = (pixels + 63) / 64;
-    const unsigned blocks = static_cast<unsigned>(tiles < 256 * 16 ? tiles : 256 * 16);
-    note_kernel("head_fwd_tiled");
-    hipLaunchKernelGGL(head_fwd_tiled_kernel, dim3(blocks), dim3(64), 64 * (C + 1) * sizeof(float), ST(stream), x, weight,
-                       bias, pixels, H * W, C,
-                       n_cls, 1.0f / (1.0f - p_drop), keep_threshold(p_drop), seed, mask, seed_dev, use_drop, out_nchw);
-    return launch_status();
-  }
-  note_kernel("head_fwd");
-  hipLaunchKernelGGL(head_fwd_kernel, dim3(grid_for(pixels)), dim3(kThreads), 0, ST(stream), x, weight, bias, pixels,
-                     H * W, C, n_cls, 1.0f / (1.0f - p_drop), keep_threshold(p_drop), seed, mask, seed_dev, use_drop, out_nchw);
-  return launch_status();
-}
-
-/* ---- ensemble head: mean of the first n_heads sigmoid heads in one pass (eval only) ---- */
-extern "C" int unetpp_heads_mean_fwd(const unetpp_heads_mean* heads, int32_t N, int32_t H, int32_t W, int32_t C,
-                                     int32_t n_cls, float* out_nchw, void* stream) {
-  if (!heads || !out_nchw || heads->n_heads < 1 || heads->n_heads > UNETPP_MAX_HEADS || !head_args_ok(N, H, W, C, n_cls, 0.f))
-    return UNETPP_EINVAL;
-  bool vec = (C & 3) == 0;
-  for (int h = 0; h < heads->n_heads; ++h) {
-    const unetpp_head_src& s = heads->head[h];
-    if (!s.x || !s.weight || !s.bias) return UNETPP_EINVAL;
-    vec = vec && aligned16(s.x) && aligned16(s.weight);
-  }
-  const long pixels = static_cast<long>(N) * H * W;
-  const int g4 = C >> 2;
-  const int pcls = n_cls <= 4 ? 4 : 8;
-  // the stream form addresses elements with 32 bits: it never takes a tensor of 2^31 elements or more
-  if (vec && (g4 & (g4 - 1)) == 0 && g4 <= 32 && pcls <= g4 && pixels * C < 0x7fffffffL) {
-    const long ppb = kThreads / g4;
-    const long want = (pixels + ppb - 1) / ppb;
-    const dim3 grid(static_cast<unsigned>(want < 256 * 16 ? want : 256 * 16));
-#define UNETPP_HEADS_MEAN(L, PC)                                                                                      \
-  do {                                                                                                                \
-    note_kernel("heads_mean_stream<" #L "," #PC ">");                                                                 \
-    hipLaunchKernelGGL((heads_mean_stream_kernel<L, PC>), grid, dim3(kThreads), 0, ST(stream), *heads,                 \
-                       static_cast<unsigned>(pixels), static_cast<unsigned>(H * W), n_cls, out_nchw);                 \
-  } while (0)
-    if (pcls == 4) {
-      switch (g4) {
-        case 4: UNETPP_HEADS_MEAN(2, 4); break;
-        case 8: UNETPP_HEADS_MEAN(3, 4); break;
-        case 16: UNETPP_HEADS_MEAN(4, 4); break;
-        default: UNETPP_HEADS_MEAN(5, 4); break;
-      }
-    } else {
-      switch (g4) {
-        case 8: UNETPP_HEADS_MEAN(3, 8); break;
-        case 16: UNETPP_HEADS_MEAN(4, 8); break;
-        default: UNETPP_HEADS_MEAN(5, 8); break;
-      }
-    }
-#undef UNETPP_HEADS_MEAN
-    return launch_status();
-  }
-  note_kernel("heads_mean");
-  hipLaunchKernelGGL(heads_mean_general_kernel<float>, dim3(grid_for(pixels)), dim3(kThreads), 0, ST(stream), *heads, pixels, H * W, C,
-                     n_cls, out_nchw);
-  return launch_status();
-}
-
-extern "C" int64_t unetpp_head_bwd_blocks(int64_t pixels) {
-  if (pixels < 1) return 0;
-  const long tiles = (pixels + 63) / 64;
-  return tiles < 4096 ? tiles : 4096;  // 16 workgroups per CU: the tile loop is a chain of dependent loads, occupancy hides it
-}
-
-extern "C" int unetpp_head_bwd(const float* d_out_nchw, const float* out_nchw, const float* x, const float* weight,
-                               int32_t N, int32_t H, int32_t W, int32_t C, int32_t n_cls, float p_drop, uint64_t seed,
-                               const uint8_t* mask, const uint64_t* seed_dev, float* dx, int32_t accumulate, int32_t gate_x, float* partial,
-                               void* stream) {
-  if (!d_out_nchw || !out_nchw || !x || !weight || !dx || !partial || !head_args_ok(N, H, W, C, n_cls, p_drop))
-    return UNETPP_EINVAL;
-  const long pixels = static_cast<long>(N) * H * W;
-  const int use_drop = p_drop > 0.f;
-  const int g4 = C >> 2;
-  if ((C & 3) == 0 && aligned16(x) && aligned16(dx) && aligned16(weight) && (g4 & (g4 - 1)) == 0 && g4 >= 2 && g4 <= 32 &&
-      pixels * C < 0x7fffffffL && (mask == nullptr || (reinterpret_cast<uintptr_t>(mask) & 3) == 0)) {
-    const size_t lds = (64 * (C + 1) + 64 * kHeadMaxCls + 2 * n_cls * C) * sizeof(float);
-    const dim3 grid(static_cast<unsigned>(unetpp_head_bwd_blocks(pixels)));
-    const int drop = !use_drop ? 0 : (mask == nullptr ? 1 : 2);
-#define UNETPP_HEAD_BWD(L, D)                    \
-  do {                                           \
-    if (n_cls <= 4) UNETPP_HEAD_BWD_P(L, D, 4);  \
-    else UNETPP_HEAD_BWD_P(L, D, 8);             \
-  } while (0)
-#define UNETPP_HEAD_BWD_P(L, D, PC)                                                                                   \
-  do {                                                                                                              \
-    note_kernel("head_bwd_pow2<" #L "," #D "," #PC ">");                                                            \
-    hipLaunchKernelGGL((head_bwd_pow2_kernel<L, D, PC>), grid, dim3(kThreads), lds, ST(stream), d_out_nchw, out_nchw, \
-                       x, weight, static_cast<unsigned>(pixels), static_cast<unsigned>(H * W), n_cls,                \
-                       1.0f / (1.0f - p_drop), keep_threshold(p_drop), seed, mask, seed_dev, dx, accumulate, gate_x,  \
-                       partial);                                                                                    \
-  } while (0)
-#define UNETPP_HEAD_BWD_L(L)              \
-  do {                                    \
-    if (drop == 0) UNETPP_HEAD_BWD(L, 0); \
-    else if (drop == 1) UNETPP_HEAD_BWD(L, 1); \
-    else UNETPP_HEAD_BWD(L, 2);           \
-  } while (0)
-    switch (g4) {
-      case 2: UNETPP_HEAD_BWD_L(1); break;
-      case 4: UNETPP_HEAD_BWD_L(2); break;
-      case 8: UNETPP_HEAD_BWD_L(3); break;
-      case 16: UNETPP_HEAD_BWD_L(4); break;
-      default: UNETPP_HEAD_BWD_L(5); break;
-    }
-#undef UNETPP_HEAD_BWD_L
-#undef UNETPP_HEAD_BWD
-#undef UNETPP_HEAD_BWD_P
-    return launch_status();
-  }
-  if ((C & 3) == 0 && aligned16(x) && aligned16(dx)) {
-    const size_t lds = (64 * (C + 1) + 64 * kHeadMaxCls + kHeadMaxCls * C + 2 * n_cls * C) * sizeof(float);
-    note_kernel("head_bwd_vec");
-    hipLaunchKernelGGL(head_bwd_vec_kernel, dim3(static_cast<unsigned>(unetpp_head_bwd_blocks(pixels))), dim3(kThreads),
-                       lds, ST(stream), d_out_nchw, out_nchw, x, weight, pixels, H * W, C, n_cls, 1.0f / (1.0f - p_drop),
-                       keep_threshold(p_drop), seed, mask, seed_dev, use_drop, dx, accumulate, gate_x, partial);
-    return launch_status();
-  }
-  note_kernel("head_bwd");
-  hipLaunchKernelGGL(head_bwd_kernel, dim3(static_cast<unsigned>(unetpp_head_bwd_blocks(pixels))), dim3(kThreads), 0,
-                     ST(stream), d_out_nchw, out_nchw, x, weight, pixels, H * W, C, n_cls, 1.0f / (1.0f - p_drop),
-                     keep_threshold(p_drop), seed, mask, seed_dev, use_drop, dx, accumulate, gate_x, partial);
   return launch_status();
 }
 
