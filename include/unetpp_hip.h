@@ -432,6 +432,32 @@ int unetpp_heads_mean_fwd(const unetpp_heads_mean* heads, int32_t N, int32_t H, 
                           float* out_nchw, void* stream);
 int unetpp_heads_mean_fwd_bf16(const unetpp_heads_mean* heads, int32_t N, int32_t H, int32_t W, int32_t C,
                                int32_t n_cls, float* out_nchw, void* stream);
+/* ---- backward of the ensemble head (added within v13: new entry points only, nothing existing changes) ----
+ * `heads` is the descriptor of the forward, d_out_nchw the gradient of its fp32 NCHW [N,n_cls,H,W] mean.  Per pixel, class
+ * and head h:  z = bias_h + x_h . w_h,  s = 1 / (1 + exp(-z)),  dl = (d_out * (1.0f / n_heads)) * (s * (1 - s)),
+ *   dx_h = W_h^T dl,   dW_h += dl x_h^T,   db_h += dl.
+ * The head maps s_h are recomputed from the feature tile the kernel stages for the weight gradient; they are never read
+ * from or written to memory.  grads->head[h]: dx (NHWC, the features' storage type) is written, or added to when
+ * accumulate != 0; gate_x: after the (optional) accumulate, dx *= (x_h > 0) (unetpp_head_bwd's semantics); partial:
+ * unetpp_head_bwd_blocks(N*H*W) rows of [n_cls*C + n_cls], finished by unetpp_sum_partials (no floating-point atomics,
+ * fixed order: two runs give the same bits).  Accepts every (C, n_cls, alignment, size) that unetpp_head_bwd (fp32) or
+ * unetpp_head_bwd_bf16 (C = 8 * 2^k, 16-byte aligned x and dx, fewer than 2^31 - 1 pixels) accepts for one head, with
+ * 1 <= n_heads <= UNETPP_MAX_HEADS and grads->n_heads == heads->n_heads; anything else, a NULL pointer included, returns
+ * UNETPP_EINVAL without touching the device. */
+typedef struct unetpp_head_grad {
+  void* dx;        /* NHWC gradient of this head's features */
+  float* partial;  /* unetpp_head_bwd_blocks(N*H*W) rows of [n_cls*C + n_cls] */
+  int32_t accumulate, gate_x;
+} unetpp_head_grad;
+typedef struct unetpp_heads_mean_grad {
+  unetpp_head_grad head[UNETPP_MAX_HEADS];
+  int32_t n_heads, reserved;
+} unetpp_heads_mean_grad;
+int unetpp_heads_mean_bwd(const unetpp_heads_mean* heads, const unetpp_heads_mean_grad* grads, const float* d_out_nchw,
+                          int32_t N, int32_t H, int32_t W, int32_t C, int32_t n_cls, void* stream);
+int unetpp_heads_mean_bwd_bf16(const unetpp_heads_mean* heads, const unetpp_heads_mean_grad* grads,
+                               const float* d_out_nchw, int32_t N, int32_t H, int32_t W, int32_t C, int32_t n_cls,
+                               void* stream);
 /* create_heatmap (tools/misc/helper.py:87-172): key points [N][P][2] as (x, y), P >= 6 -> float32 [N,4,H,W]:
  * ch0 = point 0, ch1 = points 1..3 summed / max, ch2 = point 4, ch3 = points 5..P-1 summed / max, each map
  * exp(-0.5 sqrt(dx^2 + dy^2) / radius) (the reference uses radius 3).  workspace: unetpp_heatmap_workspace_bytes(). */

@@ -109,6 +109,16 @@ class HeadsMean(C.Structure):
     _fields_ = [("head", HeadSrc * MAX_HEADS), ("n_heads", C.c_int32), ("reserved", C.c_int32)]
 
 
+class HeadGrad(C.Structure):
+    """mirror of struct unetpp_head_grad"""
+    _fields_ = [("dx", C.c_void_p), ("partial", C.c_void_p), ("accumulate", C.c_int32), ("gate_x", C.c_int32)]
+
+
+class HeadsMeanGrad(C.Structure):
+    """mirror of struct unetpp_heads_mean_grad"""
+    _fields_ = [("head", HeadGrad * MAX_HEADS), ("n_heads", C.c_int32), ("reserved", C.c_int32)]
+
+
 class WgradDesc(C.Structure):
     """mirror of struct unetpp_wgrad_desc"""
     _fields_ = [
@@ -235,6 +245,10 @@ SIGNATURES = {
     # ensemble head of the eval forward (added within ABI 12)
     "unetpp_heads_mean_fwd": (C.c_int, [C.POINTER(HeadsMean), _I32, _I32, _I32, _I32, _I32, _P, _P]),
     "unetpp_heads_mean_fwd_bf16": (C.c_int, [C.POINTER(HeadsMean), _I32, _I32, _I32, _I32, _I32, _P, _P]),
+    # backward of the ensemble head (heads.hip; added within ABI 13)
+    "unetpp_heads_mean_bwd": (C.c_int, [C.POINTER(HeadsMean), C.POINTER(HeadsMeanGrad), _P, _I32, _I32, _I32, _I32, _I32, _P]),
+    "unetpp_heads_mean_bwd_bf16": (C.c_int, [C.POINTER(HeadsMean), C.POINTER(HeadsMeanGrad), _P, _I32, _I32, _I32, _I32, _I32,
+                                             _P]),
     # backward of a BatchNorm layer that normalised with its running statistics (added within ABI 12)
     "unetpp_bn_eval_coeffs_stats": (C.c_int, [_P, _P, _P, _P, _F, _I32, _P, _P, _P, _P, _P]),
     "unetpp_bn_frozen_bwd_blocks": (_I64, [_I64, _I32]),

@@ -121,7 +121,8 @@ def load_pruned(model, path: str, map_location: Optional[str] = "cpu") -> int:
     """Loads a ``save_pruned`` file into `model` and returns the head it was pruned to.  The file's key set must be exactly
     the pruned key set of some head of this model: any other missing or unexpected key is an error that names the keys.
     Records ``model.pruned_to = head``: from then on ``forward`` and ``infer(head > pruned_to)`` raise, because the nodes
-    that were not loaded still hold their initialisation; a full ``load_state_dict`` lifts that."""
+    that were not loaded still hold their initialisation; a full ``load_state_dict`` lifts that.  ``forward_pruned(x, head <=
+    pruned_to)`` / ``train_step(..., head=)`` train such a model, and ``save_pruned`` of it round-trips."""
     target = _unwrap(model)
     state = _strip_module_prefix(torch.load(path, map_location=map_location))
     own = target.state_dict()

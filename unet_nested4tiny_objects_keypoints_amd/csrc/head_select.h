@@ -1,7 +1,8 @@
 // The deep-supervision heads: head_select decides ONCE, from the arguments of a launcher, which kernel of heads.hip takes
 // the call and everything that follows from that -- every refusal and its return code, the form and the template
-// coordinates, grid, workgroup, dynamic LDS, the bf16 backward's `active` count and the label.  The six launchers of
-// heads.hip check their pointers, fill a HeadQuery and launch what the HeadSel says.  Host only (no HIP header):
+// coordinates, grid, workgroup, dynamic LDS, the bf16 backward's `active` count and the label.  The launchers of
+// heads.hip (six, and the two of the ensemble mean's backward) check their pointers, fill a HeadQuery and launch what the
+// HeadSel says.  Host only (no HIP header):
 // tests/test_head_select.py compiles it with a plain C++17 compiler.
 #pragma once
 #include <stddef.h>
@@ -16,7 +17,7 @@ constexpr int kHeadMaxCls = 8;
 constexpr int kHeadThreads = 256;     // kThreads (heads.hip asserts it)
 constexpr int kHeadTilePixels = 256;  // pixel tile of head_bwd_bf16_kernel up to 64 channels (128 pixels at 128 channels)
 
-enum HeadOp { HEAD_FWD, HEADS_MEAN, HEAD_BWD };
+enum HeadOp { HEAD_FWD, HEADS_MEAN, HEAD_BWD, HEADS_MEAN_BWD };  // HEADS_MEAN_BWD: unetpp_heads_mean_bwd[_bf16], one launch per head
 enum HeadForm {
   HEAD_STREAM,   // fp32 forward / mean: lane = (pixel, channel quad), C = 4 * 2^log2g
   HEAD_TILED,    // fp32 forward: 64-pixel LDS tiles, any C % 4 == 0
@@ -31,10 +32,10 @@ struct HeadQuery {
   HeadOp op;
   bool bf16;
   int N, H, W, C, n_cls;
-  int n_heads;    // HEADS_MEAN only
+  int n_heads;    // HEADS_MEAN and HEADS_MEAN_BWD only
   float p_drop;   // 0 for HEADS_MEAN
   bool has_mask;  // a mask pointer was given (whether or not p_drop uses it)
-  // low four address bits per pointer role; HEADS_MEAN: x and weight OR-ed over the heads
+  // low four address bits per pointer role; HEADS_MEAN: x and weight OR-ed over the heads (HEADS_MEAN_BWD: and dx)
   unsigned x_lo, weight_lo, dx_lo, mask_lo;
   long wgs_per_cu;  // OPT_HEAD_WGS_PER_CU value (bf16 backward only)
 };
@@ -81,9 +82,9 @@ inline int head_log2(int v) {
 template <class CusFn>
 inline int head_select_with(const HeadQuery& q, CusFn&& cus_fn, HeadSel& s) {
   s = HeadSel{};
-  const bool mean = q.op == HEADS_MEAN, bwd = q.op == HEAD_BWD;
+  const bool mean = q.op == HEADS_MEAN, bwd = q.op == HEAD_BWD, mean_bwd = q.op == HEADS_MEAN_BWD;
   if (q.N < 1 || q.H < 1 || q.W < 1 || q.C < 1 || q.C > kHeadMaxC || q.n_cls < 1 || q.n_cls > kHeadMaxCls ||
-      !(q.p_drop >= 0.f && q.p_drop < 1.f) || (mean && (q.n_heads < 1 || q.n_heads > UNETPP_MAX_HEADS)))
+      !(q.p_drop >= 0.f && q.p_drop < 1.f) || ((mean || mean_bwd) && (q.n_heads < 1 || q.n_heads > UNETPP_MAX_HEADS)))
     return UNETPP_EINVAL;
   const long pixels = static_cast<long>(q.N) * q.H * q.W;
   const bool x16 = (q.x_lo & 15) == 0, w16 = (q.weight_lo & 15) == 0, dx16 = (q.dx_lo & 15) == 0;
@@ -94,6 +95,28 @@ inline int head_select_with(const HeadQuery& q, CusFn&& cus_fn, HeadSel& s) {
   // both backward grids (and the rows of `partial`) are unetpp_head_bwd_blocks: 64-pixel tiles, 16 workgroups per CU --
   // the tile loop is a chain of dependent loads, occupancy hides it
   s.grid = static_cast<unsigned>(tiles64 < 4096 ? tiles64 : 4096);
+  if (mean_bwd) {
+    // Backward of the ensemble mean: heads_mean_bwd_kernel once per head, on head_bwd_vec's 64-pixel tiles and grid.  It
+    // takes what unetpp_head_bwd (fp32: anything, 16-byte pieces where rows and pointers allow) or unetpp_head_bwd_bf16
+    // (octets only) takes for one head; the mean has no dropout.  LDS: x tile | dlogit | W | scratch, as head_bwd_vec.
+    if (q.p_drop != 0.f) return UNETPP_EINVAL;
+    if (q.bf16) {
+      const int cg = q.C >> 3;
+      if ((q.C & 7) != 0 || !head_pow2(cg) || !x16 || !dx16 || pixels >= 0x7fffffffL) return UNETPP_EINVAL;
+      s.form = HEAD_OCTET;
+      s.log2g = head_log2(cg);
+      s.pcls = q.n_cls <= 4 ? 4 : q.n_cls <= 6 ? 6 : 8;
+      s.label = "heads_mean_bwd_bf16";
+    } else {
+      const bool vec = (q.C & 3) == 0 && x16 && dx16;
+      s.form = vec ? HEAD_VEC : HEAD_GENERIC;
+      s.pcls = q.n_cls <= 4 ? 4 : 8;
+      s.log2g = head_log2((q.C >> 2) > 0 ? (q.C >> 2) : 1);
+      s.label = vec ? "heads_mean_bwd_vec" : "heads_mean_bwd";
+    }
+    s.lds = (64 * (q.C + 1) + 64 * kHeadMaxCls + kHeadMaxCls * q.C + 2 * q.n_cls * q.C) * sizeof(float);
+    return UNETPP_OK;
+  }
   const int family = q.op + 3 * (q.bf16 ? 1 : 0);
 
   if (q.bf16) {

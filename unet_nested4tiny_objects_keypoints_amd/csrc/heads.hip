@@ -1,6 +1,7 @@
 // The deep-supervision heads, fp32 and bf16 storage side by side: dropout + 1x1 convolution + sigmoid forward
-// (unetpp_head_fwd[_bf16]), the ensemble mean of several heads (unetpp_heads_mean_fwd[_bf16], eval only) and the
-// backward (unetpp_head_bwd[_bf16]: feature gradient, per-workgroup partial rows of dW and db).  Features are NHWC,
+// (unetpp_head_fwd[_bf16]), the ensemble mean of several heads (unetpp_heads_mean_fwd[_bf16], no dropout), its backward
+// (unetpp_heads_mean_bwd[_bf16]: the head maps are recomputed, never read) and the backward of one head
+// (unetpp_head_bwd[_bf16]: feature gradient, per-workgroup partial rows of dW and db).  Features are NHWC,
 // probabilities fp32 NCHW (the loss stays fp32).  head_select (head_select.h) decides which kernel takes a call; the
 // launchers at the end check pointers, ask it and launch.
 #include "bf16_common.h"
@@ -895,6 +896,169 @@ __global__ __launch_bounds__(kThreads) void head_bwd_bf16_kernel(const float* __
     dst[NW + tid] = (red[PCLS * C + tid] + red[ROW + PCLS * C + tid]) + (red[2 * ROW + PCLS * C + tid] + red[3 * ROW + PCLS * C + tid]);
 }
 
+// ------------------------------------------------------------------ backward of the ensemble mean, one head per launch
+// head_bwd_vec_kernel's 64-pixel tiles, grid and partial rows, without `out`: the mean's forward never wrote the head maps,
+// so the tile of x that the weight gradient needs in LDS anyway is staged FIRST and the logits are recomputed from it.
+//   1. x tile -> LDS as fp32 [64][C+1]            (VEC: 16-byte pieces -- fp32 quads / bf16 octets; else scalar loads)
+//   2. lane = pixel, wave = class (and class + 4): z = bias + x . w over the LDS row (stride C+1: conflict-free; the weight
+//      row is a broadcast read), s = 1 / (1 + exp(-z)), dl = (d_out * inv_heads) * (s * (1 - s)) -> LDS [64][8]
+//      (s (1 - s) as one fma: three roundings in dl beside the one in inv_heads)
+//   3. dx = W^T dl (+ old dx, ReLU gate of x) written back in the pieces of step 1
+//   4. dW[k, c] += sum_p dl[p, k] xs[p, c]: all 256 threads, two pixel halves per (k, c); db likewise
+// T = float or bf16_t (storage of x and dx).  64-bit element offsets.  LDS: xs | dl | W [8][C] | scratch [2][n_cls*C].
+template <typename T, bool VEC>
+__global__ __launch_bounds__(kThreads, 4) void heads_mean_bwd_kernel(const float* __restrict__ d_out, const T* __restrict__ x,
+                                                                  const float* __restrict__ weight,
+                                                                  const float* __restrict__ bias, long pixels, int HW, int C,
+                                                                  int n_cls, float inv_heads, T* __restrict__ dx,
+                                                                  int accumulate, int gate_x, float* __restrict__ partial) {
+  extern __shared__ __attribute__((aligned(16))) float hmb[];
+  constexpr int GW = sizeof(T) == 2 ? 8 : 4;  // elements of a 16-byte piece
+  const int XS = C + 1, NW = n_cls * C, gn = C / GW;
+  float* xs = hmb;
+  float* dl = xs + 64 * XS;
+  float* wsm = dl + 64 * kHeadMaxCls;
+  float* scratch = wsm + kHeadMaxCls * C;
+  const int tid = threadIdx.x;
+  for (int i = tid; i < NW; i += kThreads) wsm[i] = weight[i];
+  constexpr int kMaxPairs = (kHeadMaxCls * kHeadMaxC + 127) / 128;  // (k, c) pairs per thread
+  float wacc[kMaxPairs];
+#pragma unroll
+  for (int q = 0; q < kMaxPairs; ++q) wacc[q] = 0.f;
+  float bacc = 0.f;
+  const int pair0 = tid & 127, half = tid >> 7;
+  const long n_tiles = (pixels + 63) / 64;
+  for (long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    const long p0 = tile * 64;
+    __syncthreads();  // (the weights are in LDS; the previous tile's readers of xs and dl are done)
+    if constexpr (VEC) {
+      for (int it = tid; it < 64 * gn; it += kThreads) {
+        const int pl = it / gn, g = it - pl * gn;
+        const long p = p0 + pl;
+        float f[GW];
+#pragma unroll
+        for (int e = 0; e < GW; ++e) f[e] = 0.f;
+        if (p < pixels) {
+          if constexpr (GW == 8) {
+            unpack8(*reinterpret_cast<const u32x4*>(x + p * C + 8 * g), f);
+          } else {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(x + p * C + 4 * g);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) f[e] = v[e];
+          }
+        }
+        float* xd = &xs[pl * XS + GW * g];
+#pragma unroll
+        for (int e = 0; e < GW; ++e) xd[e] = f[e];
+      }
+    } else {
+      for (int it = tid; it < 64 * C; it += kThreads) {
+        const int pl = it / C, c = it - pl * C;
+        const long p = p0 + pl;
+        xs[pl * XS + c] = (p < pixels) ? head_feature(x + p * C + c) : 0.f;
+      }
+    }
+    __syncthreads();
+    for (int it = tid; it < 64 * n_cls; it += kThreads) {
+      const int pl = it & 63, k = it >> 6;
+      const long p = p0 + pl;
+      float v = 0.f;
+      if (p < pixels) {
+        float z = bias[k];
+        const float* xr = &xs[pl * XS];
+        const float* wr = &wsm[k * C];
+        for (int c = 0; c < C; ++c) z = fmaf(xr[c], wr[c], z);
+        const float s = 1.0f / (1.0f + expf(-z));
+        const long n = p / HW, hw = p - n * HW;
+        v = (d_out[(n * n_cls + k) * HW + hw] * inv_heads) * fmaf(-s, s, s);  // s (1 - s) = s - s^2, rounded once
+      }
+      dl[pl * kHeadMaxCls + k] = v;
+    }
+    __syncthreads();
+    if constexpr (VEC) {
+      for (int it = tid; it < 64 * gn; it += kThreads) {
+        const int pl = it / gn, g = it - pl * gn;
+        const long p = p0 + pl;
+        if (p >= pixels) continue;
+        float o[GW];
+#pragma unroll
+        for (int e = 0; e < GW; ++e) o[e] = 0.f;
+#pragma unroll
+        for (int k = 0; k < kHeadMaxCls; ++k) {
+          if (k < n_cls) {
+            const float dk = dl[pl * kHeadMaxCls + k];
+#pragma unroll
+            for (int e = 0; e < GW; ++e) o[e] = fmaf(wsm[k * C + GW * g + e], dk, o[e]);
+          }
+        }
+        T* dst = dx + p * C + GW * g;
+        if (accumulate) {
+          if constexpr (GW == 8) {
+            float old[8];
+            unpack8(*reinterpret_cast<const u32x4*>(dst), old);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o[e] += old[e];
+          } else {
+            const f32x4 old = *reinterpret_cast<const f32x4*>(dst);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[e] += old[e];
+          }
+        }
+        if (gate_x) {
+          const float* xr = &xs[pl * XS + GW * g];
+#pragma unroll
+          for (int e = 0; e < GW; ++e) o[e] = (xr[e] > 0.f) ? o[e] : 0.f;
+        }
+        if constexpr (GW == 8) {
+          *reinterpret_cast<u32x4*>(dst) = pack8(o);
+        } else {
+          *reinterpret_cast<f32x4*>(dst) = f32x4{o[0], o[1], o[2], o[3]};
+        }
+      }
+    } else {
+      for (int it = tid; it < 64 * C; it += kThreads) {
+        const int pl = it / C, c = it - pl * C;
+        const long p = p0 + pl;
+        if (p >= pixels) continue;
+        float s = 0.f;
+#pragma unroll
+        for (int k = 0; k < kHeadMaxCls; ++k)
+          if (k < n_cls) s = fmaf(wsm[k * C + c], dl[pl * kHeadMaxCls + k], s);
+        if (accumulate) s += head_feature(dx + p * C + c);
+        if (gate_x) s = (xs[pl * XS + c] > 0.f) ? s : 0.f;
+        dx[p * C + c] = s;
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < kMaxPairs; ++q) {
+      const int idx = pair0 + q * 128;
+      if (idx < NW) {
+        const int k = idx / C, c = idx - k * C;
+        float s = 0.f;
+#pragma unroll 4
+        for (int pl = 32 * half; pl < 32 * half + 32; ++pl) s += dl[pl * kHeadMaxCls + k] * xs[pl * XS + c];
+        wacc[q] += s;
+      }
+    }
+    if (tid < n_cls) {
+      float s = 0.f;
+      for (int pl = 0; pl < 64; ++pl) s += dl[pl * kHeadMaxCls + tid];
+      bacc += s;
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < kMaxPairs; ++q) {
+    const int idx = pair0 + q * 128;
+    if (idx < NW) scratch[half * NW + idx] = wacc[q];
+  }
+  __syncthreads();
+  float* dst = partial + static_cast<long>(blockIdx.x) * (NW + n_cls);
+  for (int i = tid; i < NW; i += kThreads) dst[i] = scratch[i] + scratch[NW + i];
+  if (tid < n_cls) dst[NW + tid] = bacc;
+}
+
+
 // ------------------------------------------------------------------ run-time triple -> instantiation
 // f(std::integral_constant<int, V>{}) for the V of the list that equals v; false when none does
 template <int... Vs, class F>
@@ -933,6 +1097,48 @@ bool heads_mean_query(const unetpp_heads_mean* heads, bool bf16, int N, int H, i
     q.weight_lo |= low4(s.weight);
   }
   return true;
+}
+
+// the query of the mean's backward: the forward's descriptor and the gradient descriptor must describe the same heads
+bool heads_mean_bwd_query(const unetpp_heads_mean* heads, const unetpp_heads_mean_grad* grads, bool bf16, int N, int H, int W,
+                          int C, int n_cls, HeadQuery& q) {
+  if (!grads || !heads_mean_query(heads, bf16, N, H, W, C, n_cls, q) || grads->n_heads != heads->n_heads) return false;
+  q.op = HEADS_MEAN_BWD;
+  for (int h = 0; h < grads->n_heads; ++h) {
+    const unetpp_head_grad& g = grads->head[h];
+    if (!g.dx || !g.partial) return false;
+    q.dx_lo |= low4(g.dx);
+  }
+  return true;
+}
+
+template <typename T>
+int heads_mean_bwd_launch(const unetpp_heads_mean* heads, const unetpp_heads_mean_grad* grads, const float* d_out_nchw, int N,
+                          int H, int W, int C, int n_cls, void* stream) {
+  HeadQuery q;
+  HeadSel s;
+  if (!d_out_nchw || !heads_mean_bwd_query(heads, grads, sizeof(T) == 2, N, H, W, C, n_cls, q)) return UNETPP_EINVAL;
+  const int rc = head_select(q, 0, s);
+  if (rc != UNETPP_OK) return rc;
+  const long pixels = static_cast<long>(N) * H * W;
+  const float inv_heads = 1.0f / static_cast<float>(heads->n_heads);
+  note_kernel(s.label);
+  for (int h = 0; h < heads->n_heads; ++h) {  // one launch per head: every head's tile goes through the same LDS layout
+    const unetpp_head_src& src = heads->head[h];
+    const unetpp_head_grad& g = grads->head[h];
+    if constexpr (sizeof(T) == 4) {  // (bf16 has the octet form only: head_select refuses the rest)
+      if (s.form == HEAD_GENERIC) {
+        hipLaunchKernelGGL((heads_mean_bwd_kernel<T, false>), dim3(s.grid), dim3(s.block), s.lds, ST(stream), d_out_nchw,
+                           static_cast<const T*>(src.x), src.weight, src.bias, pixels, H * W, C, n_cls, inv_heads,
+                           static_cast<T*>(g.dx), g.accumulate, g.gate_x, g.partial);
+        continue;
+      }
+    }
+      hipLaunchKernelGGL((heads_mean_bwd_kernel<T, true>), dim3(s.grid), dim3(s.block), s.lds, ST(stream), d_out_nchw,
+                         static_cast<const T*>(src.x), src.weight, src.bias, pixels, H * W, C, n_cls, inv_heads,
+                         static_cast<T*>(g.dx), g.accumulate, g.gate_x, g.partial);
+  }
+  return launch_status();
 }
 
 }  // namespace
@@ -1029,6 +1235,19 @@ extern "C" int unetpp_heads_mean_fwd_bf16(const unetpp_heads_mean* heads, int32_
     hipLaunchKernelGGL(heads_mean_general_kernel<bf16_t>, dim3(s.grid), dim3(s.block), 0, ST(stream), *heads, pixels,
                        H * W, C, n_cls, out_nchw);
   return launch_status();
+}
+
+/* ---- backward of the ensemble head: one launch per head, the head maps recomputed from the staged features ---- */
+extern "C" int unetpp_heads_mean_bwd(const unetpp_heads_mean* heads, const unetpp_heads_mean_grad* grads,
+                                     const float* d_out_nchw, int32_t N, int32_t H, int32_t W, int32_t C, int32_t n_cls,
+                                     void* stream) {
+  return heads_mean_bwd_launch<float>(heads, grads, d_out_nchw, N, H, W, C, n_cls, stream);
+}
+
+extern "C" int unetpp_heads_mean_bwd_bf16(const unetpp_heads_mean* heads, const unetpp_heads_mean_grad* grads,
+                                          const float* d_out_nchw, int32_t N, int32_t H, int32_t W, int32_t C,
+                                          int32_t n_cls, void* stream) {
+  return heads_mean_bwd_launch<bf16_t>(heads, grads, d_out_nchw, N, H, W, C, n_cls, stream);
 }
 
 extern "C" int64_t unetpp_head_bwd_blocks(int64_t pixels) {  // rows of `partial`; head_select sizes both backward grids alike

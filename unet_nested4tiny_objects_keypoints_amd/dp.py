@@ -45,10 +45,12 @@ import torch
 import torch.distributed as dist
 
 
-def ready_groups(model) -> List[List[torch.nn.Parameter]]:
+def ready_groups(model, head=None) -> List[List[torch.nn.Parameter]]:
     """Parameters in the order engine.backward_impl finishes their gradients, grouped as it REPORTS them (one group per
-    engine flush: all heads, then per convolution of a node -- conv2 (+BN2) before conv1 (+BN1) -- and per up-path)."""
-    d = model.depth
+    engine flush: all heads, then per convolution of a node -- conv2 (+BN2) before conv1 (+BN1) -- and per up-path).
+    head = J: the backward of the network cut at head J (``forward_pruned``) -- the same order restricted to the cut."""
+    from .engine import check_head
+    top = check_head(model.depth, head)
     out: List[List[torch.nn.Parameter]] = []
 
     def pair(blk):
@@ -64,25 +66,26 @@ def ready_groups(model) -> List[List[torch.nn.Parameter]]:
             out.append(grp)
 
     heads = []
-    for j in range(d - 1, 0, -1):
-        head = getattr(model, "final_%d" % j)
-        heads.extend([head.weight, head.bias])
+    for j in range(top, 0, -1):
+        final = getattr(model, "final_%d" % j)
+        heads.extend([final.weight, final.bias])
     out.append(heads)
-    for j in range(d - 1, 0, -1):
-        for i in range(d - 1 - j, -1, -1):
+    for j in range(top, 0, -1):
+        for i in range(top - j, -1, -1):
             mod = getattr(model, "up_concat%d%d" % (i, j))
             pair(mod.conv)
             up = mod.up if model.is_deconv else getattr(mod.up, "1")
             out.append([up.weight, up.bias])
-    for i in range(d - 1, -1, -1):
+    for i in range(top, -1, -1):
         pair(getattr(model, "conv%d0" % i))
     return out
 
 
-def ready_order(model) -> List[torch.nn.Parameter]:
-    """Parameters in the order engine.backward_impl finishes their gradients."""
-    out = [p for grp in ready_groups(model) for p in grp]
-    assert len(out) == len(list(model.parameters())) and len({id(p) for p in out}) == len(out)
+def ready_order(model, head=None) -> List[torch.nn.Parameter]:
+    """Parameters in the order engine.backward_impl finishes their gradients (head = J: of the network cut at head J)."""
+    from .engine import pruned_parameters
+    out = [p for grp in ready_groups(model, head) for p in grp]
+    assert len(out) == len(pruned_parameters(model, head)) and len({id(p) for p in out}) == len(out)
     return out
 
 
@@ -228,6 +231,7 @@ class GradientAverager:
         model._grad_alloc = self.alloc
         model._grad_sink = self._sink_and_log
         model._grad_done = self.done
+        model._grad_head = getattr(self, "head", None) or model.depth - 1   # the cut whose gradients this averager holds
         return self
 
     def _sink_and_log(self, fresh):
@@ -243,8 +247,11 @@ def broadcast_parameters(model, src: int = 0, process_group=None) -> None:
 
 
 def make_data_parallel(model, process_group=None, bucket_bytes: Optional[int] = None,
-                       always_reduce: bool = False, reserved_cus: Optional[int] = None) -> GradientAverager:
+                       always_reduce: bool = False, reserved_cus: Optional[int] = None, head=None) -> GradientAverager:
     """Broadcast rank 0's parameters/buffers, then hook the gradient averager into the model's backward.
+
+    head = J: the averager of the network cut at head J -- the flat buffer and the buckets hold the gradients of
+    engine.pruned_parameters(model, J) only, in the cut backward's ready order; train with ``train_step(..., head=J)``.
 
     reserved_cus: CUs the persistent compute grids leave free for the RCCL kernels of the side stream
     (include/unetpp_hip.h, unetpp_set_reserved_cus; without the argument the library's own UNETPP_RESERVED_CUS
@@ -255,4 +262,6 @@ def make_data_parallel(model, process_group=None, bucket_bytes: Optional[int] = 
         from . import _lib
         _lib.lib().unetpp_set_reserved_cus(int(reserved_cus))
     broadcast_parameters(model, 0, process_group)
-    return GradientAverager(ready_order(model), process_group, bucket_bytes, always_reduce).attach(model)
+    averager = GradientAverager(ready_order(model, head), process_group, bucket_bytes, always_reduce)
+    averager.head = head
+    return averager.attach(model)

@@ -293,12 +293,23 @@ def check_head(depth: int, head) -> int:
     return head
 
 
-def plan_phase(depth: int, head=None) -> str:
-    """The weight-image plan's name for a forward pass that runs needed_nodes(depth, head): "fwd" for the whole graph, a
-    name of its own per pruned depth -- such a pass records, and from then on packs in one launch, only the weights of the
-    nodes it runs (ops.phase_tag); whole and pruned passes on one model rebuild their own images each time they begin."""
+def plan_phase(depth: int, head=None, backward: bool = False) -> str:
+    """The weight-image plan's name for a pass that runs needed_nodes(depth, head): "fwd" ("bwd" for its backward) for the
+    whole graph, a name of its own per pruned depth ("fwd/J", "bwd/J") -- such a pass records, and from then on packs in one
+    launch, only the weights of the nodes it runs (ops.phase_tag); whole and pruned passes on one model rebuild their own
+    images each time they begin."""
     head = check_head(depth, head)
-    return "fwd" if head == depth - 1 else "fwd/%d" % head
+    base = "bwd" if backward else "fwd"
+    return base if head == depth - 1 else "%s/%d" % (base, head)
+
+
+def pruned_parameters(model, head=None) -> List[torch.nn.Parameter]:
+    """The parameters of the network cut at `head` -- the nodes of needed_nodes(depth, head) and final_1 .. final_head, what
+    ``forward_pruned(x, head)`` reads and gives gradients to -- in ``state_dict`` order: build the optimizer of a fine-tune
+    over them.  ``head = depth - 1`` (or None) gives every parameter."""
+    from .checkpoint import _pruned_prefixes
+    prefixes = _pruned_prefixes(model.depth, check_head(model.depth, head))
+    return [p for name, p in model.named_parameters() if name.startswith(prefixes)]
 
 
 STATS_PHASE = "stats"   # weight-image plan phase of stats_pass: its own images, as a pruned pass has (ops.phase_tag)
@@ -348,20 +359,22 @@ def stats_pass(model, x) -> None:
         flush_batch_counters()
 
 
-def forward_impl(model, x, training: bool, save: bool, head: Optional[int] = None, ensemble: bool = False):
+def forward_impl(model, x, training: bool, save: bool, head: Optional[int] = None, ensemble: bool = False,
+                 all_heads: bool = False):
     """Runs the forward DAG of models/unet.py:255-300.  Returns (outputs, saved-for-backward or None).
-    head = None: the whole graph and every head (``forward``).  head = J (``infer``): only needed_nodes(depth, J), and one
-    output -- head J, or the mean of heads 1 .. J when `ensemble`."""
+    head = None: the whole graph and every head (``forward``).  head = J: only needed_nodes(depth, J), and one output --
+    head J, or the mean of heads 1 .. J when `ensemble` (``infer``) -- or, with `all_heads` and no `ensemble`, the heads
+    1 .. J (``forward_pruned``: the reference's output tuple, shortened)."""
     _check_input(model, x)
     _PENDING_COUNTERS.clear()
     try:
         if not USE_PACK_PLAN:
-            return _forward_impl(model, x, training, save, head, ensemble)
+            return _forward_impl(model, x, training, save, head, ensemble, all_heads)
         plan = _plan_of(model)
         plan.begin(plan_phase(model.depth, head))  # every weight image of the pass in one launch (after the first pass recorded the jobs)
         ops.set_pack_plan(plan)
         try:
-            return _forward_impl(model, x, training, save, head, ensemble)
+            return _forward_impl(model, x, training, save, head, ensemble, all_heads)
         finally:
             ops.set_pack_plan(None)
     finally:
@@ -396,7 +409,8 @@ def _plan_of(model) -> "ops.PackPlan":
     return plan
 
 
-def _forward_impl(model, x, training: bool, save: bool, head: Optional[int] = None, ensemble: bool = False):
+def _forward_impl(model, x, training: bool, save: bool, head: Optional[int] = None, ensemble: bool = False,
+                  all_heads: bool = False):
     b, _, h0, w0 = x.shape
     d = model.depth
     top = d - 1 if head is None else head   # the last diagonal that runs; its encoder node is the deepest and is not pooled
@@ -430,7 +444,7 @@ def _forward_impl(model, x, training: bool, save: bool, head: Optional[int] = No
                            [f.weight.detach().view(model.n_classes, -1) for f in finals],
                            [f.bias.detach() for f in finals], o)
         outs.append(o)
-    for j in (range(1, d) if head is None else () if ensemble else (head,)):  # heads (:283-286)
+    for j in (range(1, d) if head is None else () if ensemble else range(1, head + 1) if all_heads else (head,)):  # heads (:283-286)
         final = getattr(model, "final_%d" % j)
         o = torch.empty((b, model.n_classes, h0, w0), dtype=torch.float32, device=x.device)
         ops.head_fwd(X[(0, j)], final.weight.detach().view(model.n_classes, -1), final.bias.detach(), p_drop,
@@ -442,6 +456,7 @@ def _forward_impl(model, x, training: bool, save: bool, head: Optional[int] = No
     s.x_nhwc, s.X, s.pairs, s.ups, s.outs = x_nhwc, X, pairs, ups, outs
     s.p_drop, s.seeds, s.masks, s.seed_dev = p_drop, seeds, masks, seed_dev
     s.shape = (b, h0, w0)
+    s.top, s.ensemble = top, bool(head is not None and ensemble)
     return outs, s
 
 
@@ -449,7 +464,8 @@ def _forward_impl(model, x, training: bool, save: bool, head: Optional[int] = No
 class _GradBook:
     """Gradient buffers of the node outputs; tracks whether a buffer already holds a contribution."""
 
-    def __init__(self, X, depth, gate_keys, grouped=False):
+    def __init__(self, X, top, gate_keys, grouped=False):
+        # top: the last diagonal of the pass -- depth - 1 for the whole graph, J for the network cut at head J
         self.X = X
         self.buf: Dict[Tuple[int, int], torch.Tensor] = {}
         self.got: Dict[Tuple[int, int], int] = {}
@@ -459,10 +475,10 @@ class _GradBook:
         self.expected = {}
         for (i, j) in X:
             n = (1 if (i == 0 and j >= 1) else 0)            # its deep-supervision head
-            consumers = max(0, (depth - 1 - i) - j)           # concat input of X[i][j'] for j' > j
+            consumers = max(0, (top - i) - j)                 # concat input of X[i][j'] for j' > j
             n += min(consumers, 1) if grouped else consumers  # (grouped: ONE launch for all of them)
             n += 1 if i >= 1 else 0                           # upsampled into X[i-1][j+1]
-            n += 1 if (j == 0 and i < depth - 1) else 0       # max-pooled into X[i+1][0]
+            n += 1 if (j == 0 and i < top) else 0             # max-pooled into X[i+1][0]
             self.expected[(i, j)] = n
 
     def target(self, key, can_gate=False):
@@ -585,37 +601,42 @@ def _up_bwd(upmod, is_deconv, u: _UpRec, d_up, d_src, accumulate, gate, b, grads
         ops.bilinear2x_bwd(d_interp, d_src, accumulate, gate)  # (gate: bf16 storage only, see backward_impl)
 
 
-def _grouped_weights(model, refresh=False, plan=None):
+def _grouped_weights(model, refresh=False, plan=None, top=None):
     """{(i, jj): [sum of consumer widths, f_i, 3, 3]}: for every skip tensor X[i][jj] the input-channel slices that read it
     in conv1 of its consumers (i, jj+1), (i, jj+2), ..., concatenated along the OUTPUT-channel axis -- as a convolution
     weight its input gradient is the sum of the consumers' contributions.  Buffers are kept (stable addresses: the
     pack plan prepacks their images with everything else) and refilled from the current parameters when `refresh`:
     by one torch.cat each the first time, from then on by the plan's one copy launch at ``plan.begin("bwd")`` (the slices
-    are strided copies: ops.PackPlan.copy_for; 6 launches per step at depth 4, 10 at depth 5 otherwise)."""
-    cache = getattr(model, "_grouped_dgrad_w", None)
+    are strided copies: ops.PackPlan.copy_for; 6 launches per step at depth 4, 10 at depth 5 otherwise).
+    top = J < depth - 1: the network cut at head J -- only the consumers inside the cut are concatenated, in buffers, under
+    plan keys and in a plan phase ("bwd/J") of the cut's own; the whole network's entries stay exactly what they are."""
     d = model.depth
+    top = d - 1 if top is None else top
+    whole = top == d - 1
+    phase = plan_phase(d, top, backward=True)
+    cache = getattr(model, "_grouped_dgrad_w", None) if whole else (getattr(model, "_grouped_dgrad_w_cut", None) or {}).get(top)
     if cache is None or refresh:
         fresh = {}
-        for i in range(d - 1):
-            for jj in range(d - 1 - i):
+        for i in range(top):
+            for jj in range(top - i):
                 ws = [getattr(getattr(model, "up_concat%d%d" % (i, jc)).conv.conv1, "0").weight.detach()
-                      for jc in range(jj + 1, d - i)]
+                      for jc in range(jj + 1, top + 1 - i)]
                 f = ws[0].shape[0]
                 parts = [w[:, (1 + jj) * f:(2 + jj) * f] for w in ws]
                 old = None if cache is None else cache.get((i, jj))
                 if old is not None and not (old.device == parts[0].device and old.dtype == parts[0].dtype):
                     old = None
                 if plan is not None and all(w.is_contiguous() and w.dtype == torch.float32 for w in ws):
-                    key, sig = ("grouped", i, jj), tuple(w.data_ptr() for w in ws)
-                    if old is not None and plan.knows_copy(key, "bwd", sig + (old.data_ptr(),)):
-                        plan.copy_for(key, "bwd", sig + (old.data_ptr(),), None)   # (marks the entry used)
+                    key, sig = ("grouped", i, jj) + ops.phase_tag(phase), tuple(w.data_ptr() for w in ws)
+                    if old is not None and plan.knows_copy(key, phase, sig + (old.data_ptr(),)):
+                        plan.copy_for(key, phase, sig + (old.data_ptr(),), None)   # (marks the entry used)
                         fresh[(i, jj)] = old
                         continue
                     buf = old if old is not None else torch.empty((len(ws) * f, f) + tuple(ws[0].shape[2:]),
                                                                    dtype=ws[0].dtype, device=ws[0].device)
                     t = ws[0].shape[2] * ws[0].shape[3]
                     items = [(w, (1 + jj) * f * t, q * f * f * t, f, f * t, w.shape[1] * t, f * t) for q, w in enumerate(ws)]
-                    plan.copy_for(key, "bwd", sig + (buf.data_ptr(),), lambda: (buf, list(ws), items))
+                    plan.copy_for(key, phase, sig + (buf.data_ptr(),), lambda: (buf, list(ws), items))
                     old = buf
                 if old is not None:
                     torch.cat(parts, 0, out=old)
@@ -623,7 +644,12 @@ def _grouped_weights(model, refresh=False, plan=None):
                 else:
                     fresh[(i, jj)] = torch.cat(parts, 0).contiguous()
         cache = fresh
-        model._grouped_dgrad_w = cache
+        if whole:
+            model._grouped_dgrad_w = cache
+        else:
+            if getattr(model, "_grouped_dgrad_w_cut", None) is None:
+                model._grouped_dgrad_w_cut = {}
+            model._grouped_dgrad_w_cut[top] = cache
     return cache
 
 
@@ -631,11 +657,12 @@ def backward_impl(model, s: _Saved, d_outs, want_input_grad: bool, grad_sink=Non
     """Returns (dict param -> grad, dx NHWC or None).  grad_sink(list of (param, grad)) is called each time a
     node's parameter gradients are final (used by the data-parallel bucketed all-reduce)."""
     if USE_GROUPED_DGRAD:   # before the pack plan packs this pass's weight images
-        _grouped_weights(model, refresh=True, plan=_plan_of(model) if (USE_PACK_PLAN and USE_PLAN_COPIES) else None)
+        _grouped_weights(model, refresh=True, plan=_plan_of(model) if (USE_PACK_PLAN and USE_PLAN_COPIES) else None,
+                         top=s.top)
     if not USE_PACK_PLAN:
         return _backward_impl(model, s, d_outs, want_input_grad, grad_sink)
     plan = _plan_of(model)
-    plan.begin("bwd")
+    plan.begin(plan_phase(model.depth, s.top, backward=True))   # "bwd", or the cut's own "bwd/J"
     ops.set_pack_plan(plan)
     try:
         return _backward_impl(model, s, d_outs, want_input_grad, grad_sink)
@@ -645,13 +672,13 @@ def backward_impl(model, s: _Saved, d_outs, want_input_grad: bool, grad_sink=Non
 
 def _backward_impl(model, s: _Saved, d_outs, want_input_grad: bool, grad_sink=None):
     b, h0, w0 = s.shape
-    d = model.depth
+    top = s.top   # the last diagonal of the forward: depth - 1, or J for the network cut at head J -- only its nodes ran
     grads: Dict[torch.nn.Parameter, torch.Tensor] = {}
     # Nodes without BatchNorm end in a plain ReLU whose mask the last gradient contributor can apply for free
     # (decoder nodes always; encoder nodes only when is_batchnorm=False -- with BN the mask lives in BN backward).
     gate_keys = {k for k in s.X if k[1] >= 1 or not model.is_batchnorm}
     grouped = USE_GROUPED_DGRAD
-    book = _GradBook(s.X, d, gate_keys, grouped)
+    book = _GradBook(s.X, top, gate_keys, grouped)
     bf16 = s.X[(0, 0)].dtype == torch.bfloat16
     dy1s: Dict[Tuple[int, int], V] = {}   # grouped input gradients: dY of conv1 of the decoder nodes done so far
     seen = set()
@@ -663,7 +690,25 @@ def _backward_impl(model, s: _Saved, d_outs, want_input_grad: bool, grad_sink=No
             if fresh:
                 grad_sink(fresh)
 
-    for j in range(d - 1, 0, -1):  # heads: the first contribution to d X[0][j]
+    if s.ensemble:   # the mean of heads 1 .. top: its forward never wrote the head maps, its backward recomputes them
+        finals = [getattr(model, "final_%d" % j) for j in range(1, top + 1)]
+        go = d_outs[0]
+        if go is None:
+            go = torch.zeros_like(s.outs[0])
+        tg = {j: book.target((0, j), can_gate=True) for j in range(top, 0, -1)}
+        cols = range(1, top + 1)
+        got = ops.heads_mean_bwd([s.X[(0, j)] for j in cols], [f.weight.detach().view(model.n_classes, -1) for f in finals],
+                                 [f.bias.detach() for f in finals], go.contiguous(), [tg[j][0] for j in cols],
+                                 [tg[j][1] for j in cols], [tg[j][2] is not None for j in cols])
+        for j in range(top, 0, -1):
+            head, (dw, db) = finals[j - 1], got[j - 1]
+            if _ALLOC[0] is not None:
+                gw, gb = _new_grad(head.weight), _new_grad(head.bias)
+                gw.copy_(dw)
+                gb.copy_(db)
+                dw, db = gw, gb
+            grads[head.weight], grads[head.bias] = dw, db
+    for j in (() if s.ensemble else range(top, 0, -1)):  # heads: the first contribution to d X[0][j]
         head = getattr(model, "final_%d" % j)
         go = d_outs[j - 1]
         if go is None:
@@ -680,8 +725,8 @@ def _backward_impl(model, s: _Saved, d_outs, want_input_grad: bool, grad_sink=No
             dw, db = gw, gb
         grads[head.weight], grads[head.bias] = dw, db
     flush()
-    for j in range(d - 1, 0, -1):  # decoder columns, last column first
-        for i in range(d - 1 - j, -1, -1):
+    for j in range(top, 0, -1):  # decoder columns, last column first
+        for i in range(top - j, -1, -1):
             mod = getattr(model, "up_concat%d%d" % (i, j))
             r, u = s.pairs[(i, j)], s.ups[(i, j)]
             d_out, pre_gated = book.take((i, j))
@@ -694,11 +739,11 @@ def _backward_impl(model, s: _Saved, d_outs, want_input_grad: bool, grad_sink=No
                 # in the order of _grouped_weights), written -- or added to the head / upsampling contribution -- once
                 c_up = u.up.shape[3]
                 dy1s[(i, j)] = _pair_bwd(mod.conv, r, d_out, targets, b, grads, pre_gated, flush=flush, in_slice=(0, c_up))
-                consumers = list(range(j, d - i))
+                consumers = list(range(j, top + 1 - i))
                 t, acc, gate = book.target((i, j - 1), can_gate=True)
                 ops.gemm_fwd(b, r.h, r.w, 9, [dy1s[(i, jc)] for jc in consumers],
                              [V(t, accumulate=acc, gate=gate, gate_sum=True)],
-                             pack_conv_dgrad(_grouped_weights(model)[(i, j - 1)]))
+                             pack_conv_dgrad(_grouped_weights(model, top=top)[(i, j - 1)]))
                 if j == 1:
                     for jc in consumers:   # level i is done with its dY tensors
                         del dy1s[(i, jc)]
@@ -715,7 +760,7 @@ def _backward_impl(model, s: _Saved, d_outs, want_input_grad: bool, grad_sink=No
             flush()
     dx_in = None
     pool_grad = None  # (d_pooled, pool_idx) of the node below, still to be added to this node's gradient
-    for i in range(d - 1, -1, -1):  # encoder column, deepest first
+    for i in range(top, -1, -1):  # encoder column, deepest first
         blk = getattr(model, "conv%d0" % i)
         r = s.pairs[(i, 0)]
         d_out, pre_gated = book.take((i, 0))
@@ -747,9 +792,14 @@ def _backward_impl(model, s: _Saved, d_outs, want_input_grad: bool, grad_sink=No
 
 
 class _UNetNestedFn(torch.autograd.Function):
+    # cut = None: the whole network (``forward``); cut = (J, ensemble): the network cut at head J (``forward_pruned``) with
+    # `params` = pruned_parameters(model, J) -- a parameter outside the cut is no input of the node and gets no gradient
     @staticmethod
-    def forward(ctx, model, x, *params):
-        outs, saved = forward_impl(model, x, model.training, save=True)
+    def forward(ctx, model, x, cut, *params):
+        if cut is None:
+            outs, saved = forward_impl(model, x, model.training, save=True)
+        else:
+            outs, saved = forward_impl(model, x, model.training, save=True, head=cut[0], ensemble=cut[1], all_heads=True)
         if getattr(model, "_debug_keep_saved", False):  # test hook: expose the activations kept for backward
             model._debug_saved = saved
         ctx.model, ctx.saved = model, saved
@@ -776,16 +826,41 @@ class _UNetNestedFn(torch.autograd.Function):
         if done is not None and done():
             # data parallel: the averager has put (or accumulated) the averaged gradients into p.grad itself; handing
             # the flat-buffer views to autograd as well would let AccumulateGrad alias p.grad with the work buffer
-            return (None, dx_nchw) + (None,) * len(ctx.params)
-        return (None, dx_nchw) + tuple(grads.get(p) if need else None
-                                      for p, need in zip(ctx.params, ctx.needs_input_grad[2:]))
+            return (None, dx_nchw, None) + (None,) * len(ctx.params)
+        return (None, dx_nchw, None) + tuple(grads.get(p) if need else None
+                                            for p, need in zip(ctx.params, ctx.needs_input_grad[3:]))
 
 
 def run(model, x):
     """The body of UNet_Nested.forward."""
+    if getattr(model, "_grad_sink", None) is not None and getattr(model, "_grad_head", model.depth - 1) != model.depth - 1:
+        raise RuntimeError("the attached data-parallel averager holds the gradients of the network cut at head %d only: "
+                           "use forward_pruned / train_step(..., head=%d)" % (model._grad_head, model._grad_head))
     params = tuple(model.parameters())
     track = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
     if track:
-        return _UNetNestedFn.apply(model, x, *params)
+        return _UNetNestedFn.apply(model, x, None, *params)
     outs, _ = forward_impl(model, x, model.training, save=False)
     return tuple(outs)
+
+
+def run_pruned(model, x, head=None, ensemble: bool = False):
+    """The body of UNet_Nested.forward_pruned."""
+    top = check_head(model.depth, head)
+    pruned_to = getattr(model, "pruned_to", None)
+    if pruned_to is not None and top > pruned_to:
+        raise RuntimeError("this model holds a checkpoint pruned to head %d: the nodes head %d needs were never loaded"
+                           % (pruned_to, top))
+    ensemble = bool(ensemble)
+    if ensemble and model.training and model.drop_out.training and float(model.drop_out.p) > 0.0:
+        raise RuntimeError("the ensemble mean has no dropout: call model.drop_out.eval() before "
+                           "forward_pruned(..., ensemble=True)")
+    if getattr(model, "_grad_sink", None) is not None and getattr(model, "_grad_head", model.depth - 1) != top:
+        raise RuntimeError("the attached data-parallel averager holds the gradients of another cut: build it with "
+                           "make_data_parallel(model, head=%d)" % top)
+    params = tuple(pruned_parameters(model, top))
+    if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
+        outs = _UNetNestedFn.apply(model, x, (top, ensemble), *params)
+    else:
+        outs, _ = forward_impl(model, x, model.training, save=False, head=top, ensemble=ensemble, all_heads=True)
+    return outs[0] if ensemble else tuple(outs)

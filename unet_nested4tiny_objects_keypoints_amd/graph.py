@@ -123,11 +123,11 @@ class GraphedTrainStep:
     makes no host decision that depends on device data (torch.optim.Adam / AdamW with ``capturable=True``, SGD).
     The graph holds the BatchNorm modes it was captured with: a layer that was frozen (``BatchNormParams.eval()``,
     ``model.freeze_batchnorm()``) at capture stays frozen in every replay, whatever its flag says later -- build a new
-    GraphedTrainStep after changing modes or ``requires_grad``."""
+    GraphedTrainStep after changing modes or ``requires_grad``.  ``head=J`` captures ``train_step(..., head=J)``."""
 
     def __init__(self, model, optimizer, criterion, inputs: torch.Tensor, target: torch.Tensor, warmup: int = 3,
                  capture_optimizer: bool = False, restore_state: bool = True, check_topology: bool = False,
-                 debug_dot: Optional[str] = None, _threaded_backward: bool = False):
+                 debug_dot: Optional[str] = None, _threaded_backward: bool = False, head: Optional[int] = None):
         if not inputs.is_cuda or not target.is_cuda:
             raise RuntimeError("GraphedTrainStep needs GPU tensors: this path has no CPU fallback")
         if capture_optimizer:
@@ -144,6 +144,7 @@ class GraphedTrainStep:
             raise RuntimeError("a data-parallel averager is attached to the model: its all-reduces are not captured; "
                                "use train_step")
         self.model, self.optimizer, self.criterion = model, optimizer, criterion
+        self.head = head   # None: the whole network; J: train_step(..., head=J), the network cut at head J
         self.capture_optimizer = bool(capture_optimizer)
         dev = inputs.device
         self._x, self._t = inputs.clone(), target.clone()
@@ -237,7 +238,7 @@ class GraphedTrainStep:
     def _body(self, with_optimizer: bool):
         """train_step's sequence (step.py) on the static tensors"""
         self.optimizer.zero_grad(set_to_none=True)
-        outputs = self.model(self._x)
+        outputs = self.model(self._x) if self.head is None else self.model.forward_pruned(self._x, self.head)
         avgloss = loss_and_backward(self.criterion, outputs, self._t)
         if with_optimizer:
             self.optimizer.step()

@@ -391,8 +391,8 @@ def current_plan() -> Optional[PackPlan]:
 
 
 def phase_tag(phase) -> tuple:
-    """() for the two whole-network passes, (phase,) for a pruned inference pass (engine.plan_phase): part of the key of
-    whatever a plan records, so that a pruned pass owns its images and its copies -- its ``begin`` packs the weights of
+    """() for the two whole-network passes, (phase,) for a pruned pass ("fwd/J", "bwd/J": engine.plan_phase): part of the key
+    of whatever a plan records, so that a pruned pass owns its images and its copies -- its ``begin`` packs the weights of
     the nodes it runs and nothing else, and the entries of the whole-network passes stay exactly what they were."""
     return () if phase in ("fwd", "bwd") else (phase,)
 
@@ -740,6 +740,46 @@ def heads_mean_fwd(xs, weights, biases, out_nchw):
         raise ValueError("output must be [N, n_cls, H, W]")
     fn = _lib.lib().unetpp_heads_mean_fwd_bf16 if adt == torch.bfloat16 else _lib.lib().unetpp_heads_mean_fwd
     check(fn(C.byref(d), n, h, w, c, n_cls, _ptr(out_nchw), _stream()), "unetpp_heads_mean_fwd")
+
+
+def heads_mean_bwd(xs, weights, biases, d_out, dxs, accumulates, gates):
+    """Backward of heads_mean_fwd: d_out [N, n_cls, H, W] fp32 is the gradient of the mean.  For every head h the kernel
+    recomputes s_h = sigmoid(bias_h + x_h . weight_h) from the features (the forward never wrote the head maps), forms
+    dl = (d_out * (1 / n)) * (s_h * (1 - s_h)) and writes dxs[h] = W_h^T dl (added to dxs[h] when accumulates[h]; then
+    multiplied by (x_h > 0) when gates[h]).  Returns [(dW_h [n_cls, C, 1, 1], db_h [n_cls])], summed in a fixed order."""
+    lib = _lib.lib()
+    n_heads = len(xs)
+    if not (1 <= n_heads <= _lib.MAX_HEADS) or not all(len(v) == n_heads for v in (weights, biases, dxs, accumulates, gates)):
+        raise ValueError("heads_mean_bwd takes 1..%d heads with one weight, bias, dx, accumulate and gate each" % _lib.MAX_HEADS)
+    adt = xs[0].dtype
+    if adt not in _ACT_DTYPES:
+        raise TypeError("features must be float32 or bfloat16, got %s" % adt)
+    n, h, w, c = xs[0].shape
+    n_cls = weights[0].shape[0]
+    if tuple(_need(d_out, "gradient of the mean").shape) != (n, n_cls, h, w):
+        raise ValueError("d_out must be [N, n_cls, H, W]")
+    blocks = int(lib.unetpp_head_bwd_blocks(n * h * w))
+    ln = n_cls * c + n_cls
+    partial = torch.empty((n_heads, blocks * ln), dtype=torch.float32, device=d_out.device)
+    sums = torch.empty((n_heads, ln), dtype=torch.float32, device=d_out.device)
+    d, g = _lib.HeadsMean(), _lib.HeadsMeanGrad()
+    d.n_heads = g.n_heads = n_heads
+    for i, (x, wt, b, dx) in enumerate(zip(xs, weights, biases, dxs)):
+        if tuple(_need(x, "head features", adt).shape) != (n, h, w, c) or tuple(_need(dx, "feature gradient", adt).shape) != (n, h, w, c):
+            raise ValueError("every head reads a feature tensor and writes a gradient of the same shape")
+        if tuple(_need(wt, "head weight").shape) != (n_cls, c) or _need(b, "head bias").numel() != n_cls:
+            raise ValueError("head weight must be [n_cls, C] and bias [n_cls]")
+        d.head[i].x, d.head[i].weight, d.head[i].bias = x.data_ptr(), wt.data_ptr(), b.data_ptr()
+        g.head[i].dx, g.head[i].partial = dx.data_ptr(), partial[i].data_ptr()
+        g.head[i].accumulate, g.head[i].gate_x = int(bool(accumulates[i])), int(bool(gates[i]))
+    st = _stream()
+    fn = lib.unetpp_heads_mean_bwd_bf16 if adt == torch.bfloat16 else lib.unetpp_heads_mean_bwd
+    check(fn(C.byref(d), C.byref(g), _ptr(d_out), n, h, w, c, n_cls, st), "unetpp_heads_mean_bwd")
+    out = []
+    for i in range(n_heads):
+        check(lib.unetpp_sum_partials(_ptr(partial[i]), blocks, ln, _ptr(sums[i]), st), "unetpp_sum_partials")
+        out.append((sums[i, :n_cls * c].view(n_cls, c, 1, 1), sums[i, n_cls * c:]))
+    return out
 
 
 def head_bwd(d_out, out, x, weight, p_drop, seed, mask, dx, accumulate, gate_x=False, seed_dev=None):

@@ -38,9 +38,11 @@ def loss_and_backward(criterion, outputs, target):
     return avgloss
 
 
-def train_step(model, optimizer, criterion, inputs, target):
+def train_step(model, optimizer, criterion, inputs, target, head=None):
+    """head = J: the step of the network cut at deep-supervision head J (``UNet_Nested.forward_pruned``) -- the loss is the
+    mean over heads 1 .. J, only the cut's nodes run and only its parameters get gradients."""
     optimizer.zero_grad()
-    outputs = model(inputs)
+    outputs = model(inputs) if head is None else model.forward_pruned(inputs, head)
     avgloss = loss_and_backward(criterion, outputs, target)
     optimizer.step()
     return outputs, avgloss

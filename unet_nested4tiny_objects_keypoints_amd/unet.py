@@ -177,6 +177,22 @@ class UNet_Nested(nn.Module):
         ``validate_step(model, ..., forward=lambda x: (model.infer(x, 1),))`` validates a pruned network."""
         return engine.infer(self, inputs, head, ensemble)
 
+    def forward_pruned(self, inputs, head=None, ensemble=False):
+        """``forward`` of the network cut at deep-supervision head ``head``, connected to autograd as ``forward`` is: only
+        the nodes ``X_ij`` with ``i + j <= head`` run (``engine.needed_nodes``), forward and backward, every layer in the
+        mode of its own ``training`` flag.  ``head`` as in ``infer`` (``None`` = the last head, the whole network).
+
+        * ``ensemble=False`` -- the tuple of heads ``1 .. head``: the reference's output tuple, shortened.  Head ``j`` draws
+          the dropout seed (or takes the mask) ``j - 1`` of the ``depth - 1``, so the same ``torch.manual_seed`` in front of
+          ``model(x)`` and ``model.forward_pruned(x, J)`` gives ``model(x)[:J]`` bit for bit.
+        * ``ensemble=True`` -- one tensor, the mean of heads ``1 .. head``, the value of ``infer(x, head, ensemble=True)``;
+          its backward recomputes the head maps.  The mean has no dropout: with active dropout this raises.
+
+        Parameters outside the cut are not read, get no gradient (``p.grad`` stays as it was) and their BatchNorm buffers
+        do not move; ``engine.pruned_parameters(model, head)`` lists the ones inside.  This is how a ``load_pruned`` model
+        (``head <= pruned_to``) is trained: ``train_step(..., head=J)``."""
+        return engine.run_pruned(self, inputs, head, ensemble)
+
     def freeze_batchnorm(self, frozen: bool = True, affine: bool = True):
         """The fine-tuning idiom ``for bn in batchnorms: bn.eval()`` in one call: puts every ``BatchNormParams`` into eval
         mode (``frozen=True``) or back into training mode, whatever the mode of the model around them.  A frozen layer
