@@ -769,6 +769,24 @@ int unetpp_scene_stitch(const float* tiles, int32_t n_tiles, int32_t K, int32_t 
                         const int32_t* variants, const unetpp_scene_rect* rects, const unetpp_scene_rect* rects_dev,
                         float* out, int32_t S, int32_t H, int32_t W, void* stream);
 
+/* unetpp_scene_screen (added within ABI version 13: new entry points only): the device-side decision of cascaded scene
+ * inference -- which rectangles of a frame map hold anything.  maps float32 [S, C, H, W] (device).  Row t of the table
+ * names the half-open rectangle [y_lo, y_hi) x [x_lo, x_hi) of frame `frame` (oy / ox are not used here; the caller has
+ * grown and clipped the rectangle already).  Over all C classes and all pixels of the rectangle:
+ *   active[t] = any(!(v < threshold))    a value equal to the threshold activates, and so does a NaN (fail safe)
+ *   score[t]  = fmax of the values       a NaN is ignored; -inf when every value is NaN
+ * A row with frame < 0 is padding: active = 0, score = -inf.  active int32 [n_rects] and score float32 [n_rects] are
+ * device arrays.  One launch, one workgroup and one writer per rectangle, no atomics: the result is a pure function of
+ * the rectangle's values, the same bits on every run.  Nothing outside a rectangle is read; offsets into maps are 64-bit.
+ * rects / rects_dev: host and device copies of the table as for unetpp_scene_stitch -- the host copy is validated, a
+ * device row that disagrees with the frame is never followed (it is reported as padding).  A table of nothing but
+ * padding rows launches nothing and leaves active and score as they are (UNETPP_OK).
+ * UNETPP_EINVAL without touching the device for a null pointer, a size <= 0, a NaN threshold, or a live row whose frame
+ * is >= S or whose rectangle is empty or leaves the frame. */
+int unetpp_scene_screen(const float* maps, int32_t S, int32_t C, int32_t H, int32_t W, const unetpp_scene_rect* rects,
+                        const unetpp_scene_rect* rects_dev, int32_t n_rects, float threshold, int32_t* active,
+                        float* score, void* stream);
+
 /* ---- Detection (csrc/detect.hip): from the maps of a scene to a list of points per map, and from such lists to
  * true / false positives against labelled points.  The reference has no counterpart: its extraction returns a fixed
  * number of points per map (tools/misc/heatmap.py:148-200) and its matcher is unfinished.  Added within ABI version 12

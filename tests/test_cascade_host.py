@@ -1,0 +1,179 @@
+"""Host side of cascaded scene inference (scene.py CascadeSceneInference, csrc/scene.hip unetpp_scene_screen), no GPU:
+  (1) the screened rectangles: R_t contains O_t and lies inside the tile's extent; margin = 0 gives O_t (a partition of the
+      frame), a huge margin gives the tile's extent; the product's screen_rows equals the oracle's screen_rects;
+  (2) the numpy restatement itself on the rule's edge cases (equality, NaN, all NaN, -0.0 against 0.0, padding);
+  (3) the ABI entry's argument checks (status codes, no device touched);
+  (4) the constructor's refusals on a CPU model, and the Python op's refusal of CPU tensors;
+  (5) chunk selection as a pure host function.
+"""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+from tests.cascade_oracle import owner_mask, screen_ref, screen_rects
+from tests.test_scene_host import rect_rows
+
+GEOMETRY = {2: [(70, 90, 32, 10), (24, 50, 32, 10), (96, 112, 64, 24)],      # align -> (H, W, tile, halo)
+            4: [(72, 88, 32, 8), (96, 112, 64, 24), (24, 88, 32, 8)]}
+
+
+# ---- (1) ------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("align", [2, 4])
+def test_screened_rectangles(align):
+    from unet_nested4tiny_objects_keypoints_amd.scene import screen_rows
+    for (H, W, tile, halo) in GEOMETRY[align]:
+        th, tw = min(tile, H), min(tile, W)
+        owned = rect_rows(H, W, tile, halo, align, frames=2)
+        for margin in (0, 4, halo, 10 * halo):
+            rects = screen_rects(H, W, tile, halo, align, margin, frames=2)
+            assert rects == screen_rows(owned, th, tw, margin)
+            assert len(rects) == len(owned)
+            for (s, oy, ox, y0, y1, x0, x1), (s_, oy_, ox_, a0, a1, b0, b1) in zip(rects, owned):
+                assert (s, oy, ox) == (s_, oy_, ox_)
+                assert y0 <= a0 < a1 <= y1 and x0 <= b0 < b1 <= x1                      # R_t contains O_t
+                assert oy <= y0 and y1 <= oy + th and ox <= x0 and x1 <= ox + tw        # inside the tile's extent
+                assert (y0, y1, x0, x1) == (max(a0 - margin, oy), min(a1 + margin, oy + th),
+                                            max(b0 - margin, ox), min(b1 + margin, ox + tw))
+            if margin == 0:
+                assert rects == owned
+                cover = np.zeros((2, H, W), dtype=np.int32)
+                for (s, _, _, y0, y1, x0, x1) in rects:
+                    cover[s, y0:y1, x0:x1] += 1
+                assert (cover == 1).all()                                               # a partition of the frame
+            if margin == 10 * halo:
+                assert all((y0, y1, x0, x1) == (oy, oy + th, ox, ox + tw) for (_, oy, ox, y0, y1, x0, x1) in rects)
+            if margin == halo and (H > tile or W > tile):
+                assert rects != owned
+
+
+# ---- (2) ------------------------------------------------------------------------------------------------------------
+def test_the_restatement_on_the_rules_edge_cases():
+    thr = np.float32(0.25)
+    below = np.nextafter(thr, np.float32(-np.inf))
+    m = np.full((1, 2, 4, 24), -1.0, dtype=np.float32)
+    rects = [(0, 0, 0, 0, 4, 4 * i, 4 * i + 4) for i in range(6)] + [(-1, 0, 0, 0, 0, 0, 0)]
+    m[0, 1, 2, 1] = thr                     # equal: active
+    m[0, 0, 3, 5] = below                   # one step below: inactive
+    m[0, 1, 0, 9] = np.nan                  # a NaN: active, ignored by the score
+    m[0, :, :, 12:16] = np.nan              # all NaN: active, -inf
+    m[0, 0, 1, 17] = np.inf
+    active, score = screen_ref(m, rects, thr)
+    assert active.tolist() == [1, 0, 1, 1, 1, 0, 0]
+    assert score.tolist() == [thr, below, -1.0, -np.inf, np.inf, -1.0, -np.inf]
+    m[0, 0, 0, 21] = -0.0
+    active, score = screen_ref(m, rects, 0.0)
+    assert active.tolist() == [1, 1, 1, 1, 1, 1, 0] and np.signbit(score[5]) and score[5] == 0.0
+    assert screen_ref(m, rects, np.inf)[0].tolist() == [0, 0, 1, 1, 1, 0, 0]
+    assert screen_ref(m, rects, -np.inf)[0].tolist() == [1, 1, 1, 1, 1, 1, 0]
+    A = owner_mask(rects[:6], [1, 0, 1, 1, 1, 0], 1, 4, 24)
+    assert A.shape == (1, 1, 4, 24) and A[0, 0, :, :4].all() and not A[0, 0, :, 4:8].any()
+
+
+# ---- (3) ------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def built_lib():
+    import __graft_entry__ as entry
+    entry.build()
+    from unet_nested4tiny_objects_keypoints_amd import _lib
+    return _lib
+
+
+def test_scene_screen_abi_argument_checks(built_lib):
+    L = built_lib
+    lib = L.lib()
+    assert lib.unetpp_abi_version() == L.ABI_VERSION == 13     # an additive entry point: the version stays
+    p = ctypes.c_void_p(0x1000)                               # never dereferenced: every call below is refused on the host
+
+    def call(maps=p, S=2, C=3, H=32, W=48, rows=((0, 0, 0, 0, 24, 0, 24), (1, 0, 16, 4, 32, 20, 48)), table="host", dev=p,
+             n=None, threshold=0.5, active=p, score=p):
+        host = (L.SceneRect * max(1, len(rows)))()
+        for i, r in enumerate(rows):
+            (host[i].frame, host[i].oy, host[i].ox, host[i].y_lo, host[i].y_hi, host[i].x_lo, host[i].x_hi) = r
+        return lib.unetpp_scene_screen(maps, S, C, H, W, host if table == "host" else None, dev,
+                                       len(rows) if n is None else n, threshold, active, score, None)
+
+    for name in ("maps", "dev", "active", "score"):
+        assert call(**{name: None}) == -1, name
+    assert call(table=None) == -1
+    for name in ("S", "C", "H", "W", "n"):
+        assert call(**{name: 0}) == -1, name
+        assert call(**{name: -2}) == -1, name
+    assert call(threshold=float("nan")) == -1
+    ok = (0, 0, 0, 0, 24, 0, 24)
+    for bad in ((2, 0, 0, 0, 24, 0, 24),        # frame >= S
+                (0, 0, 0, 12, 12, 0, 24),       # empty in y
+                (0, 0, 0, 0, 24, 24, 24),       # empty in x
+                (0, 0, 0, 20, 8, 0, 24),        # inverted
+                (0, 0, 0, 0, 33, 0, 24),        # past H
+                (0, 0, 0, 0, 24, 0, 49),        # past W
+                (0, 0, 0, -1, 24, 0, 24),       # above the frame
+                (0, 0, 0, 0, 24, -4, 24)):      # left of the frame
+        assert call(rows=(ok, bad)) == -1, bad
+    # oy / ox are not used: a row whose tile origin is nonsense but whose rectangle is inside the frame would be followed
+    # (not launched here: the pointers are fake), and a table of nothing but padding rows is accepted without a launch
+    assert call(rows=((-1, 0, 0, 0, 0, 0, 0), (-1, 9, 9, 9, 9, 9, 9))) == 0
+    assert call(rows=((-1, 0, 0, 0, 0, 0, 0),), threshold=float("inf")) == 0
+
+
+# ---- (4) ------------------------------------------------------------------------------------------------------------
+def test_cascade_constructor_refusals_without_gpu():
+    from unet_nested4tiny_objects_keypoints_amd import CascadeSceneInference, UNet_Nested, ops
+    m = UNet_Nested(in_channels=1, feature_scale=8)
+    with pytest.raises(RuntimeError, match="eval"):
+        CascadeSceneInference(m)                                # a fresh module is in training mode
+    m.eval()
+    c = CascadeSceneInference(m)                                # depth 4: head 3 screened by head 1
+    assert (c.head, c.screen_head, c.threshold, c.margin) == (3, 1, 0.1, 56)
+    assert (c.deep.halo, c.screen.halo, c.deep.tile, c.screen.tile, c.screen.chunk) == (56, 16, 512, 512, 8)
+    assert c.screen.variants == (0,) and not c.screen.ensemble
+    c = CascadeSceneInference(m, head=2, tta="dihedral", ensemble=True, screen_tile=256, screen_chunk=32, margin=0)
+    assert c.deep.variants == tuple(range(8)) and c.deep.ensemble and c.screen.variants == (0,)
+    assert (c.screen.tile, c.screen.chunk, c.margin, c.deep.halo) == (256, 32, 0, 24)
+    for kw in (dict(screen_head=3), dict(head=2, screen_head=2), dict(head=1), dict(screen_head=0), dict(screen_head=4)):
+        with pytest.raises(ValueError):
+            CascadeSceneInference(m, **kw)
+    for kw in (dict(margin=-1), dict(margin=1.5), dict(margin=True)):
+        with pytest.raises(ValueError, match="margin"):
+            CascadeSceneInference(m, **kw)
+    for bad in (float("nan"), float("inf"), float("-inf")):
+        with pytest.raises(ValueError, match="finite"):
+            CascadeSceneInference(m, threshold=bad)
+    for kw in (dict(halo=48), dict(tile=500), dict(tile=96), dict(tta="rot"), dict(chunk=0), dict(screen_tile=20),
+               dict(screen_chunk=0)):
+        with pytest.raises(ValueError):
+            CascadeSceneInference(m, **kw)
+    with pytest.raises(ValueError, match="align_corners"):
+        CascadeSceneInference(UNet_Nested(in_channels=1, feature_scale=8, is_deconv=False).eval())
+    c = CascadeSceneInference(m)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        c(torch.zeros(1, 64, 64, 1, dtype=torch.uint8))
+    c.threshold = float("nan")
+    with pytest.raises(ValueError, match="NaN"):
+        c(torch.zeros(1, 64, 64, 1, dtype=torch.uint8))
+
+    class Detector:
+        threshold = 0.05
+
+    c.threshold = 0.1
+    with pytest.raises(ValueError, match="blind"):
+        c.detect(torch.zeros(1, 64, 64, 1, dtype=torch.uint8), Detector())
+    table = ops.scene_rects([(0, 0, 0, 0, 8, 0, 8)])
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        ops.scene_screen(torch.zeros(1, 1, 8, 8), table, table, 0.5)
+
+
+# ---- (5) ------------------------------------------------------------------------------------------------------------
+def test_chunk_selection():
+    from unet_nested4tiny_objects_keypoints_amd.scene import cascade_chunks
+    chunk = 5
+    for graphed in (False, True):
+        assert cascade_chunks([], chunk, graphed) == []                            # no active tile, no forward
+        assert cascade_chunks([7], chunk, graphed) == [[7] + [-1] * (4 if graphed else 0)]
+        full = [3, 4, 9, 11, 20]
+        assert cascade_chunks(full, chunk, graphed) == [full]                      # exactly one chunk: no padding
+        assert cascade_chunks(full + [23], chunk, graphed) == [full, [23] + [-1] * (4 if graphed else 0)]
+    got = cascade_chunks(range(12), 5, True)
+    assert [len(g) for g in got] == [5, 5, 5] and [i for g in got for i in g if i >= 0] == list(range(12))
+    assert [len(g) for g in cascade_chunks(range(12), 5)] == [5, 5, 2]

@@ -297,6 +297,8 @@ SIGNATURES = {
     # scene inference: tile maps back into the frame maps (scene.hip; added within ABI 12)
     "unetpp_scene_stitch": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, C.POINTER(C.c_int32), C.POINTER(SceneRect), _P, _P,
                                       _I32, _I32, _I32, _P]),
+    # cascaded scene inference: which rectangles of a frame map hold anything (scene.hip; added within ABI 13)
+    "unetpp_scene_screen": (C.c_int, [_P, _I32, _I32, _I32, _I32, C.POINTER(SceneRect), _P, _I32, _F, _P, _P, _P]),
     # detection: peaks of scene maps in raster order, detections against labels (detect.hip; added within ABI 12)
     "unetpp_peaks_workspace_bytes": (_I64, [_I32, _I32, _I32]),
     "unetpp_peaks_detect": (C.c_int, [_P, _I32, _I32, _I32, _F, _I32, _I32, _I32, _P, _P, _P, _P, _P]),

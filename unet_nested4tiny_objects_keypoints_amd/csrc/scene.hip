@@ -13,6 +13,9 @@
 // where aligned, reversed for a flip in x); transposing variants read with a stride of Tw floats.  The maps have
 // n_classes channels against the forward's 32 and more: the strided reads are left to L2.  No atomics, no LDS; every
 // offset into `out` is 64-bit.  Nothing outside a tile's owned rectangle is read or written.
+//
+// The second launch of this file, unetpp_scene_screen, reduces rectangles of a frame map to one flag and one maximum
+// each: the device-side decision of cascaded scene inference (described at its kernel below).
 #include "common.h"
 
 #pragma clang fp contract(off)
@@ -105,6 +108,92 @@ __global__ void __launch_bounds__(kStitchThreads) scene_stitch_kernel(
   }
 }
 
+// ---- unetpp_scene_screen: which rectangles of a frame map hold anything (cascaded scene inference) -------
+// One workgroup per rectangle, one launch, one writer per rectangle: over all classes and all pixels of the rectangle,
+// active = any(!(v < threshold)) -- so a value equal to the threshold and a NaN both activate -- and score = fmax of the
+// values (a NaN is ignored; -inf when there is nothing else).  Both are order-independent, so the result is a pure
+// function of the rectangle's values: the same bits whatever the grid.  The four waves of a workgroup take rows of the
+// rectangle in turn, four rows in flight per wave; the lanes take quads of 4 floats cut at 16-byte boundaries of MEMORY
+// (a row starts wherever ((frame * C + c) * H + y) * W + x_lo puts it), so every whole quad is one aligned 16-byte load
+// whatever W is and only a row's ragged first and last quad are read float by float.  Nothing outside a rectangle is
+// read.  Reduction by shuffles within a wave and through 2 x 4 words of LDS across waves; no atomics, no partial buffers;
+// every offset into the maps is 64-bit.
+constexpr int kScreenThreads = 256;
+constexpr int kScreenWaves = kScreenThreads / 64;
+constexpr int kScreenRowsInFlight = 4;
+
+__device__ __forceinline__ bool screen_row_ok(const unetpp_scene_rect& r, int S, int H, int W) {
+  return r.frame < S && r.y_lo >= 0 && r.y_lo < r.y_hi && r.y_hi <= H && r.x_lo >= 0 && r.x_lo < r.x_hi && r.x_hi <= W;
+}
+
+__global__ void __launch_bounds__(kScreenThreads) scene_screen_kernel(
+    const float* __restrict__ maps, const unetpp_scene_rect* __restrict__ rects, int S, int C, int H, int W,
+    float threshold, int32_t* __restrict__ active, float* __restrict__ score) {
+  __shared__ float wave_max[kScreenWaves];
+  __shared__ int wave_any[kScreenWaves];
+  const int t = blockIdx.x;
+  const unetpp_scene_rect r = rects[t];
+  const float ninf = -__builtin_inff();
+  // a padding row, or a device row that disagrees with the frame (the host checked its copy): reported empty, never followed
+  if (r.frame < 0 || !screen_row_ok(r, S, H, W)) {
+    if (threadIdx.x == 0) active[t] = 0, score[t] = ninf;
+    return;
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int rows = r.y_hi - r.y_lo, w = r.x_hi - r.x_lo;
+  const int quads = (w + 6) >> 2;   // of the row that starts 3 floats past a 16-byte boundary
+
+  float best = ninf;
+  bool any = false;
+  for (int c = 0; c < C; ++c) {
+    const float* __restrict__ plane = maps + (int64_t(r.frame) * C + c) * H * W;
+    for (int row0 = wave; row0 < rows; row0 += kScreenWaves * kScreenRowsInFlight) {
+      for (int q = lane; q < quads; q += 64) {
+        f32x4 v[kScreenRowsInFlight];
+#pragma unroll
+        for (int u = 0; u < kScreenRowsInFlight; ++u) {
+          v[u] = f32x4{ninf, ninf, ninf, ninf};   // -inf changes neither result (a live rectangle is never empty)
+          const int row = row0 + u * kScreenWaves;
+          if (row < rows) {
+            const float* p = plane + int64_t(r.y_lo + row) * W + r.x_lo;
+            const int a = static_cast<int>((reinterpret_cast<uintptr_t>(p) >> 2) & 3);   // floats past the boundary
+            const int rel = 4 * q - a;   // the quad's first float, relative to x_lo
+            const int lo = rel > 0 ? rel : 0, hi = rel + 4 < w ? rel + 4 : w;
+            if (hi - lo == 4) {
+              v[u] = *reinterpret_cast<const f32x4*>(p + rel);
+            } else {
+#pragma unroll
+              for (int k = 0; k < 4; ++k)
+                if (rel + k >= lo && rel + k < hi) v[u][k] = p[rel + k];
+            }
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < kScreenRowsInFlight; ++u) {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            any = any || !(v[u][k] < threshold);
+            best = fmaxf(best, v[u][k]);
+          }
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) best = fmaxf(best, __shfl_xor(best, off, 64));
+  const bool any_wave = __any(any) != 0;
+  if (lane == 0) wave_max[wave] = best, wave_any[wave] = any_wave;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float m = wave_max[0];
+    int f = wave_any[0];
+#pragma unroll
+    for (int i = 1; i < kScreenWaves; ++i) m = fmaxf(m, wave_max[i]), f |= wave_any[i];
+    active[t] = f;
+    score[t] = m;
+  }
+}
+
 }  // namespace
 }  // namespace unetpp
 
@@ -143,5 +232,27 @@ extern "C" int unetpp_scene_stitch(const float* tiles, int32_t n_tiles, int32_t 
   hipLaunchKernelGGL(scene_stitch_kernel, dim3(static_cast<unsigned>(blocks), C, n_tiles), dim3(kStitchThreads), 0,
                      static_cast<hipStream_t>(stream), tiles, rects_dev, var, K, C, Th, Tw, out, S, H, W, quads);
   note_kernel("scene_stitch");
+  return launch_status();
+}
+
+extern "C" int unetpp_scene_screen(const float* maps, int32_t S, int32_t C, int32_t H, int32_t W,
+                                   const unetpp_scene_rect* rects, const unetpp_scene_rect* rects_dev, int32_t n_rects,
+                                   float threshold, int32_t* active, float* score, void* stream) {
+  if (maps == nullptr || rects == nullptr || rects_dev == nullptr || active == nullptr || score == nullptr)
+    return UNETPP_EINVAL;
+  if (n_rects <= 0 || S <= 0 || C <= 0 || H <= 0 || W <= 0) return UNETPP_EINVAL;
+  if (threshold != threshold) return UNETPP_EINVAL;
+  bool live = false;
+  for (int t = 0; t < n_rects; ++t) {
+    const unetpp_scene_rect& r = rects[t];
+    if (r.frame < 0) continue;
+    if (r.frame >= S || r.y_lo < 0 || r.y_hi > H || r.x_lo < 0 || r.x_hi > W) return UNETPP_EINVAL;
+    if (r.y_lo >= r.y_hi || r.x_lo >= r.x_hi) return UNETPP_EINVAL;
+    live = true;
+  }
+  if (!live) return UNETPP_OK;   // nothing but padding rows
+  hipLaunchKernelGGL(scene_screen_kernel, dim3(static_cast<unsigned>(n_rects)), dim3(kScreenThreads), 0,
+                     static_cast<hipStream_t>(stream), maps, rects_dev, S, C, H, W, threshold, active, score);
+  note_kernel("scene_screen");
   return launch_status();
 }

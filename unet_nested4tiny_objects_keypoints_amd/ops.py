@@ -1226,6 +1226,42 @@ def scene_stitch(tiles: torch.Tensor, rects: torch.Tensor, rects_dev: torch.Tens
         "unetpp_scene_stitch"), nbytes)
 
 
+def scene_screen(maps: torch.Tensor, rects: torch.Tensor, rects_dev: torch.Tensor, threshold: float):
+    """One launch: maps [S, C, H, W] fp32 -> (active int32 [n], score float32 [n]) on the device, one entry per row of the
+    table: over all classes and all pixels of the row's rectangle [y_lo, y_hi) x [x_lo, x_hi), active = any(!(v <
+    threshold)) (a value equal to the threshold and a NaN both activate) and score = fmax of the values, -inf when all
+    are NaN (include/unetpp_hip.h: unetpp_scene_screen).  rects: the int32 [n, 8] table of scene_rects on the host,
+    rects_dev the same rows on the device; a padding row (frame < 0) gives (0, -inf).  Nothing is read back."""
+    _need(maps, "maps")
+    if maps.dim() != 4:
+        raise ValueError("maps must be [S, C, H, W]")
+    n = int(rects.shape[0]) if rects.dim() == 2 else -1
+    if rects.is_cuda or rects.dtype != torch.int32 or n < 1 or tuple(rects.shape) != (n, 8) or not rects.is_contiguous():
+        raise ValueError("rects must be a contiguous CPU int32 [n, 8] table with n >= 1 (ops.scene_rects)")
+    _need(rects_dev, "rects_dev", torch.int32)
+    if tuple(rects_dev.shape) != (n, 8) or rects_dev.device != maps.device:
+        raise ValueError("rects_dev must be int32 [%d, 8] on the device of maps" % n)
+    threshold = float(threshold)
+    if threshold != threshold:
+        raise ValueError("threshold must not be NaN")
+    s, c, h, w = (int(v) for v in maps.shape)
+    dev = maps.device
+    if not bool((rects[:, 0] >= 0).any()):   # nothing but padding rows: the library launches nothing
+        return (torch.zeros(n, dtype=torch.int32, device=dev),
+                torch.full((n,), float("-inf"), dtype=torch.float32, device=dev))
+    active = torch.empty(n, dtype=torch.int32, device=dev)
+    score = torch.empty(n, dtype=torch.float32, device=dev)
+    host = C.cast(C.c_void_p(rects.data_ptr()), C.POINTER(_lib.SceneRect))
+    nbytes = 0.0
+    if _TIMER is not None:   # one read per class and pixel of every rectangle
+        live = rects[rects[:, 0] >= 0]
+        nbytes = 4.0 * c * float((live[:, 4] - live[:, 3]).clamp_min(0).mul(live[:, 6] - live[:, 5]).sum())
+    _timed_call("scene_screen", 0.0, lambda: check(_lib.lib().unetpp_scene_screen(
+        _ptr(maps), s, c, h, w, host, _ptr(rects_dev), n, threshold, _ptr(active), _ptr(score), _stream()),
+        "unetpp_scene_screen"), nbytes)
+    return active, score
+
+
 def peaks_detect(maps: torch.Tensor, threshold: float, radius: int, cap: int, refine: bool = True):
     """maps [M, H, W] fp32 on the GPU -> (xy [M, cap, 2] as (x, y), score [M, cap], count [M] int32): the local maxima of
     every map that reach `threshold`, in raster order (include/unetpp_hip.h: unetpp_peaks_detect; rule, sub-pixel

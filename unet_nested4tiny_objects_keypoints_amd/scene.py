@@ -5,6 +5,8 @@ exact rather than blended, with dihedral test-time augmentation folded into the 
     maps = scene(frames)                      # uint8 [S, H, W, C] or float32 [S, C, H, W] on the GPU -> [S, n_classes, H, W]
     points, counts = scene.points(maps, heatmap)
     dets = scene.detect(frames, PeakDetector())   # any number of objects per map (detect.py)
+    cascade = CascadeSceneInference(model.eval(), head=3, screen_head=1, threshold=0.1, tta="dihedral")
+    maps = cascade(frames)                    # head 1 everywhere, head 3 only on the tiles where head 1 fires
 
 The frame is cut into overlapping tiles of one fixed shape; chunks of tiles run through ``model.infer`` (or one captured
 ``GraphedForward``) and ``unetpp_scene_stitch`` puts each tile's OWNED interior back.  Why the result equals the
@@ -17,7 +19,8 @@ The reference has no counterpart: its validation loop feeds whole 256x256 images
 """
 from __future__ import annotations
 
-from typing import List, Tuple
+import math
+from typing import List, NamedTuple, Tuple
 
 import torch
 
@@ -25,7 +28,8 @@ from . import _lib, engine, ops
 from .loader import _per_channel, affine_params
 from .serving import GraphedForward
 
-__all__ = ["required_halo", "plan_tiles", "SceneInference", "TTA_VARIANTS"]
+__all__ = ["required_halo", "plan_tiles", "SceneInference", "TTA_VARIANTS", "CascadeSceneInference", "CascadeAudit",
+           "screen_rows", "cascade_chunks"]
 
 _FX, _FY, _T = _lib.SCENE_FLIP_X, _lib.SCENE_FLIP_Y, _lib.SCENE_TRANSPOSE
 # variant codes (include/unetpp_hip.h): the variant is flip_y(flip_x(transpose(tile))), each step only if its bit is set
@@ -92,6 +96,9 @@ def _variant_forward(code: int, oy: int, ox: int, th: int, tw: int):
 
 class _Chunk:
     __slots__ = ("n", "index", "params", "rects", "rects_dev")
+
+
+_PAD_TILE = (-1, 0, 0, 0, 0, 0, 0)   # a padding row of a tile table
 
 
 class SceneInference:
@@ -164,35 +171,43 @@ class SceneInference:
             raise ValueError("tta='dihedral' needs square tiles: both frame sides must reach tile = %d, got %dx%d"
                              % (self.tile, H, W))
 
+    def _tiles(self, S: int, H: int, W: int):
+        """every tile of S frames in plan order: rows of (frame, oy, ox, y_lo, y_hi, x_lo, x_hi)"""
+        rows, cols = plan_tiles(H, W, self.tile, self.halo, self.align)
+        return [(s, oy, ox, y0, y1, x0, x1) for s in range(S) for (oy, y0, y1) in rows for (ox, x0, x1) in cols]
+
+    def _chunk(self, part, th: int, tw: int, device) -> _Chunk:
+        """the tables of one forward over the tiles `part` (a row with frame < 0 is an all-fill sample the stitch skips)"""
+        identity = _variant_forward(0, 0, 0, th, tw)
+        c = _Chunk()
+        c.n = len(part)
+        c.index = torch.tensor([t[0] for t in part for _ in self.variants], dtype=torch.int64).to(device)
+        fwd = [_variant_forward(code, t[1], t[2], th, tw) if t[0] >= 0 else identity
+               for t in part for code in self.variants]
+        c.params = affine_params(fwd).to(device)
+        c.rects = ops.scene_rects(part)
+        c.rects_dev = c.rects.to(device)
+        return c
+
     def _plan(self, S: int, H: int, W: int, device) -> List[_Chunk]:
         key = (S, H, W, str(device))
         plan = self._plans.get(key)
         if plan is not None:
             return plan
-        rows, cols = plan_tiles(H, W, self.tile, self.halo, self.align)
         th, tw = self.tile_shape(H, W)
-        tiles = [(s, oy, ox, y0, y1, x0, x1) for s in range(S) for (oy, y0, y1) in rows for (ox, x0, x1) in cols]
-        identity = _variant_forward(0, 0, 0, th, tw)
+        tiles = self._tiles(S, H, W)
         plan = []
         for i in range(0, len(tiles), self.chunk):
             part = tiles[i:i + self.chunk]
-            live = len(part)
             if self.graphed:   # the captured shape: pad with all-fill samples that the stitch skips
-                part = part + [(-1, 0, 0, 0, 0, 0, 0)] * (self.chunk - live)
-            c = _Chunk()
-            c.n = len(part)
-            c.index = torch.tensor([t[0] for t in part for _ in self.variants], dtype=torch.int64).to(device)
-            fwd = [_variant_forward(code, t[1], t[2], th, tw) if t[0] >= 0 else identity
-                   for t in part for code in self.variants]
-            c.params = affine_params(fwd).to(device)
-            c.rects = ops.scene_rects(part)
-            c.rects_dev = c.rects.to(device)
-            plan.append(c)
+                part = part + [_PAD_TILE] * (self.chunk - len(part))
+            plan.append(self._chunk(part, th, tw, device))
         self._plans[key] = plan
         return plan
 
     # ---- device side -------------------------------------------------------------------------------
-    def __call__(self, frames: torch.Tensor) -> torch.Tensor:
+    def _prepare(self, frames: torch.Tensor):
+        """checks of a call -> (contiguous frames, S, H, W)"""
         if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
             raise RuntimeError("frames must live on the GPU: this path has no CPU fallback")
         if frames.dtype not in (torch.uint8, torch.float32):
@@ -204,22 +219,26 @@ class SceneInference:
         u8 = frames.dtype == torch.uint8
         S = int(frames.shape[0])
         H, W, cin = (int(v) for v in (frames.shape[1:] if u8 else (frames.shape[2], frames.shape[3], frames.shape[1])))
-        model = self.model
-        if cin != model.in_channels:
-            raise ValueError("expected %d input channels, got %d" % (model.in_channels, cin))
-        if model.training:
+        if cin != self.model.in_channels:
+            raise ValueError("expected %d input channels, got %d" % (self.model.in_channels, cin))
+        if self.model.training:
             raise RuntimeError("SceneInference runs the eval forward: call model.eval() first")
         self._check_size(H, W)
-        dev = frames.device
-        frames = frames.contiguous()
+        return frames.contiguous(), S, H, W
+
+    def _run(self, frames: torch.Tensor, chunks, out: torch.Tensor) -> torch.Tensor:
+        """warp, forward and stitch of every chunk in `chunks` (each of self.chunk tiles when graphed) into out
+        [S, n_classes, H, W]; pixels no tile of the chunks owns are left as they are"""
+        model, dev = self.model, frames.device
+        H, W = int(out.shape[2]), int(out.shape[3])
+        cin = model.in_channels
         norm = self._norm.get(str(dev))
         if norm is None:
             norm = self._norm[str(dev)] = (_per_channel(self.mul, cin, dev), _per_channel(self.add, cin, dev))
         th, tw = self.tile_shape(H, W)
         K = len(self.variants)
-        out = torch.empty(S, model.n_classes, H, W, dtype=torch.float32, device=dev)
-        graph = self._graph(cin, th, tw, dev) if self.graphed else None
-        for c in self._plan(S, H, W, dev):
+        graph = self._graph(cin, th, tw, dev) if self.graphed and chunks else None
+        for c in chunks:
             if graph is not None:
                 x = ops.warp_batch(frames, c.index, c.params, (th, tw), norm[0], norm[1], 0.0, out=graph.static_input)
                 maps = graph(x)
@@ -228,6 +247,11 @@ class SceneInference:
                 maps = model.infer(x, self.head, self.ensemble)
             ops.scene_stitch(maps.view(c.n, K, model.n_classes, th, tw), c.rects, c.rects_dev, self.variants, out)
         return out
+
+    def __call__(self, frames: torch.Tensor) -> torch.Tensor:
+        frames, S, H, W = self._prepare(frames)
+        out = torch.empty(S, self.model.n_classes, H, W, dtype=torch.float32, device=frames.device)
+        return self._run(frames, self._plan(S, H, W, frames.device), out)
 
     def _graph(self, cin: int, th: int, tw: int, dev) -> GraphedForward:
         key = (cin, th, tw, str(dev))
@@ -247,3 +271,181 @@ class SceneInference:
     def detect(self, frames: torch.Tensor, detector):
         """``detector(self(frames))``: the frames' maps through a ``detect.PeakDetector`` -> ``Detections``."""
         return detector(self(frames))
+
+
+# ---- cascaded scene inference (DESIGN.md 5l) -----------------------------------------------------------
+def screen_rows(tiles, th: int, tw: int, margin: int):
+    """The screened rectangle R_t of every deep tile: its owned rectangle O_t grown by `margin` pixels on all four sides,
+    then clipped to the tile's own extent [oy, oy + th) x [ox, ox + tw).  Rows in and out are (frame, oy, ox, y_lo, y_hi,
+    x_lo, x_hi); margin = 0 returns the owned rectangles, which partition the frame."""
+    return [(s, oy, ox, max(y0 - margin, oy), min(y1 + margin, oy + th), max(x0 - margin, ox), min(x1 + margin, ox + tw))
+            for (s, oy, ox, y0, y1, x0, x1) in tiles]
+
+
+def cascade_chunks(active, chunk: int, graphed: bool = False):
+    """The deep forwards of one call: the active tile ids, in plan order, cut into lists of at most `chunk`; with
+    `graphed` the last list is filled up to `chunk` with -1 (an all-fill sample that the stitch skips), the captured
+    shape.  No active tile, no forward: []."""
+    ids = [int(i) for i in active]
+    out = [ids[i:i + chunk] for i in range(0, len(ids), chunk)]
+    if graphed and out:
+        out[-1] = out[-1] + [-1] * (chunk - len(out[-1]))
+    return out
+
+
+class CascadeAudit(NamedTuple):
+    """What ``CascadeSceneInference.audit`` found at `level`: tiles whose deep score reaches it that the screen left
+    inactive, active tiles whose deep score stays below it, and max |cascade - deep| over the frames."""
+    missed: int
+    wasted: int
+    max_abs_diff: float
+    n_active: int
+    n_tiles: int
+    level: float
+
+
+class _CascadePlan:
+    __slots__ = ("n", "tiles", "screen", "screen_dev", "owned", "owned_dev")
+
+
+class CascadeSceneInference:
+    """cascade(frames) -> float32 [S, n_classes, H, W] on the device: the shallow head `screen_head` everywhere, the deep
+    head `head` -- with its test-time augmentation and, with ``ensemble``, as the mean of heads 1 .. head -- only on the
+    tiles where the shallow head fires.
+
+    The rule.  The deep plan is the one ``SceneInference(model, head, tile=tile, halo=halo, tta=tta, chunk=chunk)``
+    builds: tile t of frame s has an origin, a shape and an owned rectangle O_t.  Its screened rectangle R_t is O_t grown
+    by ``margin`` pixels on all four sides (default: the deep halo; 0 screens exactly the owned pixels), clipped to the
+    tile's extent.  M1 is the whole-frame map of the shallow head, ``SceneInference(model, head=screen_head,
+    tile=screen_tile, chunk=screen_chunk)(frames)`` with that head's own, smaller halo.  Over all classes and all pixels
+    of R_t:  active_t = any(!(M1 < threshold)) -- a value equal to the threshold activates, and so does a NaN -- and
+    score_t = fmax of the values (-inf when all are NaN).  The result starts as M1 (the same buffer, no copy), and every
+    active tile's owned rectangle is overwritten with the deep head's value through the same stitch launch:
+    ``out == where(A, D, M1)`` bit for bit, D the plain deep ``SceneInference``'s map and A the flag of the tile that owns
+    the pixel -- wherever the deep forward selects the same kernels for the cascade's chunks as for the plain scene's.
+
+    Per call: the screen stage, ONE ``unetpp_scene_screen`` launch over all deep tiles of all frames, one copy of the
+    ``active`` flags to the host -- THE ONLY DEVICE-TO-HOST COPY OF A CALL: how many deep forwards follow depends on the
+    data, so the host has to know -- and the deep stage over the active tiles in plan order, ``chunk`` tiles per forward.
+    With no active tile the deep model never runs.  ``graphed`` captures one graph per stage (two live captures on one
+    model coexist: each pins the weight-image plan it was captured with); the deep stage's last chunk is padded with
+    all-fill samples as in ``SceneInference``.
+
+    The constructor refuses ``screen_head >= head``, a threshold that is not finite, a negative margin, and whatever
+    ``SceneInference`` refuses for either stage.  ``threshold`` is a plain attribute: set it between calls (``audit``
+    helps to choose it); +inf and -inf then mean "no tile" and "every tile", NaN is refused at the call.
+
+    After a call: ``last_active`` (host bool [n_tiles], plan order), ``last_scores`` (device float32 [n_tiles]),
+    ``last_fraction`` (active tiles over tiles) and ``last_forwards`` (deep forwards run)."""
+
+    def __init__(self, model, head=None, screen_head: int = 1, threshold: float = 0.1, ensemble: bool = False,
+                 tile: int = 512, screen_tile=None, halo=None, margin=None, tta=None, chunk: int = 8, screen_chunk=None,
+                 mul=1.0 / 255.0, add=0.0, graphed: bool = False):
+        self.deep = SceneInference(model, head=head, ensemble=ensemble, tile=tile, halo=halo, tta=tta, chunk=chunk,
+                                   mul=mul, add=add, graphed=graphed)
+        screen_head = engine.check_head(model.depth, screen_head)
+        if screen_head >= self.deep.head:
+            raise ValueError("the screen head must be shallower than the deep head, got screen_head = %d, head = %d"
+                             % (screen_head, self.deep.head))
+        self.screen = SceneInference(model, head=screen_head, tile=tile if screen_tile is None else screen_tile,
+                                     chunk=chunk if screen_chunk is None else screen_chunk, mul=mul, add=add,
+                                     graphed=graphed)
+        threshold = float(threshold)
+        if not math.isfinite(threshold):
+            raise ValueError("threshold must be finite, got %r" % threshold)
+        margin = self.deep.halo if margin is None else margin
+        if isinstance(margin, bool) or not isinstance(margin, int) or margin < 0:
+            raise ValueError("margin must be an int >= 0, got %r" % (margin,))
+        self.model, self.threshold, self.margin = model, threshold, margin
+        self.head, self.screen_head, self.chunk, self.graphed = self.deep.head, screen_head, chunk, bool(graphed)
+        self._plans = {}
+        self.last_active = self.last_scores = self._active_dev = None
+        self.last_fraction, self.last_forwards = 0.0, 0
+
+    def _plan(self, S: int, H: int, W: int, device) -> _CascadePlan:
+        key = (S, H, W, str(device))
+        p = self._plans.get(key)
+        if p is None:
+            deep = self.deep
+            th, tw = deep.tile_shape(H, W)
+            tiles = deep._tiles(S, H, W)
+            p = self._plans[key] = _CascadePlan()
+            p.n = len(tiles)
+            p.screen = ops.scene_rects(screen_rows(tiles, th, tw, self.margin))
+            p.screen_dev = p.screen.to(device)
+            p.owned = ops.scene_rects(tiles)
+            p.owned_dev = p.owned.to(device)
+            p.tiles = deep._chunk(tiles + [_PAD_TILE], th, tw, device)   # row n: the padding sample
+        return p
+
+    def _deep_chunks(self, p: _CascadePlan, active, device) -> List[_Chunk]:
+        """the tables of the call's deep forwards, gathered on the device from the plan's per-tile tables"""
+        groups = cascade_chunks(active, self.chunk, self.graphed)
+        if not groups:
+            return []
+        K = len(self.deep.variants)
+        sel = torch.tensor([p.n if i < 0 else i for g in groups for i in g], dtype=torch.int64)
+        sel_dev = sel.to(device)
+        index = p.tiles.index.view(p.n + 1, K).index_select(0, sel_dev)
+        params = p.tiles.params.view(p.n + 1, K, -1).index_select(0, sel_dev)
+        rects = p.tiles.rects.index_select(0, sel)
+        rects_dev = p.tiles.rects_dev.index_select(0, sel_dev)
+        chunks, at = [], 0
+        for g in groups:
+            c = _Chunk()
+            c.n = len(g)
+            c.index = index[at:at + c.n].reshape(-1)
+            c.params = params[at:at + c.n].reshape(c.n * K, -1)
+            c.rects = rects[at:at + c.n].contiguous()
+            c.rects_dev = rects_dev[at:at + c.n]
+            chunks.append(c)
+            at += c.n
+        return chunks
+
+    def __call__(self, frames: torch.Tensor) -> torch.Tensor:
+        """The cascade's map of the frames.  Exactly one device-to-host copy happens in a call: the ``active`` flags."""
+        threshold = float(self.threshold)
+        if threshold != threshold:
+            raise ValueError("threshold must not be NaN")
+        frames, S, H, W = self.deep._prepare(frames)
+        dev = frames.device
+        out = self.screen(frames)                                                   # M1
+        p = self._plan(S, H, W, dev)
+        active, scores = ops.scene_screen(out, p.screen, p.screen_dev, threshold)
+        host = active.cpu() != 0                                                    # the one read-back
+        chunks = self._deep_chunks(p, torch.nonzero(host).flatten().tolist(), dev)
+        self.deep._run(frames, chunks, out)
+        self.last_active, self.last_scores, self._active_dev = host, scores, active
+        self.last_fraction = float(int(host.sum())) / p.n
+        self.last_forwards = len(chunks)
+        return out
+
+    def detect(self, frames: torch.Tensor, detector):
+        """``detector(self(frames))`` -> ``Detections``.  Below the screen threshold the cascade is blind by design (an
+        inactive tile shows the shallow head's map, all of it below the threshold on its owned pixels), so a detector
+        whose threshold lies below the screen's is refused.  What holds at or above it: no detection can come from the
+        owned pixels of an inactive tile."""
+        if float(detector.threshold) < float(self.threshold):
+            raise ValueError("the detector's threshold %g lies below the screen threshold %g: the cascade is blind there"
+                             % (detector.threshold, self.threshold))
+        return detector(self(frames))
+
+    def audit(self, frames: torch.Tensor, level=None) -> CascadeAudit:
+        """The tool for choosing ``threshold``: runs the cascade AND the plain deep scene on the frames, screens the deep
+        map D with margin 0 (one more ``unetpp_scene_screen`` launch: deep_score_t = fmax of D over the tile's owned
+        pixels) and counts, on the device, the tiles with deep_score_t >= level (default: the threshold) that the screen
+        left inactive (missed) and the active tiles whose deep score stays below level (wasted); with max |out - D| these
+        few numbers are read back at the end."""
+        level = float(self.threshold if level is None else level)
+        if level != level:
+            raise ValueError("level must not be NaN")
+        out = self(frames)
+        deep = self.deep(frames)
+        p = self._plan(int(out.shape[0]), int(out.shape[2]), int(out.shape[3]), out.device)
+        _, deep_score = ops.scene_screen(deep, p.owned, p.owned_dev, level)
+        on = self._active_dev != 0
+        missed = ((deep_score >= level) & ~on).sum()
+        wasted = ((deep_score < level) & on).sum()
+        diff = (out - deep).abs().max()
+        counts = torch.stack([missed, wasted, on.sum()]).tolist()
+        return CascadeAudit(int(counts[0]), int(counts[1]), float(diff), int(counts[2]), p.n, level)
