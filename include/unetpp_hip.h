@@ -411,6 +411,29 @@ int unetpp_focal_bce_heads(const unetpp_focal_heads* heads, const float* target,
 int64_t unetpp_topk_focal_workspace_bytes(int32_t n_heads, int64_t rows, int64_t P);
 int unetpp_topk_focal_heads(const unetpp_focal_heads* heads, const float* target, int64_t rows, int64_t P, int64_t k,
                             int64_t denom, float gamma, void* workspace, float* kth, float* loss, void* stream);
+/* ---- penalty-reduced focal loss, normalised by positives (added within v13: new entry points only) ----
+ * The heat-map loss of CornerNet / CenterNet for every head against one target, n float32 elements each.  Per element of
+ * a head p (in [0, 1]) and the target t (domain [0, 1]); alpha >= 0, beta >= 0, eps in (0, 0.5), positive in (0, 1]:
+ *   lo = float32(eps), hi = float32(1) - lo (one float32 subtraction);  q = min(max(p, lo), hi), a NaN stays a NaN;
+ *   the gradient passes where lo <= p <= hi (torch.clamp's rule) and is exactly +0.0 elsewhere;
+ *   t >= positive:  l = -(1 - q)^alpha log(q);   otherwise:  l = -(1 - t)^beta q^alpha log(1 - q), the logarithm
+ *   evaluated as log1pf(-q);  0^0 = 1;
+ *   n_pos[0] = the elements of the target with t >= positive (exact; per call, hence per replica under data parallel),
+ *   denom = max(n_pos, 1);  loss[1 + h] = (sum of l over head h) * (1 / denom);
+ *   loss[0]  = (0 + loss[1] + ... + loss[n_heads]) * (1 / n_heads) as unetpp_focal_bce_heads forms it;
+ *   grad[h]  = d loss[0] / d pred[h] = ((dl / dq) * (1 / denom)) * (1 / n_heads), the float32 products in autograd's
+ *              order; grad[h] may be NULL.
+ * A NaN in pred makes the loss NaN; the gradient at that element is 0.  A label at a sub-pixel position never produces
+ * a target of exactly 1: lower `positive` for such targets.  Three launches (an integer count pass over the target, the
+ * main pass, a finish in fixed order), no host synchronisation, no atomics: two runs give the same bits, and the call
+ * may be captured in a graph.  workspace: unetpp_pr_focal_workspace_bytes(n_heads, n) bytes (0 for arguments the call
+ * would refuse), 8-byte aligned, as is n_pos; target and every pred[h] / grad[h] 16-byte aligned.  UNETPP_EINVAL, without
+ * touching the device, for a NULL pointer, n < 1 (or n above 2^42), n_heads outside 1 .. UNETPP_MAX_HEADS, a negative or
+ * NaN alpha / beta, eps outside (0, 0.5), positive outside (0, 1], a misaligned pointer. */
+int64_t unetpp_pr_focal_workspace_bytes(int32_t n_heads, int64_t n);
+int unetpp_pr_focal_heads(const unetpp_focal_heads* heads, const float* target, int64_t n, float alpha, float beta,
+                          float eps, float positive, void* workspace, int64_t* n_pos, float* loss /* [1 + n_heads] */,
+                          void* stream);
 /* ---- ensemble head of an eval forward (added within v12: new entry points only, nothing existing changes) ----
  * The output selection the UNet++ authors left as comments in models/unet.py:293-298: the mean of the first n_heads
  * deep-supervision heads, out = (((s_1 + s_2) + ...) + s_n) / (float)n with s_h = 1 / (1 + exp(-(bias_h + x_h . w_h)))

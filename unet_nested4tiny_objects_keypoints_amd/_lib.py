@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("UNETPP_LIB", os.path.join(_PKG_DIR, "libunetpp_hip.so
 CSRC = os.path.join(_PKG_DIR, "csrc")
 INCLUDE = os.path.join(_REPO, "include")
 SOURCES = ("gemm_pix.hip", "gemm_fast.hip", "gemm_pw.hip", "gemm_pw_bf16.hip", "gemm_wino.hip", "gemm_bf16.hip", "gemm_bf16_dma.hip", "wgrad_bf16.hip", "pointwise_bf16.hip", "keypoints.hip", "weight_image.hip", "wgrad.hip", "wgrad_fast.hip", "wgrad_dma.hip", "wgrad_pw.hip", "wgrad_wino.hip", "first_layer.hip", "pointwise.hip", "heads.hip", "caller.hip", "optim.hip", "validate.hip", "average.hip", "loader.hip", "scene.hip",
-           "detect.hip", "crops.hip", "topk_loss.hip")
+           "detect.hip", "crops.hip", "topk_loss.hip", "pr_focal.hip")
 HEADERS = ("common.h", "gemm_units.h", "wgrad_reduce.h", "lds_asm.h", "bf16_common.h", "dropout.h", "bn_fused.h",
            "wino_experiments.h", "dma_experiments.h", "heads_mean.h", "head_select.h", "focal_element.h", "multi_tensor.h")
 MAX_VIEWS = 8
@@ -310,6 +310,9 @@ SIGNATURES = {
     # top-k focal loss: hard-pixel mining per map, all heads in one launch (topk_loss.hip; added within ABI 12)
     "unetpp_topk_focal_workspace_bytes": (_I64, [_I32, _I64, _I64]),
     "unetpp_topk_focal_heads": (C.c_int, [C.POINTER(FocalHeads), _P, _I64, _I64, _I64, _I64, _F, _P, _P, _P, _P]),
+    # penalty-reduced focal loss normalised by positives, all heads in one call (pr_focal.hip; added within ABI 13)
+    "unetpp_pr_focal_workspace_bytes": (_I64, [_I32, _I64]),
+    "unetpp_pr_focal_heads": (C.c_int, [C.POINTER(FocalHeads), _P, _I64, _F, _F, _F, _F, _P, _P, _P, _P]),
 }
 
 _LIB = None

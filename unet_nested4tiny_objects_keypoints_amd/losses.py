@@ -165,3 +165,93 @@ class TopKFocalLoss_BCE_2d(nn.Module):
                                                 float(self.gamma))
         self.last_threshold = kth
         return loss[0], grads
+
+
+class _PRFocalFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, target, alpha, beta, eps, positive):
+        from . import ops
+        loss, grads, n_pos = ops.pr_focal_heads([pred.contiguous()], target.contiguous(), alpha, beta, eps, positive,
+                                                want_grad=ctx.needs_input_grad[0])
+        ctx.save_for_backward(grads[0] if grads is not None else None)
+        ctx.mark_non_differentiable(n_pos)
+        return loss[0], n_pos
+
+    @staticmethod
+    def backward(ctx, g, _g_n_pos):
+        (grad,) = ctx.saved_tensors
+        return (grad * g if grad is not None else None), None, None, None, None, None
+
+
+class PenaltyReducedFocalLoss(nn.Module):
+    """The penalty-reduced focal loss of CornerNet / CenterNet for heat maps of sigmoid values, normalised by the number
+    of positives.  Per element of ``input`` p and ``target`` t (same shape, t in [0, 1]), in float32:
+
+        lo = float32(eps), hi = float32(1) - lo;  q = clamp(p, lo, hi) (the gradient passes where lo <= p <= hi, as
+        ``torch.clamp`` has it, and is exactly 0 elsewhere; a NaN stays a NaN and makes the loss NaN);
+        t >= positive:  l = -(1 - q)^alpha log(q);   otherwise:  l = -(1 - t)^beta q^alpha log1p(-q);   0^0 = 1;
+        n_pos = the elements with t >= positive, over the whole target;  loss = sum(l) * (1 / max(n_pos, 1)).
+
+    The normaliser belongs to the call, hence to the replica under data parallel.  ``unetpp_points_target`` and
+    ``create_heatmap`` write exactly 1.0 at an integer label, so ``positive=1.0`` marks the centres.  A label at a sub-pixel
+    position never produces a 1.0: the largest value of ``exp(-0.5 d / radius)`` within half a pixel of it may be as low as
+    ``exp(-0.5 * 0.7071 / radius)``, and ``positive=math.exp(-0.5 * 0.7071 / radius)`` takes the nearest pixel (and, close
+    to a pixel centre, its neighbours) for such targets.
+
+    GPU fp32 tensors take one fused HIP call (csrc/pr_focal.hip: value and gradient together, backward is one scaling);
+    anything else the same rule as plain torch ops.  After a call ``last_num_positives`` holds n_pos as a 0-dim int64
+    tensor on the device of the target; the class never reads it back.
+
+    Deliberately not a subclass of ``FocalLoss_BCE_2d``: code that tests for that class computes another loss."""
+
+    def __init__(self, alpha=2.0, beta=4.0, eps=1e-4, positive=1.0):
+        super().__init__()
+        alpha, beta, eps, positive = float(alpha), float(beta), float(eps), float(positive)
+        if not (0.0 <= alpha < float("inf")) or not (0.0 <= beta < float("inf")):
+            raise ValueError("alpha and beta must be finite and >= 0, got %r and %r" % (alpha, beta))
+        lo = torch.tensor(eps, dtype=torch.float32)
+        if not 0.0 < float(lo) < 0.5:
+            raise ValueError("eps must be in (0, 0.5) as a float32, got %r" % (eps,))
+        pos32 = float(torch.tensor(positive, dtype=torch.float32))
+        if not 0.0 < pos32 <= 1.0:
+            raise ValueError("positive must be in (0, 1], got %r" % (positive,))
+        self.alpha, self.beta, self.eps, self.positive = alpha, beta, eps, positive
+        self._lo = float(lo)
+        self._hi = float(torch.tensor(1.0, dtype=torch.float32) - lo)
+        self._positive32 = pos32
+        self.last_num_positives = None
+
+    def forward(self, input, target):
+        if input.shape != target.shape:
+            raise ValueError("input and target must have the same shape")
+        if (input.is_cuda and target.is_cuda and input.dtype == torch.float32 and target.dtype == torch.float32
+                and not target.requires_grad):
+            loss, n_pos = _PRFocalFn.apply(input, target, self.alpha, self.beta, self.eps, self.positive)
+            self.last_num_positives = n_pos
+            return loss
+        q = input.clamp(self._lo, self._hi)
+        pos = target >= self._positive32
+        at_centre = -1 * (1 - q) ** self.alpha * torch.log(q)
+        elsewhere = -1 * (1 - target) ** self.beta * q ** self.alpha * torch.log1p(-q)
+        n_pos = pos.sum()
+        self.last_num_positives = n_pos
+        total = torch.where(pos, at_centre, elsewhere).sum()
+        return total * (1.0 / n_pos.clamp(min=1).to(total.dtype))
+
+    def mean_over_heads(self, outputs, target):
+        """``FocalLoss_BCE_2d.mean_over_heads`` for this criterion: the trainer's loop over the deep-supervision heads in
+        ONE call, the positives counted once -> (avg: 0-dim tensor without a graph, [d avg / d output]) or None when the
+        heads do not qualify; the caller then runs the loop.  Same bits as the loop (tests/test_gpu_prfocal.py)."""
+        from . import _lib, ops
+        if not (isinstance(outputs, (tuple, list)) and 2 <= len(outputs) <= _lib.MAX_HEADS):
+            return None
+        if not (target.is_cuda and target.dtype == torch.float32 and not target.requires_grad and target.dim() == 4):
+            return None
+        for o in outputs:
+            if not (o.is_cuda and o.dtype == torch.float32 and o.shape == target.shape and o.is_contiguous()
+                    and o.device == target.device):
+                return None
+        loss, grads, n_pos = ops.pr_focal_heads([o.detach() for o in outputs], target.contiguous(), self.alpha, self.beta,
+                                                self.eps, self.positive)
+        self.last_num_positives = n_pos
+        return loss[0], grads

@@ -929,6 +929,39 @@ def topk_focal_heads(preds, target: torch.Tensor, k: int, denom: int, gamma: flo
     return loss, grads, kth
 
 
+def pr_focal_heads(preds, target: torch.Tensor, alpha: float, beta: float, eps: float, positive: float,
+                   want_grad: bool = True):
+    """Penalty-reduced focal loss of every head against one target, normalised by the number of positives (t >=
+    positive) of the target (csrc/pr_focal.hip: a count pass, the main pass, a finish; no read-back).
+    -> (losses [1 + heads]: the mean over heads, then every head's value; d mean / d pred per head or None; n_pos: the
+    number of positives, a 0-dim int64 tensor on the device)."""
+    lib = _lib.lib()
+    if not 1 <= len(preds) <= _lib.MAX_HEADS:
+        raise ValueError("1 to %d heads" % _lib.MAX_HEADS)
+    _need(target, "target")
+    for p in preds:
+        _need(p, "pred")
+        if p.shape != target.shape:
+            raise ValueError("pred and target must have the same shape")
+    preds, target = [_aligned16(p) for p in preds], _aligned16(target)
+    n = target.numel()
+    nbytes = int(lib.unetpp_pr_focal_workspace_bytes(len(preds), n))
+    if nbytes <= 0:
+        raise ValueError("pr_focal_heads: %d elements are outside what the kernel takes" % n)
+    workspace = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=target.device)
+    grads = [torch.empty_like(p) for p in preds] if want_grad else None
+    loss = torch.empty(1 + len(preds), dtype=torch.float32, device=target.device)
+    n_pos = torch.empty((), dtype=torch.int64, device=target.device)
+    hd = _lib.FocalHeads()
+    hd.n_heads = len(preds)
+    for i, p in enumerate(preds):
+        hd.pred[i] = p.data_ptr()
+        hd.grad[i] = grads[i].data_ptr() if want_grad else None
+    check(lib.unetpp_pr_focal_heads(C.byref(hd), _ptr(target), n, float(alpha), float(beta), float(eps), float(positive),
+                                    _ptr(workspace), _ptr(n_pos), _ptr(loss), _stream()), "unetpp_pr_focal_heads")
+    return loss, grads, n_pos
+
+
 def create_heatmap(points: torch.Tensor, height: int, width: int, radius: float = 3.0) -> torch.Tensor:
     """points [N, P, 2] (x, y) fp32 on the GPU -> target heat maps [N, 4, H, W] (tools/misc/helper.py:87-172)."""
     lib = _lib.lib()
