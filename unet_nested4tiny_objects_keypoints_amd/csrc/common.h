@@ -57,6 +57,19 @@ __device__ __forceinline__ float row16_sum(float v) {
   return v;
 }
 
+// ReLU that carries a NaN: +0 for -0 and for negatives, v for everything above 0, NaN for NaN.
+// fmaxf(NaN, 0) is 0 and would hide a non-finite activation from the loss; on every ordinary value the bits are fmaxf's.
+__device__ __forceinline__ float relu_keep_nan(float v) { return !(v <= 0.f) ? v : 0.f; }
+// The same against a floor that is 0 (ReLU) or -inf (none: the identity), for a ReLU that is a wave-uniform option of a
+// launch: one compare and one select per element whether or not the option is set.  (`if (relu) v = relu_keep_nan(v)`
+// comes out as compare, scalar OR with the option, select: the scalar step between two vector ones stalls the wave.)
+__device__ __forceinline__ float relu_floor(bool relu) { return relu ? 0.f : -__builtin_inff(); }
+__device__ __forceinline__ float floor_keep_nan(float v, float floor_v) { return !(v <= floor_v) ? v : floor_v; }
+
+// 2x2 max-pool: does t replace the window's best so far?  The first maximum wins in scan order, and a NaN always takes
+// the window (the last one of several keeps it), as torch.max_pool2d has it; without a NaN this is t > best.
+__device__ __forceinline__ bool pool_takes(float t, float best) { return t > best || t != t; }
+
 // slab groups of the weight-gradient finish kernels for n_split slabs: the smallest power of two >= n_split, at most 16
 inline int finish_log2_groups(int n_split) {
   int l = 0;
@@ -105,7 +118,7 @@ __device__ __forceinline__ f32x4 view_load4(const unetpp_view& v, long off, int 
   }
   if (v.relu) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) val[i] = fmaxf(val[i], 0.f);
+    for (int i = 0; i < 4; ++i) val[i] = relu_keep_nan(val[i]);
   }
   if (v.gate != nullptr) {
     const float* g = v.gate + off + c;

@@ -148,7 +148,7 @@ __global__ __launch_bounds__(kThreads, CIN >= 3 ? 3 : 4) void small_cin_fwd_kern
         f32x4 acc = {acc_a.x, acc_a.y, acc_b.x, acc_b.y};
         if (a.relu) {
 #pragma unroll
-          for (int e = 0; e < 4; ++e) acc[e] = fmaxf(acc[e], 0.f);
+          for (int e = 0; e < 4; ++e) acc[e] = relu_keep_nan(acc[e]);
         }
         if (BF) {  // the statistics describe the stored (rounded) tensor
 #pragma unroll

@@ -225,10 +225,8 @@ __global__ __launch_bounds__(kThreads, STATS ? UNETPP_BF16_STATS_WGS : UNETPP_BF
 #pragma unroll
           for (int e = 0; e < 8; ++e) f[e] = fmaf(f[e], sc[e], sh[e]);
         }
-        if (V.relu) {
 #pragma unroll
-          for (int e = 0; e < 8; ++e) f[e] = fmaxf(f[e], 0.f);
-        }
+        for (int e = 0; e < 8; ++e) f[e] = floor_keep_nan(f[e], relu_floor(V.relu));
         v = pack8(f);
       }
 #pragma unroll
@@ -282,7 +280,7 @@ __global__ __launch_bounds__(kThreads, STATS ? UNETPP_BF16_STATS_WGS : UNETPP_BF
           const int c = (r & 3) + 8 * (r >> 2);
           const int dy = c >> LOG2TW, dx = c & (TW - 1);
           float v = acc[t][mt][r] + bj;
-          if (O.relu) v = fmaxf(v, 0.f);
+          v = floor_keep_nan(v, relu_floor(O.relu));
           v = bf_round(v);
           const bool ok = col_ok && (interior || ((g.ty0 + prow + dy < d.H) && (g.tx0 + 4 * h + dx < d.W)));
           if (ok) {
@@ -406,7 +404,7 @@ __global__ __launch_bounds__(kThreads, STATS ? UNETPP_BF16_STATS_WGS : UNETPP_BF
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             v[e] = acc[t][mt][4 * q + e] + b4[q][e];
-            if (O.relu) v[e] = fmaxf(v[e], 0.f);
+            v[e] = floor_keep_nan(v[e], relu_floor(O.relu));
             acc[t][mt][4 * q + e] = 0.f;
           }
           pk[q][0] = pack_bf2(v[0], v[1]);

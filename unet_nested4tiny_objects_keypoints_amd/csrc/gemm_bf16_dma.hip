@@ -330,15 +330,23 @@ __global__ __launch_bounds__(64 * WAVES, RMW ? 2 : 3) void gemm_bf16_dma_kernel(
       float s1 = 0.f, s2sum = 0.f;
       float* scratch = reinterpret_cast<float*>(scratch_bytes) + wave * 1024;  // [32 pixels][32 columns] fp32
 #pragma unroll
+      for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[t][mt][r] += bj;
+      if (O.relu) {  // uniform, the whole tile in one block: a launch without the ReLU (BatchNorm networks) branches past it
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) acc[t][mt][r] = relu_keep_nan(acc[t][mt][r]);
+      }
+#pragma unroll
       for (int mt = 0; mt < 2; ++mt) {
         const int prow = (64 * wave + 32 * mt) >> LOG2TW;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int c = (r & 3) + 8 * (r >> 2);
           const int dy = c >> LOG2TW, dx = c & (TW - 1);
-          float v = acc[t][mt][r] + bj;
-          if (O.relu) v = fmaxf(v, 0.f);
-          v = bf_round(v);
+          float v = bf_round(acc[t][mt][r]);
           const bool ok = col_ok && (interior || ((g.ty0 + prow + dy < d.H) && (g.tx0 + 4 * h + dx < d.W)));
           if (ok) {
             s1 += v;
@@ -469,6 +477,18 @@ __global__ __launch_bounds__(64 * WAVES, RMW ? 2 : 3) void gemm_bf16_dma_kernel(
       const unsigned row_stride = static_cast<unsigned>(O.sy) * O.Ws * O.C, col_stride = static_cast<unsigned>(O.sx) * O.C;
       const unsigned tile_base = view_pixel_offset32(O, g.n, g.ty0, g.tx0) + tc.nt * 32;
 #pragma unroll
+      for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) acc[t][mt][4 * q + e] += (8 * q + 4 * h < tc.n_cnt) ? eo.b4[t][q][e] : 0.f;
+      if (O.relu) {  // uniform, the whole tile in one block: a launch without the ReLU (BatchNorm networks) branches past it
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) acc[t][mt][r] = relu_keep_nan(acc[t][mt][r]);
+      }
+#pragma unroll
       for (int mt = 0; mt < 2; ++mt) {
         const int py = epi_py[mt], px = epi_px[mt];
         const bool pix_ok = (g.ty0 + py < d.H) && (g.tx0 + px < d.W);
@@ -479,8 +499,7 @@ __global__ __launch_bounds__(64 * WAVES, RMW ? 2 : 3) void gemm_bf16_dma_kernel(
           float v[4];
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            v[e] = acc[t][mt][4 * q + e] + ((8 * q + 4 * h < tc.n_cnt) ? eo.b4[t][q][e] : 0.f);
-            if (O.relu) v[e] = fmaxf(v[e], 0.f);
+            v[e] = acc[t][mt][4 * q + e];
             acc[t][mt][4 * q + e] = 0.f;
           }
           pk[q][0] = pack_bf2(v[0], v[1]);

@@ -157,10 +157,8 @@ __global__ __launch_bounds__(kThreads, (TAPS == 1 ? (NT == 1 ? 4 : UNETPP_FAST_P
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = fmaf(v[e], sc[e], sh[e]);
       }
-      if (V.relu) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-      }
+      for (int e = 0; e < 4; ++e) v[e] = floor_keep_nan(v[e], relu_floor(V.relu));
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[e] = keep ? v[e] : 0.f;
       if (it < NPIX * 4) *reinterpret_cast<f32x4*>(&in_tile[hp * KCP + (q4 << 2)]) = v;
@@ -218,7 +216,7 @@ __global__ __launch_bounds__(kThreads, (TAPS == 1 ? (NT == 1 ? 4 : UNETPP_FAST_P
           const int c = (r & 3) + 8 * (r >> 2);
           const int dy = c >> LOG2TW, dx = c & (TW - 1);
           float v = acc[t][mt][r] + bj;
-          if (O.relu) v = fmaxf(v, 0.f);
+          v = floor_keep_nan(v, relu_floor(O.relu));
           const bool ok = col_ok && (interior || ((g.ty0 + prow + dy < d.H) && (g.tx0 + 4 * h + dx < d.W)));
           if (ok) {
             s1 += v;
@@ -294,7 +292,7 @@ __global__ __launch_bounds__(kThreads, (TAPS == 1 ? (NT == 1 ? 4 : UNETPP_FAST_P
         const bool ok = col_ok && (interior || ((g.ty0 + prow + dy < d.H) && (g.tx0 + 4 * h + dx < d.W)));
         if (ok) {
           float v = acc[t][mt][r] + bj;
-          if (O.relu) v = fmaxf(v, 0.f);
+          v = floor_keep_nan(v, relu_floor(O.relu));
           s1 += v;
           s2sum = fmaf(v, v, s2sum);
           const long off = lane_base + dy * row_stride + dx * col_stride;

@@ -154,7 +154,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_pix_kernel(const GemmArgs a)
       const int y = ty0 + (p >> a.log2tw), x = tx0 + (p & (TW - 1));
       if (col_ok && y < d.H && x < d.W) {
         float v = acc[mt][r] + bj;
-        if (O.relu) v = fmaxf(v, 0.f);
+        v = floor_keep_nan(v, relu_floor(O.relu));
         s1 += v;
         s2 = fmaf(v, v, s2);  // explicit fma: the same rounding as the fast kernel's epilogue
         const long off = view_pixel_offset(O, n, y, x) + nt * 32 + j;

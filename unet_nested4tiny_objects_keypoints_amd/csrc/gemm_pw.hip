@@ -173,10 +173,8 @@ __global__ __launch_bounds__(1024, 1) void gemm_pw_kernel(const PwArgs a) {
 #pragma unroll
           for (int j = 0; j < GRP; ++j) {
             f32x4 v = acc[c0 + j];
-            if (relu[j]) {
 #pragma unroll
-              for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-            }
+            for (int e = 0; e < 4; ++e) v[e] = floor_keep_nan(v[e], relu_floor(relu[j]));
             if (has_gate[j] && !gsum[j]) {
 #pragma unroll
               for (int e = 0; e < 4; ++e) v[e] = (gt[j][e] > 0.f) ? v[e] : 0.f;

@@ -165,10 +165,8 @@ __global__ __launch_bounds__(1024, 1) void gemm_pw_bf16_kernel(const PwBfArgs a)
             float gv[8], ov8[8];
             if (has_gate[j]) unpack8(gt[j], gv);
             if (accum[j]) unpack8(old[j], ov8);
-            if (relu[j]) {
 #pragma unroll
-              for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
-            }
+            for (int e = 0; e < 8; ++e) v[e] = floor_keep_nan(v[e], relu_floor(relu[j]));
             if (has_gate[j] && !gsum[j]) {
 #pragma unroll
               for (int e = 0; e < 8; ++e) v[e] = (gv[e] > 0.f) ? v[e] : 0.f;

@@ -361,7 +361,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_wino_kernel(const FastArgs a
           const unsigned inside = ~static_cast<unsigned>(pix[q] >> 31);
 #pragma unroll
           for (int e = 0; e < 4; ++e)
-            v[e] = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, fmaxf(fmaf(v[e], co_sc[e], co_sh[e]), co_floor)) & inside);
+            v[e] = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, floor_keep_nan(fmaf(v[e], co_sc[e], co_sh[e]), co_floor)) & inside);
         }
         *reinterpret_cast<f32x2*>(&in_dst[(it >> 1) * WP + cc]) = f32x2{v[0], v[1]};
         *reinterpret_cast<f32x2*>(&in_dst[(it >> 1) * WP + cc + 2]) = f32x2{v[2], v[3]};
@@ -386,7 +386,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_wino_kernel(const FastArgs a
       }
       if (v_relu) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+        for (int e = 0; e < 4; ++e) v[e] = relu_keep_nan(v[e]);
       }
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[e] = keep ? v[e] : 0.f;  // zero padding AFTER the transform
@@ -444,8 +444,8 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_wino_kernel(const FastArgs a
       for (int b = 0; b < 4; ++b)
         tb[b] = (ap == 0) ? (acc[b][nh][rr] + acc[4 + b][nh][rr]) + acc[8 + b][nh][rr]
                           : (acc[4 + b][nh][rr] - acc[8 + b][nh][rr]) - acc[12 + b][nh][rr];
-      y[0] = fmaxf((tb[0] + tb[1]) + tb[2], floor_v);
-      y[1] = fmaxf((tb[1] - tb[2]) - tb[3], floor_v);
+      y[0] = floor_keep_nan((tb[0] + tb[1]) + tb[2], floor_v);
+      y[1] = floor_keep_nan((tb[1] - tb[2]) - tb[3], floor_v);
     };
     if (interior && vec_out && tc.n_cnt == 16 * NH) {
       // ---- lean path (whole patch inside the image, all columns, 16-byte stores): no per-element predicates ----
@@ -473,9 +473,8 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_wino_kernel(const FastArgs a
 #pragma unroll
             for (int nh = 0; nh < NH; ++nh) old[bp][nh] = *reinterpret_cast<const f32x4*>(obase + off[bp][nh]);
         }
-        // Output transform on column PAIRS (v_pk_add_f32 / v_pk_max_f32; same association order as out_row, so the same bits).
+        // Output transform on column PAIRS (v_pk_add_f32; same association order as out_row, so the same bits).
         f32x4 yv[2][NH];
-        const f32x2 floor2 = {floor_v, floor_v};
 #pragma unroll
         for (int nh = 0; nh < NH; ++nh) {
           f32x2 y[2][2];  // [pixel of the row][column pair]
@@ -488,8 +487,11 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_wino_kernel(const FastArgs a
               const f32x2 m2 = cp ? acc[8 + b][nh].hi : acc[8 + b][nh].lo, m3 = cp ? acc[12 + b][nh].hi : acc[12 + b][nh].lo;
               tb[b] = (ap == 0) ? (m0 + m1) + m2 : (m1 - m2) - m3;
             }
-            y[0][cp] = __builtin_elementwise_max((tb[0] + tb[1]) + tb[2], floor2);
-            y[1][cp] = __builtin_elementwise_max((tb[1] - tb[2]) - tb[3], floor2);
+            const f32x2 t0 = (tb[0] + tb[1]) + tb[2], t1 = (tb[1] - tb[2]) - tb[3];
+            // the floor per element, not v_pk_max_f32: it keeps a NaN.  (One uniform `if (O.relu)` block instead, which
+            // launches without the ReLU branch past, measured SLOWER than this: profiles/nonfinite/.)
+            y[0][cp] = f32x2{floor_keep_nan(t0.x, floor_v), floor_keep_nan(t0.y, floor_v)};
+            y[1][cp] = f32x2{floor_keep_nan(t1.x, floor_v), floor_keep_nan(t1.y, floor_v)};
           }
           yv[0][nh] = f32x4{y[0][0].x, y[0][0].y, y[0][1].x, y[0][1].y};
           yv[1][nh] = f32x4{y[1][0].x, y[1][0].y, y[1][1].x, y[1][1].y};

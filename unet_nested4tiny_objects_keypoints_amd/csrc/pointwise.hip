@@ -146,7 +146,7 @@ __global__ __launch_bounds__(kThreads) void affine_relu_kernel(const float* __re
     for (int k = 0; k < VEC; ++k) {
       float t = lane_of<VEC>(v, k);
       if (scale != nullptr) t = fmaf(t, scale[c + k], shift[c + k]);
-      if (relu) t = fmaxf(t, 0.f);
+      if (relu) t = relu_keep_nan(t);
       lane_of<VEC>(v, k) = t;
     }
     reinterpret_cast<P*>(act)[i] = v;
@@ -182,9 +182,9 @@ __global__ __launch_bounds__(kThreads) void affine_relu_pool_kernel(const float*
       for (int k = 0; k < VEC; ++k) {
         float t = lane_of<VEC>(v, k);
         if (scale != nullptr) t = fmaf(t, scale[c + k], shift[c + k]);
-        if (relu) t = fmaxf(t, 0.f);
+        if (relu) t = relu_keep_nan(t);
         lane_of<VEC>(v, k) = t;
-        if (q == 0 || t > best[k]) {  // first maximum wins, scan order (0,0),(0,1),(1,0),(1,1)
+        if (q == 0 || pool_takes(t, best[k])) {  // first maximum wins, scan order (0,0),(0,1),(1,0),(1,1)
           best[k] = t;
           bi[k] = static_cast<uint8_t>(q);
         }
@@ -264,11 +264,11 @@ __global__ __launch_bounds__(kThreads) void affine_relu_pool_rows_kernel(
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           float t = fmaf(v[q][k], sc[k], sh[k]);
-          if (relu) t = fmaxf(t, 0.f);
+          if (relu) t = relu_keep_nan(t);
           v[q][k] = t;
           if (q == 0) {
             best[k] = t;
-          } else if (t > best[k]) {  // first maximum wins, scan order (0,0),(0,1),(1,0),(1,1)
+          } else if (pool_takes(t, best[k])) {  // first maximum wins, scan order (0,0),(0,1),(1,0),(1,1)
             best[k] = t;
             bi = (bi & ~(0xffu << (8 * k))) | (static_cast<uint32_t>(q) << (8 * k));
           }

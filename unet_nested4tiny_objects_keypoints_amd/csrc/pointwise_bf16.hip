@@ -25,7 +25,7 @@ __device__ __forceinline__ void affine8(float (&f)[8], const float* scale, const
   }
   if (relu) {
 #pragma unroll
-    for (int e = 0; e < 8; ++e) f[e] = fmaxf(f[e], 0.f);
+    for (int e = 0; e < 8; ++e) f[e] = relu_keep_nan(f[e]);
   }
 }
 
@@ -75,7 +75,7 @@ __global__ __launch_bounds__(kThreads) void affine_relu_pool_bf16_kernel(const b
       unpack8(packed, f);  // compare what is stored
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        if (q == 0 || f[e] > best[e]) {
+        if (q == 0 || pool_takes(f[e], best[e])) {
           best[e] = f[e];
           bi[e] = q;
         }

@@ -230,10 +230,8 @@ __global__ __launch_bounds__(kWThreads, 2) void wgrad_bf16_kernel(const WBfArgs 
 #pragma unroll
           for (int e = 0; e < 8; ++e) f[e] = fmaf(f[e], coef[cc + e], coef[32 + cc + e]);
         }
-        if (X.relu) {
 #pragma unroll
-          for (int e = 0; e < 8; ++e) f[e] = fmaxf(f[e], 0.f);
-        }
+        for (int e = 0; e < 8; ++e) f[e] = floor_keep_nan(f[e], relu_floor(X.relu));
         v = pack8(f);
         if (x_affine) {   // the padding is zero AFTER the transform
           const bool keep = x_inside(q, s_ty0, s_tx0);
@@ -579,10 +577,8 @@ __global__ __launch_bounds__(QuadShape<TAPS>::THREADS, 1) void wgrad_bf16_quad_k
 #pragma unroll
           for (int e = 0; e < 8; ++e) f[e] = fmaf(f[e], coef[ch + e], coef[64 + ch + e]);
         }
-        if (X.relu) {
 #pragma unroll
-          for (int e = 0; e < 8; ++e) f[e] = fmaxf(f[e], 0.f);
-        }
+        for (int e = 0; e < 8; ++e) f[e] = floor_keep_nan(f[e], relu_floor(X.relu));
         v = pack8(f);
         if (x_affine) {   // the padding is zero AFTER the transform
           const bool keep = x_inside(q, s_y0, s_x0);

@@ -137,10 +137,8 @@ __global__ __launch_bounds__(kWThreads, 2) void wgrad_fast_kernel(const WFastArg
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = fmaf(v[e], sc[e], sh[e]);
       }
-      if (X.relu) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-      }
+      for (int e = 0; e < 4; ++e) v[e] = floor_keep_nan(v[e], relu_floor(X.relu));
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[e] = keep ? v[e] : 0.f;
       if (it < NPIX * 8 && ((it & 7) << 2) < k_cnt) *reinterpret_cast<f32x4*>(&buf[it * 4]) = v;
