@@ -434,6 +434,25 @@ int64_t unetpp_pr_focal_workspace_bytes(int32_t n_heads, int64_t n);
 int unetpp_pr_focal_heads(const unetpp_focal_heads* heads, const float* target, int64_t n, float alpha, float beta,
                           float eps, float positive, void* workspace, int64_t* n_pos, float* loss /* [1 + n_heads] */,
                           void* stream);
+/* ---- ignore regions in the three fused losses (added within v13: new entry points only) ----
+ * The signatures, workspaces, refusals and results of unetpp_focal_bce_heads, unetpp_topk_focal_heads and
+ * unetpp_pr_focal_heads, with one more rule: an element of the target that is negative is IGNORED.  Ignored iff
+ * t < 0.0f as an IEEE comparison: -0.0, +0.0 and a NaN are not, -inf and a negative denormal are.  For every head an
+ * ignored element's loss term is +0.0 and its gradient exactly +0.0 (sign bit clear) whatever pred holds, a NaN
+ * included; every other element runs the plain call's arithmetic, so on a target without a negative element every
+ * output equals the plain call's bit for bit.
+ *   top-k:  an ignored element's key is 0: it ranks last and is selected only when k_eff exceeds the number of non-zero
+ *           keys of the row, and contributes +0.0 selected or not; k_eff, denom and kth are otherwise as defined above.
+ *   penalty-reduced:  a negative target is never >= positive: n_pos is the plain call's.
+ * unetpp_target_ignore writes such targets. */
+int unetpp_focal_bce_heads_ignore(const unetpp_focal_heads* heads, const float* target, int64_t n, int64_t rows,
+                                  float gamma, float* partial, float* loss, void* stream);
+int unetpp_topk_focal_heads_ignore(const unetpp_focal_heads* heads, const float* target, int64_t rows, int64_t P,
+                                   int64_t k, int64_t denom, float gamma, void* workspace, float* kth, float* loss,
+                                   void* stream);
+int unetpp_pr_focal_heads_ignore(const unetpp_focal_heads* heads, const float* target, int64_t n, float alpha, float beta,
+                                 float eps, float positive, void* workspace, int64_t* n_pos,
+                                 float* loss /* [1 + n_heads] */, void* stream);
 /* ---- ensemble head of an eval forward (added within v12: new entry points only, nothing existing changes) ----
  * The output selection the UNet++ authors left as comments in models/unet.py:293-298: the mean of the first n_heads
  * deep-supervision heads, out = (((s_1 + s_2) + ...) + s_n) / (float)n with s_h = 1 / (1 + exp(-(bias_h + x_h . w_h)))
@@ -873,6 +892,26 @@ int unetpp_detect_match(const float* xy, const int32_t* n_pred, const int32_t* o
 int unetpp_points_target(const float* labels, const int32_t* label_class, int64_t M, int32_t L, const int64_t* index,
                          int32_t N, const float* params, int32_t C, int32_t Ho, int32_t Wo, float radius, float* out,
                          void* stream);
+
+/* unetpp_target_ignore (added within v13): marks the ignored elements of target float32 [N, C, Ho, Wo] (device) with
+ * exactly -1.0f, the sentinel of the *_ignore losses.  rects float32 [M, R, 4] as (x0, y0, x1, y1) in source-frame pixel
+ * coordinates, both ends inclusive; rect_class int32 [M, R]: -1 applies to every class, c in 0..C-1 to class c, any other
+ * value is padding, as is a row with x1 < x0, y1 < y0 or a NaN.  index, params: the rows of unetpp_warp_batch; Hs x Ws:
+ * the frames' size.  The source position of window pixel (x, y) of sample n is the warp's own float32 expression,
+ * xs = (P[0]*x + P[1]*y) + P[2], ys = (P[3]*x + P[4]*y) + P[5], P = params[n], no contraction.  target[n, c, y, x] is
+ * set when
+ *   index[n] lies in [0, M) and x0 <= xs && xs <= x1 && y0 <= ys && ys <= y1 (float32 comparisons: a NaN is never
+ *   inside) for a rectangle of frame index[n] whose class is -1 or c, or
+ *   outside != 0 and !(0 <= xs && xs <= Ws-1 && 0 <= ys && ys <= Hs-1): a bilinear neighbour of non-zero weight is
+ *   the fill value, or the position is a NaN; every class, and every element of an all-fill sample (index[n] outside
+ *   [0, M)).
+ * Every other element is left untouched, not even read: ignoring wins over a label.  Stores of one constant: no atomics,
+ * the same bits on any grid; 64-bit offsets into target.  R may be 0 (rects and rect_class then unread; with
+ * outside == 0 the call does nothing).  UNETPP_EINVAL without touching the device for a null pointer, a size <= 0 (R < 0),
+ * C > 65535 or a side above 2^24. */
+int unetpp_target_ignore(const float* rects, const int32_t* rect_class, int64_t M, int32_t R, const int64_t* index,
+                         int32_t N, const float* params, int32_t C, int32_t Ho, int32_t Wo, int32_t Hs, int32_t Ws,
+                         int32_t outside, float* target, void* stream);
 
 /* unetpp_crops_draw: N windows of Ho x Wo pixels in M frames of Hs x Ws, one thread per sample: params [N][16], index
  * int64 [N] (the frame), origin int32 [N, 2] as (ox, oy), all on the device.  Uniforms u_k and the meaning of

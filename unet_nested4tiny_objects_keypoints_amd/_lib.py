@@ -313,6 +313,12 @@ SIGNATURES = {
     # penalty-reduced focal loss normalised by positives, all heads in one call (pr_focal.hip; added within ABI 13)
     "unetpp_pr_focal_workspace_bytes": (_I64, [_I32, _I64]),
     "unetpp_pr_focal_heads": (C.c_int, [C.POINTER(FocalHeads), _P, _I64, _F, _F, _F, _F, _P, _P, _P, _P]),
+    # ignore regions: a negative target element is ignored (caller.hip, topk_loss.hip, pr_focal.hip, crops.hip; added
+    # within ABI 13)
+    "unetpp_focal_bce_heads_ignore": (C.c_int, [C.POINTER(FocalHeads), _P, _I64, _I64, _F, _P, _P, _P]),
+    "unetpp_topk_focal_heads_ignore": (C.c_int, [C.POINTER(FocalHeads), _P, _I64, _I64, _I64, _I64, _F, _P, _P, _P, _P]),
+    "unetpp_pr_focal_heads_ignore": (C.c_int, [C.POINTER(FocalHeads), _P, _I64, _F, _F, _F, _F, _P, _P, _P, _P]),
+    "unetpp_target_ignore": (C.c_int, [_P, _P, _I64, _I32, _P, _I32, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P]),
 }
 
 _LIB = None

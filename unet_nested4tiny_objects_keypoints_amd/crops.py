@@ -16,6 +16,10 @@ and its target comes from the frame's whole label list, any number of objects pe
 exp(-0.5 d / radius) of the distance d to the nearest label, the maximum over the labels of the package's blob, so an
 object just outside the window shines into it.  Three launches per batch (draw, warp, targets), no host data work.
 
+Partially labelled scenes: ``ignore=IgnoreRegions(...)`` and / or ``ignore_outside=True`` add a fourth launch that writes
+-1 into the target wherever the pixel's source position lies in an ignore rectangle of its frame (of that class or of
+every class) or outside the frame; a criterion built with ``ignore_negative=True`` leaves those elements out.
+
 Coordinates are (x, y) with pixel centres at integers, the labels' convention everywhere in the package.  The reference
 has no counterpart.
 """
@@ -26,6 +30,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import ops
+from .ignore import IgnoreRegions
 from .loader import Augment, _channels, _per_channel, _source_size
 
 __all__ = ["SceneCrops", "false_positive_centres"]
@@ -61,12 +66,17 @@ class SceneCrops:
     launches, nothing synchronises with the host; ``last`` holds the batch's (params [n, 16], index [n], origin [n, 2]
     as (ox, oy)).  A run is reproducible from `seed`: the per-batch seeds come from a host generator.
 
+    ignore: an ``IgnoreRegions`` over the same frames -- target = -1 where the pixel's source position lies in one of
+    the frame's rectangles (class -1: every class map; class c: map c), whatever label is there; ignore_outside: also
+    where it lies outside the frame (a bilinear neighbour is `fill`), and all of an all-fill sample.  Either makes
+    batch(n) a fourth launch (unetpp_target_ignore) after the targets, still without a host synchronisation.
+
     The centre table starts as the valid labels; set_centres / add_centres replace / extend it -- a sampling policy such
     as class balancing is a matter of what the caller puts there."""
 
     def __init__(self, frames, labels, label_class, n_classes: int, crop=(256, 256), p_object: float = 0.75,
                  jitter=(32, 32), augment: Optional[Augment] = None, radius: float = 3.0, mul=1.0 / 255.0, add=0.0,
-                 fill: float = 0.0, seed: int = 0):
+                 fill: float = 0.0, seed: int = 0, ignore=None, ignore_outside: bool = False):
         self.augment = Augment() if augment is None else augment
         self.crop = (int(crop[0]), int(crop[1]))
         if min(self.crop) < 1:
@@ -115,6 +125,14 @@ class SceneCrops:
         where = valid.nonzero()
         self.centre_frame = where[:, 0].to(torch.int32).contiguous()
         self.centre_xy = self.labels[valid].contiguous()
+        self.ignore_outside = bool(ignore_outside)
+        self.ignore = None
+        if ignore is not None:
+            if not isinstance(ignore, IgnoreRegions):
+                raise TypeError("ignore must be an IgnoreRegions")
+            if len(ignore) != s:
+                raise ValueError("ignore holds %d frames, the scenes %d" % (len(ignore), s))
+            self.ignore = ignore.to(self.device)
 
     def __len__(self):
         return int(self.frames.shape[0])
@@ -143,6 +161,10 @@ class SceneCrops:
         inputs, points, inside = ops.warp_batch(self.frames, index, params, self.crop, self.mul, self.add, self.fill,
                                                 self.labels)
         target = ops.points_target(self.labels, self.label_class, index, params, self.n_classes, self.crop, self.radius)
+        if self.ignore is not None or self.ignore_outside:
+            ign = self.ignore
+            ops.target_ignore(target, ign.rects if ign is not None else None, ign.rect_class if ign is not None else None,
+                              index, params, self.src_size, self.ignore_outside, n_frames=len(self))
         self.last = (params, index, origin)
         return inputs, target, points, inside
 
@@ -157,11 +179,17 @@ class SceneCrops:
 def false_positive_centres(dets, score, min_score: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """(frame [K] int32, xy [K, 2] float32) of the served detections that ``evaluate`` left unmatched
     (score.pred_label == -1): the false positives of `dets`, as rows for ``SceneCrops.add_centres``.  min_score: the
-    score_threshold the evaluation was made with (detections below it were not served).  Torch ops on the small arrays,
+    score_threshold the evaluation was made with (detections below it were not served).  The served set is
+    ``score.served`` when the score carries it (``evaluate`` fills it: detections inside an ignore region are not in
+    it), otherwise the first min(count, cap) slots.  Torch ops on the small arrays,
     on whatever device they live; the result's length depends on the data, so this SYNCHRONISES with the host -- it is
     meant to run between epochs, not inside the training loop."""
     cap = dets.cap
-    served = torch.arange(cap, device=dets.score.device).view(1, 1, cap) < dets.count.clamp(max=cap).unsqueeze(-1)
+    served = getattr(score, "served", None)
+    if served is None:
+        served = torch.arange(cap, device=dets.score.device).view(1, 1, cap) < dets.count.clamp(max=cap).unsqueeze(-1)
+    elif tuple(served.shape) != tuple(dets.score.shape):
+        raise ValueError("score is not the evaluation of these detections")
     if min_score is not None:
         served = served & (dets.score >= float(min_score))
     if tuple(score.pred_label.shape) != tuple(served.shape):

@@ -18,7 +18,12 @@ constexpr int kLossPerThread = 8;  // elements per thread: 2 x float4
 // The elements of one thread (2 x float4 at `base`): the gradient (times `scale`: 1 for a single head, 1 / heads under
 // the trainer's mean over heads -- a second float32 product, as autograd forms it) and the thread's part of the loss sum.
 // t[2][4]: the thread's targets, read once for all heads.  The element arithmetic (and kLow) is focal_element.h.
-template <bool kLow>
+// kIgnore: an element whose target is negative (t < 0.0f: -0.0 and a NaN are not) is ignored -- its gradient is +0.0 and
+// its term is not added, whatever pred holds; every other element runs the element arithmetic unchanged.  The term is
+// left out by the condition of the addition, not by a select on the term: `sum += le` is contracted with the product
+// inside focal_element, and a select between the two would make the sums of the two instantiations differ in the last
+// bit on a target without a negative element.
+template <bool kLow, bool kIgnore = false>
 __device__ __forceinline__ float focal_thread(const float* __restrict__ pred, float* __restrict__ grad,
                                               const float (&t)[kLossPerThread / 4][4], long base, long n, float gamma,
                                               float inv_rows, float scale) {
@@ -41,7 +46,11 @@ __device__ __forceinline__ float focal_thread(const float* __restrict__ pred, fl
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const float le = focal_element<kLow>(p[e], t[h][e], gamma, cube, inv_rows, scale, g[e]);
-      if (i + e < n) sum += le;
+      bool take = i + e < n;
+      if constexpr (kIgnore) {
+        if (t[h][e] < 0.f) take = false, g[e] = 0.f;
+      }
+      if (take) sum += le;
     }
     if (grad != nullptr) {
       if (vec) {
@@ -91,7 +100,7 @@ __global__ __launch_bounds__(kLossThreads) void focal_bce_kernel(const float* __
 
 // All deep-supervision heads against one target: the target is read once, partial[h * gridDim.x + block] as
 // focal_bce_kernel writes partial[block] for head h (same per-thread order, same wave and block sums).
-template <bool kLow>
+template <bool kLow, bool kIgnore = false>
 __global__ __launch_bounds__(kLossThreads) void focal_bce_heads_kernel(const unetpp_focal_heads hd,
                                                                       const float* __restrict__ target, long n, float gamma,
                                                                       float inv_rows, float scale,
@@ -101,7 +110,7 @@ __global__ __launch_bounds__(kLossThreads) void focal_bce_heads_kernel(const une
   float t[kLossPerThread / 4][4];
   focal_read_target(target, base, n, t);
   for (int h = 0; h < hd.n_heads; ++h) {
-    float sum = focal_thread<kLow>(hd.pred[h], hd.grad[h], t, base, n, gamma, inv_rows, scale);
+    float sum = focal_thread<kLow, kIgnore>(hd.pred[h], hd.grad[h], t, base, n, gamma, inv_rows, scale);
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off);
     if ((threadIdx.x & 63) == 0) red[h][threadIdx.x >> 6] = sum;
@@ -253,8 +262,11 @@ extern "C" int unetpp_focal_bce(const float* pred, const float* target, int64_t 
   return launch_status();
 }
 
-extern "C" int unetpp_focal_bce_heads(const unetpp_focal_heads* heads, const float* target, int64_t n, int64_t rows,
-                                      float gamma, float* partial, float* loss, void* stream) {
+namespace {
+
+template <bool kIgnore>
+int focal_bce_heads_launch(const unetpp_focal_heads* heads, const float* target, int64_t n, int64_t rows, float gamma,
+                           float* partial, float* loss, void* stream) {
   if (heads == nullptr || target == nullptr || partial == nullptr || loss == nullptr || n < 1 || rows < 1) return UNETPP_EINVAL;
   if (heads->n_heads < 1 || heads->n_heads > UNETPP_MAX_HEADS) return UNETPP_EINVAL;
   uintptr_t bits = reinterpret_cast<uintptr_t>(target);
@@ -268,12 +280,24 @@ extern "C" int unetpp_focal_bce_heads(const unetpp_focal_heads* heads, const flo
   unetpp_focal_heads hd = *heads;
   for (int h = hd.n_heads; h < UNETPP_MAX_HEADS; ++h) hd.pred[h] = nullptr, hd.grad[h] = nullptr;
   const float inv_heads = 1.0f / static_cast<float>(hd.n_heads);
-  hipLaunchKernelGGL(gamma < 1.f ? focal_bce_heads_kernel<true> : focal_bce_heads_kernel<false>,
-                     dim3(static_cast<unsigned>(blocks)), dim3(kLossThreads), 0, static_cast<hipStream_t>(stream), hd, target,
+  const auto kernel = gamma < 1.f ? focal_bce_heads_kernel<true, kIgnore> : focal_bce_heads_kernel<false, kIgnore>;
+  hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(blocks)), dim3(kLossThreads), 0, static_cast<hipStream_t>(stream), hd, target,
                      static_cast<long>(n), gamma, 1.f / static_cast<float>(rows), inv_heads, partial);
   hipLaunchKernelGGL(focal_bce_heads_finish_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), partial,
                      static_cast<long>(blocks), hd.n_heads, inv_heads, loss);
   return launch_status();
+}
+
+}  // namespace
+
+extern "C" int unetpp_focal_bce_heads(const unetpp_focal_heads* heads, const float* target, int64_t n, int64_t rows,
+                                      float gamma, float* partial, float* loss, void* stream) {
+  return focal_bce_heads_launch<false>(heads, target, n, rows, gamma, partial, loss, stream);
+}
+
+extern "C" int unetpp_focal_bce_heads_ignore(const unetpp_focal_heads* heads, const float* target, int64_t n, int64_t rows,
+                                             float gamma, float* partial, float* loss, void* stream) {
+  return focal_bce_heads_launch<true>(heads, target, n, rows, gamma, partial, loss, stream);
 }
 
 extern "C" int64_t unetpp_heatmap_workspace_bytes(int32_t N, int32_t H, int32_t W) {

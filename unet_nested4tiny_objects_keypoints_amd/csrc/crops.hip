@@ -1,5 +1,6 @@
-// Training on large scenes: where the windows of a batch are (crops_draw_kernel) and the target maps of those windows
-// from the frames' variable-length label lists (points_target_kernel).  The warp between the two is loader.hip's.
+// Training on large scenes: where the windows of a batch are (crops_draw_kernel), the target maps of those windows
+// from the frames' variable-length label lists (points_target_kernel) and their ignored elements
+// (target_ignore_kernel).  The warp between the draw and the targets is loader.hip's.
 //
 // points_target_kernel: out[n, c, y, x] = float32(exp(-0.5 * sqrt(m) / radius)), m = the least dx*dx + dy*dy (float64, the
 // expression of the two heat-map kernels) over the valid labels of class c of frame index[n], each at its position under
@@ -22,6 +23,9 @@
 // and commutative, so rounds, the order inside a list and the grid change nothing: the same bits on every run.  No
 // atomics; implicit contraction is off; offsets into out and label numbers are 64-bit; interior stores are 16 bytes
 // wide where the address allows, scalar on ragged edges.
+//
+// target_ignore_kernel: writes -1.0f into the elements of such a target whose source position lies in an ignore
+// rectangle of the frame or outside the frame; stores only, described at the kernel.
 //
 // crops_draw_kernel: one thread per sample, the uniforms and the transform of loader.hip's draw_kernel; uniforms 9..12
 // choose between an object window (a row of the centre table plus jitter) and a uniform one.
@@ -222,6 +226,103 @@ __global__ void __launch_bounds__(kThreads256) points_target_kernel(
   }
 }
 
+// target_ignore_kernel: marks the ignored elements of a target that points_target_kernel (or anything else) wrote.
+// A unit is (sample, 64 x 16 tile), a thread 4 consecutive x of one row, all classes.  The source position of a window
+// pixel is the warp's own float32 expression (loader.hip) under the inverse map P = params[n]; the tests are plain
+// float32 comparisons, so a NaN position or a NaN / reversed rectangle (padding) is never inside a rectangle and always
+// outside the frame.  The frame's R rectangles pass through LDS kRectChunk at a time; per pixel a thread keeps one bit
+// per class of the current group of 32 classes (one group for C <= 32) and one for "every class".  The kernel only
+// stores -1.0f where it ignores and reads nothing of target: idempotent stores of one constant, no atomics, the same
+// bits on any grid.
+constexpr int kRectChunk = 256;
+constexpr int kClassGroup = 32;
+
+__global__ void __launch_bounds__(kThreads256) target_ignore_kernel(
+    const float* __restrict__ rects, const int32_t* __restrict__ rect_class, int64_t M, int R,
+    const int64_t* __restrict__ index, const float* __restrict__ params, int C, int Ho, int Wo, int Hs, int Ws, int outside,
+    float* __restrict__ target, int tiles_x, int tiles_y, int64_t units) {
+  __shared__ float rc[kRectChunk][4];
+  __shared__ int32_t rcls[kRectChunk];
+  const int tid = threadIdx.x;
+  const float x_max = static_cast<float>(Ws - 1), y_max = static_cast<float>(Hs - 1);   // exact: sides <= 2^24
+
+  for (int64_t unit = blockIdx.x; unit < units; unit += gridDim.x) {
+    const int tx = static_cast<int>(unit % tiles_x);
+    const int64_t r = unit / tiles_x;
+    const int ty = static_cast<int>(r % tiles_y);
+    const int n = static_cast<int>(r / tiles_y);
+    const int x_lo = tx * kTileW, y_lo = ty * kTileH;
+    const int x_hi = (x_lo + kTileW < Wo ? x_lo + kTileW : Wo) - 1;
+    const int y_hi = (y_lo + kTileH < Ho ? y_lo + kTileH : Ho) - 1;
+    const int px = x_lo + (tid & 15) * 4, py = y_lo + (tid >> 4);
+    const bool mine = py <= y_hi && px <= x_hi;
+
+    const int64_t idx = index[n];
+    const bool live = idx >= 0 && idx < M;   // (uniform over the workgroup)
+    const float* P = params + int64_t(n) * UNETPP_WARP_PARAMS;
+    const float yf = static_cast<float>(py);
+    float xs[4], ys[4];
+    unsigned every = 0;   // bit p: pixel px + p is ignored for every class
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      const float xf = static_cast<float>(px + p);
+      xs[p] = (P[0] * xf + P[1] * yf) + P[2];
+      ys[p] = (P[3] * xf + P[4] * yf) + P[5];
+      const bool in = live && 0.f <= xs[p] && xs[p] <= x_max && 0.f <= ys[p] && ys[p] <= y_max;
+      every |= (outside != 0 && !in) ? (1u << p) : 0u;
+    }
+
+    const int n_rect = live ? R : 0;
+    for (int c0 = 0; c0 < C; c0 += kClassGroup) {
+      uint32_t cls_bits[4] = {0u, 0u, 0u, 0u};   // bit k of [p]: pixel px + p is ignored for class c0 + k
+      for (int base = 0; base < n_rect; base += kRectChunk) {
+        __syncthreads();   // (the previous chunk, group or unit has been read)
+        const int cnt = n_rect - base < kRectChunk ? n_rect - base : kRectChunk;
+        if (tid < cnt) {
+          const int64_t row = idx * R + base + tid;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) rc[tid][j] = rects[row * 4 + j];
+          rcls[tid] = rect_class[row];
+        }
+        __syncthreads();
+        for (int i = 0; i < cnt; ++i) {
+          const float x0 = rc[i][0], y0 = rc[i][1], x1 = rc[i][2], y1 = rc[i][3];
+          const int k = rcls[i];
+          const bool all = k == -1;
+          const bool here = k >= c0 && k < c0 + kClassGroup && k < C;
+          if (!all && !here) continue;   // (uniform: an LDS broadcast)
+          const uint32_t bit = here ? (1u << (k - c0)) : 0u;
+#pragma unroll
+          for (int p = 0; p < 4; ++p) {
+            const bool in = x0 <= xs[p] && xs[p] <= x1 && y0 <= ys[p] && ys[p] <= y1;
+            if (in) {
+              cls_bits[p] |= bit;
+              if (all) every |= 1u << p;
+            }
+          }
+        }
+      }
+      if (mine) {
+        const int c_end = c0 + kClassGroup < C ? c0 + kClassGroup : C;
+        for (int c = c0; c < c_end; ++c) {
+          unsigned m = every;
+#pragma unroll
+          for (int p = 0; p < 4; ++p) m |= ((cls_bits[p] >> (c - c0)) & 1u) << p;
+          if (m == 0) continue;
+          float* dst = target + ((int64_t(n) * C + c) * Ho + py) * Wo + px;
+          if (m == 15u && px + 3 <= x_hi && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
+            *reinterpret_cast<f32x4*>(dst) = f32x4{-1.f, -1.f, -1.f, -1.f};
+          } else {
+#pragma unroll
+            for (int p = 0; p < 4; ++p)
+              if (((m >> p) & 1u) && px + p <= x_hi) dst[p] = -1.f;
+          }
+        }
+      }
+    }
+  }
+}
+
 __device__ __forceinline__ double uniform24(uint64_t seed, int n, int k) {
   const uint64_t bits = mix64(seed + 0x9E3779B97F4A7C15ULL * (static_cast<uint64_t>(n) * 16 + k + 1));
   return static_cast<double>(static_cast<float>(bits >> 40) * 0x1p-24f);   // 24 bits: exact in fp32
@@ -332,6 +433,25 @@ extern "C" int unetpp_points_target(const float* labels, const int32_t* label_cl
                      label_class, M, L, index, N, params, C, Ho, Wo, static_cast<double>(radius), out, tiles_x, tiles_y,
                      groups, units);
   note_kernel("points_target");
+  return launch_status();
+}
+
+extern "C" int unetpp_target_ignore(const float* rects, const int32_t* rect_class, int64_t M, int32_t R,
+                                    const int64_t* index, int32_t N, const float* params, int32_t C, int32_t Ho,
+                                    int32_t Wo, int32_t Hs, int32_t Ws, int32_t outside, float* target, void* stream) {
+  if (index == nullptr || params == nullptr || target == nullptr) return UNETPP_EINVAL;
+  if (M <= 0 || R < 0 || N <= 0 || C <= 0 || Ho <= 0 || Wo <= 0 || Hs <= 0 || Ws <= 0) return UNETPP_EINVAL;
+  if (R > 0 && (rects == nullptr || rect_class == nullptr)) return UNETPP_EINVAL;
+  if (C > kMaxClasses || Ho > kMaxSide || Wo > kMaxSide || Hs > kMaxSide || Ws > kMaxSide) return UNETPP_EINVAL;
+  if (R == 0 && outside == 0) return UNETPP_OK;   // nothing to mark
+  const int tiles_x = (Wo + kTileW - 1) / kTileW, tiles_y = (Ho + kTileH - 1) / kTileH;
+  const int64_t units = int64_t(N) * tiles_y * tiles_x;
+  const int cus = device_cu_count();
+  const int64_t cap = int64_t(cus > 0 ? cus : 256) * 8;   // the rest of the units are grid-strided
+  const unsigned grid = static_cast<unsigned>(units < cap ? units : cap);
+  hipLaunchKernelGGL(target_ignore_kernel, dim3(grid), dim3(kThreads256), 0, static_cast<hipStream_t>(stream), rects,
+                     rect_class, M, R, index, params, C, Ho, Wo, Hs, Ws, outside, target, tiles_x, tiles_y, units);
+  note_kernel("target_ignore");
   return launch_status();
 }
 

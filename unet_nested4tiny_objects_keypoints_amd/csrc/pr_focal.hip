@@ -155,6 +155,11 @@ __global__ __launch_bounds__(kPrThreads) void pr_count_kernel(const float* __res
   if (threadIdx.x == 0) counts[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// kIgnore: an element with a negative target (t < 0.0f: -0.0 and a NaN are not) is ignored -- its term and its gradient
+// are +0.0 whatever pred holds (the term is left out by the condition of the addition, so that `sum += le` contracts as
+// in the plain instantiation); every other element runs pr_element unchanged.  Such a target is never >= positive, so the
+// count pass and n_pos are those of the plain call.
+template <bool kIgnore = false>
 __global__ __launch_bounds__(kPrThreads) void pr_focal_kernel(const unetpp_focal_heads hd, const float* __restrict__ target,
                                                               long n, const PrParams k, float scale,
                                                               const pr_count_t* __restrict__ counts, int n_counts,
@@ -163,6 +168,7 @@ __global__ __launch_bounds__(kPrThreads) void pr_focal_kernel(const unetpp_focal
   const long base = (blockIdx.x * static_cast<long>(kPrThreads) + threadIdx.x) * kPrPerThread;
   float w[kPrPerThread / 4][4];
   unsigned pos = 0;   // bit 4 * v + e: the element is positive
+  [[maybe_unused]] unsigned ign = 0;   // bit 4 * v + e: the element is ignored (kIgnore)
   float t[kPrPerThread / 4][4];
 #pragma unroll
   for (int v = 0; v < kPrPerThread / 4; ++v) pr_load4(target, base + 4 * v, n, 0.f, t[v]);
@@ -174,6 +180,7 @@ __global__ __launch_bounds__(kPrThreads) void pr_focal_kernel(const unetpp_focal
     for (int e = 0; e < 4; ++e) {
       const bool is_pos = t[v][e] >= k.positive;
       pos |= is_pos ? (1u << (4 * v + e)) : 0u;
+      if constexpr (kIgnore) ign |= (t[v][e] < 0.f) ? (1u << (4 * v + e)) : 0u;
       w[v][e] = is_pos ? 1.f : pr_pow(1.f - t[v][e], k.bmode, k.beta);
     }
   const float inv_denom = pr_inv_denom(total);
@@ -191,7 +198,11 @@ __global__ __launch_bounds__(kPrThreads) void pr_focal_kernel(const unetpp_focal
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const float le = pr_element(p[v][e], w[v][e], (pos >> (4 * v + e)) & 1u, k, inv_denom, scale, g[e]);
-        if (i + e < n) sum += le;
+        bool take = i + e < n;
+        if constexpr (kIgnore) {
+          if ((ign >> (4 * v + e)) & 1u) take = false, g[e] = 0.f;
+        }
+        if (take) sum += le;
       }
       if (grad != nullptr) {
         if (i + 4 <= n) {
@@ -270,8 +281,11 @@ extern "C" int64_t unetpp_pr_focal_workspace_bytes(int32_t n_heads, int64_t n) {
          static_cast<int64_t>(n_heads) * pr_blocks(n) * 4;
 }
 
-extern "C" int unetpp_pr_focal_heads(const unetpp_focal_heads* heads, const float* target, int64_t n, float alpha, float beta,
-                                     float eps, float positive, void* workspace, int64_t* n_pos, float* loss, void* stream) {
+namespace {
+
+template <bool kIgnore>
+int pr_focal_heads_launch(const unetpp_focal_heads* heads, const float* target, int64_t n, float alpha, float beta, float eps,
+                          float positive, void* workspace, int64_t* n_pos, float* loss, void* stream) {
   if (heads == nullptr || target == nullptr || workspace == nullptr || n_pos == nullptr || loss == nullptr) return UNETPP_EINVAL;
   if (!pr_args_ok(heads->n_heads, n)) return UNETPP_EINVAL;
   if (!(alpha >= 0.f) || !(beta >= 0.f) || !(eps > 0.f && eps < 0.5f) || !(positive > 0.f && positive <= 1.f))
@@ -302,10 +316,23 @@ extern "C" int unetpp_pr_focal_heads(const unetpp_focal_heads* heads, const floa
   const float inv_heads = 1.0f / static_cast<float>(hd.n_heads);
   hipLaunchKernelGGL(pr_count_kernel, dim3(static_cast<unsigned>(n_counts)), dim3(kPrThreads), 0, st, target,
                      static_cast<long>(n), positive, counts);
-  hipLaunchKernelGGL(pr_focal_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kPrThreads), 0, st, hd, target,
+  hipLaunchKernelGGL(pr_focal_kernel<kIgnore>, dim3(static_cast<unsigned>(blocks)), dim3(kPrThreads), 0, st, hd, target,
                      static_cast<long>(n), k, inv_heads, static_cast<const pr_count_t*>(counts), n_counts, partial,
                      reinterpret_cast<long long*>(n_pos));
   hipLaunchKernelGGL(pr_focal_finish_kernel, dim3(1), dim3(1024), 0, st, static_cast<const float*>(partial),
                      static_cast<long>(blocks), hd.n_heads, inv_heads, static_cast<const pr_count_t*>(counts), n_counts, loss);
   return launch_status();
+}
+
+}  // namespace
+
+extern "C" int unetpp_pr_focal_heads(const unetpp_focal_heads* heads, const float* target, int64_t n, float alpha, float beta,
+                                     float eps, float positive, void* workspace, int64_t* n_pos, float* loss, void* stream) {
+  return pr_focal_heads_launch<false>(heads, target, n, alpha, beta, eps, positive, workspace, n_pos, loss, stream);
+}
+
+extern "C" int unetpp_pr_focal_heads_ignore(const unetpp_focal_heads* heads, const float* target, int64_t n, float alpha,
+                                            float beta, float eps, float positive, void* workspace, int64_t* n_pos,
+                                            float* loss, void* stream) {
+  return pr_focal_heads_launch<true>(heads, target, n, alpha, beta, eps, positive, workspace, n_pos, loss, stream);
 }

@@ -19,6 +19,9 @@
 //     workgroup's strides.  Loss: thread (in index order) -> 6 wave shuffles -> (w0 + w1) + (w2 + w3) -> times 1 / denom.
 // Rows start at r * P floats and are 16-byte aligned only when that is a multiple of 4: the workgroup walks the row in
 // 4-element chunks of the ALIGNED index space (the row's first and last chunk may be partial and take scalar accesses).
+// kIgnore (unetpp_topk_focal_heads_ignore): an element whose target is negative has key 0 and is never emitted, so it
+// ranks last, takes a tie's rank when tau is 0, and adds +0.0 to the loss and the gradient selected or not; k >= P then
+// runs unetpp_focal_bce_heads_ignore.  The plain instantiation is the code it was.
 // The finish kernel sums the row partials per head in fixed order and forms the mean over heads as
 // focal_bce_heads_finish_kernel (caller.hip) does.  k >= P is FocalLoss_BCE_2d itself: value and gradient come from
 // unetpp_focal_bce_heads (same bits), this file's kernel then only finds kth (the smallest |d| of the row).
@@ -35,7 +38,15 @@ constexpr int kTopkPasses = 3;
 constexpr int kTopkAhead = 4;     // strides whose loads a thread issues before it works on the first of them
 constexpr int kTopkCand = 2048;   // keys of the first pass's bin the second pass lists in LDS for the third
 
-__device__ __forceinline__ uint32_t topk_key(float p, float t) { return __float_as_uint(fabsf(p - t)); }
+// kIgnore: an element whose target is negative (t < 0.0f) has key 0 -- it ranks last, and selected or not it
+// contributes +0.0 to the loss and the gradient
+template <bool kIgnore = false>
+__device__ __forceinline__ uint32_t topk_key(float p, float t) {
+  if constexpr (kIgnore) {
+    if (t < 0.f) return 0u;
+  }
+  return __float_as_uint(fabsf(p - t));
+}
 
 // Elements 4c .. 4c+3 of the aligned index space of a row (a = the row's pointer rounded down to 16 bytes); an element
 // j belongs to the row iff lo <= j < hi.  -> bit e set iff 4c + e does; elements outside are not touched.
@@ -58,7 +69,7 @@ __device__ __forceinline__ unsigned topk_load4(const float* __restrict__ a, long
 }
 
 // grid (rows, heads).  k: k_eff, 1 <= k <= P.  emit false: kth only.
-template <bool kLow>
+template <bool kLow, bool kIgnore = false>
 __global__ __launch_bounds__(kTopkThreads) void topk_focal_kernel(const unetpp_focal_heads hd,
                                                                   const float* __restrict__ target, long P, uint32_t k,
                                                                   float gamma, float inv_denom, float scale, int emit,
@@ -115,7 +126,7 @@ __global__ __launch_bounds__(kTopkThreads) void topk_focal_kernel(const unetpp_f
         for (int ae = 0; ae < 4 * kTopkAhead; ++ae) {
           const int e = ae & 3;
           const unsigned valid = vv[ae >> 2];
-          const uint32_t key = topk_key(pp[ae >> 2][e], tt[ae >> 2][e]);
+          const uint32_t key = topk_key<kIgnore>(pp[ae >> 2][e], tt[ae >> 2][e]);
           const bool act = ((valid >> e) & 1u) && ((key & prefix_mask) == prefix);
           const uint32_t bin = (key >> shift) & static_cast<uint32_t>(bins - 1);
           const uint64_t am = __ballot(act);
@@ -208,7 +219,7 @@ __global__ __launch_bounds__(kTopkThreads) void topk_focal_kernel(const unetpp_f
       uint32_t before = 0, mine = 0;   // ties in the lower lanes of this wave, ties of this thread
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const uint32_t key = topk_key(p[e], t[e]);
+        const uint32_t key = topk_key<kIgnore>(p[e], t[e]);
         const bool v = (valid >> e) & 1u;
         big[e] = v && key > tau;
         tie[e] = v && key == tau;
@@ -229,7 +240,8 @@ __global__ __launch_bounds__(kTopkThreads) void topk_focal_kernel(const unetpp_f
       taken += total;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const bool sel = big[e] || (tie[e] && rank < need);
+        bool sel = big[e] || (tie[e] && rank < need);
+        if constexpr (kIgnore) sel = sel && !(t[e] < 0.f);   // (a selected ignored element still takes its rank)
         rank += tie[e] ? 1u : 0u;
         g[e] = 0.f;
         if (sel) {
@@ -296,9 +308,11 @@ extern "C" int64_t unetpp_topk_focal_workspace_bytes(int32_t n_heads, int64_t ro
   return static_cast<int64_t>(n_heads) * (rows > blocks ? rows : blocks) * 4;
 }
 
-extern "C" int unetpp_topk_focal_heads(const unetpp_focal_heads* heads, const float* target, int64_t rows, int64_t P,
-                                       int64_t k, int64_t denom, float gamma, void* workspace, float* kth, float* loss,
-                                       void* stream) {
+namespace {
+
+template <bool kIgnore>
+int topk_focal_heads_launch(const unetpp_focal_heads* heads, const float* target, int64_t rows, int64_t P, int64_t k,
+                            int64_t denom, float gamma, void* workspace, float* kth, float* loss, void* stream) {
   if (heads == nullptr || target == nullptr || workspace == nullptr || kth == nullptr || loss == nullptr) return UNETPP_EINVAL;
   if (rows < 1 || rows > kTopkMaxRows || P < 1 || P > kTopkMaxP || k < 1 || denom < 1) return UNETPP_EINVAL;
   if (rows > INT64_MAX / P) return UNETPP_EINVAL;
@@ -314,16 +328,32 @@ extern "C" int unetpp_topk_focal_heads(const unetpp_focal_heads* heads, const fl
   const hipStream_t st = static_cast<hipStream_t>(stream);
   const bool all = k >= P;
   if (all) {
-    const int status = unetpp_focal_bce_heads(&hd, target, rows * P, denom, gamma, static_cast<float*>(workspace), loss, stream);
+    const int status = (kIgnore ? unetpp_focal_bce_heads_ignore : unetpp_focal_bce_heads)(
+        &hd, target, rows * P, denom, gamma, static_cast<float*>(workspace), loss, stream);
     if (status != UNETPP_OK) return status;
   }
   const float inv_heads = 1.0f / static_cast<float>(hd.n_heads);
   const dim3 grid(static_cast<unsigned>(rows), static_cast<unsigned>(hd.n_heads));
-  hipLaunchKernelGGL(gamma < 1.f ? topk_focal_kernel<true> : topk_focal_kernel<false>, grid, dim3(kTopkThreads), 0, st, hd,
+  const auto kernel = gamma < 1.f ? topk_focal_kernel<true, kIgnore> : topk_focal_kernel<false, kIgnore>;
+  hipLaunchKernelGGL(kernel, grid, dim3(kTopkThreads), 0, st, hd,
                      target, static_cast<long>(P), static_cast<uint32_t>(all ? P : k), gamma,
                      1.f / static_cast<float>(denom), inv_heads, all ? 0 : 1, static_cast<float*>(workspace), kth);
   if (!all)
     hipLaunchKernelGGL(topk_focal_finish_kernel, dim3(1), dim3(1024), 0, st, static_cast<const float*>(workspace),
                        static_cast<long>(rows), hd.n_heads, inv_heads, loss);
   return launch_status();
+}
+
+}  // namespace
+
+extern "C" int unetpp_topk_focal_heads(const unetpp_focal_heads* heads, const float* target, int64_t rows, int64_t P,
+                                       int64_t k, int64_t denom, float gamma, void* workspace, float* kth, float* loss,
+                                       void* stream) {
+  return topk_focal_heads_launch<false>(heads, target, rows, P, k, denom, gamma, workspace, kth, loss, stream);
+}
+
+extern "C" int unetpp_topk_focal_heads_ignore(const unetpp_focal_heads* heads, const float* target, int64_t rows, int64_t P,
+                                              int64_t k, int64_t denom, float gamma, void* workspace, float* kth,
+                                              float* loss, void* stream) {
+  return topk_focal_heads_launch<true>(heads, target, rows, P, k, denom, gamma, workspace, kth, loss, stream);
 }

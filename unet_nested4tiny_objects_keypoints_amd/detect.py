@@ -88,7 +88,9 @@ class DetectionScore:
     (0-d float64) and per class over all frames (class_* [C]), 0 / 0 = 0; mean_distance: float64 mean of the Euclidean
     distance of the matched pairs, NaN when nothing matched; average_precision (0-d) and class_average_precision [C]: the
     all-points area under the precision envelope, predictions of all frames pooled (0 without labels); pred_label
-    [S, C, cap] / label_pred [S, L] int32: the matcher's indices (-1: unmatched)."""
+    [S, C, cap] / label_pred [S, L] int32: the matcher's indices (-1: unmatched); served [S, C, cap] bool: the detections
+    that took part (inside the list's count, at or above the score threshold, outside every ignore region) -- ``evaluate``
+    always fills it, a hand-built score may leave it None."""
     tp: torch.Tensor
     fp: torch.Tensor
     fn: torch.Tensor
@@ -106,6 +108,7 @@ class DetectionScore:
     class_average_precision: torch.Tensor
     pred_label: torch.Tensor
     label_pred: torch.Tensor
+    served: Optional[torch.Tensor] = None
 
 
 def _ratio(num: torch.Tensor, den: torch.Tensor) -> torch.Tensor:
@@ -156,16 +159,19 @@ def score_matches(xy, score, served, pred_label, label_pred, stats, labels, labe
     ap = _average_precision(score.reshape(-1), served.reshape(-1), hit.reshape(-1), tpt + fnt)
     return DetectionScore(tp, fp, fn, tpt, fpt, fnt, _ratio(tpt, tpt + fpt), _ratio(tpt, tpt + fnt),
                           _ratio(2 * tpt, 2 * tpt + fpt + fnt), _ratio(tpc, tpc + fpc), _ratio(tpc, tpc + fnc),
-                          _ratio(2 * tpc, 2 * tpc + fpc + fnc), mean_distance, ap, class_ap, pred_label, label_pred)
+                          _ratio(2 * tpc, 2 * tpc + fpc + fnc), mean_distance, ap, class_ap, pred_label, label_pred, served)
 
 
 def evaluate(dets: Detections, labels, label_class, tolerance: float,
-             score_threshold: Optional[float] = None) -> DetectionScore:
+             score_threshold: Optional[float] = None, ignore=None) -> DetectionScore:
     """Score detections against labelled points.  labels [S, L, 2] (x, y); label_class [S, L] or [L]: the class (map
     index) of every label, -1 for padding; a label at (-1, -1) is padding whatever its class.  Per (frame, class) the
     detections are served brightest first and each takes the nearest label of its class within `tolerance` (Euclidean,
     inclusive) that no brighter detection took, ties to the lowest label index (unetpp_detect_match).
-    score_threshold: detections below it are dropped before matching.  Nothing is read back."""
+    score_threshold: detections below it are dropped before matching.  ignore: an ``IgnoreRegions`` over the same frames
+    -- a detection inside a rectangle of its frame and class (or of every class) is dropped before matching, neither a
+    true nor a false positive; a label inside one becomes padding, neither matched nor a false negative.  Nothing is
+    read back."""
     xy, score, count = dets.xy, dets.score, dets.count
     dev = xy.device
     S, C, cap = (int(v) for v in score.shape)
@@ -183,10 +189,19 @@ def evaluate(dets: Detections, labels, label_class, tolerance: float,
         cls = torch.full((S, 1), -1, dtype=torch.int32, device=dev)
     padding = (labels[..., 0] == -1) & (labels[..., 1] == -1)
     cls = torch.where(padding, torch.full_like(cls, -1), cls).contiguous()
+    if ignore is not None:
+        if len(ignore) != S:
+            raise ValueError("ignore holds %d frames, the detections %d" % (len(ignore), S))
+        ignore = ignore.to(dev)
+        frame = torch.arange(S, device=dev)
+        dropped = ignore.contains(frame.view(S, 1), cls, labels)
+        cls = torch.where(dropped, torch.full_like(cls, -1), cls).contiguous()
     labels = labels.contiguous()
     served = torch.arange(cap, device=dev).view(1, 1, cap) < count.clamp(max=cap).unsqueeze(-1)
     if score_threshold is not None:
         served = served & (score >= float(score_threshold))
+    if ignore is not None:
+        served = served & ~ignore.contains(frame.view(S, 1, 1), torch.arange(C, device=dev).view(1, C, 1), xy)
     key = torch.where(served, score, torch.full_like(score, float("-inf")))
     order = torch.sort(key, dim=-1, descending=True, stable=True).indices.to(torch.int32)
     n_pred = served.sum(-1).to(torch.int32)

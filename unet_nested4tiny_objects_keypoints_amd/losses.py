@@ -10,6 +10,23 @@ import torch
 from torch import nn
 
 
+class _FocalBCEIgnoreFn(torch.autograd.Function):
+    """The one-head ``mean_over_heads`` value of a criterion with ignore_negative (unetpp_focal_bce_heads_ignore)."""
+
+    @staticmethod
+    def forward(ctx, pred, target, rows, gamma):
+        from . import ops
+        loss, grads = ops.focal_bce_heads([pred.contiguous()], target.contiguous(), rows, gamma,
+                                          want_grad=ctx.needs_input_grad[0], ignore=True)
+        ctx.save_for_backward(grads[0] if grads is not None else None)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return (grad * g if grad is not None else None), None, None, None
+
+
 class _FocalBCEFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pred, target, rows, gamma):
@@ -25,11 +42,15 @@ class _FocalBCEFn(torch.autograd.Function):
 
 
 class FocalLoss_BCE_2d(nn.Module):
-    def __init__(self, gamma=3, alpha=0.25, size_average=False):
+    """ignore_negative: an element whose target is negative (``target < 0``: -0.0 and a NaN are not) is ignored -- its
+    term and its gradient are +0.0 whatever the input holds; the divisor stays what it is without."""
+
+    def __init__(self, gamma=3, alpha=0.25, size_average=False, ignore_negative=False):
         super().__init__()
         self.gamma = gamma
         self.alpha = alpha  # kept for signature parity; the reference never uses it in forward
         self.size_average = size_average
+        self.ignore_negative = bool(ignore_negative)
 
     def forward(self, input, target):
         if input.dim() > 2:
@@ -39,9 +60,15 @@ class FocalLoss_BCE_2d(nn.Module):
         if (input.is_cuda and target.is_cuda and input.dtype == torch.float32 and target.dtype == torch.float32
                 and not target.requires_grad):
             rows = input.numel() if self.size_average else samples_num  # mean over elements / sum over N*C rows
-            return _FocalBCEFn.apply(input, target, rows, float(self.gamma))
-        error = 1 - torch.abs(input - target) + 1e-20
+            fn = _FocalBCEIgnoreFn if self.ignore_negative else _FocalBCEFn
+            return fn.apply(input, target, rows, float(self.gamma))
+        d = input - target
+        if self.ignore_negative:   # (d = 0 under an ignored element as well: autograd's 0 * NaN through where is a NaN)
+            d = torch.where(target < 0, torch.zeros_like(d), d)
+        error = 1 - torch.abs(d) + 1e-20
         loss = -1 * (1 - error) ** self.gamma * torch.log(error)
+        if self.ignore_negative:
+            loss = torch.where(target < 0, torch.zeros_like(loss), loss)
         if self.size_average:
             return loss.mean()
         return loss.sum() / samples_num
@@ -63,16 +90,17 @@ class FocalLoss_BCE_2d(nn.Module):
                 return None
         t = target.contiguous()
         rows = t.numel() if self.size_average else t.shape[0] * t.shape[1]
-        loss, grads = ops.focal_bce_heads([o.detach() for o in outputs], t, rows, float(self.gamma))
+        loss, grads = ops.focal_bce_heads([o.detach() for o in outputs], t, rows, float(self.gamma),
+                                          ignore=self.ignore_negative)
         return loss[0], grads
 
 
 class _TopKFocalBCEFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, pred, target, k, denom, gamma):
+    def forward(ctx, pred, target, k, denom, gamma, ignore=False):
         from . import ops
         loss, grads, kth = ops.topk_focal_heads([pred.contiguous()], target.contiguous(), k, denom, gamma,
-                                                want_grad=ctx.needs_input_grad[0])
+                                                want_grad=ctx.needs_input_grad[0], ignore=ignore)
         ctx.save_for_backward(grads[0] if grads is not None else None)
         kth = kth[0]
         ctx.mark_non_differentiable(kth)
@@ -81,7 +109,7 @@ class _TopKFocalBCEFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g, _g_kth):
         (grad,) = ctx.saved_tensors
-        return (grad * g if grad is not None else None), None, None, None, None
+        return (grad * g if grad is not None else None), None, None, None, None, None
 
 
 class TopKFocalLoss_BCE_2d(nn.Module):
@@ -95,10 +123,15 @@ class TopKFocalLoss_BCE_2d(nn.Module):
     value and gradient together); CPU tensors the same rule as plain torch ops.  After a call ``last_threshold`` holds the
     k-th largest ``|input - target|`` of every map: [N*C] after ``forward``, [heads, N*C] after ``mean_over_heads``.
 
+    ignore_negative: an element whose target is negative (``target < 0``: -0.0 and a NaN are not) ranks as
+    ``|input - target| = 0`` -- last -- and contributes +0.0 to the loss and the gradient whether selected or not; k and
+    the divisor stay what they are without.
+
     Deliberately not a subclass of ``FocalLoss_BCE_2d``: code that tests for that class computes the unselected loss."""
 
-    def __init__(self, k=None, fraction=None, gamma=3, size_average=False):
+    def __init__(self, k=None, fraction=None, gamma=3, size_average=False, ignore_negative=False):
         super().__init__()
+        self.ignore_negative = bool(ignore_negative)
         if (k is None) == (fraction is None):
             raise ValueError("give exactly one of k and fraction")
         if k is not None:
@@ -133,16 +166,22 @@ class TopKFocalLoss_BCE_2d(nn.Module):
         denom = self._denom(rows, k_eff)
         if (input.is_cuda and target.is_cuda and input.dtype == torch.float32 and target.dtype == torch.float32
                 and not target.requires_grad):
-            loss, kth = _TopKFocalBCEFn.apply(input, target, k_eff, denom, float(self.gamma))
+            loss, kth = _TopKFocalBCEFn.apply(input, target, k_eff, denom, float(self.gamma), self.ignore_negative)
             self.last_threshold = kth
             return loss
         d = (input - target).reshape(rows, pixels)
+        ignored = target.reshape(rows, pixels) < 0 if self.ignore_negative else None
+        if ignored is not None:   # key 0, and no NaN reaches autograd through the where below
+            d = torch.where(ignored, torch.zeros_like(d), d)
+        key = d.detach().abs()
         # descending and stable: the lowest index first among equals (a NaN sorts first, as in the kernel)
-        ranked, order = torch.sort(d.detach().abs(), dim=1, descending=True, stable=True)
+        ranked, order = torch.sort(key, dim=1, descending=True, stable=True)
         selected = torch.zeros(rows, pixels, dtype=torch.bool).scatter_(1, order[:, :k_eff], True)
         self.last_threshold = ranked[:, k_eff - 1]
         error = 1 - torch.abs(d) + 1e-20
         loss = -1 * (1 - error) ** self.gamma * torch.log(error)
+        if ignored is not None:
+            selected = selected & ~ignored
         return torch.where(selected, loss, torch.zeros_like(loss)).sum() / denom
 
     def mean_over_heads(self, outputs, target):
@@ -162,17 +201,17 @@ class TopKFocalLoss_BCE_2d(nn.Module):
         rows, pixels = t.shape[0] * t.shape[1], t.shape[2] * t.shape[3]
         k_eff = self.k_for(pixels)
         loss, grads, kth = ops.topk_focal_heads([o.detach() for o in outputs], t, k_eff, self._denom(rows, k_eff),
-                                                float(self.gamma))
+                                                float(self.gamma), ignore=self.ignore_negative)
         self.last_threshold = kth
         return loss[0], grads
 
 
 class _PRFocalFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, pred, target, alpha, beta, eps, positive):
+    def forward(ctx, pred, target, alpha, beta, eps, positive, ignore=False):
         from . import ops
         loss, grads, n_pos = ops.pr_focal_heads([pred.contiguous()], target.contiguous(), alpha, beta, eps, positive,
-                                                want_grad=ctx.needs_input_grad[0])
+                                                want_grad=ctx.needs_input_grad[0], ignore=ignore)
         ctx.save_for_backward(grads[0] if grads is not None else None)
         ctx.mark_non_differentiable(n_pos)
         return loss[0], n_pos
@@ -180,7 +219,7 @@ class _PRFocalFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g, _g_n_pos):
         (grad,) = ctx.saved_tensors
-        return (grad * g if grad is not None else None), None, None, None, None, None
+        return (grad * g if grad is not None else None), None, None, None, None, None, None
 
 
 class PenaltyReducedFocalLoss(nn.Module):
@@ -202,10 +241,14 @@ class PenaltyReducedFocalLoss(nn.Module):
     anything else the same rule as plain torch ops.  After a call ``last_num_positives`` holds n_pos as a 0-dim int64
     tensor on the device of the target; the class never reads it back.
 
+    ignore_negative: an element whose target is negative (``target < 0``: -0.0 and a NaN are not) is ignored -- its term
+    and its gradient are +0.0 whatever the input holds; n_pos is unchanged (a negative target is never >= positive).
+
     Deliberately not a subclass of ``FocalLoss_BCE_2d``: code that tests for that class computes another loss."""
 
-    def __init__(self, alpha=2.0, beta=4.0, eps=1e-4, positive=1.0):
+    def __init__(self, alpha=2.0, beta=4.0, eps=1e-4, positive=1.0, ignore_negative=False):
         super().__init__()
+        self.ignore_negative = bool(ignore_negative)
         alpha, beta, eps, positive = float(alpha), float(beta), float(eps), float(positive)
         if not (0.0 <= alpha < float("inf")) or not (0.0 <= beta < float("inf")):
             raise ValueError("alpha and beta must be finite and >= 0, got %r and %r" % (alpha, beta))
@@ -226,16 +269,24 @@ class PenaltyReducedFocalLoss(nn.Module):
             raise ValueError("input and target must have the same shape")
         if (input.is_cuda and target.is_cuda and input.dtype == torch.float32 and target.dtype == torch.float32
                 and not target.requires_grad):
-            loss, n_pos = _PRFocalFn.apply(input, target, self.alpha, self.beta, self.eps, self.positive)
+            loss, n_pos = _PRFocalFn.apply(input, target, self.alpha, self.beta, self.eps, self.positive,
+                                           self.ignore_negative)
             self.last_num_positives = n_pos
             return loss
         q = input.clamp(self._lo, self._hi)
+        if self.ignore_negative:   # (finite operands under an ignored element: autograd's 0 * NaN through where is a NaN)
+            ignored = target < 0
+            q = torch.where(ignored, torch.full_like(q, 0.5), q)
+            target = torch.where(ignored, torch.zeros_like(target), target)
         pos = target >= self._positive32
         at_centre = -1 * (1 - q) ** self.alpha * torch.log(q)
         elsewhere = -1 * (1 - target) ** self.beta * q ** self.alpha * torch.log1p(-q)
         n_pos = pos.sum()
         self.last_num_positives = n_pos
-        total = torch.where(pos, at_centre, elsewhere).sum()
+        term = torch.where(pos, at_centre, elsewhere)
+        if self.ignore_negative:
+            term = torch.where(ignored, torch.zeros_like(term), term)
+        total = term.sum()
         return total * (1.0 / n_pos.clamp(min=1).to(total.dtype))
 
     def mean_over_heads(self, outputs, target):
@@ -252,6 +303,6 @@ class PenaltyReducedFocalLoss(nn.Module):
                     and o.device == target.device):
                 return None
         loss, grads, n_pos = ops.pr_focal_heads([o.detach() for o in outputs], target.contiguous(), self.alpha, self.beta,
-                                                self.eps, self.positive)
+                                                self.eps, self.positive, ignore=self.ignore_negative)
         self.last_num_positives = n_pos
         return loss[0], grads

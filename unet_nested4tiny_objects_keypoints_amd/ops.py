@@ -863,10 +863,11 @@ def focal_bce(pred: torch.Tensor, target: torch.Tensor, rows: int, gamma: float,
     return loss.reshape(()), grad
 
 
-def focal_bce_heads(preds, target: torch.Tensor, rows: int, gamma: float, want_grad: bool = True):
+def focal_bce_heads(preds, target: torch.Tensor, rows: int, gamma: float, want_grad: bool = True, ignore: bool = False):
     """The trainer's loop over the deep-supervision heads (criterion on every head, mean over heads) in one launch:
     -> (losses [1 + heads]: the mean, then every head's FocalLoss_BCE_2d value; d mean / d pred per head or None).
-    Bit for bit what the loop computes with focal_bce and tensor arithmetic (tests/test_gpu_caller.py)."""
+    Bit for bit what the loop computes with focal_bce and tensor arithmetic (tests/test_gpu_caller.py).
+    ignore: a negative target element contributes +0.0 to loss and gradient (unetpp_focal_bce_heads_ignore)."""
     lib = _lib.lib()
     if not 1 <= len(preds) <= _lib.MAX_HEADS:
         raise ValueError("1 to %d heads" % _lib.MAX_HEADS)
@@ -886,17 +887,20 @@ def focal_bce_heads(preds, target: torch.Tensor, rows: int, gamma: float, want_g
     for i, p in enumerate(preds):
         hd.pred[i] = p.data_ptr()
         hd.grad[i] = grads[i].data_ptr() if want_grad else None
-    check(lib.unetpp_focal_bce_heads(C.byref(hd), _ptr(target), n, rows, float(gamma), _ptr(partial), _ptr(loss),
-                                     _stream()), "unetpp_focal_bce_heads")
+    fn = lib.unetpp_focal_bce_heads_ignore if ignore else lib.unetpp_focal_bce_heads
+    check(fn(C.byref(hd), _ptr(target), n, rows, float(gamma), _ptr(partial), _ptr(loss), _stream()),
+          "unetpp_focal_bce_heads_ignore" if ignore else "unetpp_focal_bce_heads")
     return loss, grads
 
 
-def topk_focal_heads(preds, target: torch.Tensor, k: int, denom: int, gamma: float, want_grad: bool = True):
+def topk_focal_heads(preds, target: torch.Tensor, k: int, denom: int, gamma: float, want_grad: bool = True,
+                     ignore: bool = False):
     """Top-k focal loss of every head against one target [..., H, W] (a row is one map of P = H*W pixels): per head and
     row only the min(k, P) pixels with the largest |pred - target| enter FocalLoss_BCE_2d, ties at the threshold taken in
     index order (csrc/topk_loss.hip: an exact radix select, one launch for all heads).
     -> (losses [1 + heads]: the mean over heads, then every head's value; d mean / d pred per head (+0.0 on every pixel
-    that is not selected) or None; kth [heads, rows]: the k-th largest |pred - target| of every head and row)."""
+    that is not selected) or None; kth [heads, rows]: the k-th largest |pred - target| of every head and row).
+    ignore: a negative target element has key 0 and contributes +0.0 (unetpp_topk_focal_heads_ignore)."""
     lib = _lib.lib()
     if not 1 <= len(preds) <= _lib.MAX_HEADS:
         raise ValueError("1 to %d heads" % _lib.MAX_HEADS)
@@ -924,17 +928,19 @@ def topk_focal_heads(preds, target: torch.Tensor, k: int, denom: int, gamma: flo
     for i, p in enumerate(preds):
         hd.pred[i] = p.data_ptr()
         hd.grad[i] = grads[i].data_ptr() if want_grad else None
-    check(lib.unetpp_topk_focal_heads(C.byref(hd), _ptr(target), rows, pixels, int(k), int(denom), float(gamma),
-                                      _ptr(workspace), _ptr(kth), _ptr(loss), _stream()), "unetpp_topk_focal_heads")
+    fn = lib.unetpp_topk_focal_heads_ignore if ignore else lib.unetpp_topk_focal_heads
+    check(fn(C.byref(hd), _ptr(target), rows, pixels, int(k), int(denom), float(gamma), _ptr(workspace), _ptr(kth),
+             _ptr(loss), _stream()), "unetpp_topk_focal_heads_ignore" if ignore else "unetpp_topk_focal_heads")
     return loss, grads, kth
 
 
 def pr_focal_heads(preds, target: torch.Tensor, alpha: float, beta: float, eps: float, positive: float,
-                   want_grad: bool = True):
+                   want_grad: bool = True, ignore: bool = False):
     """Penalty-reduced focal loss of every head against one target, normalised by the number of positives (t >=
     positive) of the target (csrc/pr_focal.hip: a count pass, the main pass, a finish; no read-back).
     -> (losses [1 + heads]: the mean over heads, then every head's value; d mean / d pred per head or None; n_pos: the
-    number of positives, a 0-dim int64 tensor on the device)."""
+    number of positives, a 0-dim int64 tensor on the device).
+    ignore: a negative target element contributes +0.0 to loss and gradient (unetpp_pr_focal_heads_ignore)."""
     lib = _lib.lib()
     if not 1 <= len(preds) <= _lib.MAX_HEADS:
         raise ValueError("1 to %d heads" % _lib.MAX_HEADS)
@@ -957,8 +963,9 @@ def pr_focal_heads(preds, target: torch.Tensor, alpha: float, beta: float, eps: 
     for i, p in enumerate(preds):
         hd.pred[i] = p.data_ptr()
         hd.grad[i] = grads[i].data_ptr() if want_grad else None
-    check(lib.unetpp_pr_focal_heads(C.byref(hd), _ptr(target), n, float(alpha), float(beta), float(eps), float(positive),
-                                    _ptr(workspace), _ptr(n_pos), _ptr(loss), _stream()), "unetpp_pr_focal_heads")
+    fn = lib.unetpp_pr_focal_heads_ignore if ignore else lib.unetpp_pr_focal_heads
+    check(fn(C.byref(hd), _ptr(target), n, float(alpha), float(beta), float(eps), float(positive), _ptr(workspace),
+             _ptr(n_pos), _ptr(loss), _stream()), "unetpp_pr_focal_heads_ignore" if ignore else "unetpp_pr_focal_heads")
     return loss, grads, n_pos
 
 
@@ -1403,6 +1410,46 @@ def points_target(labels: torch.Tensor, label_class: torch.Tensor, index: torch.
         _ptr(labels), _ptr(label_class), m, n_labels, _ptr(index), n, _ptr(params), c, ho, wo, radius, _ptr(out),
         _stream()), "unetpp_points_target"), 4.0 * n * c * ho * wo)
     return out
+
+
+def target_ignore(target: torch.Tensor, rects: Optional[torch.Tensor], rect_class: Optional[torch.Tensor],
+                  index: torch.Tensor, params: torch.Tensor, src_size, outside: bool = False,
+                  n_frames: Optional[int] = None) -> torch.Tensor:
+    """One launch: writes -1.0 into the ignored elements of target [N, C, Ho, Wo] fp32, in place, and returns it.  rects
+    [M, R, 4] fp32 as (x0, y0, x1, y1) in source pixels with rect_class [M, R] int32 (-1: every class), or None / R = 0
+    for no rectangles -- then n_frames says how many frames there are (an index outside [0, M) is an all-fill sample);
+    index [N] int64 and params [N, 16]: the rows of the warp; src_size = (Hs, Ws); outside: also mark what lies outside
+    the frame (include/unetpp_hip.h: unetpp_target_ignore).  Nothing else of target is touched."""
+    _need(target, "target")
+    _need(index, "index", torch.int64)
+    _need(params, "params")
+    if target.dim() != 4:
+        raise ValueError("target must be [N, C, Ho, Wo]")
+    n, c, ho, wo = (int(v) for v in target.shape)
+    if index.dim() != 1 or int(index.numel()) != n or tuple(params.shape) != (n, _lib.WARP_PARAMS):
+        raise ValueError("index [N] and params [N, %d] for a target of N = %d samples" % (_lib.WARP_PARAMS, n))
+    dev = target.device
+    m, r = n_frames, 0
+    if rects is not None and rects.numel() > 0:
+        _need(rects, "rects")
+        _need(rect_class, "rect_class", torch.int32)
+        if rects.dim() != 3 or rects.shape[2] != 4 or tuple(rect_class.shape) != tuple(rects.shape[:2]):
+            raise ValueError("rects must be [M, R, 4] and rect_class [M, R]")
+        m, r = int(rects.shape[0]), int(rects.shape[1])
+    elif rects is not None and rects.dim() == 3 and rects.shape[0] > 0:
+        m = int(rects.shape[0])
+    if m is None or (n_frames is not None and int(n_frames) != m):
+        raise ValueError("the number of frames: give n_frames without rectangles, and the rectangles' own M with them")
+    m = int(m)
+    if any(t.device != dev for t in (index, params) + ((rects, rect_class) if r else ())):
+        raise ValueError("all tensors must live on one device")
+    hs, ws = int(src_size[0]), int(src_size[1])
+    if min(m, n, c, ho, wo, hs, ws) < 1 or c > 65535:
+        raise ValueError("N, the window and the frame must be positive and C in 1..65535")
+    _timed_call("target_ignore", 0.0, lambda: check(_lib.lib().unetpp_target_ignore(
+        _ptr(rects) if r else None, _ptr(rect_class) if r else None, m, r, _ptr(index), n, _ptr(params), c, ho, wo, hs, ws,
+        1 if outside else 0, _ptr(target), _stream()), "unetpp_target_ignore"), 4.0 * n * c * ho * wo)
+    return target
 
 
 def crops_draw(n: int, seed: int, n_frames: int, src_size, out_size, centre_frame: Optional[torch.Tensor],
