@@ -364,6 +364,20 @@ int unetpp_head_bwd(const float* d_out_nchw, const float* out_nchw, const float*
                     int32_t N, int32_t H, int32_t W, int32_t C, int32_t n_cls, float p_drop, uint64_t seed,
                     const uint8_t* mask, const uint64_t* seed_dev, float* dx, int32_t accumulate, int32_t gate_x, float* partial,
                     void* stream); /* gate_x: after the (optional) accumulate, dx *= (x > 0) -- the ReLU mask of x */
+/* ---- one head of a training step in one pass (added within v13: new entry points only, nothing existing changes) ----
+ * What unetpp_head_fwd, the gradient of unetpp_focal_bce_heads for this head (the mean over n_heads of FocalLoss_BCE_2d
+ * against target_nchw [N,n_cls,H,W], `rows` and `gamma` as there) and unetpp_head_bwd (accumulate = 0) compute in three
+ * launches, with the same bits: out_nchw, dx and every row of partial (unetpp_head_bwd_blocks(N*H*W) rows of
+ * [n_cls*C + n_cls], finished by unetpp_sum_partials).  x is read once, the map is written and not read back, the loss
+ * gradient is never written; the loss VALUE is unetpp_focal_bce_heads over the maps without gradient pointers.
+ * Accepts fp32 calls that unetpp_head_fwd takes with its streaming kernel AND unetpp_head_bwd with its power-of-two one
+ * (C = 4 * 2^k, 16 <= C <= 128, n_cls padded to 4 or 8 at most C / 4, 16-byte aligned x, weight and dx, a 4-byte
+ * aligned mask, fewer than 2^31 - 1 elements of x), rows >= 1 and 1 <= n_heads <= UNETPP_MAX_HEADS; anything else
+ * returns UNETPP_EINVAL without touching the device, and the caller runs the three launches. */
+int unetpp_head_train(const float* x, const float* weight, const float* bias, const float* target_nchw, int32_t N,
+                      int32_t H, int32_t W, int32_t C, int32_t n_cls, float p_drop, uint64_t seed, const uint8_t* mask,
+                      const uint64_t* seed_dev, int64_t rows, float gamma, int32_t n_heads, float* out_nchw, float* dx,
+                      int32_t gate_x, float* partial, void* stream);
 /* out[i] = sum_b partial[b][i], i < len (used for head dW/db) */
 int unetpp_sum_partials(const float* partial, int64_t n_blocks, int64_t len, float* out, void* stream);
 

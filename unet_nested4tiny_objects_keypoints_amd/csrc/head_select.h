@@ -1,8 +1,8 @@
 // The deep-supervision heads: head_select decides ONCE, from the arguments of a launcher, which kernel of heads.hip takes
 // the call and everything that follows from that -- every refusal and its return code, the form and the template
 // coordinates, grid, workgroup, dynamic LDS, the bf16 backward's `active` count and the label.  The launchers of
-// heads.hip (six, and the two of the ensemble mean's backward) check their pointers, fill a HeadQuery and launch what the
-// HeadSel says.  Host only (no HIP header):
+// heads.hip (six, the two of the ensemble mean's backward and the training pass unetpp_head_train) check their pointers,
+// fill a HeadQuery and launch what the HeadSel says.  Host only (no HIP header):
 // tests/test_head_select.py compiles it with a plain C++17 compiler.
 #pragma once
 #include <stddef.h>
@@ -17,7 +17,11 @@ constexpr int kHeadMaxCls = 8;
 constexpr int kHeadThreads = 256;     // kThreads (heads.hip asserts it)
 constexpr int kHeadTilePixels = 256;  // pixel tile of head_bwd_bf16_kernel up to 64 channels (128 pixels at 128 channels)
 
-enum HeadOp { HEAD_FWD, HEADS_MEAN, HEAD_BWD, HEADS_MEAN_BWD };  // HEADS_MEAN_BWD: unetpp_heads_mean_bwd[_bf16], one launch per head
+enum HeadOp {
+  HEAD_FWD, HEADS_MEAN, HEAD_BWD,
+  HEADS_MEAN_BWD,  // unetpp_heads_mean_bwd[_bf16], one launch per head
+  HEAD_TRAIN,      // unetpp_head_train: forward, loss gradient and backward of one head in one pass (fp32 only)
+};
 enum HeadForm {
   HEAD_STREAM,   // fp32 forward / mean: lane = (pixel, channel quad), C = 4 * 2^log2g
   HEAD_TILED,    // fp32 forward: 64-pixel LDS tiles, any C % 4 == 0
@@ -32,7 +36,7 @@ struct HeadQuery {
   HeadOp op;
   bool bf16;
   int N, H, W, C, n_cls;
-  int n_heads;    // HEADS_MEAN and HEADS_MEAN_BWD only
+  int n_heads;    // HEADS_MEAN, HEADS_MEAN_BWD and HEAD_TRAIN (the heads the loss is averaged over) only
   float p_drop;   // 0 for HEADS_MEAN
   bool has_mask;  // a mask pointer was given (whether or not p_drop uses it)
   // low four address bits per pointer role; HEADS_MEAN: x and weight OR-ed over the heads (HEADS_MEAN_BWD: and dx)
@@ -52,13 +56,14 @@ struct HeadSel {
 // "head_bwd_pow2<3,1,8>" and the like for every (family, log2g, drop, pcls): a constant table, so that a label is a
 // pointer into static storage (note_kernel keeps it) and the launch path formats nothing
 struct HeadLabels {
-  char s[6][6][3][3][24];  // [op + 3 * bf16][log2g][drop][pcls / 2 - 2]
+  char s[7][6][3][3][24];  // [op + 3 * bf16, 6: the training pass][log2g][drop][pcls / 2 - 2]
 };
 constexpr HeadLabels make_head_labels() {
-  const char* pattern[6] = {"head_fwd_stream<L,P,D>", "heads_mean_stream<L,P>", "head_bwd_pow2<L,D,P>",  // L, D, P: the
-                            "head_fwd_bf16<L,D,P>",   "heads_mean_bf16<L,P>",   "head_bwd_bf16<L,D,P>"};  // coordinates
+  const char* pattern[7] = {"head_fwd_stream<L,P,D>", "heads_mean_stream<L,P>", "head_bwd_pow2<L,D,P>",  // L, D, P: the
+                            "head_fwd_bf16<L,D,P>",   "heads_mean_bf16<L,P>",   "head_bwd_bf16<L,D,P>",   // coordinates
+                            "head_train_pow2<L,D,P>"};
   HeadLabels t{};
-  for (int f = 0; f < 6; ++f)
+  for (int f = 0; f < 7; ++f)
     for (int l = 0; l < 6; ++l)
       for (int d = 0; d < 3; ++d)
         for (int p = 0; p < 3; ++p)
@@ -82,9 +87,10 @@ inline int head_log2(int v) {
 template <class CusFn>
 inline int head_select_with(const HeadQuery& q, CusFn&& cus_fn, HeadSel& s) {
   s = HeadSel{};
-  const bool mean = q.op == HEADS_MEAN, bwd = q.op == HEAD_BWD, mean_bwd = q.op == HEADS_MEAN_BWD;
+  const bool mean = q.op == HEADS_MEAN, bwd = q.op == HEAD_BWD, mean_bwd = q.op == HEADS_MEAN_BWD, train = q.op == HEAD_TRAIN;
   if (q.N < 1 || q.H < 1 || q.W < 1 || q.C < 1 || q.C > kHeadMaxC || q.n_cls < 1 || q.n_cls > kHeadMaxCls ||
-      !(q.p_drop >= 0.f && q.p_drop < 1.f) || ((mean || mean_bwd) && (q.n_heads < 1 || q.n_heads > UNETPP_MAX_HEADS)))
+      !(q.p_drop >= 0.f && q.p_drop < 1.f) ||
+      ((mean || mean_bwd || train) && (q.n_heads < 1 || q.n_heads > UNETPP_MAX_HEADS)))
     return UNETPP_EINVAL;
   const long pixels = static_cast<long>(q.N) * q.H * q.W;
   const bool x16 = (q.x_lo & 15) == 0, w16 = (q.weight_lo & 15) == 0, dx16 = (q.dx_lo & 15) == 0;
@@ -117,6 +123,7 @@ inline int head_select_with(const HeadQuery& q, CusFn&& cus_fn, HeadSel& s) {
     s.lds = (64 * (q.C + 1) + 64 * kHeadMaxCls + kHeadMaxCls * q.C + 2 * q.n_cls * q.C) * sizeof(float);
     return UNETPP_OK;
   }
+  if (train && q.bf16) return UNETPP_EINVAL;  // fp32 storage only
   const int family = q.op + 3 * (q.bf16 ? 1 : 0);
 
   if (q.bf16) {
@@ -170,6 +177,16 @@ inline int head_select_with(const HeadQuery& q, CusFn&& cus_fn, HeadSel& s) {
                     (!q.has_mask || (q.mask_lo & 3) == 0);
   s.pcls = q.n_cls <= 4 ? 4 : 8;
   s.log2g = head_log2(g4 > 0 ? g4 : 1);
+  if (train) {
+    // The training pass is head_fwd_stream's logits inside head_bwd_pow2's tile walk: it takes a call only where BOTH of
+    // them take the three-launch path's calls (its results are theirs bit for bit), on the backward's grid and LDS plan.
+    // Anything else is refused; the caller then runs the three launches.
+    if (!(pow2 && dx16 && s.pcls <= g4)) return UNETPP_EINVAL;
+    s.form = HEAD_POW2;
+    s.lds = (64 * (q.C + 1) + 64 * kHeadMaxCls + 2 * q.n_cls * q.C) * sizeof(float);  // x tile | dlogit | scratch
+    s.label = kHeadLabels.s[6][s.log2g][s.drop][s.pcls / 2 - 2];
+    return UNETPP_OK;
+  }
   if (!bwd) {
     if (pow2 && s.pcls <= g4) {  // the reduce-scatter deals the classes to the lanes of a pixel: at most one each
       s.form = HEAD_STREAM;

@@ -8,6 +8,7 @@
 #include "common.h"
 #include "lds_asm.h"
 #include "dropout.h"
+#include "focal_element.h"
 #include "heads_mean.h"
 #include "head_select.h"
 
@@ -610,6 +611,247 @@ __global__ __launch_bounds__(kThreads, 4) void head_bwd_pow2_kernel(const float*
         float sum = 0.f;
 #pragma unroll 4
         for (int pl = 32 * half; pl < 32 * half + 32; ++pl) sum += dl[pl * kHeadMaxCls + k] * xs[pl * XS + c];
+        wacc[q] += sum;
+      }
+    }
+    if (tid < n_cls) {
+      float sum = 0.f;
+      for (int pl = 0; pl < 64; ++pl) sum += dl[pl * kHeadMaxCls + tid];
+      bacc += sum;
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < kMaxPairs; ++q) {
+    const int idx = pair0 + q * 128;
+    if (idx < NW) scratch[half * NW + idx] = wacc[q];
+  }
+  __syncthreads();
+  float* dst = partial + static_cast<long>(blockIdx.x) * (NW + n_cls);
+  for (int i = tid; i < NW; i += kThreads) dst[i] = scratch[i] + scratch[NW + i];
+  if (tid < n_cls) dst[NW + tid] = bacc;
+}
+
+// The class head_pixel_logit leaves with the lane of channel quad gq (its `cls`): a function of gq alone.
+template <int LOG2G, int P>
+__device__ __forceinline__ int head_lane_class(int gq) {
+  constexpr int G = 1 << LOG2G;
+  int c = 0;
+  static_for<LOG2G>([&](auto sc) {
+    constexpr int step = decltype(sc)::v, off = G >> (1 + step);
+    constexpr int live = (P >> step) > 1 ? (P >> step) : 1;
+    if constexpr (live > 1) c += (gq & off) != 0 ? (live >> 1) : 0;
+  });
+  return c;
+}
+
+// One head of a training step in ONE pass over x (unetpp_head_train): what head_fwd_stream_kernel, the gradient half of
+// focal_bce_heads_kernel (caller.hip) and head_bwd_pow2_kernel do in three, with the same bits in the map, dx and every
+// partial row.  Once the target is known everything the backward needs is in the forward's registers, so the map is
+// written and never read back, d_out is never written, and x is read once.  head_bwd_pow2_kernel's tile walk, grid,
+// partial rows and LDS plan; per 64-pixel tile
+//   1. a thread's 16-byte pieces of x (lane = (pixel, channel quad), as both kernels have it): keep flags as the forward
+//      takes them, x*keep*scale -> LDS for the weight gradient, the logits by head_pixel_logit (the forward's function,
+//      lanes and order); the lane that ends up with a class adds the bias, stores the sigmoid, reads the target element
+//      and forms d_out by focal_element (the mean over n_heads: scale = 1 / n_heads at the same place) and
+//      dlogit = d_out * out * (1 - out) -> LDS
+//   2. dx = keep*scale * (W^T dlogit) (+ 0, ReLU gate) from the pieces still in registers; the head is always the first
+//      contribution to its node, so dx is never accumulated (the `+ 0.f` is head_bwd_pow2's `+ old` without an old
+//      value: -0 becomes +0 there too)
+//   3. the dW / db sums of head_bwd_pow2_kernel, same loops, same order
+// A tile is a chain load -> logits -> loss -> barrier -> dx: with the target loaded after the sigmoid (a second memory
+// latency per tile) and nothing in flight during steps 2 and 3 the pass took 171 us per head at 32 x 256 x 256 x 32, more
+// than half again what its bytes cost.  The target is therefore loaded with x, and up to 32 channels the next tile's x
+// and target are loaded before this tile's barrier: 118 us, head_bwd_pow2_kernel's own time.
+// Where head_bwd_pow2_kernel's sums are written `s += a * b` the compiler contracts every one of them into an fma; this
+// kernel says fmaf, because around its other code the same source came out as packed products and separate additions.
+// No atomics: partial rows and unetpp_sum_partials' fixed-order finish.  PCLS <= G (the forward's reduce-scatter deals the
+// classes to the lanes of a pixel), so a tile is ITEMS = G / 4 whole rounds of the workgroup.
+template <int LOG2G, int DROP, int PCLS>
+__global__ __launch_bounds__(kThreads, 4) void head_train_pow2_kernel(const float* __restrict__ x,
+                                                                   const float* __restrict__ weight,
+                                                                   const float* __restrict__ bias,
+                                                                   const float* __restrict__ target, unsigned pixels,
+                                                                   unsigned HW, int n_cls, float keep_scale, uint32_t thr16,
+                                                                   uint64_t seed, const uint8_t* __restrict__ mask,
+                                                                   const uint64_t* __restrict__ seed_dev, float gamma,
+                                                                   float inv_rows, float inv_heads, float* __restrict__ out,
+                                                                   float* __restrict__ dx, int gate_x,
+                                                                   float* __restrict__ partial) {
+  if (seed_dev != nullptr) seed += *seed_dev;  // graph-captured steps: the varying part of the seed lives in device memory
+  extern __shared__ __attribute__((aligned(16))) float hsm[];
+  constexpr int G = 1 << LOG2G, C = 4 * G, XS = C + 1;
+  static_assert(G >= 4 && PCLS <= G, "a tile is whole rounds of the workgroup, and every class has a lane");
+  constexpr int ITEMS = 64 * G / kThreads;   // 16-byte pieces of a 64-pixel tile per thread
+  constexpr int PPR = kThreads >> LOG2G;     // pixels of one round
+  // Up to 32 channels (two pieces per thread) the pieces of x stay in registers from step 1 to step 2 and the next tile's
+  // are loaded a tile ahead; at 64 and 128 channels that does not fit 128 registers: step 1 loads two pieces at a time
+  // and step 2 reads x again (from the cache) where the ReLU gate needs it
+  constexpr bool kKeepX = ITEMS <= 2, kPrefetch = kKeepX;
+  constexpr int kUnroll1 = kKeepX ? ITEMS : 2;
+  constexpr int kDup = (G > PCLS) ? G / PCLS : 1;  // lanes that end with the same class total
+  const int NW = n_cls * C;
+  float* xs = hsm;
+  float* dl = xs + 64 * XS;
+  float* scratch = dl + 64 * kHeadMaxCls;
+  const int tid = threadIdx.x;
+  const int gq = tid & (G - 1);  // channel quad of every piece of this thread
+  f32x4 wq[PCLS];
+#pragma unroll
+  for (int k = 0; k < PCLS; ++k)
+    wq[k] = (k < n_cls) ? *reinterpret_cast<const f32x4*>(weight + k * C + 4 * gq) : f32x4{0.f, 0.f, 0.f, 0.f};
+  constexpr int kMaxPairs = (PCLS * C + 127) / 128;  // (k, c) pairs per thread
+  float wacc[kMaxPairs];
+  const int pair0 = tid & 127, half = tid >> 7;
+#pragma unroll
+  for (int q = 0; q < kMaxPairs; ++q) wacc[q] = 0.f;
+  float bacc = 0.f;
+  const bool cube = gamma == 3.f, low = gamma < 1.f;
+  // the class this lane ends up with in head_pixel_logit depends on its channel quad alone: the lane that stores a class
+  // knows it, its bias and the target element before the logits exist, so the target is loaded WITH x, not after them
+  const int my_cls = head_lane_class<LOG2G, PCLS>(gq);
+  const bool owner = my_cls < n_cls && (gq & (kDup - 1)) == 0;
+  const float my_bias = owner ? bias[my_cls] : 0.f;
+  // one piece: x, the mask word, and for an owner the offset of its map element and the target there
+  auto fetch = [&](unsigned p, f32x4& X, uint32_t& M, unsigned& O, float& T) {
+    const bool valid = p < pixels;
+    const unsigned off = (p << (LOG2G + 2)) + 4 * gq;
+    X = valid ? *reinterpret_cast<const f32x4*>(x + off) : f32x4{0.f, 0.f, 0.f, 0.f};
+    M = 0xffffffffu;
+    if constexpr (DROP == 2) M = valid ? *reinterpret_cast<const uint32_t*>(mask + off) : 0xffffffffu;
+    O = 0u;
+    T = 0.f;
+    if (owner && valid) {
+      const unsigned n = p / HW, hw = p - n * HW;
+      O = (n * n_cls + my_cls) * HW + hw;  // < pixels * 8 <= 2^31 * 8 / C: 32 bits
+      T = target[O];
+    }
+  };
+  constexpr int NK = kKeepX ? ITEMS : 1;
+  f32x4 xv[NK], xn[kPrefetch ? NK : 1];     // the tile's pieces (kept for the ReLU gate of step 2) / the next tile's
+  uint32_t mv[NK], mn[kPrefetch ? NK : 1];
+  unsigned ov[NK], on[kPrefetch ? NK : 1];
+  float tv[NK], tn[kPrefetch ? NK : 1];
+  for (int i = tid; i < 64 * kHeadMaxCls; i += kThreads) dl[i] = 0.f;  // classes past n_cls are never written again
+  const unsigned n_tiles = (pixels + 63) / 64;
+  if constexpr (kPrefetch) {
+    if (blockIdx.x < n_tiles) {
+#pragma unroll
+      for (int u = 0; u < NK; ++u) fetch(blockIdx.x * 64 + (tid >> LOG2G) + u * PPR, xn[u], mn[u], on[u], tn[u]);
+    }
+  }
+  for (unsigned tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    const unsigned p0 = tile * 64;
+    if constexpr (kPrefetch) {  // this tile's loads were issued a tile ago; the next tile's go out now
+#pragma unroll
+      for (int u = 0; u < NK; ++u) xv[u] = xn[u], mv[u] = mn[u], ov[u] = on[u], tv[u] = tn[u];
+      const unsigned next = tile + gridDim.x;
+      if (next < n_tiles) {
+#pragma unroll
+        for (int u = 0; u < NK; ++u) fetch(next * 64 + (tid >> LOG2G) + u * PPR, xn[u], mn[u], on[u], tn[u]);
+      }
+    } else if constexpr (kKeepX) {
+#pragma unroll
+      for (int u = 0; u < NK; ++u) fetch(p0 + (tid >> LOG2G) + u * PPR, xv[u], mv[u], ov[u], tv[u]);
+    }
+    __syncthreads();
+    unsigned kept = 0u;  // keep flags of the pieces, bit 4 * u + q
+#pragma unroll kUnroll1
+    for (int u = 0; u < ITEMS; ++u) {
+      const int pl = (tid >> LOG2G) + u * PPR;
+      const unsigned p = p0 + pl;
+      const bool valid = p < pixels;  // (every lane stays: the logits are lane exchanges)
+      f32x4 xu;
+      uint32_t m4;
+      unsigned o;
+      float t;
+      if constexpr (kKeepX)
+        xu = xv[u], m4 = mv[u], o = ov[u], t = tv[u];
+      else
+        fetch(p, xu, m4, o, t);
+      unsigned kb = 0xfu;
+      if constexpr (DROP == 1) {
+        const uint64_t bits = keep_bits(seed, p, G, gq);
+        kb = 0u;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) kb |= keep_one(bits, q, thr16) ? (1u << q) : 0u;
+      } else if constexpr (DROP == 2) {
+        kb = 0u;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) kb |= ((m4 >> (8 * q)) & 0xffu) != 0 ? (1u << q) : 0u;
+      }
+      kept |= kb << (4 * u);
+      f32x4 v = xu;  // the forward's operand: a dropped element is 0, whatever x holds
+      float* xd = &xs[pl * XS + 4 * gq];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        if constexpr (DROP != 0) {
+          const bool keep = ((kb >> q) & 1u) != 0;
+          v[q] = keep ? xu[q] * keep_scale : 0.f;
+          xd[q] = xu[q] * (keep ? keep_scale : 0.f);  // the backward's x * keep * scale
+        } else {
+          xd[q] = xu[q] * 1.f;
+        }
+      }
+      int cls;  // class this lane ends up with: my_cls
+      const float logit = head_pixel_logit<LOG2G, PCLS>(v, wq, gq, cls);
+      if (owner) {
+        float dlv = 0.f;
+        if (valid) {
+          const float pr = 1.0f / (1.0f + __expf(-(logit + my_bias)));
+          out[o] = pr;
+          float g;
+          if (low)
+            focal_element<true>(pr, t, gamma, cube, inv_rows, inv_heads, g);
+          else
+            focal_element<false>(pr, t, gamma, cube, inv_rows, inv_heads, g);
+          {
+            // head_bwd_pow2 forms d_out * out * (1 - out) as a subtraction and two products; spelled out, so that no
+            // contraction into fma(-out, d_out * out, d_out * out) can make this kernel's rounding another one
+#pragma clang fp contract(off)
+            const float om = 1.f - pr;
+            dlv = (g * pr) * om;
+          }
+        }
+        dl[pl * kHeadMaxCls + cls] = dlv;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < ITEMS; ++u) {
+      const int pl = (tid >> LOG2G) + u * PPR;
+      const unsigned p = p0 + pl;
+      if (p < pixels) {
+        const unsigned off = (p << (LOG2G + 2)) + 4 * gq;
+        f32x4 xg = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (kKeepX)
+          xg = xv[u];
+        else if (gate_x)
+          xg = *reinterpret_cast<const f32x4*>(x + off);  // (64 and 128 channels: from the cache)
+        f32x4 sacc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int k = 0; k < PCLS; ++k) {
+          const float dk = dl[pl * kHeadMaxCls + k];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) sacc[q] = fmaf(wq[k][q], dk, sacc[q]);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const float ms = DROP == 0 ? 1.f : (((kept >> (4 * u + q)) & 1u) != 0 ? keep_scale : 0.f);
+          float v = fmaf(sacc[q], ms, 0.f);
+          if (gate_x) v = (xg[q] > 0.f) ? v : 0.f;
+          sacc[q] = v;
+        }
+        *reinterpret_cast<f32x4*>(dx + off) = sacc;
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < kMaxPairs; ++q) {
+      if (pair0 + q * 128 < NW) {
+        const int idx = pair0 + q * 128, k = idx >> (LOG2G + 2), c = idx & (C - 1);  // (decoded here: registers)
+        float sum = 0.f;
+#pragma unroll 4
+        for (int pl = 32 * half; pl < 32 * half + 32; ++pl) sum = fmaf(dl[pl * kHeadMaxCls + k], xs[pl * XS + c], sum);
         wacc[q] += sum;
       }
     }
@@ -1283,6 +1525,35 @@ extern "C" int unetpp_head_bwd(const float* d_out_nchw, const float* out_nchw, c
     hipLaunchKernelGGL(head_bwd_kernel, dim3(s.grid), dim3(s.block), 0, ST(stream), d_out_nchw, out_nchw, x, weight, pixels,
                        H * W, C, n_cls, keep_scale, keep_threshold(p_drop), seed, mask, seed_dev, s.drop != 0, dx,
                        accumulate, gate_x, partial);
+  return launch_status();
+}
+
+/* ---- one head of a training step in one pass: forward, gradient of the mean focal loss over n_heads, backward ---- */
+extern "C" int unetpp_head_train(const float* x, const float* weight, const float* bias, const float* target_nchw, int32_t N,
+                                 int32_t H, int32_t W, int32_t C, int32_t n_cls, float p_drop, uint64_t seed,
+                                 const uint8_t* mask, const uint64_t* seed_dev, int64_t rows, float gamma, int32_t n_heads,
+                                 float* out_nchw, float* dx, int32_t gate_x, float* partial, void* stream) {
+  if (!x || !weight || !bias || !target_nchw || !out_nchw || !dx || !partial || rows < 1) return UNETPP_EINVAL;
+  HeadQuery q = head_query(HEAD_TRAIN, false, N, H, W, C, n_cls, p_drop, x, weight, dx, mask);
+  q.n_heads = n_heads;
+  HeadSel s;
+  const int rc = head_select(q, 0, s);
+  if (rc != UNETPP_OK) return rc;
+  const long pixels = static_cast<long>(N) * H * W;
+  const float keep_scale = 1.0f / (1.0f - p_drop);
+  bool launched = false;
+  with_head_instance(s, [&](auto l, auto d, auto pc) {
+    constexpr int L = decltype(l)::value, D = decltype(d)::value, PC = decltype(pc)::value;
+    if constexpr (L >= 2 && PC != 6 && PC <= (1 << L)) {
+      hipLaunchKernelGGL((head_train_pow2_kernel<L, D, PC>), dim3(s.grid), dim3(s.block), s.lds, ST(stream), x, weight, bias,
+                         target_nchw, static_cast<unsigned>(pixels), static_cast<unsigned>(H * W), n_cls, keep_scale,
+                         keep_threshold(p_drop), seed, mask, seed_dev, gamma, 1.f / static_cast<float>(rows),
+                         1.0f / static_cast<float>(n_heads), out_nchw, dx, gate_x, partial);
+      launched = true;
+    }
+  });
+  if (!launched) return UNETPP_EINVAL;  // (head_select accepts nothing without an instance)
+  note_kernel(s.label);
   return launch_status();
 }
 

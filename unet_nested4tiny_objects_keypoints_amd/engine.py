@@ -134,6 +134,30 @@ class _Saved:
     pass
 
 
+_HEAD_TRAIN = [None]  # set for the duration of one forward by HeadTrainContext
+
+
+class HeadTrainContext:
+    """with HeadTrainContext(target, gamma, size_average) as ctx: outputs = model(x)  -- step.train_step's way of telling
+    the forward that the loss is the mean over heads of FocalLoss_BCE_2d(gamma, size_average) against `target` (fp32 GPU
+    [N, n_classes, H, W], contiguous, no gradient): a training forward in fp32 storage that saves for backward then runs
+    ops.head_train per head and keeps dX_0j, dW and db with the saved state; ``ctx.used`` says that it did.  The
+    backward of such a forward ignores the output gradients it is given: the caller owes it the loss it announced."""
+
+    def __init__(self, target, gamma, size_average):
+        self.target, self.gamma, self.size_average = target, float(gamma), bool(size_average)
+        self.used = False
+
+    def __enter__(self):
+        self._before = _HEAD_TRAIN[0]
+        _HEAD_TRAIN[0] = self
+        return self
+
+    def __exit__(self, *exc):
+        _HEAD_TRAIN[0] = self._before
+        return False
+
+
 # nn.BatchNorm2d counts its training batches; the counters of a pass are bumped together by one multi-tensor add
 # at the end of the forward (eight separate one-element adds cost 5 us of device time each)
 _PENDING_COUNTERS: list = []
@@ -444,11 +468,31 @@ def _forward_impl(model, x, training: bool, save: bool, head: Optional[int] = No
                            [f.weight.detach().view(model.n_classes, -1) for f in finals],
                            [f.bias.detach() for f in finals], o)
         outs.append(o)
-    for j in (range(1, d) if head is None else () if ensemble else range(1, head + 1) if all_heads else (head,)):  # heads (:283-286)
+    cols = list(range(1, d) if head is None else () if ensemble else range(1, head + 1) if all_heads else (head,))
+    # train_step with FocalLoss_BCE_2d (HeadTrainContext): the target is known now, so every head's forward, its gradient
+    # of the mean loss over `cols` and its backward are ONE launch each; backward finds dX_0j, dW and db here
+    ctx = _HEAD_TRAIN[0]
+    head_train = None
+    if (ctx is not None and save and training and cols and adt == torch.float32
+            and ctx.target.device == x.device and tuple(ctx.target.shape) == (b, model.n_classes, h0, w0)):
+        head_train = {}
+    for j in cols:  # heads (:283-286)
         final = getattr(model, "final_%d" % j)
         o = torch.empty((b, model.n_classes, h0, w0), dtype=torch.float32, device=x.device)
-        ops.head_fwd(X[(0, j)], final.weight.detach().view(model.n_classes, -1), final.bias.detach(), p_drop,
-                     seeds[j - 1], None if masks is None else masks[j - 1], o, seed_dev=seed_dev)
+        wt, mask = final.weight.detach().view(model.n_classes, -1), None if masks is None else masks[j - 1]
+        got = None
+        if head_train is not None:
+            dx = torch.empty_like(X[(0, j)])
+            rows = ctx.target.numel() if ctx.size_average else b * model.n_classes
+            # the head is the node's first gradient contribution; its only one (the ReLU mask is due) at the last column
+            got = ops.head_train(X[(0, j)], wt, final.bias.detach(), ctx.target, rows, ctx.gamma, len(cols), p_drop,
+                                 seeds[j - 1], mask, o, dx, gate_x=(j == top), seed_dev=seed_dev)
+            if got is None:   # refused (shape or alignment): every head takes the three-launch path
+                head_train = None
+            else:
+                head_train[j] = (dx,) + got
+        if got is None:
+            ops.head_fwd(X[(0, j)], wt, final.bias.detach(), p_drop, seeds[j - 1], mask, o, seed_dev=seed_dev)
         outs.append(o)
     if not save:
         return outs, None
@@ -457,6 +501,9 @@ def _forward_impl(model, x, training: bool, save: bool, head: Optional[int] = No
     s.p_drop, s.seeds, s.masks, s.seed_dev = p_drop, seeds, masks, seed_dev
     s.shape = (b, h0, w0)
     s.top, s.ensemble = top, bool(head is not None and ensemble)
+    s.head_train = head_train
+    if head_train is not None:
+        ctx.used = True
     return outs, s
 
 
@@ -495,6 +542,16 @@ class _GradBook:
         t = torch.empty_like(self.X[key])
         self.buf[key] = t
         return t, False, gate
+
+    def preset(self, key, tensor, gated):
+        """d X[key] arrives with its first contribution already in `tensor` (the forward's ops.head_train), `gated` when
+        that launch applied the node's ReLU mask: what target(key, can_gate=True) and the launch would have left."""
+        assert key not in self.buf and self.got.get(key, 0) == 0, "a preset gradient is the node's first contribution"
+        assert gated == (key in self.gate_keys and self.expected[key] == 1), "ReLU mask of node %s" % (key,)
+        self.got[key] = 1
+        self.buf[key] = tensor
+        if gated:
+            self.gated.add(key)
 
     def take(self, key):
         assert self.got.get(key, 0) == self.expected[key], "gradient fan-in mismatch at node %s" % (key,)
@@ -682,6 +739,7 @@ def _backward_impl(model, s: _Saved, d_outs, want_input_grad: bool, grad_sink=No
     bf16 = s.X[(0, 0)].dtype == torch.bfloat16
     dy1s: Dict[Tuple[int, int], V] = {}   # grouped input gradients: dY of conv1 of the decoder nodes done so far
     seen = set()
+    head_train = getattr(s, "head_train", None)
 
     def flush():
         if grad_sink is not None and len(grads) > len(seen):
@@ -710,14 +768,18 @@ def _backward_impl(model, s: _Saved, d_outs, want_input_grad: bool, grad_sink=No
             grads[head.weight], grads[head.bias] = dw, db
     for j in (() if s.ensemble else range(top, 0, -1)):  # heads: the first contribution to d X[0][j]
         head = getattr(model, "final_%d" % j)
-        go = d_outs[j - 1]
-        if go is None:
-            go = torch.zeros_like(s.outs[j - 1])
-        go = go.contiguous()
-        dx, acc, gate = book.target((0, j), can_gate=True)
-        dw, db = ops.head_bwd(go, s.outs[j - 1], s.X[(0, j)], head.weight.detach().view(model.n_classes, -1), s.p_drop,
-                              s.seeds[j - 1], None if s.masks is None else s.masks[j - 1], dx, acc,
-                              gate_x=gate is not None, seed_dev=s.seed_dev)
+        if head_train is not None:   # the forward's ops.head_train made this head's gradients
+            dx, dw, db = head_train.pop(j)
+            book.preset((0, j), dx, gated=(j == top))
+        else:
+            go = d_outs[j - 1]
+            if go is None:
+                go = torch.zeros_like(s.outs[j - 1])
+            go = go.contiguous()
+            dx, acc, gate = book.target((0, j), can_gate=True)
+            dw, db = ops.head_bwd(go, s.outs[j - 1], s.X[(0, j)], head.weight.detach().view(model.n_classes, -1), s.p_drop,
+                                  s.seeds[j - 1], None if s.masks is None else s.masks[j - 1], dx, acc,
+                                  gate_x=gate is not None, seed_dev=s.seed_dev)
         if _ALLOC[0] is not None:
             gw, gb = _new_grad(head.weight), _new_grad(head.bias)
             gw.copy_(dw)

@@ -55,7 +55,7 @@ from typing import Optional
 
 import torch
 
-from .step import loss_and_backward
+from .step import forward_loss_backward
 
 _HIP_NODE_TYPES = {0: "kernel", 1: "memcpy", 2: "memset", 3: "host", 4: "graph", 5: "empty", 6: "wait_event",
                    7: "event_record", 8: "ext_sem_signal", 9: "ext_sem_wait", 10: "mem_alloc", 11: "mem_free",
@@ -238,8 +238,7 @@ class GraphedTrainStep:
     def _body(self, with_optimizer: bool):
         """train_step's sequence (step.py) on the static tensors"""
         self.optimizer.zero_grad(set_to_none=True)
-        outputs = self.model(self._x) if self.head is None else self.model.forward_pruned(self._x, self.head)
-        avgloss = loss_and_backward(self.criterion, outputs, self._t)
+        outputs, avgloss = forward_loss_backward(self.model, self.criterion, self._x, self._t, self.head)
         if with_optimizer:
             self.optimizer.step()
         return outputs, avgloss

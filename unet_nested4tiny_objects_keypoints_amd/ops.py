@@ -799,6 +799,39 @@ def head_bwd(d_out, out, x, weight, p_drop, seed, mask, dx, accumulate, gate_x=F
     return sums[:n_cls * c].view(n_cls, c, 1, 1), sums[n_cls * c:]
 
 
+def head_train(x, weight, bias, target, rows, gamma, n_heads, p_drop, seed, mask, out_nchw, dx, gate_x=False,
+               seed_dev=None, partial=None):
+    """One head of a training step in ONE launch: head_fwd, this head's gradient of focal_bce_heads (the mean over
+    `n_heads` against `target`) and head_bwd (accumulate = 0), bit for bit.  out_nchw and dx are written.
+    -> (dW [n_cls, C, 1, 1], db [n_cls]), or None when the library refuses the call (anything but the fp32 power-of-two
+    channel-quad form): nothing was launched and the caller runs the three launches.
+    partial: the caller's unetpp_head_bwd_blocks(N*H*W) * (n_cls*C + n_cls) floats (tests read the rows)."""
+    lib = _lib.lib()
+    n, h, w, c = x.shape
+    n_cls = weight.shape[0]
+    if _is_bf16(x):
+        return None
+    _need(x, "head features"), _need(dx, "feature gradient"), _need(target, "target"), _need(out_nchw, "output")
+    if tuple(dx.shape) != (n, h, w, c) or tuple(target.shape) != (n, n_cls, h, w) or tuple(out_nchw.shape) != (n, n_cls, h, w):
+        raise ValueError("dx must be [N, H, W, C], target and output [N, n_cls, H, W]")
+    blocks = int(lib.unetpp_head_bwd_blocks(n * h * w))
+    ln = n_cls * c + n_cls
+    if partial is None:
+        partial = torch.empty(blocks * ln, dtype=torch.float32, device=x.device)
+    elif _need(partial, "partial rows").numel() != blocks * ln:
+        raise ValueError("partial must hold %d rows of %d floats" % (blocks, ln))
+    st = _stream()
+    status = lib.unetpp_head_train(_ptr(x), _ptr(weight), _ptr(bias), _ptr(target), n, h, w, c, n_cls, float(p_drop),
+                                   C.c_uint64(seed), _ptr(mask), _ptr(seed_dev), int(rows), float(gamma), int(n_heads),
+                                   _ptr(out_nchw), _ptr(dx), int(bool(gate_x)), _ptr(partial), st)
+    if status == -1:   # UNETPP_EINVAL: a refusal, before anything ran
+        return None
+    check(status, "unetpp_head_train")
+    sums = torch.empty(ln, dtype=torch.float32, device=x.device)
+    check(lib.unetpp_sum_partials(_ptr(partial), blocks, ln, _ptr(sums), st), "unetpp_sum_partials")
+    return sums[:n_cls * c].view(n_cls, c, 1, 1), sums[n_cls * c:]
+
+
 def bilinear2x_fwd(x, y):
     n, h, w, c = x.shape
     if _is_bf16(x):
