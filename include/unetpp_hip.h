@@ -378,6 +378,27 @@ int unetpp_head_train(const float* x, const float* weight, const float* bias, co
                       int32_t H, int32_t W, int32_t C, int32_t n_cls, float p_drop, uint64_t seed, const uint8_t* mask,
                       const uint64_t* seed_dev, int64_t rows, float gamma, int32_t n_heads, float* out_nchw, float* dx,
                       int32_t gate_x, float* partial, void* stream);
+/* ---- Monte-Carlo dropout at one head (added within v13: a new entry point only, nothing existing changes) ----
+ * `samples` = K draws of the head's dropout over ONE read of x; two maps leave, fp32 NCHW [N, n_cls, H, W]:
+ *   seed_k = seed + 0xD6E8FEB86659FD93 * k (mod 2^64), k = 0 .. K-1; *seed_dev (may be NULL) is added to each, as in
+ *            unetpp_head_fwd.
+ *   s_k    = at every pixel and class, bit for bit what unetpp_head_fwd with p_drop, seed_k, mask = NULL and seed_dev
+ *            writes through its streaming kernel: the same keep flags and keep scale, the same order of the dot
+ *            product and of its sum over the lanes of a pixel, the same sigmoid expression.
+ *   mean   = (((s_0 + s_1) + ...) + s_{K-1}) / (float)K                        a true division
+ *   var    = (((d_0*d_0 + d_1*d_1) + ...) + d_{K-1}*d_{K-1}) / (float)(K-1),   d_k = s_k - mean
+ *            every difference, product, sum and quotient rounded on its own: no fused multiply-add in the fold.
+ * No square root here (the caller derives a standard deviation), no atomics: the result does not depend on the grid.
+ * x is read once, 16 bytes per lane and pixel; the K samples never reach memory.
+ * Accepts exactly the fp32 calls that unetpp_head_fwd takes with its streaming kernel under hashed dropout (C = 4 * 2^k,
+ * 16 <= C <= 128, n_cls padded to 4 or 8 at most C / 4, 16-byte aligned x and weight, fewer than 2^31 - 1 elements of
+ * x) with 0 < p_drop < 1 and 2 <= samples <= UNETPP_MC_MAX_SAMPLES; anything else, a NULL x / weight / bias / mean_nchw /
+ * var_nchw included, returns UNETPP_EINVAL without touching the device (the caller then composes K unetpp_head_fwd
+ * launches). */
+#define UNETPP_MC_MAX_SAMPLES 32
+int unetpp_head_mc(const float* x, const float* weight, const float* bias, int32_t N, int32_t H, int32_t W, int32_t C,
+                   int32_t n_cls, float p_drop, uint64_t seed, const uint64_t* seed_dev, int32_t samples,
+                   float* mean_nchw, float* var_nchw, void* stream);
 /* out[i] = sum_b partial[b][i], i < len (used for head dW/db) */
 int unetpp_sum_partials(const float* partial, int64_t n_blocks, int64_t len, float* out, void* stream);
 

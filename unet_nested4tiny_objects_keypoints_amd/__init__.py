@@ -13,7 +13,7 @@ library, or with CPU tensors, raises.
 from .unet import UNet, UNet_Nested, count_param  # noqa: F401
 from .losses import FocalLoss_BCE_2d, PenaltyReducedFocalLoss, TopKFocalLoss_BCE_2d  # noqa: F401
 from .step import train_step  # noqa: F401
-from .engine import pruned_parameters  # noqa: F401
+from .engine import McMaps, pruned_parameters  # noqa: F401
 from .targets import create_heatmap  # noqa: F401
 from .keypoints import Heatmap  # noqa: F401
 from .serving import GraphedForward  # noqa: F401
@@ -32,4 +32,4 @@ __all__ = ["UNet_Nested", "UNet", "count_param", "FocalLoss_BCE_2d", "train_step
            "validate_outputs", "WeightAverager", "clip_grad_norm_", "DeviceLoader", "Augment", "affine_params",
            "warp_batch", "SceneInference", "CascadeSceneInference", "PeakDetector", "Detections", "DetectionScore",
            "evaluate", "classes_from_pattern", "SceneCrops", "false_positive_centres", "TopKFocalLoss_BCE_2d",
-           "pruned_parameters", "PenaltyReducedFocalLoss", "IgnoreRegions"]
+           "pruned_parameters", "PenaltyReducedFocalLoss", "IgnoreRegions", "McMaps"]

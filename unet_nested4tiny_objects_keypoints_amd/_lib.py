@@ -18,7 +18,7 @@ INCLUDE = os.path.join(_REPO, "include")
 SOURCES = ("gemm_pix.hip", "gemm_fast.hip", "gemm_pw.hip", "gemm_pw_bf16.hip", "gemm_wino.hip", "gemm_bf16.hip", "gemm_bf16_dma.hip", "wgrad_bf16.hip", "pointwise_bf16.hip", "keypoints.hip", "weight_image.hip", "wgrad.hip", "wgrad_fast.hip", "wgrad_dma.hip", "wgrad_pw.hip", "wgrad_wino.hip", "first_layer.hip", "pointwise.hip", "heads.hip", "caller.hip", "optim.hip", "validate.hip", "average.hip", "loader.hip", "scene.hip",
            "detect.hip", "crops.hip", "topk_loss.hip", "pr_focal.hip")
 HEADERS = ("common.h", "gemm_units.h", "wgrad_reduce.h", "lds_asm.h", "bf16_common.h", "dropout.h", "bn_fused.h",
-           "wino_experiments.h", "dma_experiments.h", "heads_mean.h", "head_select.h", "focal_element.h", "multi_tensor.h")
+           "wino_experiments.h", "dma_experiments.h", "heads_mean.h", "head_select.h", "head_mc_select.h", "focal_element.h", "multi_tensor.h")
 MAX_VIEWS = 8
 ABI_VERSION = 13
 # packed-f32 VALU (SLP-vectorised add pairs) costs issue slots beside MFMAs: keep the Winograd transforms scalar
@@ -200,6 +200,8 @@ SCENE_MAX_VARIANTS = 8                             # variants of a tile unetpp_s
 SCENE_FLIP_X, SCENE_FLIP_Y, SCENE_TRANSPOSE = 1, 2, 4   # bits of a variant code
 PEAKS_MAX_RADIUS, PEAKS_MAX_MAPS = 8, 65535         # unetpp_peaks_detect: window radius 1..8, maps per call
 MATCH_MAX = 64                                     # UNETPP_MATCH_MAX: labels / predictions per map of the matcher
+MC_MAX_SAMPLES = 32                                # UNETPP_MC_MAX_SAMPLES: dropout draws of one unetpp_head_mc call
+MC_SEED_STEP = 0xD6E8FEB86659FD93                  # sample k of unetpp_head_mc draws from seed + MC_SEED_STEP * k
 
 _P, _I32, _I64, _F, _U64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_uint64
 
@@ -240,6 +242,8 @@ SIGNATURES = {
     "unetpp_head_bwd": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _F, _U64, _P, _P, _P, _I32, _I32, _P, _P]),
     "unetpp_head_train": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _F, _U64, _P, _P, _I64, _F, _I32, _P, _P,
                                     _I32, _P, _P]),
+    # Monte-Carlo dropout at one head: mean and variance maps in one pass (heads.hip; added within ABI 13)
+    "unetpp_head_mc": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _F, _U64, _P, _I32, _P, _P, _P]),
     "unetpp_sum_partials": (C.c_int, [_P, _I64, _I64, _P, _P]),
     "unetpp_focal_bce_blocks": (_I64, [_I64]),
     "unetpp_focal_bce": (C.c_int, [_P, _P, _I64, _I64, _F, _P, _P, _P, _P]),

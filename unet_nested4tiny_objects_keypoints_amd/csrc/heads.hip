@@ -1,7 +1,8 @@
 // The deep-supervision heads, fp32 and bf16 storage side by side: dropout + 1x1 convolution + sigmoid forward
 // (unetpp_head_fwd[_bf16]), the ensemble mean of several heads (unetpp_heads_mean_fwd[_bf16], no dropout), its backward
 // (unetpp_heads_mean_bwd[_bf16]: the head maps are recomputed, never read) and the backward of one head
-// (unetpp_head_bwd[_bf16]: feature gradient, per-workgroup partial rows of dW and db).  Features are NHWC,
+// (unetpp_head_bwd[_bf16]: feature gradient, per-workgroup partial rows of dW and db); fp32 only: one head of a training
+// step in one pass (unetpp_head_train) and Monte-Carlo dropout at one head (unetpp_head_mc).  Features are NHWC,
 // probabilities fp32 NCHW (the loss stays fp32).  head_select (head_select.h) decides which kernel takes a call; the
 // launchers at the end check pointers, ask it and launch.
 #include "bf16_common.h"
@@ -11,6 +12,7 @@
 #include "focal_element.h"
 #include "heads_mean.h"
 #include "head_select.h"
+#include "head_mc_select.h"
 
 #include <type_traits>
 
@@ -643,6 +645,104 @@ __device__ __forceinline__ int head_lane_class(int gq) {
     if constexpr (live > 1) c += (gq & off) != 0 ? (live >> 1) : 0;
   });
   return c;
+}
+
+// acc + d * d in two roundings: the product on its own, then the sum.  Left to the compiler `acc += d * d` becomes one
+// fma (as every such sum of head_bwd_pow2_kernel does), which is not the fold unetpp_head_mc promises.
+__device__ __forceinline__ float mc_add_square(float acc, float d) {
+#pragma clang fp contract(off)
+  const float sq = d * d;
+  return acc + sq;
+}
+
+// Monte-Carlo dropout at one head (unetpp_head_mc): head_fwd_stream_kernel<LOG2G, P, 1>'s layout, loop, loads and carried
+// (image, position), with the samples as an inner loop over ONE read of x -- sample k redraws the keep flags from
+// seed + kMcSeedStep * k and goes through the forward's own expressions (keep_bits / keep_one / keep_scale,
+// head_pixel_logit, the __expf sigmoid), so s_k has the bits head_fwd_stream_kernel stores for that seed.  Two maps leave:
+//   mean = (((s_0 + s_1) + ...) + s_{K-1}) / float(K)
+//   var  = (((d_0 d_0 + d_1 d_1) + ...) + d_{K-1} d_{K-1}) / float(K - 1),   d_k = s_k - mean
+// every product, sum and quotient rounded on its own (mc_add_square; nothing here is an fmaf but the dot product inside
+// head_pixel_logit, which is spelled fmaf there).  The deviations need the mean, so the K samples of a pixel wait in LDS:
+// a thread owns the column slab[k * kThreads + threadIdx.x], k < K (K * 1 KiB per workgroup, no bank conflict, no barrier:
+// nobody else reads it), written in the sample loop and read back once.  Four pixels are loaded ahead as in the forward;
+// their samples are drawn one pixel after the other, so one column serves all four.  No atomics; the result does not
+// depend on the grid.
+template <int LOG2G, int P>
+__global__ __launch_bounds__(kThreads) void head_mc_kernel(const float* __restrict__ x, const float* __restrict__ weight,
+                                                           const float* __restrict__ bias, unsigned pixels, unsigned HW,
+                                                           int n_cls, float keep_scale, uint32_t thr16, uint64_t seed,
+                                                           const uint64_t* __restrict__ seed_dev, int samples,
+                                                           float* __restrict__ mean_out, float* __restrict__ var_out) {
+  if (seed_dev != nullptr) seed += *seed_dev;
+  extern __shared__ __attribute__((aligned(16))) float slab[];  // [samples][kThreads]
+  constexpr int G = 1 << LOG2G;  // lanes (channel quads) per pixel
+  const int gq = threadIdx.x & (G - 1);
+  f32x4 wq[P];
+#pragma unroll
+  for (int k = 0; k < P; ++k)
+    wq[k] = (k < n_cls) ? *reinterpret_cast<const f32x4*>(weight + k * 4 * G + 4 * gq) : f32x4{0.f, 0.f, 0.f, 0.f};
+  constexpr unsigned ppb = kThreads >> LOG2G;
+  constexpr int U = 4;
+  constexpr int kDup = (G > P) ? G / P : 1;  // lanes that end with the same class total
+  const unsigned span = gridDim.x * ppb, outer = U * span;
+  const unsigned pl = threadIdx.x >> LOG2G;
+  const unsigned span_n = span / HW, span_hw = span - span_n * HW;
+  const int cls = head_lane_class<LOG2G, P>(gq);  // the class head_pixel_logit leaves with this lane
+  const bool writer = cls < n_cls && (gq & (kDup - 1)) == 0;
+  const float b = cls < n_cls ? bias[cls] : 0.f;
+  const float count = static_cast<float>(samples), count1 = static_cast<float>(samples - 1);
+  float* mine = slab + threadIdx.x;
+  unsigned p0 = blockIdx.x * ppb + pl;
+  unsigned n0 = p0 / HW, hw0 = p0 - n0 * HW;
+  for (; p0 - pl < pixels; p0 += outer) {  // wave-uniform trip count
+    f32x4 v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const unsigned p = p0 + u * span;
+      v[u] = (p < pixels) ? *reinterpret_cast<const f32x4*>(x + ((p << (LOG2G + 2)) + 4 * gq)) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const unsigned p = p0 + u * span;
+      float sum = 0.f;  // 0 + s_0 is s_0 (a sigmoid is never -0)
+      uint64_t seed_k = seed;
+      for (int k = 0; k < samples; ++k, seed_k += kMcSeedStep) {  // every lane of the wave: the logits are exchanged
+        const uint64_t bits = keep_bits(seed_k, p, G, gq);
+        f32x4 d;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) d[q] = keep_one(bits, q, thr16) ? v[u][q] * keep_scale : 0.f;
+        int c;
+        const float logit = head_pixel_logit<LOG2G, P>(d, wq, gq, c);
+        const float s = 1.0f / (1.0f + __expf(-(logit + b)));
+        mine[k * kThreads] = s;
+        sum += s;
+      }
+      const float mean = sum / count;
+      float sq = 0.f;  // 0 + d_0 d_0 is d_0 d_0 (a square is never -0)
+      for (int k = 0; k < samples; ++k) sq = mc_add_square(sq, mine[k * kThreads] - mean);
+      const float var = sq / count1;
+      unsigned n = n0 + u * span_n, hw = hw0 + u * span_hw;
+#pragma unroll
+      for (int c = 0; c < U - 1; ++c) {  // at most u carries
+        const bool carry = c < u && hw >= HW;
+        hw -= carry ? HW : 0u;
+        n += carry ? 1u : 0u;
+      }
+      if (p < pixels && writer) {
+        const long o = (static_cast<long>(n) * n_cls + cls) * HW + hw;
+        mean_out[o] = mean;
+        var_out[o] = var;
+      }
+    }
+    n0 += U * span_n;
+    hw0 += U * span_hw;
+#pragma unroll
+    for (int c = 0; c < U; ++c) {
+      const bool carry = hw0 >= HW;
+      hw0 -= carry ? HW : 0u;
+      n0 += carry ? 1u : 0u;
+    }
+  }
 }
 
 // One head of a training step in ONE pass over x (unetpp_head_train): what head_fwd_stream_kernel, the gradient half of
@@ -1553,6 +1653,33 @@ extern "C" int unetpp_head_train(const float* x, const float* weight, const floa
     }
   });
   if (!launched) return UNETPP_EINVAL;  // (head_select accepts nothing without an instance)
+  note_kernel(s.label);
+  return launch_status();
+}
+
+/* ---- Monte-Carlo dropout at one head: mean and variance of `samples` dropout draws in one pass over x ---- */
+extern "C" int unetpp_head_mc(const float* x, const float* weight, const float* bias, int32_t N, int32_t H, int32_t W,
+                              int32_t C, int32_t n_cls, float p_drop, uint64_t seed, const uint64_t* seed_dev,
+                              int32_t samples, float* mean_nchw, float* var_nchw, void* stream) {
+  if (!x || !weight || !bias || !mean_nchw || !var_nchw) return UNETPP_EINVAL;
+  HeadSel s;
+  const int rc = head_mc_select(N, H, W, C, n_cls, p_drop, samples, low4(x), low4(weight), s);
+  if (rc != UNETPP_OK) return rc;
+  const long pixels = static_cast<long>(N) * H * W;
+  const float keep_scale = 1.0f / (1.0f - p_drop);
+  bool launched = false;
+  with_const<2, 3, 4, 5>(s.log2g, [&](auto l) {
+    with_const<4, 8>(s.pcls, [&](auto pc) {
+      constexpr int L = decltype(l)::value, PC = decltype(pc)::value;
+      if constexpr (PC <= (1 << L)) {
+        hipLaunchKernelGGL((head_mc_kernel<L, PC>), dim3(s.grid), dim3(s.block), s.lds, ST(stream), x, weight, bias,
+                           static_cast<unsigned>(pixels), static_cast<unsigned>(H * W), n_cls, keep_scale,
+                           keep_threshold(p_drop), seed, seed_dev, samples, mean_nchw, var_nchw);
+        launched = true;
+      }
+    });
+  });
+  if (!launched) return UNETPP_EINVAL;  // (head_mc_select accepts nothing without an instance)
   note_kernel(s.label);
   return launch_status();
 }

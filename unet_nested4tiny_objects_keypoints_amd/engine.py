@@ -14,11 +14,11 @@ from __future__ import annotations
 
 import os
 
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 
-from . import ops
+from . import _lib, ops
 from .ops import V
 
 
@@ -384,45 +384,84 @@ def stats_pass(model, x) -> None:
 
 
 def forward_impl(model, x, training: bool, save: bool, head: Optional[int] = None, ensemble: bool = False,
-                 all_heads: bool = False):
+                 all_heads: bool = False, mc=None):
     """Runs the forward DAG of models/unet.py:255-300.  Returns (outputs, saved-for-backward or None).
     head = None: the whole graph and every head (``forward``).  head = J: only needed_nodes(depth, J), and one output --
     head J, or the mean of heads 1 .. J when `ensemble` (``infer``) -- or, with `all_heads` and no `ensemble`, the heads
-    1 .. J (``forward_pruned``: the reference's output tuple, shortened)."""
+    1 .. J (``forward_pruned``: the reference's output tuple, shortened).  mc = (samples, p, seed) with head = J
+    (``infer_mc``): the two outputs are the Monte-Carlo dropout mean and variance of head J (ops.head_mc)."""
     _check_input(model, x)
     _PENDING_COUNTERS.clear()
     try:
         if not USE_PACK_PLAN:
-            return _forward_impl(model, x, training, save, head, ensemble, all_heads)
+            return _forward_impl(model, x, training, save, head, ensemble, all_heads, mc)
         plan = _plan_of(model)
         plan.begin(plan_phase(model.depth, head))  # every weight image of the pass in one launch (after the first pass recorded the jobs)
         ops.set_pack_plan(plan)
         try:
-            return _forward_impl(model, x, training, save, head, ensemble, all_heads)
+            return _forward_impl(model, x, training, save, head, ensemble, all_heads, mc)
         finally:
             ops.set_pack_plan(None)
     finally:
         flush_batch_counters()
 
 
-def infer(model, x, head=None, ensemble: bool = False):
-    """The body of UNet_Nested.infer."""
-    top = check_head(model.depth, head)
+def _check_infer(model, top: int, what: str = "infer") -> None:
+    """The mode checks of the eval forward cut at head `top` (infer, infer_mc)."""
     if model.training:
-        raise RuntimeError("UNet_Nested.infer is the eval forward: call model.eval() first")
+        raise RuntimeError("UNet_Nested.%s is the eval forward: call model.eval() first" % what)
     pruned_to = getattr(model, "pruned_to", None)
     if pruned_to is not None and top > pruned_to:
         raise RuntimeError("this model holds a checkpoint pruned to head %d: the nodes head %d needs were never loaded"
                            % (pruned_to, top))
-    if model.is_batchnorm:   # infer() is the eval forward of every layer: a layer left in training mode is an error, not ignored
+    if model.is_batchnorm:   # the eval forward of every layer: a layer left in training mode is an error, not ignored
         for i in range(top + 1):
             for stage in ("conv1", "conv2"):
                 if getattr(getattr(getattr(model, "conv%d0" % i), stage), "1").training:
-                    raise RuntimeError("UNet_Nested.infer is the eval forward, but BatchNorm layer conv%d0.%s.1 is in training "
-                                       "mode: call model.eval() (or .eval() on that layer) first" % (i, stage))
+                    raise RuntimeError("UNet_Nested.%s is the eval forward, but BatchNorm layer conv%d0.%s.1 is in training "
+                                       "mode: call model.eval() (or .eval() on that layer) first" % (what, i, stage))
+
+
+def infer(model, x, head=None, ensemble: bool = False):
+    """The body of UNet_Nested.infer."""
+    top = check_head(model.depth, head)
+    _check_infer(model, top)
     with torch.no_grad():
         outs, _ = forward_impl(model, x, False, save=False, head=top, ensemble=bool(ensemble))
     return outs[0]
+
+
+class McMaps(NamedTuple):
+    """Monte-Carlo dropout maps (``UNet_Nested.infer_mc``, ``SceneInference.uncertainty``): the per-pixel mean of the
+    sampled head maps and their unbiased variance, both fp32 ``[B, n_classes, H, W]``."""
+    mean: torch.Tensor
+    var: torch.Tensor
+
+    @property
+    def std(self) -> torch.Tensor:
+        return self.var.sqrt()
+
+
+HEAD_SEED_STEP = 0x632BE59BD9B4E019   # head j of a pass draws from base + HEAD_SEED_STEP * j (_dropout_config)
+
+
+def infer_mc(model, x, head=None, samples: int = 16, p=None, seed=None) -> McMaps:
+    """The body of UNet_Nested.infer_mc: infer's checks and pass, the one head launch replaced by ops.head_mc."""
+    top = check_head(model.depth, head)
+    _check_infer(model, top, "infer_mc")
+    if isinstance(samples, bool) or not isinstance(samples, int) or not 2 <= samples <= _lib.MC_MAX_SAMPLES:
+        raise ValueError("samples must be an int in 2..%d, got %r" % (_lib.MC_MAX_SAMPLES, samples))
+    p = float(model.drop_out.p if p is None else p)
+    if not 0.0 < p < 1.0:
+        raise ValueError("p must lie in (0, 1): without dropout every sample is the same map, got %r" % p)
+    if seed is None:   # as _dropout_config draws a step's base seed: torch.manual_seed reproduces it
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    if isinstance(seed, bool) or not isinstance(seed, int):
+        raise ValueError("seed must be an int (or None to draw one), got %r" % (seed,))
+    mc = (samples, p, (seed + HEAD_SEED_STEP * top) & 0xFFFFFFFFFFFFFFFF)
+    with torch.no_grad():
+        outs, _ = forward_impl(model, x, False, save=False, head=top, mc=mc)
+    return McMaps(outs[0], outs[1])
 
 
 def _plan_of(model) -> "ops.PackPlan":
@@ -434,7 +473,7 @@ def _plan_of(model) -> "ops.PackPlan":
 
 
 def _forward_impl(model, x, training: bool, save: bool, head: Optional[int] = None, ensemble: bool = False,
-                  all_heads: bool = False):
+                  all_heads: bool = False, mc=None):
     b, _, h0, w0 = x.shape
     d = model.depth
     top = d - 1 if head is None else head   # the last diagonal that runs; its encoder node is the deepest and is not pooled
@@ -459,6 +498,14 @@ def _forward_impl(model, x, training: bool, save: bool, head: Optional[int] = No
             ins = [V(u.up)] + [V(X[(i, jj)]) for jj in range(j)]  # up first, then X_i0.. (:198-202)
             r = _pair_fwd(mod.conv, ins, b, hi, wi, training, pool=False, adt=adt, stats=save)
             ups[(i, j)], pairs[(i, j)], X[(i, j)] = u, r, r.out
+    if mc is not None:  # Monte-Carlo dropout at head `head` alone: K draws over one read of X_0J (never with save)
+        samples, p_mc, seed_mc = mc
+        final = getattr(model, "final_%d" % head)
+        mean = torch.empty((b, model.n_classes, h0, w0), dtype=torch.float32, device=x.device)
+        var = torch.empty_like(mean)
+        ops.head_mc(X[(0, head)], final.weight.detach().view(model.n_classes, -1), final.bias.detach(), p_mc, seed_mc,
+                    samples, mean, var)
+        return [mean, var], None
     p_drop, seeds, masks, seed_dev = _dropout_config(model, training)
     outs = []
     if head is not None and ensemble:  # the mean of heads 1 .. head in one launch; the head maps are never written

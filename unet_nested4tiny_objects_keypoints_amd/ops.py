@@ -716,6 +716,62 @@ def head_fwd(x, weight, bias, p_drop, seed, mask, out_nchw, seed_dev=None):
              _ptr(seed_dev), _ptr(out_nchw), _stream()), "unetpp_head_fwd")
 
 
+# A/B switch (measurements only): the composition of head_fwd launches and torch reductions instead of unetpp_head_mc
+_FUSED_HEAD_MC = os.environ.get("UNETPP_NO_FUSED_HEAD_MC") is None
+
+
+def mc_sample_seeds(seed: int, samples: int):
+    """The seeds of the `samples` dropout draws of head_mc: seed + MC_SEED_STEP * k (mod 2^64), k = 0 .. samples-1."""
+    return [(int(seed) + _lib.MC_SEED_STEP * k) & 0xFFFFFFFFFFFFFFFF for k in range(samples)]
+
+
+def head_mc(x, weight, bias, p_drop, seed, samples, mean_out, var_out, seed_dev=None):
+    """Monte-Carlo dropout at one head: mean_out and var_out (fp32 [N, n_cls, H, W]) over `samples` = K draws of the head's
+    dropout, sample k being head_fwd(x, weight, bias, p_drop, mc_sample_seeds(seed, K)[k], None, ..., seed_dev):
+        mean = (((s_0 + s_1) + ...) + s_{K-1}) / float(K)
+        var  = (((d_0 d_0 + d_1 d_1) + ...) + d_{K-1} d_{K-1}) / float(K - 1),   d_k = s_k - mean   (unbiased)
+    every operation rounded on its own, both quotients true divisions.  ONE launch that reads x once where the library
+    takes the call (unetpp_head_mc: fp32 features on the streaming forward's shapes); otherwise -- other channel counts,
+    bf16 features, UNETPP_NO_FUSED_HEAD_MC set -- K head_fwd launches and the same fold in torch elementwise ops, with the
+    same bits wherever head_fwd runs the same kernel.  ValueError for samples outside 2..32 or p_drop outside (0, 1)."""
+    if isinstance(samples, bool) or not isinstance(samples, int) or not 2 <= samples <= _lib.MC_MAX_SAMPLES:
+        raise ValueError("samples must be an int in 2..%d, got %r" % (_lib.MC_MAX_SAMPLES, samples))
+    p_drop = float(p_drop)
+    if not 0.0 < p_drop < 1.0:
+        raise ValueError("p_drop must lie in (0, 1): without dropout every sample is the same map, got %r" % p_drop)
+    if x.dtype not in _ACT_DTYPES:
+        raise TypeError("features must be float32 or bfloat16, got %s" % x.dtype)
+    _need(x, "head features", x.dtype)
+    n, h, w, c = x.shape
+    n_cls = weight.shape[0]
+    if tuple(_need(weight, "head weight").shape) != (n_cls, c) or _need(bias, "head bias").numel() != n_cls:
+        raise ValueError("head weight must be [n_cls, C] and bias [n_cls]")
+    for t, what in ((mean_out, "mean map"), (var_out, "variance map")):
+        if tuple(_need(t, what).shape) != (n, n_cls, h, w):
+            raise ValueError("mean and variance maps must be [N, n_cls, H, W]")
+    if _FUSED_HEAD_MC and not _is_bf16(x):
+        status = _lib.lib().unetpp_head_mc(_ptr(x), _ptr(weight), _ptr(bias), n, h, w, c, n_cls, p_drop, C.c_uint64(seed),
+                                           _ptr(seed_dev), samples, _ptr(mean_out), _ptr(var_out), _stream())
+        if status != -1:   # UNETPP_EINVAL: a refusal for the shape or an alignment, before anything ran
+            check(status, "unetpp_head_mc")
+            return
+    # the composition: K maps, then the fold in the kernel's order.  (On the GPU torch divides by a Python scalar through
+    # a multiplication with its reciprocal: the divisors are device tensors, so that both quotients are true divisions.)
+    maps = torch.empty((samples, n, n_cls, h, w), dtype=torch.float32, device=x.device)
+    for k, seed_k in enumerate(mc_sample_seeds(seed, samples)):
+        head_fwd(x, weight, bias, p_drop, seed_k, None, maps[k], seed_dev=seed_dev)
+    total = maps[0].clone()
+    for k in range(1, samples):
+        total.add_(maps[k])
+    torch.div(total, torch.full((), float(samples), dtype=torch.float32, device=x.device), out=mean_out)
+    d = torch.sub(maps[0], mean_out, out=total)
+    squares = torch.mul(d, d)
+    for k in range(1, samples):
+        torch.sub(maps[k], mean_out, out=d)
+        squares.add_(torch.mul(d, d, out=d))
+    torch.div(squares, torch.full((), float(samples - 1), dtype=torch.float32, device=x.device), out=var_out)
+
+
 def heads_mean_fwd(xs, weights, biases, out_nchw):
     """out_nchw [N, n_cls, H, W] fp32 = (((s_1 + s_2) + ...) + s_n) / float(n), s_h = sigmoid(bias_h + x_h . weight_h): the
     mean of n = len(xs) <= 8 sigmoid heads in ONE launch that reads every NHWC feature tensor xs[h] (all fp32, or all

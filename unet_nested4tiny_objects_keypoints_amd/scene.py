@@ -253,6 +253,46 @@ class SceneInference:
         out = torch.empty(S, self.model.n_classes, H, W, dtype=torch.float32, device=frames.device)
         return self._run(frames, self._plan(S, H, W, frames.device), out)
 
+    def uncertainty(self, frames: torch.Tensor, samples: int = 16, seed: int = 0) -> engine.McMaps:
+        """Monte-Carlo dropout over whole frames -> ``McMaps(mean, var)``, each float32 [S, n_classes, H, W]: where the
+        head's response depends on which features are present -- which unlabelled region to label next, where a screen
+        threshold sits on unstable responses.
+
+        The plan, the gather and the ownership of ``__call__``, eager only (``graphed`` is not used here): chunk i of the
+        plan is ONE ``model.infer_mc(tiles, head, samples, seed=chunk_seed(seed, i))`` over its batch of tiles, and the
+        tiles' mean maps and variance maps are each put back by the stitch launch as a copy of the owned pixels.  So a
+        pixel's statistics are those of ``samples`` draws of the head on the tile that owns it; tiles draw independent
+        masks (the keep flags are keyed by the pixel's index in the chunk's batch), and a call is reproducible from
+        ``seed``.  Not available with test-time augmentation or the ensemble mean: see the message."""
+        if self.tta is not None or self.ensemble:
+            raise ValueError(
+                "uncertainty() has no form for tta=%r, ensemble=%r: the stitch would average the variants' variance maps, "
+                "and a mean of per-variant variances is not the variance of the averaged map (the variants' draws are "
+                "independent and their maps are averaged before anything is thresholded); build the scene with tta=None "
+                "and ensemble=False" % (self.tta, self.ensemble))
+        if isinstance(seed, bool) or not isinstance(seed, int):
+            raise ValueError("seed must be an int, got %r" % (seed,))
+        frames, S, H, W = self._prepare(frames)
+        model, dev = self.model, frames.device
+        cin = model.in_channels
+        norm = self._norm.get(str(dev))
+        if norm is None:
+            norm = self._norm[str(dev)] = (_per_channel(self.mul, cin, dev), _per_channel(self.add, cin, dev))
+        th, tw = self.tile_shape(H, W)
+        mean = torch.empty(S, model.n_classes, H, W, dtype=torch.float32, device=dev)
+        var = torch.empty_like(mean)
+        for i, c in enumerate(self._plan(S, H, W, dev)):   # (a graphed scene's padding samples run too; the stitch skips them)
+            x = ops.warp_batch(frames, c.index, c.params, (th, tw), norm[0], norm[1], 0.0)
+            maps = model.infer_mc(x, self.head, samples, seed=self.chunk_seed(seed, i))
+            for tiles, out in ((maps.mean, mean), (maps.var, var)):
+                ops.scene_stitch(tiles.view(c.n, 1, model.n_classes, th, tw), c.rects, c.rects_dev, (0,), out)
+        return engine.McMaps(mean, var)
+
+    @staticmethod
+    def chunk_seed(seed: int, chunk_index: int) -> int:
+        """The ``infer_mc`` seed of chunk `chunk_index` (0-based, plan order) of ``uncertainty(frames, samples, seed)``."""
+        return (seed + 0xA0761D6478BD642F * (chunk_index + 1)) & 0xFFFFFFFFFFFFFFFF
+
     def _graph(self, cin: int, th: int, tw: int, dev) -> GraphedForward:
         key = (cin, th, tw, str(dev))
         g = self._graphs.get(key)

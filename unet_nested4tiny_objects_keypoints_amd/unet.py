@@ -177,6 +177,25 @@ class UNet_Nested(nn.Module):
         ``validate_step(model, ..., forward=lambda x: (model.infer(x, 1),))`` validates a pruned network."""
         return engine.infer(self, inputs, head, ensemble)
 
+    def infer_mc(self, inputs, head=None, samples=16, p=None, seed=None):
+        """Monte-Carlo dropout at deep-supervision head ``head``: ``McMaps(mean, var)``, both fp32
+        ``[B, n_classes, H, W]`` without ``grad_fn`` (``.std`` is ``var.sqrt()``).
+
+        The network's one stochastic element is the ``Dropout`` in front of each head's 1x1 convolution; nothing upstream
+        of ``X_0J`` is random.  So the pass is ``infer(x, head)``'s -- the same checks (eval mode, ``pruned_to``, BatchNorm
+        layers in eval), the same nodes, the same weight-image plan -- and only the head, ``sigmoid(W . dropout(x) + b)``, is
+        drawn ``samples`` (2 .. 32) times, in one launch that reads ``X_0J`` once (``ops.head_mc``; a composition of
+        ``head_fwd`` launches with the same bits where the channel count or bf16 storage keeps a call off that kernel).
+        ``mean`` is the fold ``(((s_0 + s_1) + ...) + s_{K-1}) / K`` and ``var`` the unbiased variance around it: how
+        strongly a response depends on which features are present.
+
+        ``p``: drop probability in (0, 1), ``None`` = ``self.drop_out.p``.  ``seed``: ``None`` draws one with
+        ``torch.randint`` (so ``torch.manual_seed`` reproduces a call).  Sample ``k`` is the map that ``ops.head_fwd``
+        writes for the seed ``seed + 0x632BE59BD9B4E019 * head + 0xD6E8FEB86659FD93 * k (mod 2^64)``.
+        ``self.dropout_masks`` (the test hook of the training forward) is ignored: the draws always come from the
+        in-kernel generator.  The ensemble mean has no Monte-Carlo form."""
+        return engine.infer_mc(self, inputs, head, samples, p, seed)
+
     def forward_pruned(self, inputs, head=None, ensemble=False):
         """``forward`` of the network cut at deep-supervision head ``head``, connected to autograd as ``forward`` is: only
         the nodes ``X_ij`` with ``i + j <= head`` run (``engine.needed_nodes``), forward and backward, every layer in the
