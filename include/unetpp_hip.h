@@ -968,6 +968,84 @@ int unetpp_crops_draw(float* params, int64_t* index, int32_t* origin, int32_t N,
                       int32_t Ws, int32_t Ho, int32_t Wo, const int32_t* centre_frame, const float* centre_xy, int32_t V,
                       float p_object, float jitter_x, float jitter_y, const unetpp_augment* augment, void* stream);
 
+/* ---- Copy-paste augmentation of tiny objects (csrc/paste.hip; added within v13): an object's few pixels are copied to
+ * new places of a window, with their label.  Three launches between those above: unetpp_crops_draw, unetpp_warp_batch,
+ * unetpp_paste_draw, unetpp_paste_apply, unetpp_points_target, unetpp_paste_target, unetpp_target_ignore.  The reference
+ * has no counterpart.
+ *
+ * The source table: src_frame int32 [T], src_xy float32 [T, 2] as (x, y), src_class int32 [T] (device).  Row t can be
+ * pasted when its frame lies in [0, M), its class in [0, C) and the patch of (2R+1) x (2R+1) whole pixels about its
+ * rounded centre (cx, cy) = floor(src_xy + 0.5) lies inside the Hs x Ws frame: R <= cx <= Ws-1-R, R <= cy <= Hs-1-R,
+ * compared as doubles, so a NaN or an infinity is not inside.  Both kernels that read the table test this themselves.
+ *
+ * A code 0..7 is one of the eight flips and quarter turns: q = code & 3 quarter turns, then a flip in x when code & 4,
+ * T_code = D Q^q, Q^q = [[qc, -qs], [qs, qc]] with (qc, qs) = (1, 0), (0, 1), (-1, 0), (0, -1) as in unetpp_crops_draw,
+ * D = diag(-1, 1) with the flip.  Source offset (i, j) from (cx, cy) lands at destination offset T_code (i, j):
+ *   T_code (i, j) = (dx (qc i - qs j), qs i + qc j),   T_code^-1 (i, j) = (qc (dx i) + qs j, qc j - qs (dx i)). ---- */
+#define UNETPP_PASTE_MAX_SLOTS 64    /* K, the paste slots of a window */
+#define UNETPP_PASTE_MAX_RADIUS 16   /* R, the patch radius */
+
+/* unetpp_paste_draw: what is pasted where, one workgroup per window, slots k = 0 .. K-1 in order.  Outputs (device):
+ * src int32 [N, K] (the table row, or -1: the slot is void), dst int32 [N, K, 2] as (px, py), code int32 [N, K],
+ * xy float32 [N, K, 2] (the pasted label; (-1, -1) when void), cls int32 [N, K] (the source class; -1 when void).
+ * labels, label_class, M, L, index, params: as unetpp_points_target takes them; Hs x Ws: the frames, Ho x Wo: the window.
+ * Uniform j of slot k of window n is 24 bits wide,
+ *   u_j = float32(mix64(seed + 0x9E3779B97F4A7C15 * ((n * 64 + k) * 8 + j + 1)) >> 40) * 2^-24
+ * (mix64: the splitmix64 finaliser of unetpp_augment_draw; 64 = UNETPP_PASTE_MAX_SLOTS whatever K is), and
+ *   j = 0:  the slot attempts a paste iff (float)u < p
+ *   j = 1:  t = min(floor(u T), T - 1), the source row
+ *   j = 2:  code = floor(8 u), or 0 when dihedral == 0
+ *   j = 3:  px = R + min(floor(u (Wo - 2R)), Wo - 2R - 1)        j = 4:  py likewise with Ho
+ * so the patch is inside the window.  dst and code are written as drawn, void or not.  The slot is void when it does not
+ * attempt, when index[n] lies outside [0, M), when row t cannot be pasted (above), when a label of frame index[n] with
+ * class >= 0 and neither coordinate negative, at its window position (xo, yo) in the float32 expression of
+ * unetpp_points_target, has dx*dx + dy*dy < clearance*clearance in float64 (dx = (double)xo - px), or when an earlier
+ * slot k' < k of the window that was accepted has max(|px - px'|, |py - py'|) <= 2R: accepted patches are pairwise
+ * disjoint.  The label of an accepted slot is xy = dst + T_code (src_xy[t] - floor(src_xy[t] + 0.5)), formed in float64
+ * (the difference is exact) and rounded once.  No atomics; the same bits on any grid.
+ * UNETPP_EINVAL without touching the device for a null pointer, a size <= 0, K > UNETPP_PASTE_MAX_SLOTS, C > 65535, a side
+ * above 2^24, R outside 0..UNETPP_PASTE_MAX_RADIUS, a window side below 2R + 1, or a negative or NaN p or clearance. */
+int unetpp_paste_draw(int32_t* src, int32_t* dst, int32_t* code, float* xy, int32_t* cls, int32_t N, int32_t K,
+                      uint64_t seed, const int32_t* src_frame, const float* src_xy, const int32_t* src_class, int32_t T,
+                      const float* labels, const int32_t* label_class, int64_t M, int32_t L, const int64_t* index,
+                      const float* params, int32_t C, int32_t Hs, int32_t Ws, int32_t Ho, int32_t Wo, float p, int32_t R,
+                      float clearance, int32_t dihedral, void* stream);
+
+/* unetpp_paste_apply: the pixels, in place on inputs float32 [N, Cin, Ho, Wo] (device); a unit of work is (n, k).  src,
+ * dst, code: rows as unetpp_paste_draw writes them, but any values are safe: a row is skipped unless src lies in [0, T),
+ * the table row can be pasted (above), code lies in 0..7 and R <= px <= Wo-1-R, R <= py <= Ho-1-R; no address outside
+ * the store or inputs is formed.  store, store_type, M, Hs, Ws, mul, add: as unetpp_warp_batch takes them (Cin channels);
+ * params [N][16]: entries 12 and 13 of row n are the window's gain and bias; alpha float32 [2R+1][2R+1]: the blend
+ * weights, indexed [j + R][i + R], symmetric under the eight codes.  For every offset (i, j) in [-R, R]^2 and channel c:
+ *   v   = the store's pixel at (cx, cy) + T_code^-1 (i, j) of frame src_frame[t], channel c
+ *   p   = gain * (v * mul[c] + add[c]) + bias                      (the expression of unetpp_warp_batch, float32)
+ *   d   = inputs[n, c, py + j, px + i]
+ *   out = alpha == 1 ? p : alpha == 0 ? d : d + alpha * (p - d)    (float32, no contraction)
+ * The patches of a window must be pairwise disjoint (unetpp_paste_draw makes them so): units are then independent and
+ * the result is the same in any order and on any grid.  No atomics; 64-bit offsets.
+ * UNETPP_EINVAL without touching the device for a null pointer, a size <= 0, K > UNETPP_PASTE_MAX_SLOTS, Cin >
+ * UNETPP_WARP_MAX_C, C > 65535, a side above 2^24, R outside 0..UNETPP_PASTE_MAX_RADIUS or an unknown store_type. */
+int unetpp_paste_apply(float* inputs, int32_t N, int32_t K, int32_t Cin, int32_t Ho, int32_t Wo, const int32_t* src,
+                       const int32_t* dst, const int32_t* code, const int32_t* src_frame, const float* src_xy,
+                       const int32_t* src_class, int32_t T, const void* store, int32_t store_type, int64_t M, int32_t Hs,
+                       int32_t Ws, int32_t C, const float* params, const float* mul, const float* add,
+                       const float* alpha, int32_t R, void* stream);
+
+/* unetpp_paste_target: folds the pasted labels into target float32 [N, C, Ho, Wo] (device), in place, after
+ * unetpp_points_target: the target is a maximum over labels, so the result is what that call would have written had the
+ * pasted labels been in the frame's list.  xy float32 [N, K, 2], cls int32 [N, K]: of unetpp_paste_draw; slot k of window
+ * n is live when cls lies in [0, C).  A window without a live slot is skipped, nothing of it read or written.  Otherwise,
+ * per class c that has a live slot and per pixel (x, y):
+ *   m = min over the live slots of class c of dx*dx + dy*dy,  dx = (double)x - (double)xy[0],  dy likewise
+ *   v = (float)exp(-0.5 * sqrt(m) / (double)radius)
+ *   target[n, c, y, x] = v  where v > t and !(t < 0), t the value there: an ignored (negative) element stays.
+ * The tiles of unetpp_target_ignore; the K rows of a window pass through LDS once per unit.  No atomics, no contraction,
+ * 64-bit offsets; a pure function of target and the rows per element: the same bits on any grid.
+ * UNETPP_EINVAL without touching the device for a null pointer, a size <= 0, K > UNETPP_PASTE_MAX_SLOTS, C > 65535, a
+ * window side above 2^24, or a radius that is not > 0 (a NaN included). */
+int unetpp_paste_target(float* target, int32_t N, int32_t K, int32_t C, int32_t Ho, int32_t Wo, const float* xy,
+                        const int32_t* cls, float radius, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

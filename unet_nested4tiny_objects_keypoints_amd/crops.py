@@ -20,20 +20,28 @@ Partially labelled scenes: ``ignore=IgnoreRegions(...)`` and / or ``ignore_outsi
 -1 into the target wherever the pixel's source position lies in an ignore rectangle of its frame (of that class or of
 every class) or outside the frame; a criterion built with ``ignore_negative=True`` leaves those elements out.
 
+Copy-paste of tiny objects: ``paste=ObjectPaste(max_pastes=4, p=0.5, patch_radius=4)`` copies the few pixels of labelled
+objects to new places of a window, with their label (csrc/paste.hip): three more launches per batch
+(where, the pixels, the targets), still without host data work.  ``points`` and ``inside`` stay the frame's labels; the
+pasted ones are in ``last_paste``.
+
 Coordinates are (x, y) with pixel centres at integers, the labels' convention everywhere in the package.  The reference
 has no counterpart.
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+import math
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 
-from . import ops
+from . import _lib, ops
 from .ignore import IgnoreRegions
 from .loader import Augment, _channels, _per_channel, _source_size
 
-__all__ = ["SceneCrops", "false_positive_centres"]
+__all__ = ["SceneCrops", "ObjectPaste", "PasteRows", "false_positive_centres"]
+
+_PASTE_SEED = 0x5041535445524F57   # the paste's seed is the batch's seed xor this: one draw of the host generator per batch
 
 
 def _centre_table(frame, xy, n_frames: int, device) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -54,6 +62,124 @@ def _centre_table(frame, xy, n_frames: int, device) -> Tuple[torch.Tensor, torch
     return (frame.to(device=device, dtype=torch.int32).contiguous(), xy.to(device=device).contiguous())
 
 
+class PasteRows(NamedTuple):
+    """What a batch pasted, K slots per window, on the device: src [N, K] int32 (the row of the source table, -1: a void
+    slot), dst [N, K, 2] int32 as (px, py), code [N, K] int32 (0..7: q = code & 3 quarter turns, then a flip in x when
+    code & 4), xy [N, K, 2] float32 (the pasted label, (-1, -1) when void), cls [N, K] int32 (its class, -1 when void)."""
+    src: torch.Tensor
+    dst: torch.Tensor
+    code: torch.Tensor
+    xy: torch.Tensor
+    cls: torch.Tensor
+
+
+def paste_alpha(patch_radius: int, core: float) -> torch.Tensor:
+    """The blend weights [2R+1, 2R+1] float32 (CPU): clamp((R + 0.5 - d) / (R + 0.5 - core), 0, 1) of the distance d from
+    the patch's centre, formed in float64 and rounded once; 1 within `core`, 0 from R + 0.5 on, linear between.  The
+    table is symmetric under the eight flips and quarter turns."""
+    r = int(patch_radius)
+    edge = r + 0.5
+    rows = [[min(1.0, max(0.0, (edge - math.sqrt(float(i * i + j * j))) / (edge - float(core))))
+             for i in range(-r, r + 1)] for j in range(-r, r + 1)]
+    return torch.tensor(rows, dtype=torch.float64).to(torch.float32)
+
+
+def paste_source_table(labels: torch.Tensor, label_class: torch.Tensor, n_classes: int, src_size, patch_radius: int,
+                       ignore: Optional[IgnoreRegions] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(frame [T] int32, xy [T, 2] float32, cls [T] int32) of the labels whose patch can be pasted, on the labels' device:
+    labels [S, L, 2] float32 and label_class [S, L] of frames of src_size = (Hs, Ws).  A label is admitted when it is valid
+    (class in [0, n_classes), no negative coordinate), the (2R+1) x (2R+1) patch about its rounded centre c = floor(xy +
+    0.5) lies inside the frame, no other valid label of the frame lies within Chebyshev distance R + 1 of c (the patch
+    then holds exactly one object), and c lies in no rectangle of `ignore` of its frame.  Torch ops, frame by frame; the
+    length depends on the data, so this synchronises with the host: for a constructor, not for the training loop."""
+    r, (hs, ws) = int(patch_radius), (int(src_size[0]), int(src_size[1]))
+    xy = labels.to(torch.float64)
+    cls = label_class.to(torch.int64)
+    valid = (cls >= 0) & (cls < int(n_classes)) & ~(labels[..., 0] < 0) & ~(labels[..., 1] < 0)
+    c = torch.floor(xy + 0.5)
+    inside = (c[..., 0] >= r) & (c[..., 0] <= ws - 1 - r) & (c[..., 1] >= r) & (c[..., 1] <= hs - 1 - r)
+    ok = valid & inside
+    for s in range(int(labels.shape[0])):   # [L, L] per frame: centre a against label b
+        cheb = (xy[s].unsqueeze(0) - c[s].unsqueeze(1)).abs().amax(dim=-1)
+        crowd = (cheb <= r + 1) & valid[s].unsqueeze(0)
+        crowd.fill_diagonal_(False)
+        ok[s] &= ~crowd.any(dim=1)
+    if ignore is not None and int(ignore.rects.shape[1]) > 0:
+        rc = ignore.rects.to(labels.device).to(torch.float64).unsqueeze(1)         # [S, 1, R, 4]
+        k = ignore.rect_class.to(labels.device).unsqueeze(1)
+        cx, cy = c[..., 0].unsqueeze(-1), c[..., 1].unsqueeze(-1)
+        hit = (rc[..., 0] <= cx) & (cx <= rc[..., 2]) & (rc[..., 1] <= cy) & (cy <= rc[..., 3])
+        ok &= ~(hit & (k >= -1) & (k < int(n_classes))).any(dim=-1)
+    where = ok.nonzero()
+    return (where[:, 0].to(torch.int32).contiguous(), labels[ok].to(torch.float32).contiguous(),
+            label_class[ok].to(torch.int32).contiguous())
+
+
+class ObjectPaste:
+    """Copy-paste augmentation for ``SceneCrops(..., paste=ObjectPaste(...))``: per window max_pastes = K slots, each of
+    which attempts a paste with probability p.  A paste copies the (2R+1) x (2R+1) whole pixels (R = patch_radius) about a
+    row of the source table to a place of the window where no label of the frame lies within `clearance` (default 2R)
+    and no earlier paste of the window overlaps, under one of the eight flips and quarter turns (dihedral) -- or is void.
+    The patch is blended in with weight 1 within `core` pixels of its centre (core < R + 0.5), falling linearly to 0 at
+    R + 0.5.  The source table is built by ``SceneCrops`` from its labels (``paste_source_table``); ``set_sources``
+    replaces it.  One object serves one ``SceneCrops``."""
+
+    def __init__(self, max_pastes: int = 4, p: float = 0.5, patch_radius: int = 4, core: float = 2.5,
+                 clearance: Optional[float] = None, dihedral: bool = True):
+        for name, v in (("max_pastes", max_pastes), ("patch_radius", patch_radius)):
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise ValueError("%s must be an int, got %r" % (name, v))
+        if not 1 <= max_pastes <= _lib.PASTE_MAX_SLOTS:
+            raise ValueError("max_pastes must lie in 1..%d, got %r" % (_lib.PASTE_MAX_SLOTS, max_pastes))
+        if not 0 <= patch_radius <= _lib.PASTE_MAX_RADIUS:
+            raise ValueError("patch_radius must lie in 0..%d, got %r" % (_lib.PASTE_MAX_RADIUS, patch_radius))
+        self.max_pastes, self.patch_radius = max_pastes, patch_radius
+        self.p, self.core = float(p), float(core)
+        if not 0.0 <= self.p <= 1.0:
+            raise ValueError("p lies in [0, 1], got %r" % (p,))
+        if not 0.0 <= self.core < patch_radius + 0.5:
+            raise ValueError("core must lie in [0, patch_radius + 0.5), got %r" % (core,))
+        self.clearance = 2.0 * patch_radius if clearance is None else float(clearance)
+        if not self.clearance >= 0.0 or math.isinf(self.clearance):
+            raise ValueError("clearance must be a finite number that is not negative, got %r" % (clearance,))
+        self.dihedral = bool(dihedral)
+        self.alpha = paste_alpha(patch_radius, self.core)
+        self.src_frame = self.src_xy = self.src_class = None
+        self._frames = self._classes = None
+
+    def _bind(self, crops: "SceneCrops") -> None:
+        """the source table from the scenes' labels; ValueError when no label can be pasted"""
+        r = self.patch_radius
+        if min(crops.crop) < 2 * r + 1:
+            raise ValueError("the window must be at least %d on both sides for patch_radius %d" % (2 * r + 1, r))
+        self._frames, self._classes = len(crops), crops.n_classes
+        self.alpha = self.alpha.to(crops.device).contiguous()
+        f, xy, c = paste_source_table(crops.labels, crops.label_class, crops.n_classes, crops.src_size, r, crops.ignore)
+        if f.numel() == 0:
+            raise ValueError("no label can be pasted: none is valid, %d pixels inside its frame, alone in its patch and "
+                             "outside every ignore rectangle" % r)
+        self.src_frame, self.src_xy, self.src_class = f, xy, c
+
+    def set_sources(self, frame, xy, cls) -> None:
+        """Replace the source table: frame [T] whole numbers in [0, S), xy [T, 2] as (x, y), finite, cls [T] whole numbers
+        in [0, n_classes); T >= 1.  A row whose patch is not inside its frame is never pasted (the kernels test it).  Reads
+        back to check: between epochs, not per step."""
+        if self._frames is None:
+            raise ValueError("set_sources needs the scenes: pass the object to SceneCrops(paste=...) first")
+        device = self.alpha.device
+        f, p = _centre_table(frame, xy, self._frames, device)
+        c = torch.as_tensor(cls).reshape(-1)
+        if c.is_floating_point() or c.dtype == torch.bool:
+            raise ValueError("cls must hold whole numbers")
+        if c.numel() != f.numel() or f.numel() == 0:
+            raise ValueError("one class per source and at least one source: got %d frames and %d classes"
+                             % (f.numel(), c.numel()))
+        if int(c.min()) < 0 or int(c.max()) >= self._classes:
+            raise ValueError("a source's class must lie in [0, %d)" % self._classes)
+        self.src_frame, self.src_xy = f, p
+        self.src_class = c.to(device=device, dtype=torch.int32).contiguous()
+
+
 class SceneCrops:
     """Windows of scenes held on the device, with their targets.  frames: uint8 [S, H, W, C] (decoded, channels last) or
     float32 [S, C, H, W]; labels [S, L, 2] as (x, y) and label_class [S, L] or [L] as ``evaluate`` takes them (class -1
@@ -71,12 +197,19 @@ class SceneCrops:
     where it lies outside the frame (a bilinear neighbour is `fill`), and all of an all-fill sample.  Either makes
     batch(n) a fourth launch (unetpp_target_ignore) after the targets, still without a host synchronisation.
 
+    paste: an ``ObjectPaste`` -- batch(n) then also copies objects of its source table into the windows (three more
+    launches: unetpp_paste_draw, unetpp_paste_apply after the warp, unetpp_paste_target after the targets and before the
+    ignore marks, so a patch that lands in an ignore region is ignored like anything else there); ``last_paste`` holds
+    the batch's ``PasteRows``.  points and inside stay the frame's labels.  The paste draws from the batch's own seed:
+    with p = 0 the batches are those of an object without paste, bit for bit.
+
     The centre table starts as the valid labels; set_centres / add_centres replace / extend it -- a sampling policy such
     as class balancing is a matter of what the caller puts there."""
 
     def __init__(self, frames, labels, label_class, n_classes: int, crop=(256, 256), p_object: float = 0.75,
                  jitter=(32, 32), augment: Optional[Augment] = None, radius: float = 3.0, mul=1.0 / 255.0, add=0.0,
-                 fill: float = 0.0, seed: int = 0, ignore=None, ignore_outside: bool = False):
+                 fill: float = 0.0, seed: int = 0, ignore=None, ignore_outside: bool = False,
+                 paste: Optional[ObjectPaste] = None):
         self.augment = Augment() if augment is None else augment
         self.crop = (int(crop[0]), int(crop[1]))
         if min(self.crop) < 1:
@@ -133,6 +266,12 @@ class SceneCrops:
             if len(ignore) != s:
                 raise ValueError("ignore holds %d frames, the scenes %d" % (len(ignore), s))
             self.ignore = ignore.to(self.device)
+        self.paste, self.last_paste = None, None
+        if paste is not None:
+            if not isinstance(paste, ObjectPaste):
+                raise TypeError("paste must be an ObjectPaste")
+            paste._bind(self)
+            self.paste = paste
 
     def __len__(self):
         return int(self.frames.shape[0])
@@ -155,12 +294,23 @@ class SceneCrops:
 
     def batch(self, n: int):
         """n windows: (inputs [n, C, Ho, Wo], target [n, n_classes, Ho, Wo], points [n, L, 2], inside [n, L] uint8)."""
-        params, index, origin = ops.crops_draw(n, self._next_seed(), len(self), self.src_size, self.crop,
+        seed = self._next_seed()
+        params, index, origin = ops.crops_draw(n, seed, len(self), self.src_size, self.crop,
                                                self.centre_frame, self.centre_xy, self.p_object, self.jitter,
                                                self.augment.desc(), self.device)
         inputs, points, inside = ops.warp_batch(self.frames, index, params, self.crop, self.mul, self.add, self.fill,
                                                 self.labels)
+        ps = self.paste
+        if ps is not None:
+            rows = PasteRows(*ops.paste_draw(ps.max_pastes, seed ^ _PASTE_SEED, ps.src_frame, ps.src_xy, ps.src_class,
+                                             self.labels, self.label_class, index, params, self.n_classes, self.src_size,
+                                             self.crop, ps.p, ps.patch_radius, ps.clearance, ps.dihedral))
+            ops.paste_apply(inputs, rows.src, rows.dst, rows.code, ps.src_frame, ps.src_xy, ps.src_class, self.frames,
+                            params, self.mul, self.add, ps.alpha, self.n_classes)
         target = ops.points_target(self.labels, self.label_class, index, params, self.n_classes, self.crop, self.radius)
+        if ps is not None:
+            ops.paste_target(target, rows.xy, rows.cls, self.radius)
+            self.last_paste = rows
         if self.ignore is not None or self.ignore_outside:
             ign = self.ignore
             ops.target_ignore(target, ign.rects if ign is not None else None, ign.rect_class if ign is not None else None,

@@ -1569,3 +1569,139 @@ def crops_draw(n: int, seed: int, n_frames: int, src_size, out_size, centre_fram
         _ptr(centre_xy) if v else None, v, float(p_object), float(jitter[0]), float(jitter[1]), C.byref(desc), _stream()),
         "unetpp_crops_draw")
     return params, index, origin
+
+
+def _paste_sources(src_frame: torch.Tensor, src_xy: torch.Tensor, src_class: torch.Tensor, dev) -> int:
+    _need(src_frame, "src_frame", torch.int32)
+    _need(src_xy, "src_xy")
+    _need(src_class, "src_class", torch.int32)
+    t = int(src_frame.numel())
+    if t < 1 or src_frame.dim() != 1 or tuple(src_xy.shape) != (t, 2) or tuple(src_class.shape) != (t,):
+        raise ValueError("the source table is src_frame [T], src_xy [T, 2] and src_class [T] with T >= 1")
+    if any(v.device != dev for v in (src_frame, src_xy, src_class)):
+        raise ValueError("the source table must live on %s" % dev)
+    return t
+
+
+def _paste_radius(patch_radius: int) -> int:
+    r = int(patch_radius)
+    if not 0 <= r <= _lib.PASTE_MAX_RADIUS:
+        raise ValueError("patch_radius must lie in 0..%d, got %r" % (_lib.PASTE_MAX_RADIUS, patch_radius))
+    return r
+
+
+def paste_draw(max_pastes: int, seed: int, src_frame: torch.Tensor, src_xy: torch.Tensor, src_class: torch.Tensor,
+               labels: torch.Tensor, label_class: torch.Tensor, index: torch.Tensor, params: torch.Tensor,
+               n_classes: int, src_size, out_size, p: float, patch_radius: int, clearance: float, dihedral: bool = True):
+    """One launch: what is pasted where in N windows, K = max_pastes slots each -> (src [N, K] int32: the row of the
+    source table or -1, dst [N, K, 2] int32 as (px, py), code [N, K] int32, xy [N, K, 2] fp32: the pasted label, cls
+    [N, K] int32: its class or -1) on the device.  src_frame [T] int32, src_xy [T, 2] fp32, src_class [T] int32: the
+    source table; labels, label_class, index, params: as points_target takes them (include/unetpp_hip.h:
+    unetpp_paste_draw)."""
+    _need(labels, "labels")
+    _need(label_class, "label_class", torch.int32)
+    _need(index, "index", torch.int64)
+    _need(params, "params")
+    dev = params.device
+    t = _paste_sources(src_frame, src_xy, src_class, dev)
+    if labels.dim() != 3 or labels.shape[2] != 2 or tuple(label_class.shape) != tuple(labels.shape[:2]):
+        raise ValueError("labels must be [M, L, 2] and label_class [M, L]")
+    m, n_labels = int(labels.shape[0]), int(labels.shape[1])
+    n, k, r = int(index.numel()), int(max_pastes), _paste_radius(patch_radius)
+    if index.dim() != 1 or tuple(params.shape) != (n, _lib.WARP_PARAMS):
+        raise ValueError("index [N] and params [N, %d]" % _lib.WARP_PARAMS)
+    if any(v.device != dev for v in (labels, label_class, index)):
+        raise ValueError("all tensors must live on one device")
+    if not 1 <= k <= _lib.PASTE_MAX_SLOTS:
+        raise ValueError("max_pastes must lie in 1..%d, got %r" % (_lib.PASTE_MAX_SLOTS, max_pastes))
+    c, (hs, ws), (ho, wo) = int(n_classes), (int(src_size[0]), int(src_size[1])), (int(out_size[0]), int(out_size[1]))
+    if min(m, n_labels, n, hs, ws) < 1 or not 1 <= c <= 65535 or min(ho, wo) < 2 * r + 1:
+        raise ValueError("M, L, N and the frame must be positive, n_classes in 1..65535 and the window at least "
+                         "%d on both sides" % (2 * r + 1))
+    p, clearance = float(p), float(clearance)
+    if not p >= 0.0 or not clearance >= 0.0:
+        raise ValueError("p and clearance must not be negative")
+    src = torch.empty(n, k, dtype=torch.int32, device=dev)
+    dst = torch.empty(n, k, 2, dtype=torch.int32, device=dev)
+    code = torch.empty(n, k, dtype=torch.int32, device=dev)
+    xy = torch.empty(n, k, 2, dtype=torch.float32, device=dev)
+    cls = torch.empty(n, k, dtype=torch.int32, device=dev)
+    check(_lib.lib().unetpp_paste_draw(
+        _ptr(src), _ptr(dst), _ptr(code), _ptr(xy), _ptr(cls), n, k, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(src_frame),
+        _ptr(src_xy), _ptr(src_class), t, _ptr(labels), _ptr(label_class), m, n_labels, _ptr(index), _ptr(params), c, hs,
+        ws, ho, wo, p, r, clearance, 1 if dihedral else 0, _stream()), "unetpp_paste_draw")
+    return src, dst, code, xy, cls
+
+
+def paste_apply(inputs: torch.Tensor, src: torch.Tensor, dst: torch.Tensor, code: torch.Tensor, src_frame: torch.Tensor,
+                src_xy: torch.Tensor, src_class: torch.Tensor, store: torch.Tensor, params: torch.Tensor,
+                mul: torch.Tensor, add: torch.Tensor, alpha: torch.Tensor, n_classes: int) -> torch.Tensor:
+    """One launch: blends the patches of the rows (src [N, K], dst [N, K, 2], code [N, K], all int32) into inputs
+    [N, C, Ho, Wo] fp32, in place, and returns it.  store: the frames as warp_batch takes them; params [N, 16]: the
+    windows' gain and bias; alpha [2R+1, 2R+1] fp32: the blend weights.  Rows of any content are safe: one that names no
+    patch inside its frame and window is skipped (include/unetpp_hip.h: unetpp_paste_apply)."""
+    _need(inputs, "inputs")
+    for name, v in (("src", src), ("dst", dst), ("code", code)):
+        _need(v, name, torch.int32)
+    for name, v in (("params", params), ("mul", mul), ("add", add), ("alpha", alpha)):
+        _need(v, name)
+    if not store.is_cuda:
+        raise RuntimeError("store must live on the GPU: this path has no CPU fallback")
+    if store.dtype not in (torch.uint8, torch.float32):
+        raise TypeError("store must be uint8 [M, Hs, Ws, C] or float32 [M, C, Hs, Ws], got %s" % store.dtype)
+    if store.dim() != 4 or not store.is_contiguous() or inputs.dim() != 4:
+        raise ValueError("store must be a contiguous 4-d tensor and inputs [N, C, Ho, Wo]")
+    u8 = store.dtype == torch.uint8
+    m, (hs, ws, cin) = int(store.shape[0]), (store.shape[1:] if u8 else (store.shape[2], store.shape[3], store.shape[1]))
+    hs, ws, cin = int(hs), int(ws), int(cin)
+    n, ci, ho, wo = (int(v) for v in inputs.shape)
+    dev = inputs.device
+    t = _paste_sources(src_frame, src_xy, src_class, dev)
+    if ci != cin or not 1 <= cin <= _lib.WARP_MAX_C:
+        raise ValueError("inputs and the store must have the same 1 to %d channels" % _lib.WARP_MAX_C)
+    if src.dim() != 2 or src.shape[0] != n or tuple(dst.shape) != tuple(src.shape) + (2,) or code.shape != src.shape:
+        raise ValueError("src [N, K], dst [N, K, 2] and code [N, K] for inputs of N = %d windows" % n)
+    k = int(src.shape[1])
+    side = int(alpha.shape[0]) if alpha.dim() == 2 else 0
+    if side < 1 or side % 2 == 0 or tuple(alpha.shape) != (side, side):
+        raise ValueError("alpha must be [2R+1, 2R+1]")
+    r = _paste_radius(side // 2)
+    if tuple(params.shape) != (n, _lib.WARP_PARAMS) or tuple(mul.shape) != (cin,) or tuple(add.shape) != (cin,):
+        raise ValueError("params [N, %d], mul and add [%d]" % (_lib.WARP_PARAMS, cin))
+    c = int(n_classes)
+    if min(m, n, ho, wo, hs, ws) < 1 or not 1 <= k <= _lib.PASTE_MAX_SLOTS or not 1 <= c <= 65535:
+        raise ValueError("sizes must be positive, K in 1..%d and n_classes in 1..65535" % _lib.PASTE_MAX_SLOTS)
+    if any(v.device != dev for v in (src, dst, code, store, params, mul, add, alpha)):
+        raise ValueError("all tensors must live on one device")
+    _timed_call(None, 0.0, lambda: check(_lib.lib().unetpp_paste_apply(
+        _ptr(inputs), n, k, cin, ho, wo, _ptr(src), _ptr(dst), _ptr(code), _ptr(src_frame), _ptr(src_xy), _ptr(src_class),
+        t, _ptr(store), _lib.STORE_U8 if u8 else _lib.STORE_F32, m, hs, ws, c, _ptr(params), _ptr(mul), _ptr(add),
+        _ptr(alpha), r, _stream()), "unetpp_paste_apply"), (9.0 if u8 else 12.0) * n * k * cin * side * side)
+    return inputs
+
+
+def paste_target(target: torch.Tensor, xy: torch.Tensor, cls: torch.Tensor, radius: float) -> torch.Tensor:
+    """One launch: folds the pasted labels xy [N, K, 2] fp32 of class cls [N, K] int32 (outside [0, C): no label) into
+    target [N, C, Ho, Wo] fp32, in place, and returns it: per live class exp(-0.5 d / radius) of the distance to the
+    nearest pasted label, stored where it exceeds a target that is not negative -- what points_target would have written
+    with those labels in the frame's list (include/unetpp_hip.h: unetpp_paste_target)."""
+    _need(target, "target")
+    _need(xy, "xy")
+    _need(cls, "cls", torch.int32)
+    if target.dim() != 4:
+        raise ValueError("target must be [N, C, Ho, Wo]")
+    n, c, ho, wo = (int(v) for v in target.shape)
+    if cls.dim() != 2 or cls.shape[0] != n or tuple(xy.shape) != tuple(cls.shape) + (2,):
+        raise ValueError("xy [N, K, 2] and cls [N, K] for a target of N = %d windows" % n)
+    k = int(cls.shape[1])
+    radius = float(radius)
+    if not radius > 0.0:
+        raise ValueError("radius must be a positive number, got %r" % (radius,))
+    if min(n, ho, wo) < 1 or not 1 <= k <= _lib.PASTE_MAX_SLOTS or not 1 <= c <= 65535:
+        raise ValueError("N and the window must be positive, K in 1..%d and C in 1..65535" % _lib.PASTE_MAX_SLOTS)
+    if xy.device != target.device or cls.device != target.device:
+        raise ValueError("all tensors must live on one device")
+    _timed_call("paste_target", 0.0, lambda: check(_lib.lib().unetpp_paste_target(
+        _ptr(target), n, k, c, ho, wo, _ptr(xy), _ptr(cls), radius, _stream()), "unetpp_paste_target"),
+        8.0 * n * c * ho * wo)
+    return target
