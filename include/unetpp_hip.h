@@ -488,6 +488,33 @@ int unetpp_topk_focal_heads_ignore(const unetpp_focal_heads* heads, const float*
 int unetpp_pr_focal_heads_ignore(const unetpp_focal_heads* heads, const float* target, int64_t n, float alpha, float beta,
                                  float eps, float positive, void* workspace, int64_t* n_pos,
                                  float* loss /* [1 + n_heads] */, void* stream);
+/* ---- self-distillation across the heads (csrc/distill.hip; added within v13: new entry points only) ----
+ * unetpp_focal_bce_heads (ignore = 0) or unetpp_focal_bce_heads_ignore (ignore = 1) with one more term: every head but the
+ * deepest is also held, by the same element rule, against a deeper head's map -- its teacher, read as data (no gradient
+ * reaches a head through its role as teacher).  Heads pred[0 .. n_heads - 1] are ordered shallow to deep.
+ *   teacher:  UNETPP_DISTILL_LAST: the deepest head teaches every other;  UNETPP_DISTILL_NEXT: head h + 1 teaches head h.
+ *   S_h = FocalLoss_BCE_2d(pred[h], target): unetpp_focal_bce_heads' loss[1 + h], bit for bit;
+ *   D_h = the FocalLoss_BCE_2d sum of pred[h] against its teacher's map q over the ADMITTED elements, same divisor rows:
+ *         without gate and ignore rule unetpp_focal_bce(pred[h], q)'s loss, bit for bit;  D of the deepest head = +0.0;
+ *   L_h = S_h + w * D_h, one rounded float32 product and one rounded float32 sum, w = weight[0] read on the device;
+ *   loss[0] = (0 + L_0 + ... ) * (1 / n_heads) as unetpp_focal_bce_heads forms it;  loss[1 + h] = L_h;
+ *   loss[1 + n_heads + h] = S_h;  loss[1 + 2 * n_heads + h] = D_h;   loss holds 1 + 3 * n_heads floats;
+ *   grad[h] = g_s + w * g_d on an admitted element (g_s: unetpp_focal_bce_heads' gradient element, g_d: the same rule
+ *             against q, both with the factor 1 / n_heads; one rounded product, one rounded sum), g_s itself on an element
+ *             that is not admitted and on every element of the deepest head; grad[h] may be NULL.
+ * Admitted: gate = 0: every element.  gate = 1: where |q - t| < |p - t|, a float32 comparison of the absolute values of the
+ * two float32 differences (false with a NaN on either side).  ignore = 1: an element with t < 0.0f has S term and g_s +0.0,
+ * counts as having passed the gate, and is admitted iff distill_ignored = 1.
+ * partial: workspace of 2 * n_heads * unetpp_focal_bce_blocks(n) floats.  weight: one float32 on the device, finite and
+ * >= 0 (not checked: the call does not read it on the host).  Two launches, no host synchronisation, no atomics: two runs
+ * give the same bits, and a captured call follows later changes of weight[0].  UNETPP_EINVAL, without touching the device,
+ * for a NULL pointer (grad[h] excepted), n < 1, rows < 1, n_heads outside 1 .. UNETPP_MAX_HEADS, a negative or NaN gamma,
+ * a flag outside its values, target or a pred[h] / grad[h] not 16-byte aligned, weight not 4-byte aligned. */
+#define UNETPP_DISTILL_LAST 0
+#define UNETPP_DISTILL_NEXT 1
+int unetpp_distill_heads(const unetpp_focal_heads* heads, const float* target, int64_t n, int64_t rows, float gamma,
+                         const float* weight, int32_t teacher, int32_t gate, int32_t ignore, int32_t distill_ignored,
+                         float* partial, float* loss /* [1 + 3 * n_heads] */, void* stream);
 /* ---- ensemble head of an eval forward (added within v12: new entry points only, nothing existing changes) ----
  * The output selection the UNet++ authors left as comments in models/unet.py:293-298: the mean of the first n_heads
  * deep-supervision heads, out = (((s_1 + s_2) + ...) + s_n) / (float)n with s_h = 1 / (1 + exp(-(bias_h + x_h . w_h)))

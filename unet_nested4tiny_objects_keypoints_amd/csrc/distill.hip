@@ -1,0 +1,277 @@
+// Self-distillation across the deep-supervision heads (losses.HeadDistillLoss): FocalLoss_BCE_2d of every head against
+// the target, plus the same element rule of every shallower head against a deeper head's map -- its teacher, read as data:
+// no gradient reaches a head through its role as teacher.  For heads p_0 .. p_{J-1} (shallow to deep), target t, weight w:
+//   teacher of head j < J-1:  the deepest head ("last") or head j + 1 ("next");  the deepest head has none;
+//   S_j = sum l(p_j, t) / rows,   D_j = sum over the admitted elements of l(p_j, q) / rows  (q: the teacher's element),
+//   L_j = S_j + w D_j (one rounded product, one rounded sum),  D_{J-1} = +0.0,
+//   loss[0] = (0 + L_0 + ... + L_{J-1}) * (1 / J) as focal_bce_heads_finish_kernel (caller.hip) forms it,
+//   grad_j = g_s + w g_d per admitted element (one rounded product, one rounded sum); g_s itself, with its bits, on an
+//            element that is kept out of D_j and on every element of the deepest head.
+// l, g_s and g_d are focal_element.h's rule (distill_element below) with the same inv_rows and scale = float32(1 / J);
+// S_j and the supervised gradients are unetpp_focal_bce_heads' bits, D_j without gate and ignore rule is
+// unetpp_focal_bce(p_j, q)'s.
+// An element is admitted to D_j
+//   gate:    where |q - t| < |p - t|, a float32 comparison of the absolute values of the two float32 differences (a NaN on
+//            either side compares false and keeps the element out);
+//   ignore:  an ignored element (t < 0.0f; S term and g_s are +0.0 as in unetpp_focal_bce_heads_ignore) passes the gate
+//            and keeps its distillation term when distill_ignored is set, and is kept out when it is not.
+// One main launch in the grid and per-thread layout of focal_bce_heads_kernel: a thread reads its 8 targets once and walks
+// the heads from the deepest to the shallowest with the teacher's 8 values in registers, so every map is read once and
+// every gradient written once.  Two partial sums per head and block (S, D), each in the order focal_bce_kernel uses for
+// its one sum: the thread's 8 in index order, 6 shuffles, ((r0 + r1) + (r2 + r3)) * inv_rows; then a one-block finish
+// (1024 strided sums, a 10-level tree).  w is read from device memory, so a captured graph follows a schedule of w.
+// No atomics; the result depends on the inputs alone.
+#include "common.h"
+
+namespace unetpp {
+namespace {
+
+constexpr int kLossThreads = 256;
+constexpr int kLossPerThread = 8;  // elements per thread: 2 x float4, as caller.hip
+constexpr int kVecs = kLossPerThread / 4;
+
+// a + w * b in two roundings.  Left to the compiler the pair becomes one fma, which is neither what float32 tensor
+// arithmetic over the two stored gradients gives nor the S_j and D_j this call reports.
+__device__ __forceinline__ float distill_combine(float a, float w, float b) {
+#pragma clang fp contract(off)
+  const float wb = w * b;
+  return a + wb;
+}
+
+__device__ __forceinline__ void distill_load(const float* __restrict__ src, long base, long n, float (&v)[kVecs][4]) {
+#pragma unroll
+  for (int h = 0; h < kVecs; ++h) {
+    const long i = base + 4 * h;
+    if (i + 4 <= n) {
+      const f32x4 q = *reinterpret_cast<const f32x4*>(src + i);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[h][e] = q[e];
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[h][e] = (i + e < n) ? src[i + e] : 0.f;
+    }
+  }
+}
+
+__device__ __forceinline__ void distill_store(float* __restrict__ grad, long i, long n, const float (&g)[4]) {
+  if (grad == nullptr) return;
+  if (i + 4 <= n) {
+    *reinterpret_cast<f32x4*>(grad + i) = f32x4{g[0], g[1], g[2], g[3]};
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (i + e < n) grad[i + e] = g[e];
+  }
+}
+
+struct DistillFlags {
+  int next;             // teacher: the head visited before this one (j + 1) instead of the deepest
+  int gate;             // teacher_better
+  int distill_ignored;  // kIgnore only: an ignored element keeps its distillation term
+};
+
+// One element of FocalLoss_BCE_2d with every rounding written out: focal_element.h's statements in their order, compiled
+// without contraction, and the loss term handed out as its two factors.  The bits focal_element has in caller.hip are
+// not those of a plain inlining here: there the vectoriser pairs u^(gamma-1) u with gamma u^(gamma-1) log e into one
+// packed product, which leaves `gamma u^(gamma-1) log e - u^gamma / e` a rounded product and a rounded difference, and the
+// only fused operation is `sum += le` (an fma of log e and u^gamma; with kLow, where le goes through a select, a plain sum).
+// With two elements per pixel in one loop the vectoriser pairs other products, the backend fuses that difference for some
+// elements and not for others, and the term reaches the sum through a select.  Written out, the bits do not depend on
+// either: they are unetpp_focal_bce's and unetpp_focal_bce_heads' (tests/test_gpu_distill.py holds them against both).
+template <bool kLow>
+__device__ __forceinline__ void distill_element(float p, float t, float gamma, bool cube, float inv_rows, float scale,
+                                                float& lg, float& ug, float& le, float& g) {
+#pragma clang fp contract(off)
+  const float d = p - t;
+  const float err = (1.f - fabsf(d)) + 1e-20f;
+  const float u = 1.f - err;
+  lg = logf(err);
+  const float ug1 = cube ? u * u : powf(u, gamma - 1.f);  // u^(gamma-1)
+  ug = ug1 * u;
+  le = -ug * lg;
+  float dl_de = gamma * ug1 * lg - ug / err;
+  if constexpr (kLow) {
+    if (u == 0.f) {
+      le = 0.f;
+      dl_de = (gamma == 0.f) ? -1.f / err : 0.f;
+    }
+  }
+  const float sgn = (d > 0.f) ? 1.f : ((d < 0.f) ? -1.f : 0.f);
+  g = (-dl_de * sgn * inv_rows) * scale;
+}
+
+// sum += le as focal_thread (caller.hip) compiles it
+template <bool kLow>
+__device__ __forceinline__ float distill_add_term(float sum, float lg, float ug, float le) {
+  if constexpr (kLow) {
+    return sum + le;
+  } else {
+    return __builtin_fmaf(-lg, ug, sum);
+  }
+}
+
+// One head of one thread.  kStudent: q holds the teacher's elements and sum_d receives the distillation terms.
+template <bool kLow, bool kIgnore, bool kStudent>
+__device__ __forceinline__ void distill_head(const float (&p)[kVecs][4], const float (&t)[kVecs][4],
+                                             const float (&q)[kVecs][4], float* __restrict__ grad, long base, long n,
+                                             float gamma, float inv_rows, float scale, float w, const DistillFlags f,
+                                             float& sum_s, float& sum_d) {
+#pragma clang fp contract(off)
+  const bool cube = gamma == 3.f;
+  sum_s = 0.f;
+  sum_d = 0.f;
+#pragma unroll
+  for (int h = 0; h < kVecs; ++h) {
+    const long i = base + 4 * h;
+    if (i >= n) break;
+    float g[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float lg, ug, le, gs;
+      distill_element<kLow>(p[h][e], t[h][e], gamma, cube, inv_rows, scale, lg, ug, le, gs);
+      const bool inside = i + e < n;
+      bool take = inside;
+      bool ignored = false;
+      if constexpr (kIgnore) {
+        if (t[h][e] < 0.f) ignored = true, take = false, gs = 0.f;
+      }
+      if (take) sum_s = distill_add_term<kLow>(sum_s, lg, ug, le);
+      if constexpr (kStudent) {
+        float gd;
+        distill_element<kLow>(p[h][e], q[h][e], gamma, cube, inv_rows, scale, lg, ug, le, gd);
+        bool admit = true;
+        if (f.gate) admit = fabsf(q[h][e] - t[h][e]) < fabsf(p[h][e] - t[h][e]);
+        if constexpr (kIgnore) {
+          if (ignored) admit = f.distill_ignored != 0;
+        }
+        if (admit && inside) sum_d = distill_add_term<kLow>(sum_d, lg, ug, le);
+        g[e] = admit ? distill_combine(gs, w, gd) : gs;   // kept out: the supervised gradient's own bits
+      } else {
+        g[e] = gs;
+      }
+    }
+    distill_store(grad, i, n, g);
+  }
+}
+
+template <bool kLow, bool kIgnore>
+__global__ __launch_bounds__(kLossThreads) void distill_heads_kernel(const unetpp_focal_heads hd,
+                                                                    const float* __restrict__ target, long n, float gamma,
+                                                                    float inv_rows, float scale,
+                                                                    const float* __restrict__ weight, const DistillFlags f,
+                                                                    float* __restrict__ partial) {
+  __shared__ float red[2][UNETPP_MAX_HEADS][kLossThreads / 64];
+  const long base = (blockIdx.x * static_cast<long>(kLossThreads) + threadIdx.x) * kLossPerThread;
+  const float w = weight[0];
+  float t[kVecs][4], p[kVecs][4];
+  float q[kVecs][4] = {};   // the teacher's elements (set by the deepest head before a student reads them)
+  distill_load(target, base, n, t);
+  const int last = hd.n_heads - 1;
+  for (int h = last; h >= 0; --h) {
+    distill_load(hd.pred[h], base, n, p);
+    float sum_s, sum_d;
+    if (h == last)
+      distill_head<kLow, kIgnore, false>(p, t, q, hd.grad[h], base, n, gamma, inv_rows, scale, w, f, sum_s, sum_d);
+    else
+      distill_head<kLow, kIgnore, true>(p, t, q, hd.grad[h], base, n, gamma, inv_rows, scale, w, f, sum_s, sum_d);
+    if (h == last || f.next) {
+#pragma unroll
+      for (int v = 0; v < kVecs; ++v)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) q[v][e] = p[v][e];
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+      sum_s += __shfl_xor(sum_s, off);
+      sum_d += __shfl_xor(sum_d, off);
+    }
+    if ((threadIdx.x & 63) == 0) {
+      red[0][h][threadIdx.x >> 6] = sum_s;
+      red[1][h][threadIdx.x >> 6] = sum_d;
+    }
+  }
+  __syncthreads();
+  if (static_cast<int>(threadIdx.x) < 2 * hd.n_heads) {
+    const int h = threadIdx.x >> 1, k = threadIdx.x & 1;
+    const float* r = red[k][h];
+    partial[static_cast<long>(threadIdx.x) * gridDim.x + blockIdx.x] = ((r[0] + r[1]) + (r[2] + r[3])) * inv_rows;
+  }
+}
+
+// the sum of n_blocks partials in focal_bce_finish_kernel's order, valid in thread 0
+__device__ __forceinline__ float distill_finish_sum(const float* __restrict__ partial, long n_blocks, float* red) {
+  float s = 0.f;
+  for (long i = threadIdx.x; i < n_blocks; i += 1024) s += partial[i];
+  __syncthreads();  // (the previous sum's red[0] has been read)
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int w = 512; w >= 1; w >>= 1) {
+    if (static_cast<int>(threadIdx.x) < w) red[threadIdx.x] += red[threadIdx.x + w];
+    __syncthreads();
+  }
+  return red[0];
+}
+
+// one block: S_h and D_h as focal_bce_finish_kernel sums them, L_h = S_h + w D_h, then the trainer's mean over heads in
+// its order (focal_bce_heads_finish_kernel).  loss: [0] the mean, [1 + h] L_h, [1 + H + h] S_h, [1 + 2 H + h] D_h.
+__global__ __launch_bounds__(1024) void distill_finish_kernel(const float* __restrict__ partial, long n_blocks, int n_heads,
+                                                              float inv_heads, const float* __restrict__ weight,
+                                                              float* __restrict__ loss) {
+  __shared__ float red[1024];
+  const float w = weight[0];
+  float avg = 0.f;
+  for (int h = 0; h < n_heads; ++h) {
+    const float s = distill_finish_sum(partial + (2 * h) * n_blocks, n_blocks, red);
+    const float d = distill_finish_sum(partial + (2 * h + 1) * n_blocks, n_blocks, red);
+    if (threadIdx.x == 0) {
+      const float l = distill_combine(s, w, d);
+      loss[1 + h] = l;
+      loss[1 + n_heads + h] = s;
+      loss[1 + 2 * n_heads + h] = d;
+      avg = avg + l;
+    }
+  }
+  if (threadIdx.x == 0) loss[0] = (1.0f * avg) * inv_heads;
+}
+
+}  // namespace
+}  // namespace unetpp
+
+using namespace unetpp;
+
+extern "C" int unetpp_distill_heads(const unetpp_focal_heads* heads, const float* target, int64_t n, int64_t rows, float gamma,
+                                    const float* weight, int32_t teacher, int32_t gate, int32_t ignore,
+                                    int32_t distill_ignored, float* partial, float* loss, void* stream) {
+  if (heads == nullptr || target == nullptr || weight == nullptr || partial == nullptr || loss == nullptr || n < 1 || rows < 1)
+    return UNETPP_EINVAL;
+  if (heads->n_heads < 1 || heads->n_heads > UNETPP_MAX_HEADS) return UNETPP_EINVAL;
+  if ((teacher != UNETPP_DISTILL_LAST && teacher != UNETPP_DISTILL_NEXT) || (gate != 0 && gate != 1) ||
+      (ignore != 0 && ignore != 1) || (distill_ignored != 0 && distill_ignored != 1))
+    return UNETPP_EINVAL;
+  if (!(gamma >= 0.f)) return UNETPP_EINVAL;
+  uintptr_t bits = reinterpret_cast<uintptr_t>(target);
+  for (int h = 0; h < heads->n_heads; ++h) {
+    if (heads->pred[h] == nullptr) return UNETPP_EINVAL;
+    bits |= reinterpret_cast<uintptr_t>(heads->pred[h]) | reinterpret_cast<uintptr_t>(heads->grad[h]);
+  }
+  if ((bits & 15) != 0 || (reinterpret_cast<uintptr_t>(weight) & 3) != 0) return UNETPP_EINVAL;
+  const int64_t per_block = static_cast<int64_t>(kLossThreads) * kLossPerThread;
+  const int64_t blocks = (n + per_block - 1) / per_block;   // unetpp_focal_bce_blocks(n)
+  if (blocks > 0x7fffffffLL) return UNETPP_EINVAL;
+  unetpp_focal_heads hd = *heads;
+  for (int h = hd.n_heads; h < UNETPP_MAX_HEADS; ++h) hd.pred[h] = nullptr, hd.grad[h] = nullptr;
+  const float inv_heads = 1.0f / static_cast<float>(hd.n_heads);
+  DistillFlags f;
+  f.next = teacher == UNETPP_DISTILL_NEXT;
+  f.gate = gate;
+  f.distill_ignored = distill_ignored;
+  const bool low = gamma < 1.f;
+  const auto kernel = ignore ? (low ? distill_heads_kernel<true, true> : distill_heads_kernel<false, true>)
+                             : (low ? distill_heads_kernel<true, false> : distill_heads_kernel<false, false>);
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(blocks)), dim3(kLossThreads), 0, st, hd, target, static_cast<long>(n),
+                     gamma, 1.f / static_cast<float>(rows), inv_heads, weight, f, partial);
+  hipLaunchKernelGGL(distill_finish_kernel, dim3(1), dim3(1024), 0, st, static_cast<const float*>(partial),
+                     static_cast<long>(blocks), hd.n_heads, inv_heads, weight, loss);
+  return launch_status();
+}

@@ -306,3 +306,175 @@ class PenaltyReducedFocalLoss(nn.Module):
                                                 self.eps, self.positive, ignore=self.ignore_negative)
         self.last_num_positives = n_pos
         return loss[0], grads
+
+
+class _HeadDistillFn(torch.autograd.Function):
+    """``HeadDistillLoss.heads_loss``: the value and every head's gradient come from one call; backward scales them."""
+
+    @staticmethod
+    def forward(ctx, criterion, target, *outputs):
+        avg, grads = criterion.mean_over_heads(tuple(o.detach() for o in outputs), target)
+        ctx.save_for_backward(*grads)
+        return avg.clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        return (None, None) + tuple(grad * g for grad in ctx.saved_tensors)
+
+
+class HeadDistillLoss(nn.Module):
+    """Self-distillation across the deep-supervision heads: every head is trained against the labels as
+    ``FocalLoss_BCE_2d`` trains it, and every head but the deepest also against a deeper head's map -- its teacher, used
+    detached: no gradient reaches a head through its role as teacher.  For heads p_1 .. p_J (a tuple, shallow to deep,
+    as ``forward`` and ``forward_pruned`` of the network return them) and the target t:
+
+        teacher="last":  T(j) = J for j < J;   teacher="next":  T(j) = j + 1 for j < J;   head J has no teacher;
+        S_j = FocalLoss_BCE_2d(gamma, size_average, ignore_negative)(p_j, t);
+        D_j = the FocalLoss_BCE_2d(gamma, size_average) sum of p_j against p_T(j) over the admitted elements, divided by
+              S_j's divisor;  D_J = +0.0;
+        L_j = S_j + weight * D_j;   loss = the trainer's mean over heads of L_j.
+
+    gate="teacher_better" admits an element only where the teacher is closer to the target than the student,
+    ``|q - t| < |p - t|`` on the float32 differences; a NaN on either side keeps the element out.  With
+    ``ignore_negative`` an element with ``t < 0`` has a supervised term and gradient of +0.0 as in ``FocalLoss_BCE_2d``,
+    counts as having passed the gate, and keeps its distillation term when ``distill_ignored`` (the only training signal
+    inside an ignore region) or is kept out when not.
+
+    ``weight`` (finite, >= 0) lives in a one-element float32 tensor per device, created on first use, which the kernel
+    reads: ``set_weight(w)`` changes it with a ``fill_``, so a captured ``GraphedTrainStep`` follows a warm-up schedule of
+    the weight without a new capture.
+
+    ``forward(input, target)`` takes ONE map, which has no teacher: it returns ``FocalLoss_BCE_2d``'s value with the same
+    bits, so a per-head loop (``validate_step``, a ``no_grad`` report) shows the supervised loss.  The distillation term
+    exists only over the tuple of heads: ``mean_over_heads`` (what ``train_step`` and ``GraphedTrainStep`` call) and
+    ``heads_loss``.  GPU fp32 heads take one fused HIP call (csrc/distill.hip: every map read once, value and gradients
+    together); anything else the same rule as plain torch ops.  After a call over the heads ``last_supervised`` and
+    ``last_distill`` hold S_j and D_j as [heads] tensors on the device of the target; the class never reads them back.
+
+    Deliberately not a subclass of ``FocalLoss_BCE_2d``: code that tests for that class computes the loss without the
+    distillation term."""
+
+    def __init__(self, weight=0.5, teacher="last", gate="none", distill_ignored=True, gamma=3, size_average=False,
+                 ignore_negative=False):
+        super().__init__()
+        if teacher not in ("last", "next"):
+            raise ValueError("teacher must be 'last' or 'next', got %r" % (teacher,))
+        if gate not in ("none", "teacher_better"):
+            raise ValueError("gate must be 'none' or 'teacher_better', got %r" % (gate,))
+        if not float(gamma) >= 0.0:
+            raise ValueError("gamma must be >= 0, got %r" % (gamma,))
+        self.teacher, self.gate = teacher, gate
+        self.distill_ignored = bool(distill_ignored)
+        self.gamma = gamma
+        self.size_average = size_average
+        self.ignore_negative = bool(ignore_negative)
+        self._supervised = FocalLoss_BCE_2d(gamma=gamma, size_average=size_average, ignore_negative=ignore_negative)
+        self._weight_dev = {}   # device -> the one-element float32 tensor the kernel reads
+        self.weight = self._checked_weight(weight)
+        self.last_supervised = None
+        self.last_distill = None
+
+    @staticmethod
+    def _checked_weight(w):
+        if isinstance(w, bool) or torch.is_tensor(w):
+            raise TypeError("weight must be a Python number (the class keeps the device tensor itself)")
+        w32 = float(torch.tensor(float(w), dtype=torch.float32))
+        if not 0.0 <= w32 < float("inf"):
+            raise ValueError("weight must be a finite float32 >= 0, got %r" % (w,))
+        return w32
+
+    def set_weight(self, w):
+        """The weight of the distillation term from now on: a ``fill_`` of the device tensors, no host synchronisation;
+        a captured step reads the new value at its next replay."""
+        self.weight = self._checked_weight(w)
+        for t in self._weight_dev.values():
+            t.fill_(self.weight)
+
+    def weight_tensor(self, device):
+        """the one-element float32 tensor on `device` that holds the weight (created on first use)"""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        t = self._weight_dev.get(device)
+        if t is None:
+            t = self._weight_dev[device] = torch.full((1,), self.weight, dtype=torch.float32, device=device)
+        return t
+
+    def forward(self, input, target):
+        return self._supervised(input, target)
+
+    def _teacher_of(self, j, heads):
+        return heads - 1 if self.teacher == "last" else j + 1
+
+    def _rule(self, outputs, target):
+        """the rule as plain torch ops -> (avg with a graph, S [heads], D [heads])"""
+        heads = len(outputs)
+        dtype = outputs[0].dtype
+        rows = target.numel() if self.size_average else target.numel() // (target.size(-2) * target.size(-1))
+        w = self.weight_tensor(target.device)[0].to(dtype)
+        ignored = (target < 0) if self.ignore_negative else None
+        sup, dis = [], []
+        avg = 0
+        for j, p in enumerate(outputs):
+            s = self._supervised(p, target)
+            if j < heads - 1:
+                q = outputs[self._teacher_of(j, heads)].detach()
+                admit = torch.ones_like(target, dtype=torch.bool)
+                if self.gate == "teacher_better":
+                    admit = (q - target).abs() < (p.detach() - target).abs()
+                if ignored is not None:
+                    admit = torch.where(ignored, torch.full_like(admit, self.distill_ignored), admit)
+                # (finite operands under an element that is kept out: autograd's 0 * NaN through where is a NaN)
+                d = torch.where(admit, p - q, torch.full_like(p, 0.5))
+                error = 1 - torch.abs(d) + 1e-20
+                term = -1 * (1 - error) ** self.gamma * torch.log(error)
+                dj = torch.where(admit, term, torch.zeros_like(term)).sum() / rows
+            else:
+                dj = torch.zeros((), dtype=dtype, device=target.device)
+            sup.append(s.detach())
+            dis.append(dj.detach())
+            avg = avg + (s + w * dj)
+        avg = 1.0 * avg / heads
+        return avg, torch.stack(sup), torch.stack(dis)
+
+    def _check_heads(self, outputs, target):
+        from . import _lib
+        if not isinstance(outputs, (tuple, list)) or not 1 <= len(outputs) <= _lib.MAX_HEADS:
+            raise ValueError("HeadDistillLoss takes a tuple of 1 to %d heads" % _lib.MAX_HEADS)
+        if target.dim() < 3:
+            raise ValueError("target must be [..., H, W]")
+        for o in outputs:
+            if o.shape != target.shape:
+                raise ValueError("every head must have the shape of the target")
+
+    def mean_over_heads(self, outputs, target):
+        """The loss over the tuple of heads and its gradients in one call -> (avg: 0-dim tensor without a graph,
+        [d avg / d output]) for 1 to ``MAX_HEADS`` heads; more raise.  Fp32 contiguous GPU heads take the fused launch;
+        anything else the same rule as torch ops with the gradients from ``torch.autograd.grad``.  Never None: the
+        written-out loop the caller would fall back to calls ``forward`` per head and would train without the
+        distillation term."""
+        from . import ops
+        self._check_heads(outputs, target)
+        fused = (target.is_cuda and target.dtype == torch.float32 and not target.requires_grad and
+                 all(o.is_cuda and o.dtype == torch.float32 and o.is_contiguous() and o.device == target.device
+                     for o in outputs))
+        if fused:
+            t = target.contiguous()
+            rows = t.numel() if self.size_average else t.numel() // (t.size(-2) * t.size(-1))
+            loss, grads, sup, dis = ops.distill_heads([o.detach() for o in outputs], t, rows, float(self.gamma),
+                                                      self.weight_tensor(t.device), self.teacher, self.gate,
+                                                      ignore=self.ignore_negative, distill_ignored=self.distill_ignored)
+            self.last_supervised, self.last_distill = sup, dis
+            return loss[0], grads
+        with torch.enable_grad():
+            leaves = [o.detach().requires_grad_(True) for o in outputs]
+            avg, sup, dis = self._rule(leaves, target.detach())
+            grads = torch.autograd.grad(avg, leaves)
+        self.last_supervised, self.last_distill = sup, dis
+        return avg.detach(), list(grads)
+
+    def heads_loss(self, outputs, target):
+        """The loss over the tuple of heads as a differentiable 0-dim tensor, for callers that do not go through
+        ``train_step``: one autograd node whose backward is one scaling of the gradients ``mean_over_heads`` produced."""
+        self._check_heads(outputs, target)
+        return _HeadDistillFn.apply(self, target, *outputs)

@@ -1058,6 +1058,56 @@ def pr_focal_heads(preds, target: torch.Tensor, alpha: float, beta: float, eps: 
     return loss, grads, n_pos
 
 
+DISTILL_TEACHERS = {"last": _lib.DISTILL_LAST, "next": _lib.DISTILL_NEXT}
+DISTILL_GATES = {"none": 0, "teacher_better": 1}
+
+
+def distill_heads(preds, target: torch.Tensor, rows: int, gamma: float, weight_dev: torch.Tensor, teacher: str = "last",
+                  gate: str = "none", want_grad: bool = True, ignore: bool = False, distill_ignored: bool = True):
+    """focal_bce_heads with self-distillation across the heads (csrc/distill.hip, one call): every head but the deepest
+    is also held against its teacher's map -- the deepest head ("last") or the next deeper one ("next"), read as data --
+    by the same element rule, over the elements the gate ("none" / "teacher_better": where the teacher is closer to the
+    target than the student) and the ignore rule admit; L_h = S_h + w D_h with w = weight_dev[0], read on the device.
+    preds: shallow to deep.
+    -> (losses [1 + heads]: the mean over heads of L_h, then every L_h; d mean / d pred per head or None;
+    supervised [heads]: S_h, focal_bce_heads' values bit for bit; distill [heads]: D_h, +0.0 for the deepest head).
+    ignore: a negative target element has a supervised term of +0.0, counts as having passed the gate, and keeps its
+    distillation term iff distill_ignored."""
+    if not 1 <= len(preds) <= _lib.MAX_HEADS:
+        raise ValueError("1 to %d heads" % _lib.MAX_HEADS)
+    if teacher not in DISTILL_TEACHERS:
+        raise ValueError("teacher must be one of %s, got %r" % (sorted(DISTILL_TEACHERS), teacher))
+    if gate not in DISTILL_GATES:
+        raise ValueError("gate must be one of %s, got %r" % (sorted(DISTILL_GATES), gate))
+    if not torch.is_tensor(weight_dev) or weight_dev.numel() != 1:
+        raise ValueError("weight_dev must be a tensor of one element")
+    if weight_dev.dtype != torch.float32:
+        raise TypeError("weight_dev must be torch.float32, got %s" % weight_dev.dtype)
+    if weight_dev.device != target.device:
+        raise ValueError("weight_dev must live on the device of the target")
+    lib = _lib.lib()
+    _need(target, "target")
+    for p in preds:
+        _need(p, "pred")
+        if p.shape != target.shape:
+            raise ValueError("pred and target must have the same shape")
+    preds, target = [_aligned16(p) for p in preds], _aligned16(target)
+    heads, n = len(preds), target.numel()
+    blocks = int(lib.unetpp_focal_bce_blocks(n))
+    partial = torch.empty(2 * heads * blocks, dtype=torch.float32, device=target.device)
+    grads = [torch.empty_like(p) for p in preds] if want_grad else None
+    loss = torch.empty(1 + 3 * heads, dtype=torch.float32, device=target.device)
+    hd = _lib.FocalHeads()
+    hd.n_heads = heads
+    for i, p in enumerate(preds):
+        hd.pred[i] = p.data_ptr()
+        hd.grad[i] = grads[i].data_ptr() if want_grad else None
+    check(lib.unetpp_distill_heads(C.byref(hd), _ptr(target), n, rows, float(gamma), _ptr(weight_dev),
+                                   DISTILL_TEACHERS[teacher], DISTILL_GATES[gate], int(bool(ignore)),
+                                   int(bool(distill_ignored)), _ptr(partial), _ptr(loss), _stream()), "unetpp_distill_heads")
+    return loss[:1 + heads], grads, loss[1 + heads:1 + 2 * heads], loss[1 + 2 * heads:]
+
+
 def create_heatmap(points: torch.Tensor, height: int, width: int, radius: float = 3.0) -> torch.Tensor:
     """points [N, P, 2] (x, y) fp32 on the GPU -> target heat maps [N, 4, H, W] (tools/misc/helper.py:87-172)."""
     lib = _lib.lib()
