@@ -975,6 +975,60 @@ int unetpp_target_ignore(const float* rects, const int32_t* rect_class, int64_t 
                          int32_t N, const float* params, int32_t C, int32_t Ho, int32_t Wo, int32_t Hs, int32_t Ws,
                          int32_t outside, float* target, void* stream);
 
+/* ---- Ignore masks (csrc/mask.hip; added within ABI version 13: new entry points only): a second producer of the same
+ * -1 elements, for outlines that are not rectangles -- raster no-data masks and polygon rings.
+ *
+ * A mask is packed bit planes: bits int32 [S, P, H, Wd] (device), Wd = ceil(W / 32); bit (x & 31) of word (x >> 5) of
+ * row y is pixel (x, y), the unused high bits of a row's last word are zero.  plane_class int32 [P]: -1 applies the
+ * plane to every class, c in 0..C-1 to class c, any other value to none -- the meanings of rect_class.
+ *
+ * The lookup rule (unetpp_target_ignore_mask; IgnoreMask.contains restates it): a float32 position (xs, ys) is in the
+ * frame iff 0 <= xs && xs <= W-1 && 0 <= ys && ys <= H-1 (a NaN is outside); its pixel is xi = clamp((int)floorf(xs +
+ * 0.5f), 0, W-1), yi likewise; it is ignored for class c iff some plane of class -1 or c has that bit set.  Outside the
+ * frame nothing is contained.
+ *
+ * The polygon rule (unetpp_mask_polygons): a pixel is its centre, the integer point (px, py).  For each used edge of a
+ * ring, the closing edge included, the endpoints are ordered so that y0 <= y1; an edge with y0 == y1 is skipped.  The
+ * edge straddles iff y0 <= py && py < y1, and then toggles the pixel iff d > 0,
+ *   d = (x1 - x0) * (py - y0) - (px - x0) * (y1 - y0)      in float64, this order, every operation rounded on its own.
+ * The pixel is inside the ring iff the number of toggles is odd.  Two rings that share an edge form the same d, so a
+ * pixel on the shared edge belongs to exactly one of them.  The rings of a plane are walked in list order: an inside
+ * pixel is set by a plain ring and cleared by a clearing ring. ---- */
+#define UNETPP_MASK_U8 0    /* unetpp_mask_pack kinds: one byte per pixel (uint8 or bool) */
+#define UNETPP_MASK_F32 1   /* float32 per pixel */
+
+/* unetpp_mask_pack: bits of `rows` rows of W pixels from a raster of `kind`: mask [rows, W] (device, contiguous), bits
+ * int32 [rows, ceil(W / 32)].  A pixel's bit is set iff !(v == 0): a NaN sets it, -0.0 does not.  A wave packs 64
+ * consecutive x of a row by one ballot into two words stored separately (no alignment demanded of a row); tail bits
+ * are zero; one writer per word, no atomics.  UNETPP_EINVAL without touching the device for a null pointer, a size
+ * <= 0, W above 2^24, an unknown kind, or rows * W above 2^31 - 1. */
+int unetpp_mask_pack(const void* mask, int32_t kind, int64_t rows, int32_t W, int32_t* bits, void* stream);
+
+/* unetpp_mask_polygons: rasterises rings into bits int32 [S, P, H, ceil(W / 32)] by the polygon rule; EVERY word is
+ * written (zero where no ring sets a bit).  vertices float32 [S, G, V, 2] as (x, y); counts int32 [S, G], the vertices
+ * used per ring -- a ring with a count outside 3..V or with a NaN / infinity in a used vertex is padding; poly_plane
+ * int32 [S, G], the plane a ring writes (outside 0..P-1: padding); poly_clear int32 [S, G], non-zero: a clearing ring.
+ * G may be 0 (the lists are then unread).  A unit is (frame, plane, 16 rows x 64 pixels); the rings whose float
+ * bounding box can matter to the tile are compacted in list order with wave ballots, their edges stream through LDS
+ * 256 at a time; the culling drops a ring only where no pixel of the tile can be inside it, so it changes no bit.  No
+ * atomics; the same bits on any grid and on every run.  UNETPP_EINVAL without touching the device for a null pointer, a
+ * size <= 0 (G, V < 0), a side above 2^24, or a word or vertex count above 2^31 - 1. */
+int unetpp_mask_polygons(const float* vertices, const int32_t* counts, const int32_t* poly_plane,
+                         const int32_t* poly_clear, int32_t S, int32_t G, int32_t V, int32_t P, int32_t H, int32_t W,
+                         int32_t* bits, void* stream);
+
+/* unetpp_target_ignore_mask: unetpp_target_ignore with the frame's rectangles replaced by the P bit planes of frame
+ * index[n] (bits int32 [M, P, Hs, ceil(Ws / 32)], plane_class int32 [P]): target[n, c, y, x] = -1.0f when the source
+ * position of (x, y) -- the same float32 expression -- is ignored for class c by the lookup rule, or when outside != 0
+ * and it lies outside the frame or index[n] outside [0, M).  Everything else is left untouched, not even read.  The
+ * cost per pixel is one word load per plane, whatever the outline.  P may be 0 (bits and plane_class then unread: the
+ * `outside` rule alone; with outside == 0 the call does nothing).  Stores of one constant, no atomics, the same bits on
+ * any grid; 64-bit offsets.  UNETPP_EINVAL without touching the device for a null pointer, a size <= 0 (P < 0),
+ * C > 65535, a side above 2^24, or a frame of more than 2^31 - 1 words. */
+int unetpp_target_ignore_mask(const int32_t* bits, const int32_t* plane_class, int64_t M, int32_t P, int32_t Hs,
+                              int32_t Ws, const int64_t* index, int32_t N, const float* params, int32_t C, int32_t Ho,
+                              int32_t Wo, int32_t outside, float* target, void* stream);
+
 /* unetpp_crops_draw: N windows of Ho x Wo pixels in M frames of Hs x Ws, one thread per sample: params [N][16], index
  * int64 [N] (the frame), origin int32 [N, 2] as (ox, oy), all on the device.  Uniforms u_k and the meaning of
  * k = 0, 1, 2, 3, 4, 7, 8 are unetpp_augment_draw's; k = 5, 6 are unused (max_tx and max_ty must be 0).  centre_frame

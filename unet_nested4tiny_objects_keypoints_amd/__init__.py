@@ -25,12 +25,12 @@ from .loader import Augment, DeviceLoader, affine_params, warp_batch  # noqa: F4
 from .scene import CascadeSceneInference, SceneInference  # noqa: F401
 from .detect import DetectionScore, Detections, PeakDetector, classes_from_pattern, evaluate  # noqa: F401
 from .crops import ObjectPaste, PasteRows, SceneCrops, false_positive_centres  # noqa: F401
-from .ignore import IgnoreRegions  # noqa: F401
+from .ignore import IgnoreMask, IgnoreRegions, IgnoreUnion  # noqa: F401
 
 __all__ = ["UNet_Nested", "UNet", "count_param", "FocalLoss_BCE_2d", "train_step", "create_heatmap", "Heatmap",
            "GraphedForward", "GraphedTrainStep", "AdamW", "AdaBound", "SGDW", "validate_step",
            "validate_outputs", "WeightAverager", "clip_grad_norm_", "DeviceLoader", "Augment", "affine_params",
            "warp_batch", "SceneInference", "CascadeSceneInference", "PeakDetector", "Detections", "DetectionScore",
            "evaluate", "classes_from_pattern", "SceneCrops", "false_positive_centres", "TopKFocalLoss_BCE_2d",
-           "pruned_parameters", "PenaltyReducedFocalLoss", "IgnoreRegions", "McMaps", "ObjectPaste",
+           "pruned_parameters", "PenaltyReducedFocalLoss", "IgnoreRegions", "IgnoreMask", "IgnoreUnion", "McMaps", "ObjectPaste",
            "PasteRows", "HeadDistillLoss"]

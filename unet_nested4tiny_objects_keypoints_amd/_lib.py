@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("UNETPP_LIB", os.path.join(_PKG_DIR, "libunetpp_hip.so
 CSRC = os.path.join(_PKG_DIR, "csrc")
 INCLUDE = os.path.join(_REPO, "include")
 SOURCES = ("gemm_pix.hip", "gemm_fast.hip", "gemm_pw.hip", "gemm_pw_bf16.hip", "gemm_wino.hip", "gemm_bf16.hip", "gemm_bf16_dma.hip", "wgrad_bf16.hip", "pointwise_bf16.hip", "keypoints.hip", "weight_image.hip", "wgrad.hip", "wgrad_fast.hip", "wgrad_dma.hip", "wgrad_pw.hip", "wgrad_wino.hip", "first_layer.hip", "pointwise.hip", "heads.hip", "caller.hip", "optim.hip", "validate.hip", "average.hip", "loader.hip", "scene.hip",
-           "detect.hip", "crops.hip", "topk_loss.hip", "pr_focal.hip", "paste.hip", "distill.hip")
+           "detect.hip", "crops.hip", "topk_loss.hip", "pr_focal.hip", "paste.hip", "distill.hip", "mask.hip")
 HEADERS = ("common.h", "gemm_units.h", "wgrad_reduce.h", "lds_asm.h", "bf16_common.h", "dropout.h", "bn_fused.h",
            "wino_experiments.h", "dma_experiments.h", "heads_mean.h", "head_select.h", "head_mc_select.h", "focal_element.h", "multi_tensor.h")
 MAX_VIEWS = 8
@@ -204,6 +204,7 @@ MC_MAX_SAMPLES = 32                                # UNETPP_MC_MAX_SAMPLES: drop
 MC_SEED_STEP = 0xD6E8FEB86659FD93                  # sample k of unetpp_head_mc draws from seed + MC_SEED_STEP * k
 DISTILL_LAST, DISTILL_NEXT = 0, 1                  # unetpp_distill_heads teachers
 PASTE_MAX_SLOTS, PASTE_MAX_RADIUS = 64, 16         # UNETPP_PASTE_MAX_SLOTS / _RADIUS: slots of a window, patch radius
+MASK_U8, MASK_F32 = 0, 1                           # unetpp_mask_pack kinds
 
 _P, _I32, _I64, _F, _U64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_uint64
 
@@ -336,6 +337,11 @@ SIGNATURES = {
     # self-distillation across the heads: the deep head's map as a soft target of the shallow ones (distill.hip; added
     # within ABI 13)
     "unetpp_distill_heads": (C.c_int, [C.POINTER(FocalHeads), _P, _I64, _I64, _F, _P, _I32, _I32, _I32, _I32, _P, _P, _P]),
+    # ignore masks: packed bit planes from a raster or from polygon rings, and the per-step mark (mask.hip; added within
+    # ABI 13)
+    "unetpp_mask_pack": (C.c_int, [_P, _I32, _I64, _I32, _P, _P]),
+    "unetpp_mask_polygons": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P]),
+    "unetpp_target_ignore_mask": (C.c_int, [_P, _P, _I64, _I32, _I32, _I32, _P, _I32, _P, _I32, _I32, _I32, _I32, _P, _P]),
 }
 
 _LIB = None

@@ -36,7 +36,7 @@ from typing import NamedTuple, Optional, Tuple
 import torch
 
 from . import _lib, ops
-from .ignore import IgnoreRegions
+from .ignore import IgnoreMask, IgnoreRegions, IgnoreUnion
 from .loader import Augment, _channels, _per_channel, _source_size
 
 __all__ = ["SceneCrops", "ObjectPaste", "PasteRows", "false_positive_centres"]
@@ -85,13 +85,14 @@ def paste_alpha(patch_radius: int, core: float) -> torch.Tensor:
 
 
 def paste_source_table(labels: torch.Tensor, label_class: torch.Tensor, n_classes: int, src_size, patch_radius: int,
-                       ignore: Optional[IgnoreRegions] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                       ignore=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """(frame [T] int32, xy [T, 2] float32, cls [T] int32) of the labels whose patch can be pasted, on the labels' device:
     labels [S, L, 2] float32 and label_class [S, L] of frames of src_size = (Hs, Ws).  A label is admitted when it is valid
     (class in [0, n_classes), no negative coordinate), the (2R+1) x (2R+1) patch about its rounded centre c = floor(xy +
     0.5) lies inside the frame, no other valid label of the frame lies within Chebyshev distance R + 1 of c (the patch
-    then holds exactly one object), and c lies in no rectangle of `ignore` of its frame.  Torch ops, frame by frame; the
-    length depends on the data, so this synchronises with the host: for a constructor, not for the training loop."""
+    then holds exactly one object), and c lies in no rectangle of `ignore` of its frame -- for an ``IgnoreMask`` or an
+    ``IgnoreUnion``: ``ignore.contains`` is false at c for the label's class.  Torch ops, frame by frame; the length
+    depends on the data, so this synchronises with the host: for a constructor, not for the training loop."""
     r, (hs, ws) = int(patch_radius), (int(src_size[0]), int(src_size[1]))
     xy = labels.to(torch.float64)
     cls = label_class.to(torch.int64)
@@ -104,7 +105,11 @@ def paste_source_table(labels: torch.Tensor, label_class: torch.Tensor, n_classe
         crowd = (cheb <= r + 1) & valid[s].unsqueeze(0)
         crowd.fill_diagonal_(False)
         ok[s] &= ~crowd.any(dim=1)
-    if ignore is not None and int(ignore.rects.shape[1]) > 0:
+    if isinstance(ignore, (IgnoreMask, IgnoreUnion)):
+        frame = torch.arange(int(labels.shape[0]), device=labels.device).view(-1, 1)
+        known = torch.where(valid, cls, torch.full_like(cls, -2))      # (an invalid label is dropped anyway)
+        ok &= ~ignore.contains(frame, known, c.to(torch.float32)).to(labels.device)
+    elif ignore is not None and int(ignore.rects.shape[1]) > 0:
         rc = ignore.rects.to(labels.device).to(torch.float64).unsqueeze(1)         # [S, 1, R, 4]
         k = ignore.rect_class.to(labels.device).unsqueeze(1)
         cx, cy = c[..., 0].unsqueeze(-1), c[..., 1].unsqueeze(-1)
@@ -157,7 +162,7 @@ class ObjectPaste:
         f, xy, c = paste_source_table(crops.labels, crops.label_class, crops.n_classes, crops.src_size, r, crops.ignore)
         if f.numel() == 0:
             raise ValueError("no label can be pasted: none is valid, %d pixels inside its frame, alone in its patch and "
-                             "outside every ignore rectangle" % r)
+                             "outside every ignore region" % r)
         self.src_frame, self.src_xy, self.src_class = f, xy, c
 
     def set_sources(self, frame, xy, cls) -> None:
@@ -195,7 +200,10 @@ class SceneCrops:
     ignore: an ``IgnoreRegions`` over the same frames -- target = -1 where the pixel's source position lies in one of
     the frame's rectangles (class -1: every class map; class c: map c), whatever label is there; ignore_outside: also
     where it lies outside the frame (a bilinear neighbour is `fill`), and all of an all-fill sample.  Either makes
-    batch(n) a fourth launch (unetpp_target_ignore) after the targets, still without a host synchronisation.
+    batch(n) a fourth launch (unetpp_target_ignore) after the targets, still without a host synchronisation.  An
+    ``IgnoreMask`` of the frames' size (bit planes from a raster or from polygons) marks by one bit lookup per pixel and
+    plane instead (unetpp_target_ignore_mask); an ``IgnoreUnion`` takes one launch per part, and ignore_outside is
+    applied by exactly one of them.
 
     paste: an ``ObjectPaste`` -- batch(n) then also copies objects of its source table into the windows (three more
     launches: unetpp_paste_draw, unetpp_paste_apply after the warp, unetpp_paste_target after the targets and before the
@@ -261,10 +269,13 @@ class SceneCrops:
         self.ignore_outside = bool(ignore_outside)
         self.ignore = None
         if ignore is not None:
-            if not isinstance(ignore, IgnoreRegions):
-                raise TypeError("ignore must be an IgnoreRegions")
+            if not isinstance(ignore, (IgnoreRegions, IgnoreMask, IgnoreUnion)):
+                raise TypeError("ignore must be an IgnoreRegions, an IgnoreMask or an IgnoreUnion")
             if len(ignore) != s:
                 raise ValueError("ignore holds %d frames, the scenes %d" % (len(ignore), s))
+            for part in ignore.parts if isinstance(ignore, IgnoreUnion) else (ignore,):
+                if isinstance(part, IgnoreMask) and tuple(part.size) != tuple(self.src_size):
+                    raise ValueError("an ignore mask of %d x %d over frames of %d x %d" % (part.size + tuple(self.src_size)))
             self.ignore = ignore.to(self.device)
         self.paste, self.last_paste = None, None
         if paste is not None:
@@ -313,8 +324,16 @@ class SceneCrops:
             self.last_paste = rows
         if self.ignore is not None or self.ignore_outside:
             ign = self.ignore
-            ops.target_ignore(target, ign.rects if ign is not None else None, ign.rect_class if ign is not None else None,
-                              index, params, self.src_size, self.ignore_outside, n_frames=len(self))
+            parts = ign.parts if isinstance(ign, IgnoreUnion) else (ign,)
+            for i, part in enumerate(parts):
+                outside = self.ignore_outside and i == 0          # applied by exactly one launch
+                if isinstance(part, IgnoreMask):
+                    ops.target_ignore_mask(target, part.bits, part.plane_class, index, params, self.src_size, outside,
+                                           n_frames=len(self))
+                else:
+                    ops.target_ignore(target, part.rects if part is not None else None,
+                                      part.rect_class if part is not None else None, index, params, self.src_size,
+                                      outside, n_frames=len(self))
         self.last = (params, index, origin)
         return inputs, target, points, inside
 

@@ -170,8 +170,9 @@ def evaluate(dets: Detections, labels, label_class, tolerance: float,
     inclusive) that no brighter detection took, ties to the lowest label index (unetpp_detect_match).
     score_threshold: detections below it are dropped before matching.  ignore: an ``IgnoreRegions`` over the same frames
     -- a detection inside a rectangle of its frame and class (or of every class) is dropped before matching, neither a
-    true nor a false positive; a label inside one becomes padding, neither matched nor a false negative.  Nothing is
-    read back."""
+    true nor a false positive; a label inside one becomes padding, neither matched nor a false negative.  An
+    ``IgnoreMask`` or an ``IgnoreUnion`` serves as well: only ``len``, ``to`` and ``contains`` are used, and a mask's
+    ``contains`` looks up the nearest pixel's bit (ignore.py).  Nothing is read back."""
     xy, score, count = dets.xy, dets.score, dets.count
     dev = xy.device
     S, C, cap = (int(v) for v in score.shape)

@@ -1591,6 +1591,103 @@ def target_ignore(target: torch.Tensor, rects: Optional[torch.Tensor], rect_clas
     return target
 
 
+def mask_pack(mask: torch.Tensor) -> torch.Tensor:
+    """One launch: packs a raster mask [..., H, W] (bool, uint8 or float32; another type is compared with zero first)
+    into bit planes int32 [..., H, ceil(W / 32)]: bit x & 31 of word x >> 5 is pixel x, set iff the pixel is non-zero (a
+    NaN is, -0.0 is not); tail bits are zero (include/unetpp_hip.h: unetpp_mask_pack)."""
+    if not mask.is_cuda:
+        raise RuntimeError("mask must live on the GPU: this path has no CPU fallback")
+    if mask.dim() < 2:
+        raise ValueError("mask must be [..., H, W]")
+    if mask.dtype == torch.bool:
+        src, kind = mask.contiguous().view(torch.uint8), _lib.MASK_U8
+    elif mask.dtype == torch.uint8:
+        src, kind = mask.contiguous(), _lib.MASK_U8
+    elif mask.dtype == torch.float32:
+        src, kind = mask.contiguous(), _lib.MASK_F32
+    else:
+        src, kind = (mask != 0).contiguous().view(torch.uint8), _lib.MASK_U8
+    w = int(mask.shape[-1])
+    rows = int(mask.numel()) // max(w, 1)
+    if w < 1 or rows < 1:
+        raise ValueError("mask must hold at least one pixel")
+    if rows * w > 2 ** 31 - 1:
+        raise ValueError("a mask of more than 2^31 - 1 pixels must be packed in parts")
+    bits = torch.empty(tuple(mask.shape[:-1]) + ((w + 31) // 32,), dtype=torch.int32, device=mask.device)
+    _timed_call("mask_pack", 0.0, lambda: check(_lib.lib().unetpp_mask_pack(
+        _ptr(src), kind, rows, w, _ptr(bits), _stream()), "unetpp_mask_pack"), float(src.element_size() * rows * w))
+    return bits
+
+
+def mask_polygons(vertices: torch.Tensor, counts: torch.Tensor, poly_plane: torch.Tensor, poly_clear: torch.Tensor,
+                  planes: int, size) -> torch.Tensor:
+    """One launch: rasterises polygon rings into bit planes int32 [S, planes, H, ceil(W / 32)] by the polygon rule of
+    ignore.py.  vertices [S, G, V, 2] fp32 as (x, y); counts, poly_plane, poly_clear int32 [S, G]; size = (H, W); G may
+    be 0 (include/unetpp_hip.h: unetpp_mask_polygons)."""
+    _need(vertices, "vertices")
+    if vertices.dim() != 4 or vertices.shape[3] != 2:
+        raise ValueError("vertices must be [S, G, V, 2]")
+    s, g, v = (int(x) for x in vertices.shape[:3])
+    for t, what in ((counts, "counts"), (poly_plane, "poly_plane"), (poly_clear, "poly_clear")):
+        _need(t, what, torch.int32)
+        if tuple(t.shape) != (s, g):
+            raise ValueError("%s must be [%d, %d]" % (what, s, g))
+        if t.device != vertices.device:
+            raise ValueError("all tensors must live on one device")
+    h, w, p = int(size[0]), int(size[1]), int(planes)
+    if min(s, p, h, w) < 1:
+        raise ValueError("S, the planes and the frame must be positive")
+    bits = torch.empty(s, p, h, (w + 31) // 32, dtype=torch.int32, device=vertices.device)
+    some = g > 0
+    _timed_call("mask_polygons", 0.0, lambda: check(_lib.lib().unetpp_mask_polygons(
+        _ptr(vertices) if some and v > 0 else None, _ptr(counts) if some else None, _ptr(poly_plane) if some else None,
+        _ptr(poly_clear) if some else None, s, g, v, p, h, w, _ptr(bits), _stream()), "unetpp_mask_polygons"),
+        4.0 * bits.numel())
+    return bits
+
+
+def target_ignore_mask(target: torch.Tensor, bits: Optional[torch.Tensor], plane_class: Optional[torch.Tensor],
+                       index: torch.Tensor, params: torch.Tensor, src_size, outside: bool = False,
+                       n_frames: Optional[int] = None) -> torch.Tensor:
+    """One launch: ``target_ignore`` with bit planes in place of rectangles.  Writes -1.0 into target [N, C, Ho, Wo] fp32,
+    in place, where the pixel's source position is ignored by the lookup rule of ignore.py, and returns it.  bits int32
+    [M, P, Hs, ceil(Ws / 32)] with plane_class int32 [P], or None / P = 0 for the `outside` rule alone -- then n_frames
+    says how many frames there are; index [N] int64, params [N, 16]; src_size = (Hs, Ws) must be the planes' size
+    (include/unetpp_hip.h: unetpp_target_ignore_mask)."""
+    _need(target, "target")
+    _need(index, "index", torch.int64)
+    _need(params, "params")
+    if target.dim() != 4:
+        raise ValueError("target must be [N, C, Ho, Wo]")
+    n, c, ho, wo = (int(v) for v in target.shape)
+    if index.dim() != 1 or int(index.numel()) != n or tuple(params.shape) != (n, _lib.WARP_PARAMS):
+        raise ValueError("index [N] and params [N, %d] for a target of N = %d samples" % (_lib.WARP_PARAMS, n))
+    dev = target.device
+    hs, ws = int(src_size[0]), int(src_size[1])
+    m, p = n_frames, 0
+    if bits is not None and bits.numel() > 0:
+        _need(bits, "bits", torch.int32)
+        _need(plane_class, "plane_class", torch.int32)
+        if bits.dim() != 4 or plane_class.dim() != 1 or int(plane_class.numel()) != int(bits.shape[1]):
+            raise ValueError("bits must be [M, P, Hs, ceil(Ws / 32)] and plane_class [P]")
+        if int(bits.shape[2]) != hs or int(bits.shape[3]) != (ws + 31) // 32:
+            raise ValueError("bits %s do not hold frames of src_size %d x %d" % (tuple(bits.shape), hs, ws))
+        m, p = int(bits.shape[0]), int(bits.shape[1])
+    elif bits is not None and bits.dim() == 4 and bits.shape[0] > 0:
+        m = int(bits.shape[0])
+    if m is None or (n_frames is not None and int(n_frames) != m):
+        raise ValueError("the number of frames: give n_frames without planes, and the planes' own M with them")
+    m = int(m)
+    if any(t.device != dev for t in (index, params) + ((bits, plane_class) if p else ())):
+        raise ValueError("all tensors must live on one device")
+    if min(m, n, c, ho, wo, hs, ws) < 1 or c > 65535:
+        raise ValueError("N, the window and the frame must be positive and C in 1..65535")
+    _timed_call("target_ignore_mask", 0.0, lambda: check(_lib.lib().unetpp_target_ignore_mask(
+        _ptr(bits) if p else None, _ptr(plane_class) if p else None, m, p, hs, ws, _ptr(index), n, _ptr(params), c, ho, wo,
+        1 if outside else 0, _ptr(target), _stream()), "unetpp_target_ignore_mask"), 4.0 * n * c * ho * wo)
+    return target
+
+
 def crops_draw(n: int, seed: int, n_frames: int, src_size, out_size, centre_frame: Optional[torch.Tensor],
                centre_xy: Optional[torch.Tensor], p_object: float, jitter, desc: "_lib.AugmentDesc", device):
     """One launch: n windows of out_size in n_frames frames of src_size drawn from a 64-bit seed -> (params [n, 16] fp32,
