@@ -142,6 +142,29 @@ def test_large_n_one_region_at_a_time(dev, region):
     assert inside > 0.999 * float(exp.l_want.sum())             # a lost block would lose the loss
 
 
+def test_two_heads_loss_in_the_finish_kernels_second_trip(dev):
+    """two heads of 1024 * 2048 + 5 elements -- 1025 workgroups, the last over the 5-element tail: p = 0 against t = 0
+    everywhere (as PO.region_inputs) except 300 elements of block 1023 and the tail, a quarter of them positives, so each
+    head's loss sits in the last partial of the finish's first trip and in the one partial of its second"""
+    n = 1024 * PO.BLOCK + 5
+    rng = np.random.default_rng(7400)
+    idx = np.concatenate([1023 * PO.BLOCK + np.sort(rng.choice(PO.BLOCK, 300, replace=False)), np.arange(n - 5, n)])
+    t = np.zeros(n, F32)
+    t[idx] = rng.random(idx.size).astype(F32)
+    t[idx[::4]] = 1.0
+    preds = [np.zeros(n, F32) for _ in range(2)]
+    for p in preds:
+        p[idx] = (rng.random(idx.size).astype(F32) * F32(0.998) + F32(0.001)).astype(F32)
+    got = _ops(dev, preds, t)
+    assert got[2] == int((t >= 1.0).sum()) == 77                 # n_pos exactly; the tail holds two of them
+    assert PO.check_all(preds, t, got, **PO.DEFAULTS) == []
+    for p in preds:
+        exp = PO.expected(p, t, heads=2)
+        tail, block = float(exp.l_want[n - 5:].sum()), float(exp.l_want[1023 * PO.BLOCK:1024 * PO.BLOCK].sum())
+        assert tail + block > 0.999 * float(exp.l_want.sum())
+        assert min(tail, block) / exp.denom > 100 * (exp.loss[2] - exp.loss[1])   # a lost partial leaves the bound
+
+
 def test_large_n_positives_in_every_count_trip(dev):
     """positives spread over all 513 count chunks, two heads"""
     rng = np.random.default_rng(77)

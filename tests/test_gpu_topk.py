@@ -262,6 +262,25 @@ def test_heads_form_is_the_written_out_loop_bit_for_bit(dev, heads, shape, kw):
     assert TO.check(want, got[0].cpu().numpy(), got_kth[0].cpu().numpy(), loss[1].item()) == []
 
 
+def test_loss_in_the_finish_kernels_second_trip(dev):
+    """1027 rows of 8 pixels, two heads, k = 3: the heads equal the target except in rows 1023, 1024 and 1026, so the
+    loss sits in the last partial of the finish's first trip over the rows and in two of its second trip"""
+    rows, pixels, k, hot = 1027, 8, 3, [1023, 1024, 1026]
+    rand, target = TO.random_inputs(rows, pixels, seed=57, heads=2)
+    preds = [target.copy() for _ in rand]
+    for p, r in zip(preds, rand):
+        p[hot] = r[hot]
+    loss, grads, kth = _abi_topk(dev, preds, target, k, rows, 3)
+    for h in range(2):
+        want = TO.expected(preds[h], target, k, 3, rows, heads=2)
+        assert TO.check(want, grads[h], kth[h], loss[1 + h]) == []          # (kth bit for bit)
+        assert np.flatnonzero(kth[h]).tolist() == hot
+        second = float(want.iv.l_want.reshape(rows, pixels)[1024:][want.selected[1024:]].sum()) / rows
+        assert second > 0.1 * want.loss[0] > 0 and want.loss[2] - want.loss[1] < 1e-3 * second   # a lost trip shows
+    avg = (F32(0) + loss[1]) + loss[2]
+    assert loss[0].view(U32) == ((F32(1.0) * avg) * F32(0.5)).view(U32)
+
+
 def test_one_long_row(dev):
     pixels = 2 ** 20 + 3
     (pred,), target = TO.random_inputs(1, pixels, seed=31)

@@ -21,7 +21,7 @@ from tests.helpers import gamma as higham_gamma
 
 F32, F64, U32 = np.float32, np.float64, np.uint32
 THREADS = 256            # kTopkThreads: a thread takes 4 consecutive elements per stride of 1024
-FINISH_THREADS = 1024    # topk_focal_finish_kernel: partial[h * R + i], i += 1024, then a 10-level tree
+FINISH_THREADS = 1024    # loss_heads_finish_kernel: partial[h * R + i], i += 1024, then a 10-level tree
 DIGIT_BITS = (11, 10, 10)   # bits 30..20, 19..10, 9..0 of the key, most significant first
 
 

@@ -2,18 +2,16 @@
 // the CPU each step (trainer/trainer.py:122-135; both carry a "put on GPU" TODO there).
 //   * FocalLoss_BCE_2d (tools/losses/focal_loss.py:255-301), forward and gradient in one pass over (pred, target):
 //       e = 1 - |p - t| + 1e-20,  L = sum -(1 - e)^gamma log e / rows,  dL/dp = [u^gamma / e - gamma u^(gamma-1) log e] sign(p - t) / rows
-//     (u = 1 - e; abs'(0) = 0 as in autograd).  Per-block fp32 partial sums, fixed-order finish (unetpp_sum_partials).
+//     (u = 1 - e; abs'(0) = 0 as in autograd).  Geometry, partial sums and the fixed-order finish: loss_heads.h.
 //   * create_heatmap (tools/misc/helper.py:87-172): Gaussian-of-distance maps exp(-0.5 sqrt(dx^2 + dy^2) / R) of the
 //     key points, channels 1 and 3 divided by their per-image maximum.  Each map is evaluated in fp64; the sums of channels 1 and 3
 //     are float32 running sums and the quotient is float32, as in the reference's numpy code.
 #include "common.h"
 #include "focal_element.h"
+#include "loss_heads.h"
 
 namespace unetpp {
 namespace {
-
-constexpr int kLossThreads = 256;
-constexpr int kLossPerThread = 8;  // elements per thread: 2 x float4
 
 // The elements of one thread (2 x float4 at `base`): the gradient (times `scale`: 1 for a single head, 1 / heads under
 // the trainer's mean over heads -- a second float32 product, as autograd forms it) and the thread's part of the loss sum.
@@ -25,12 +23,12 @@ constexpr int kLossPerThread = 8;  // elements per thread: 2 x float4
 // bit on a target without a negative element.
 template <bool kLow, bool kIgnore = false>
 __device__ __forceinline__ float focal_thread(const float* __restrict__ pred, float* __restrict__ grad,
-                                              const float (&t)[kLossPerThread / 4][4], long base, long n, float gamma,
+                                              const float (&t)[kLossVecs][4], long base, long n, float gamma,
                                               float inv_rows, float scale) {
   const bool cube = gamma == 3.f;
   float sum = 0.f;
 #pragma unroll
-  for (int h = 0; h < kLossPerThread / 4; ++h) {
+  for (int h = 0; h < kLossVecs; ++h) {
     const long i = base + 4 * h;
     if (i >= n) break;
     float p[4], g[4];
@@ -65,22 +63,6 @@ __device__ __forceinline__ float focal_thread(const float* __restrict__ pred, fl
   return sum;
 }
 
-__device__ __forceinline__ void focal_read_target(const float* __restrict__ target, long base, long n,
-                                                  float (&t)[kLossPerThread / 4][4]) {
-#pragma unroll
-  for (int h = 0; h < kLossPerThread / 4; ++h) {
-    const long i = base + 4 * h;
-    if (i + 4 <= n) {
-      const f32x4 tv = *reinterpret_cast<const f32x4*>(target + i);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) t[h][e] = tv[e];
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) t[h][e] = (i + e < n) ? target[i + e] : 0.f;
-    }
-  }
-}
-
 template <bool kLow>
 __global__ __launch_bounds__(kLossThreads) void focal_bce_kernel(const float* __restrict__ pred,
                                                                 const float* __restrict__ target, long n, float gamma,
@@ -88,8 +70,8 @@ __global__ __launch_bounds__(kLossThreads) void focal_bce_kernel(const float* __
                                                                 float* __restrict__ partial) {
   __shared__ float red[kLossThreads / 64];
   const long base = (blockIdx.x * static_cast<long>(kLossThreads) + threadIdx.x) * kLossPerThread;
-  float t[kLossPerThread / 4][4];
-  focal_read_target(target, base, n, t);
+  float t[kLossVecs][4];
+  load_thread(target, base, n, t);
   float sum = focal_thread<kLow>(pred, grad, t, base, n, gamma, inv_rows, 1.f);
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off);
@@ -107,8 +89,8 @@ __global__ __launch_bounds__(kLossThreads) void focal_bce_heads_kernel(const une
                                                                       float* __restrict__ partial) {
   __shared__ float red[UNETPP_MAX_HEADS][kLossThreads / 64];
   const long base = (blockIdx.x * static_cast<long>(kLossThreads) + threadIdx.x) * kLossPerThread;
-  float t[kLossPerThread / 4][4];
-  focal_read_target(target, base, n, t);
+  float t[kLossVecs][4];
+  load_thread(target, base, n, t);
   for (int h = 0; h < hd.n_heads; ++h) {
     float sum = focal_thread<kLow, kIgnore>(hd.pred[h], hd.grad[h], t, base, n, gamma, inv_rows, scale);
 #pragma unroll
@@ -122,44 +104,20 @@ __global__ __launch_bounds__(kLossThreads) void focal_bce_heads_kernel(const une
   }
 }
 
-// one block: loss = sum of the per-block partials, fixed order (1024 strided sums, then an LDS tree)
-__global__ __launch_bounds__(1024) void focal_bce_finish_kernel(const float* __restrict__ partial, long n_blocks,
-                                                                float* __restrict__ loss) {
-  __shared__ float red[1024];
-  float s = 0.f;
-  for (long i = threadIdx.x; i < n_blocks; i += 1024) s += partial[i];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int w = 512; w >= 1; w >>= 1) {
-    if (static_cast<int>(threadIdx.x) < w) red[threadIdx.x] += red[threadIdx.x + w];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) loss[0] = red[0];
+// one block: loss = the sum of the per-block partials
+__global__ __launch_bounds__(kFinishThreads) void focal_bce_finish_kernel(const float* __restrict__ partial, long n_blocks,
+                                                                          float* __restrict__ loss) {
+  __shared__ float red[kFinishThreads];
+  const float s = finish_sum(partial, n_blocks, red);
+  if (threadIdx.x == 0) loss[0] = s;
 }
 
-// one block: every head's loss as focal_bce_finish_kernel sums it, then the trainer's mean over heads in ITS order:
-// avg = 0; avg = avg + loss_h (h = 0, 1, ...); avg = 1.0 * avg / heads -- float32 tensor arithmetic, the division by a
-// Python scalar being a product with float32(1 / heads).
-__global__ __launch_bounds__(1024) void focal_bce_heads_finish_kernel(const float* __restrict__ partial, long n_blocks,
-                                                                      int n_heads, float inv_heads, float* __restrict__ loss) {
-  __shared__ float red[1024];
-  float avg = 0.f;
-  for (int h = 0; h < n_heads; ++h) {
-    float s = 0.f;
-    for (long i = threadIdx.x; i < n_blocks; i += 1024) s += partial[h * n_blocks + i];
-    __syncthreads();  // (the previous head's red[0] has been read)
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = 512; w >= 1; w >>= 1) {
-      if (static_cast<int>(threadIdx.x) < w) red[threadIdx.x] += red[threadIdx.x + w];
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-      loss[1 + h] = red[0];
-      avg = avg + red[0];
-    }
-  }
-  if (threadIdx.x == 0) loss[0] = (1.0f * avg) * inv_heads;
+// one block: every head's loss as focal_bce_finish_kernel sums it, then the mean over heads
+__global__ __launch_bounds__(kFinishThreads) void loss_heads_finish_kernel(const float* __restrict__ partial, long n_blocks,
+                                                                           int n_heads, float inv_heads,
+                                                                           float* __restrict__ loss) {
+  __shared__ float red[kFinishThreads];
+  finish_heads(n_heads, inv_heads, loss, [&](int h) { return finish_sum(partial + h * n_blocks, n_blocks, red); });
 }
 
 // grid (blocks per image, N): unnormalised maps of the 4 channels + per-block maxima of channels 1 and 3
@@ -237,27 +195,28 @@ __global__ __launch_bounds__(256) void heatmap_norm_kernel(int H, int W, float* 
 }
 
 }  // namespace
+
+void launch_loss_heads_finish(const float* partial, long n_blocks, int n_heads, float inv_heads, float* loss, hipStream_t st) {
+  hipLaunchKernelGGL(loss_heads_finish_kernel, dim3(1), dim3(kFinishThreads), 0, st, partial, n_blocks, n_heads, inv_heads, loss);
+}
+
 }  // namespace unetpp
 
 using namespace unetpp;
 
-extern "C" int64_t unetpp_focal_bce_blocks(int64_t n) {
-  if (n < 1) return 0;
-  const int64_t per_block = static_cast<int64_t>(kLossThreads) * kLossPerThread;
-  return (n + per_block - 1) / per_block;
-}
+extern "C" int64_t unetpp_focal_bce_blocks(int64_t n) { return loss_blocks(n); }
 
 extern "C" int unetpp_focal_bce(const float* pred, const float* target, int64_t n, int64_t rows, float gamma, float* grad,
                                 float* partial, float* loss, void* stream) {
   if (pred == nullptr || target == nullptr || partial == nullptr || loss == nullptr || n < 1 || rows < 1) return UNETPP_EINVAL;
   if (((reinterpret_cast<uintptr_t>(pred) | reinterpret_cast<uintptr_t>(target) | reinterpret_cast<uintptr_t>(grad)) & 15) != 0)
     return UNETPP_EINVAL;
-  const int64_t blocks = unetpp_focal_bce_blocks(n);
+  const int64_t blocks = loss_blocks(n);
   if (blocks > 0x7fffffffLL) return UNETPP_EINVAL;
   hipLaunchKernelGGL(gamma < 1.f ? focal_bce_kernel<true> : focal_bce_kernel<false>, dim3(static_cast<unsigned>(blocks)),
                      dim3(kLossThreads), 0, static_cast<hipStream_t>(stream), pred, target, static_cast<long>(n), gamma,
                      1.f / static_cast<float>(rows), grad, partial);
-  hipLaunchKernelGGL(focal_bce_finish_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), partial,
+  hipLaunchKernelGGL(focal_bce_finish_kernel, dim3(1), dim3(kFinishThreads), 0, static_cast<hipStream_t>(stream), partial,
                      static_cast<long>(blocks), loss);
   return launch_status();
 }
@@ -267,24 +226,16 @@ namespace {
 template <bool kIgnore>
 int focal_bce_heads_launch(const unetpp_focal_heads* heads, const float* target, int64_t n, int64_t rows, float gamma,
                            float* partial, float* loss, void* stream) {
-  if (heads == nullptr || target == nullptr || partial == nullptr || loss == nullptr || n < 1 || rows < 1) return UNETPP_EINVAL;
-  if (heads->n_heads < 1 || heads->n_heads > UNETPP_MAX_HEADS) return UNETPP_EINVAL;
-  uintptr_t bits = reinterpret_cast<uintptr_t>(target);
-  for (int h = 0; h < heads->n_heads; ++h) {
-    if (heads->pred[h] == nullptr) return UNETPP_EINVAL;
-    bits |= reinterpret_cast<uintptr_t>(heads->pred[h]) | reinterpret_cast<uintptr_t>(heads->grad[h]);
-  }
-  if ((bits & 15) != 0) return UNETPP_EINVAL;
-  const int64_t blocks = unetpp_focal_bce_blocks(n);
+  unetpp_focal_heads hd;
+  if (loss_heads_checked(heads, target, hd) != UNETPP_OK) return UNETPP_EINVAL;
+  if (partial == nullptr || loss == nullptr || n < 1 || rows < 1) return UNETPP_EINVAL;
+  const int64_t blocks = loss_blocks(n);
   if (blocks > 0x7fffffffLL) return UNETPP_EINVAL;
-  unetpp_focal_heads hd = *heads;
-  for (int h = hd.n_heads; h < UNETPP_MAX_HEADS; ++h) hd.pred[h] = nullptr, hd.grad[h] = nullptr;
   const float inv_heads = 1.0f / static_cast<float>(hd.n_heads);
   const auto kernel = gamma < 1.f ? focal_bce_heads_kernel<true, kIgnore> : focal_bce_heads_kernel<false, kIgnore>;
   hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(blocks)), dim3(kLossThreads), 0, static_cast<hipStream_t>(stream), hd, target,
                      static_cast<long>(n), gamma, 1.f / static_cast<float>(rows), inv_heads, partial);
-  hipLaunchKernelGGL(focal_bce_heads_finish_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), partial,
-                     static_cast<long>(blocks), hd.n_heads, inv_heads, loss);
+  launch_loss_heads_finish(partial, static_cast<long>(blocks), hd.n_heads, inv_heads, loss, static_cast<hipStream_t>(stream));
   return launch_status();
 }
 

@@ -4,7 +4,7 @@
 //   teacher of head j < J-1:  the deepest head ("last") or head j + 1 ("next");  the deepest head has none;
 //   S_j = sum l(p_j, t) / rows,   D_j = sum over the admitted elements of l(p_j, q) / rows  (q: the teacher's element),
 //   L_j = S_j + w D_j (one rounded product, one rounded sum),  D_{J-1} = +0.0,
-//   loss[0] = (0 + L_0 + ... + L_{J-1}) * (1 / J) as focal_bce_heads_finish_kernel (caller.hip) forms it,
+//   loss[0] = the mean over heads of L_j in the trainer's order (loss_heads.h),
 //   grad_j = g_s + w g_d per admitted element (one rounded product, one rounded sum); g_s itself, with its bits, on an
 //            element that is kept out of D_j and on every element of the deepest head.
 // l, g_s and g_d are focal_element.h's rule (distill_element below) with the same inv_rows and scale = float32(1 / J);
@@ -15,20 +15,17 @@
 //            either side compares false and keeps the element out);
 //   ignore:  an ignored element (t < 0.0f; S term and g_s are +0.0 as in unetpp_focal_bce_heads_ignore) passes the gate
 //            and keeps its distillation term when distill_ignored is set, and is kept out when it is not.
-// One main launch in the grid and per-thread layout of focal_bce_heads_kernel: a thread reads its 8 targets once and walks
-// the heads from the deepest to the shallowest with the teacher's 8 values in registers, so every map is read once and
-// every gradient written once.  Two partial sums per head and block (S, D), each in the order focal_bce_kernel uses for
-// its one sum: the thread's 8 in index order, 6 shuffles, ((r0 + r1) + (r2 + r3)) * inv_rows; then a one-block finish
-// (1024 strided sums, a 10-level tree).  w is read from device memory, so a captured graph follows a schedule of w.
-// No atomics; the result depends on the inputs alone.
+// One main launch in the geometry of loss_heads.h: a thread reads its 8 targets once and walks the heads from the deepest
+// to the shallowest with the teacher's 8 values in registers, so every map is read once and every gradient written once.
+// Two partial sums per head and block (S, D), each formed as loss_heads.h has it and times inv_rows, then its finish per
+// sum.  w is read from device memory, so a captured graph follows a schedule of w.
 #include "common.h"
+#include "loss_heads.h"
 
 namespace unetpp {
 namespace {
 
-constexpr int kLossThreads = 256;
-constexpr int kLossPerThread = 8;  // elements per thread: 2 x float4, as caller.hip
-constexpr int kVecs = kLossPerThread / 4;
+constexpr int kVecs = kLossVecs;
 
 // a + w * b in two roundings.  Left to the compiler the pair becomes one fma, which is neither what float32 tensor
 // arithmetic over the two stored gradients gives nor the S_j and D_j this call reports.
@@ -36,32 +33,6 @@ __device__ __forceinline__ float distill_combine(float a, float w, float b) {
 #pragma clang fp contract(off)
   const float wb = w * b;
   return a + wb;
-}
-
-__device__ __forceinline__ void distill_load(const float* __restrict__ src, long base, long n, float (&v)[kVecs][4]) {
-#pragma unroll
-  for (int h = 0; h < kVecs; ++h) {
-    const long i = base + 4 * h;
-    if (i + 4 <= n) {
-      const f32x4 q = *reinterpret_cast<const f32x4*>(src + i);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[h][e] = q[e];
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[h][e] = (i + e < n) ? src[i + e] : 0.f;
-    }
-  }
-}
-
-__device__ __forceinline__ void distill_store(float* __restrict__ grad, long i, long n, const float (&g)[4]) {
-  if (grad == nullptr) return;
-  if (i + 4 <= n) {
-    *reinterpret_cast<f32x4*>(grad + i) = f32x4{g[0], g[1], g[2], g[3]};
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if (i + e < n) grad[i + e] = g[e];
-  }
 }
 
 struct DistillFlags {
@@ -150,7 +121,7 @@ __device__ __forceinline__ void distill_head(const float (&p)[kVecs][4], const f
         g[e] = gs;
       }
     }
-    distill_store(grad, i, n, g);
+    store4(grad, i, n, g);
   }
 }
 
@@ -165,10 +136,10 @@ __global__ __launch_bounds__(kLossThreads) void distill_heads_kernel(const unetp
   const float w = weight[0];
   float t[kVecs][4], p[kVecs][4];
   float q[kVecs][4] = {};   // the teacher's elements (set by the deepest head before a student reads them)
-  distill_load(target, base, n, t);
+  load_thread(target, base, n, t);
   const int last = hd.n_heads - 1;
   for (int h = last; h >= 0; --h) {
-    distill_load(hd.pred[h], base, n, p);
+    load_thread(hd.pred[h], base, n, p);
     float sum_s, sum_d;
     if (h == last)
       distill_head<kLow, kIgnore, false>(p, t, q, hd.grad[h], base, n, gamma, inv_rows, scale, w, f, sum_s, sum_d);
@@ -198,40 +169,23 @@ __global__ __launch_bounds__(kLossThreads) void distill_heads_kernel(const unetp
   }
 }
 
-// the sum of n_blocks partials in focal_bce_finish_kernel's order, valid in thread 0
-__device__ __forceinline__ float distill_finish_sum(const float* __restrict__ partial, long n_blocks, float* red) {
-  float s = 0.f;
-  for (long i = threadIdx.x; i < n_blocks; i += 1024) s += partial[i];
-  __syncthreads();  // (the previous sum's red[0] has been read)
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int w = 512; w >= 1; w >>= 1) {
-    if (static_cast<int>(threadIdx.x) < w) red[threadIdx.x] += red[threadIdx.x + w];
-    __syncthreads();
-  }
-  return red[0];
-}
-
-// one block: S_h and D_h as focal_bce_finish_kernel sums them, L_h = S_h + w D_h, then the trainer's mean over heads in
-// its order (focal_bce_heads_finish_kernel).  loss: [0] the mean, [1 + h] L_h, [1 + H + h] S_h, [1 + 2 H + h] D_h.
-__global__ __launch_bounds__(1024) void distill_finish_kernel(const float* __restrict__ partial, long n_blocks, int n_heads,
-                                                              float inv_heads, const float* __restrict__ weight,
-                                                              float* __restrict__ loss) {
-  __shared__ float red[1024];
+// one block: S_h and D_h summed, L_h = S_h + w D_h, then the mean over heads.
+// loss: [0] the mean, [1 + h] L_h, [1 + H + h] S_h, [1 + 2 H + h] D_h.
+__global__ __launch_bounds__(kFinishThreads) void distill_finish_kernel(const float* __restrict__ partial, long n_blocks,
+                                                                        int n_heads, float inv_heads,
+                                                                        const float* __restrict__ weight,
+                                                                        float* __restrict__ loss) {
+  __shared__ float red[kFinishThreads];
   const float w = weight[0];
-  float avg = 0.f;
-  for (int h = 0; h < n_heads; ++h) {
-    const float s = distill_finish_sum(partial + (2 * h) * n_blocks, n_blocks, red);
-    const float d = distill_finish_sum(partial + (2 * h + 1) * n_blocks, n_blocks, red);
+  finish_heads(n_heads, inv_heads, loss, [&](int h) {
+    const float s = finish_sum(partial + (2 * h) * n_blocks, n_blocks, red);
+    const float d = finish_sum(partial + (2 * h + 1) * n_blocks, n_blocks, red);
     if (threadIdx.x == 0) {
-      const float l = distill_combine(s, w, d);
-      loss[1 + h] = l;
       loss[1 + n_heads + h] = s;
       loss[1 + 2 * n_heads + h] = d;
-      avg = avg + l;
     }
-  }
-  if (threadIdx.x == 0) loss[0] = (1.0f * avg) * inv_heads;
+    return distill_combine(s, w, d);
+  });
 }
 
 }  // namespace
@@ -242,24 +196,16 @@ using namespace unetpp;
 extern "C" int unetpp_distill_heads(const unetpp_focal_heads* heads, const float* target, int64_t n, int64_t rows, float gamma,
                                     const float* weight, int32_t teacher, int32_t gate, int32_t ignore,
                                     int32_t distill_ignored, float* partial, float* loss, void* stream) {
-  if (heads == nullptr || target == nullptr || weight == nullptr || partial == nullptr || loss == nullptr || n < 1 || rows < 1)
-    return UNETPP_EINVAL;
-  if (heads->n_heads < 1 || heads->n_heads > UNETPP_MAX_HEADS) return UNETPP_EINVAL;
+  unetpp_focal_heads hd;
+  if (loss_heads_checked(heads, target, hd) != UNETPP_OK) return UNETPP_EINVAL;
+  if (weight == nullptr || partial == nullptr || loss == nullptr || n < 1 || rows < 1) return UNETPP_EINVAL;
   if ((teacher != UNETPP_DISTILL_LAST && teacher != UNETPP_DISTILL_NEXT) || (gate != 0 && gate != 1) ||
       (ignore != 0 && ignore != 1) || (distill_ignored != 0 && distill_ignored != 1))
     return UNETPP_EINVAL;
   if (!(gamma >= 0.f)) return UNETPP_EINVAL;
-  uintptr_t bits = reinterpret_cast<uintptr_t>(target);
-  for (int h = 0; h < heads->n_heads; ++h) {
-    if (heads->pred[h] == nullptr) return UNETPP_EINVAL;
-    bits |= reinterpret_cast<uintptr_t>(heads->pred[h]) | reinterpret_cast<uintptr_t>(heads->grad[h]);
-  }
-  if ((bits & 15) != 0 || (reinterpret_cast<uintptr_t>(weight) & 3) != 0) return UNETPP_EINVAL;
-  const int64_t per_block = static_cast<int64_t>(kLossThreads) * kLossPerThread;
-  const int64_t blocks = (n + per_block - 1) / per_block;   // unetpp_focal_bce_blocks(n)
+  if ((reinterpret_cast<uintptr_t>(weight) & 3) != 0) return UNETPP_EINVAL;
+  const int64_t blocks = loss_blocks(n);
   if (blocks > 0x7fffffffLL) return UNETPP_EINVAL;
-  unetpp_focal_heads hd = *heads;
-  for (int h = hd.n_heads; h < UNETPP_MAX_HEADS; ++h) hd.pred[h] = nullptr, hd.grad[h] = nullptr;
   const float inv_heads = 1.0f / static_cast<float>(hd.n_heads);
   DistillFlags f;
   f.next = teacher == UNETPP_DISTILL_NEXT;
@@ -271,7 +217,7 @@ extern "C" int unetpp_distill_heads(const unetpp_focal_heads* heads, const float
   const hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(blocks)), dim3(kLossThreads), 0, st, hd, target, static_cast<long>(n),
                      gamma, 1.f / static_cast<float>(rows), inv_heads, weight, f, partial);
-  hipLaunchKernelGGL(distill_finish_kernel, dim3(1), dim3(1024), 0, st, static_cast<const float*>(partial),
+  hipLaunchKernelGGL(distill_finish_kernel, dim3(1), dim3(kFinishThreads), 0, st, static_cast<const float*>(partial),
                      static_cast<long>(blocks), hd.n_heads, inv_heads, weight, loss);
   return launch_status();
 }

@@ -9,7 +9,7 @@
 //     otherwise:  l = -(1 - t)^beta q^alpha log(1 - q),   log(1 - q) evaluated as log1pf(-q);
 //   0^0 = 1;  n_pos = the positive elements of the target (an exact integer), denom = max(n_pos, 1);
 //   loss_h = (sum of l over head h) * (1 / denom),  1 / denom = float32(1) / float32(denom);
-//   loss[0] = (0 + loss_1 + ... + loss_n) * (1 / n_heads) in that order, as unetpp_focal_bce_heads forms it;
+//   loss[0] = the mean over heads of loss_h in the trainer's order (loss_heads.h);
 //   grad_h = ((dl / dq) * (1 / denom)) * (1 / n_heads): the two float32 products in autograd's order.
 // A NaN in p makes the loss NaN (its own gradient element is 0: the gate compares false).  eps below 2^-25 makes hi = 1,
 // and the rule itself is then infinite at p = 1.
@@ -18,17 +18,14 @@
 //   count   reads the target once: at most kPrCountBlocks workgroups, each over chunks of kPrCountChunk elements
 //           (kPrCountLoads float4 loads in flight per lane) at a stride of the whole grid -> counts[block], 64-bit
 //           integers.  Integer sums are exact in any order.
-//   main    one workgroup per kPrThreads * kPrPerThread elements, as focal_bce_heads_kernel (caller.hip): the thread's
-//           targets are read once for all heads, their weights (1 - t)^beta formed once; every WAVE adds the count
-//           partials itself (at most four per lane, then six shuffles), so 1 / denom is known before the first gradient
-//           is written and no launch stands between count and main.  Every pred[h] is read once, every grad[h] written
-//           once.  Loss terms: the thread's 8 in index order -> 6 wave shuffles -> (w0 + w1) + (w2 + w3) ->
-//           partial[h * blocks + block].  Workgroup 0 writes n_pos.
-//   finish  one workgroup: per head 1024 strided sums over the partials, a 10-level LDS tree, the product with
-//           1 / denom (formed from the counts as the main pass forms it), then the mean over heads.
-// alpha and beta in {0, 1, 2, 3, 4} take multiply chains instead of powf.  16-byte loads and stores wherever four
-// elements remain, scalar accesses on the last one to three.
+//   main    the geometry and partial sums of loss_heads.h: the thread's targets are read once for all heads, their
+//           weights (1 - t)^beta formed once; every WAVE adds the count partials itself (at most four per lane, then six
+//           shuffles), so 1 / denom is known before the first gradient is written and no launch stands between count
+//           and main.  Every pred[h] is read once, every grad[h] written once.  Workgroup 0 writes n_pos.
+//   finish  loss_heads.h's, a head's sum times 1 / denom (formed from the counts as the main pass forms it).
+// alpha and beta in {0, 1, 2, 3, 4} take multiply chains instead of powf.
 #include "common.h"
+#include "loss_heads.h"
 
 #include <cmath>
 
@@ -37,6 +34,7 @@ namespace {
 
 constexpr int kPrThreads = 256;
 constexpr int kPrPerThread = 8;       // main pass: elements per thread, 2 x float4 per tensor
+static_assert(kPrThreads == kLossThreads && kPrPerThread == kLossPerThread, "the main pass runs in loss_heads.h's geometry");
 constexpr int kPrCountLoads = 4;      // count pass: float4 loads a lane issues before it looks at the first
 constexpr int kPrCountChunk = kPrThreads * kPrCountLoads * 4;   // elements of one workgroup trip
 constexpr int kPrCountBlocks = 256;   // count partials at most: four per lane of a wave of the main pass
@@ -118,17 +116,6 @@ __device__ __forceinline__ float pr_inv_denom(pr_count_t total) {
   return 1.f / static_cast<float>(total > 0 ? total : 1ull);
 }
 
-__device__ __forceinline__ void pr_load4(const float* __restrict__ src, long i, long n, float pad, float (&v)[4]) {
-  if (i + 4 <= n) {
-    const f32x4 q = *reinterpret_cast<const f32x4*>(src + i);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = q[e];
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = (i + e < n) ? src[i + e] : pad;
-  }
-}
-
 // counts[block] = the elements t >= positive of the block's chunks (a padded element is 0 and positive > 0)
 __global__ __launch_bounds__(kPrThreads) void pr_count_kernel(const float* __restrict__ target, long n, float positive,
                                                               pr_count_t* __restrict__ counts) {
@@ -140,7 +127,7 @@ __global__ __launch_bounds__(kPrThreads) void pr_count_kernel(const float* __res
     float v[kPrCountLoads][4];
 #pragma unroll
     for (int a = 0; a < kPrCountLoads; ++a)
-      pr_load4(target, start + (static_cast<long>(a) * kPrThreads + threadIdx.x) * 4, n, 0.f, v[a]);
+      load4(target, start + (static_cast<long>(a) * kPrThreads + threadIdx.x) * 4, n, 0.f, v[a]);
     unsigned here = 0;
 #pragma unroll
     for (int a = 0; a < kPrCountLoads; ++a)
@@ -171,7 +158,7 @@ __global__ __launch_bounds__(kPrThreads) void pr_focal_kernel(const unetpp_focal
   [[maybe_unused]] unsigned ign = 0;   // bit 4 * v + e: the element is ignored (kIgnore)
   float t[kPrPerThread / 4][4];
 #pragma unroll
-  for (int v = 0; v < kPrPerThread / 4; ++v) pr_load4(target, base + 4 * v, n, 0.f, t[v]);
+  for (int v = 0; v < kPrPerThread / 4; ++v) load4(target, base + 4 * v, n, 0.f, t[v]);
   const pr_count_t total = pr_total(counts, n_counts);   // (its loads are in flight beside the target's)
   if (blockIdx.x == 0 && threadIdx.x == 0) *n_pos = static_cast<long long>(total);
 #pragma unroll
@@ -189,7 +176,7 @@ __global__ __launch_bounds__(kPrThreads) void pr_focal_kernel(const unetpp_focal
     float* __restrict__ grad = hd.grad[h];
     float p[kPrPerThread / 4][4];
 #pragma unroll
-    for (int v = 0; v < kPrPerThread / 4; ++v) pr_load4(pred, base + 4 * v, n, 0.5f, p[v]);   // both loads first
+    for (int v = 0; v < kPrPerThread / 4; ++v) load4(pred, base + 4 * v, n, 0.5f, p[v]);   // both loads first
     float sum = 0.f;
 #pragma unroll
     for (int v = 0; v < kPrPerThread / 4; ++v) {
@@ -225,39 +212,18 @@ __global__ __launch_bounds__(kPrThreads) void pr_focal_kernel(const unetpp_focal
   }
 }
 
-// one block: every head's sum in fixed order (1024 strided sums, then an LDS tree) times 1 / denom, then the trainer's
-// mean over heads in its order (focal_bce_heads_finish_kernel of caller.hip)
-__global__ __launch_bounds__(1024) void pr_focal_finish_kernel(const float* __restrict__ partial, long n_blocks, int n_heads,
-                                                               float inv_heads, const pr_count_t* __restrict__ counts,
-                                                               int n_counts, float* __restrict__ loss) {
+// one block: every head's sum times 1 / denom, then the mean over heads
+__global__ __launch_bounds__(kFinishThreads) void pr_focal_finish_kernel(const float* __restrict__ partial, long n_blocks,
+                                                                         int n_heads, float inv_heads,
+                                                                         const pr_count_t* __restrict__ counts, int n_counts,
+                                                                         float* __restrict__ loss) {
   // (no contraction: fused into the addition to avg, the product with 1 / denom would not be rounded, and the mean
   // would not be the sum of the values written to loss[1 + h], which is what the loop over single-head calls adds)
 #pragma clang fp contract(off)
-  __shared__ float red[1024];
+  __shared__ float red[kFinishThreads];
   const float inv_denom = pr_inv_denom(pr_total(counts, n_counts));
-  float avg = 0.f;
-  for (int h = 0; h < n_heads; ++h) {
-    float s = 0.f;
-    for (long i = threadIdx.x; i < n_blocks; i += 1024) s += partial[h * n_blocks + i];
-    __syncthreads();  // (the previous head's red[0] has been read)
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = 512; w >= 1; w >>= 1) {
-      if (static_cast<int>(threadIdx.x) < w) red[threadIdx.x] += red[threadIdx.x + w];
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-      const float v = red[0] * inv_denom;
-      loss[1 + h] = v;
-      avg = avg + v;
-    }
-  }
-  if (threadIdx.x == 0) loss[0] = (1.0f * avg) * inv_heads;
-}
-
-inline int64_t pr_blocks(int64_t n) {
-  const int64_t per_block = static_cast<int64_t>(kPrThreads) * kPrPerThread;
-  return (n - 1) / per_block + 1;
+  finish_heads(n_heads, inv_heads, loss,
+               [&](int h) { return finish_sum(partial + h * n_blocks, n_blocks, red) * inv_denom; });
 }
 
 inline int pr_mode(float e) {
@@ -267,7 +233,7 @@ inline int pr_mode(float e) {
 }
 
 inline bool pr_args_ok(int32_t n_heads, int64_t n) {
-  return n_heads >= 1 && n_heads <= UNETPP_MAX_HEADS && n >= 1 && pr_blocks(n) <= 0x7fffffffLL;
+  return n_heads >= 1 && n_heads <= UNETPP_MAX_HEADS && n >= 1 && loss_blocks(n) <= 0x7fffffffLL;
 }
 
 }  // namespace
@@ -278,7 +244,7 @@ using namespace unetpp;
 extern "C" int64_t unetpp_pr_focal_workspace_bytes(int32_t n_heads, int64_t n) {
   if (!pr_args_ok(n_heads, n)) return 0;
   return static_cast<int64_t>(kPrCountBlocks) * static_cast<int64_t>(sizeof(pr_count_t)) +
-         static_cast<int64_t>(n_heads) * pr_blocks(n) * 4;
+         static_cast<int64_t>(n_heads) * loss_blocks(n) * 4;
 }
 
 namespace {
@@ -286,19 +252,12 @@ namespace {
 template <bool kIgnore>
 int pr_focal_heads_launch(const unetpp_focal_heads* heads, const float* target, int64_t n, float alpha, float beta, float eps,
                           float positive, void* workspace, int64_t* n_pos, float* loss, void* stream) {
-  if (heads == nullptr || target == nullptr || workspace == nullptr || n_pos == nullptr || loss == nullptr) return UNETPP_EINVAL;
-  if (!pr_args_ok(heads->n_heads, n)) return UNETPP_EINVAL;
+  unetpp_focal_heads hd;
+  if (loss_heads_checked(heads, target, hd) != UNETPP_OK) return UNETPP_EINVAL;
+  if (workspace == nullptr || n_pos == nullptr || loss == nullptr || !pr_args_ok(hd.n_heads, n)) return UNETPP_EINVAL;
   if (!(alpha >= 0.f) || !(beta >= 0.f) || !(eps > 0.f && eps < 0.5f) || !(positive > 0.f && positive <= 1.f))
     return UNETPP_EINVAL;   // (a NaN fails every comparison)
-  uintptr_t bits = reinterpret_cast<uintptr_t>(target);
-  for (int h = 0; h < heads->n_heads; ++h) {
-    if (heads->pred[h] == nullptr) return UNETPP_EINVAL;
-    bits |= reinterpret_cast<uintptr_t>(heads->pred[h]) | reinterpret_cast<uintptr_t>(heads->grad[h]);
-  }
-  if ((bits & 15) != 0) return UNETPP_EINVAL;
   if (((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(n_pos)) & 7) != 0) return UNETPP_EINVAL;
-  unetpp_focal_heads hd = *heads;
-  for (int h = hd.n_heads; h < UNETPP_MAX_HEADS; ++h) hd.pred[h] = nullptr, hd.grad[h] = nullptr;
   PrParams k;
   k.alpha = alpha;
   k.beta = beta;
@@ -308,7 +267,7 @@ int pr_focal_heads_launch(const unetpp_focal_heads* heads, const float* target, 
   k.amode = pr_mode(alpha);
   k.bmode = pr_mode(beta);
   const hipStream_t st = static_cast<hipStream_t>(stream);
-  const int64_t blocks = pr_blocks(n);
+  const int64_t blocks = loss_blocks(n);
   const int64_t chunks = (n - 1) / kPrCountChunk + 1;
   const int n_counts = static_cast<int>(chunks < kPrCountBlocks ? chunks : kPrCountBlocks);
   pr_count_t* counts = static_cast<pr_count_t*>(workspace);
@@ -319,7 +278,7 @@ int pr_focal_heads_launch(const unetpp_focal_heads* heads, const float* target, 
   hipLaunchKernelGGL(pr_focal_kernel<kIgnore>, dim3(static_cast<unsigned>(blocks)), dim3(kPrThreads), 0, st, hd, target,
                      static_cast<long>(n), k, inv_heads, static_cast<const pr_count_t*>(counts), n_counts, partial,
                      reinterpret_cast<long long*>(n_pos));
-  hipLaunchKernelGGL(pr_focal_finish_kernel, dim3(1), dim3(1024), 0, st, static_cast<const float*>(partial),
+  hipLaunchKernelGGL(pr_focal_finish_kernel, dim3(1), dim3(kFinishThreads), 0, st, static_cast<const float*>(partial),
                      static_cast<long>(blocks), hd.n_heads, inv_heads, static_cast<const pr_count_t*>(counts), n_counts, loss);
   return launch_status();
 }

@@ -22,11 +22,12 @@
 // kIgnore (unetpp_topk_focal_heads_ignore): an element whose target is negative has key 0 and is never emitted, so it
 // ranks last, takes a tie's rank when tau is 0, and adds +0.0 to the loss and the gradient selected or not; k >= P then
 // runs unetpp_focal_bce_heads_ignore.  The plain instantiation is the code it was.
-// The finish kernel sums the row partials per head in fixed order and forms the mean over heads as
-// focal_bce_heads_finish_kernel (caller.hip) does.  k >= P is FocalLoss_BCE_2d itself: value and gradient come from
-// unetpp_focal_bce_heads (same bits), this file's kernel then only finds kth (the smallest |d| of the row).
+// The row partials take the finish of loss_heads.h (launch_loss_heads_finish, over rows instead of blocks).  k >= P is
+// FocalLoss_BCE_2d itself: value and gradient come from unetpp_focal_bce_heads (same bits), this file's kernel then
+// only finds kth (the smallest |d| of the row).
 #include "common.h"
 #include "focal_element.h"
+#include "loss_heads.h"
 
 namespace unetpp {
 namespace {
@@ -269,30 +270,6 @@ __global__ __launch_bounds__(kTopkThreads) void topk_focal_kernel(const unetpp_f
   if (tid == 0) partial[static_cast<long>(h) * rows + r] = ((red[0] + red[1]) + (red[2] + red[3])) * inv_denom;
 }
 
-// one block: every head's loss = its row partials in fixed order (1024 strided sums, then an LDS tree), then the
-// trainer's mean over heads in its order (focal_bce_heads_finish_kernel of caller.hip, over rows instead of blocks)
-__global__ __launch_bounds__(1024) void topk_focal_finish_kernel(const float* __restrict__ partial, long rows, int n_heads,
-                                                                 float inv_heads, float* __restrict__ loss) {
-  __shared__ float red[1024];
-  float avg = 0.f;
-  for (int h = 0; h < n_heads; ++h) {
-    float s = 0.f;
-    for (long i = threadIdx.x; i < rows; i += 1024) s += partial[h * rows + i];
-    __syncthreads();  // (the previous head's red[0] has been read)
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = 512; w >= 1; w >>= 1) {
-      if (static_cast<int>(threadIdx.x) < w) red[threadIdx.x] += red[threadIdx.x + w];
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-      loss[1 + h] = red[0];
-      avg = avg + red[0];
-    }
-  }
-  if (threadIdx.x == 0) loss[0] = (1.0f * avg) * inv_heads;
-}
-
 constexpr int64_t kTopkMaxP = 0x7fffffffLL;      // P < 2^31: 32-bit counts, the aligned index space in a long
 constexpr int64_t kTopkMaxRows = 0x7fffffffLL;   // gridDim.x
 
@@ -304,7 +281,7 @@ using namespace unetpp;
 extern "C" int64_t unetpp_topk_focal_workspace_bytes(int32_t n_heads, int64_t rows, int64_t P) {
   if (n_heads < 1 || n_heads > UNETPP_MAX_HEADS || rows < 1 || rows > kTopkMaxRows || P < 1 || P > kTopkMaxP) return 0;
   if (rows > INT64_MAX / P) return 0;
-  const int64_t blocks = unetpp_focal_bce_blocks(rows * P);   // k >= P runs unetpp_focal_bce_heads on this workspace
+  const int64_t blocks = loss_blocks(rows * P);   // k >= P runs unetpp_focal_bce_heads on this workspace
   return static_cast<int64_t>(n_heads) * (rows > blocks ? rows : blocks) * 4;
 }
 
@@ -313,18 +290,11 @@ namespace {
 template <bool kIgnore>
 int topk_focal_heads_launch(const unetpp_focal_heads* heads, const float* target, int64_t rows, int64_t P, int64_t k,
                             int64_t denom, float gamma, void* workspace, float* kth, float* loss, void* stream) {
-  if (heads == nullptr || target == nullptr || workspace == nullptr || kth == nullptr || loss == nullptr) return UNETPP_EINVAL;
+  unetpp_focal_heads hd;
+  if (loss_heads_checked(heads, target, hd) != UNETPP_OK) return UNETPP_EINVAL;
+  if (workspace == nullptr || kth == nullptr || loss == nullptr) return UNETPP_EINVAL;
   if (rows < 1 || rows > kTopkMaxRows || P < 1 || P > kTopkMaxP || k < 1 || denom < 1) return UNETPP_EINVAL;
   if (rows > INT64_MAX / P) return UNETPP_EINVAL;
-  if (heads->n_heads < 1 || heads->n_heads > UNETPP_MAX_HEADS) return UNETPP_EINVAL;
-  uintptr_t bits = reinterpret_cast<uintptr_t>(target);
-  for (int h = 0; h < heads->n_heads; ++h) {
-    if (heads->pred[h] == nullptr) return UNETPP_EINVAL;
-    bits |= reinterpret_cast<uintptr_t>(heads->pred[h]) | reinterpret_cast<uintptr_t>(heads->grad[h]);
-  }
-  if ((bits & 15) != 0) return UNETPP_EINVAL;
-  unetpp_focal_heads hd = *heads;
-  for (int h = hd.n_heads; h < UNETPP_MAX_HEADS; ++h) hd.pred[h] = nullptr, hd.grad[h] = nullptr;
   const hipStream_t st = static_cast<hipStream_t>(stream);
   const bool all = k >= P;
   if (all) {
@@ -339,8 +309,7 @@ int topk_focal_heads_launch(const unetpp_focal_heads* heads, const float* target
                      target, static_cast<long>(P), static_cast<uint32_t>(all ? P : k), gamma,
                      1.f / static_cast<float>(denom), inv_heads, all ? 0 : 1, static_cast<float*>(workspace), kth);
   if (!all)
-    hipLaunchKernelGGL(topk_focal_finish_kernel, dim3(1), dim3(1024), 0, st, static_cast<const float*>(workspace),
-                       static_cast<long>(rows), hd.n_heads, inv_heads, loss);
+    launch_loss_heads_finish(static_cast<const float*>(workspace), static_cast<long>(rows), hd.n_heads, inv_heads, loss, st);
   return launch_status();
 }
 

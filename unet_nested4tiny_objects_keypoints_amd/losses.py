@@ -10,35 +10,46 @@ import torch
 from torch import nn
 
 
-class _FocalBCEIgnoreFn(torch.autograd.Function):
-    """The one-head ``mean_over_heads`` value of a criterion with ignore_negative (unetpp_focal_bce_heads_ignore)."""
+class _FusedLossFn(torch.autograd.Function):
+    """One map through a fused loss call: ``call(pred, target, want_grad)`` -> (the 0-dim loss, d loss / d pred or None,
+    a tuple of further outputs without a gradient).  The gradient comes with the value, so backward is one scaling."""
 
     @staticmethod
-    def forward(ctx, pred, target, rows, gamma):
-        from . import ops
-        loss, grads = ops.focal_bce_heads([pred.contiguous()], target.contiguous(), rows, gamma,
-                                          want_grad=ctx.needs_input_grad[0], ignore=True)
-        ctx.save_for_backward(grads[0] if grads is not None else None)
-        return loss[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        (grad,) = ctx.saved_tensors
-        return (grad * g if grad is not None else None), None, None, None
-
-
-class _FocalBCEFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, pred, target, rows, gamma):
-        from . import ops
-        loss, grad = ops.focal_bce(pred.contiguous(), target.contiguous(), rows, gamma, want_grad=ctx.needs_input_grad[0])
+    def forward(ctx, pred, target, call):
+        loss, grad, extras = call(pred.contiguous(), target.contiguous(), ctx.needs_input_grad[0])
         ctx.save_for_backward(grad)
-        return loss
+        ctx.mark_non_differentiable(*extras)
+        return (loss,) + tuple(extras)
 
     @staticmethod
-    def backward(ctx, g):
+    def backward(ctx, g, *_g_extras):
         (grad,) = ctx.saved_tensors
-        return (grad * g if grad is not None else None), None, None, None
+        return (grad * g if grad is not None else None), None, None
+
+
+def _one_head(loss, grads, *extras):
+    """the results of an ops.*_heads call over one head, as _FusedLossFn's call returns them"""
+    return loss[0], (grads[0] if grads is not None else None), extras
+
+
+def _fused_map_ok(input, target):
+    """One map and its target take the fused call: GPU fp32, and the target needs no gradient."""
+    return (input.is_cuda and target.is_cuda and input.dtype == torch.float32 and target.dtype == torch.float32
+            and not target.requires_grad)
+
+
+def _fused_heads_ok(outputs, target, min_heads=2, any_rank=False):
+    """The head outputs and their target take the fused call over all heads: ``min_heads`` to ``MAX_HEADS`` contiguous
+    GPU fp32 maps of the target's shape on its device, a target that needs no gradient and is [N, C, H, W] (any_rank:
+    the caller has checked the rank itself)."""
+    from . import _lib
+    if not (isinstance(outputs, (tuple, list)) and min_heads <= len(outputs) <= _lib.MAX_HEADS):
+        return False
+    if not (target.is_cuda and target.dtype == torch.float32 and not target.requires_grad
+            and (any_rank or target.dim() == 4)):
+        return False
+    return all(o.is_cuda and o.dtype == torch.float32 and o.shape == target.shape and o.is_contiguous()
+               and o.device == target.device for o in outputs)
 
 
 class FocalLoss_BCE_2d(nn.Module):
@@ -57,11 +68,15 @@ class FocalLoss_BCE_2d(nn.Module):
             input = input.reshape(-1, input.size(2), input.size(3))
         target = target.reshape(-1, target.size(2), target.size(3))
         samples_num = target.shape[0]
-        if (input.is_cuda and target.is_cuda and input.dtype == torch.float32 and target.dtype == torch.float32
-                and not target.requires_grad):
+        if _fused_map_ok(input, target):
+            from . import ops
             rows = input.numel() if self.size_average else samples_num  # mean over elements / sum over N*C rows
-            fn = _FocalBCEIgnoreFn if self.ignore_negative else _FocalBCEFn
-            return fn.apply(input, target, rows, float(self.gamma))
+            gamma = float(self.gamma)
+            if self.ignore_negative:   # (the one-head value of unetpp_focal_bce_heads_ignore)
+                call = lambda p, t, want: _one_head(*ops.focal_bce_heads([p], t, rows, gamma, want_grad=want, ignore=True))
+            else:
+                call = lambda p, t, want: ops.focal_bce(p, t, rows, gamma, want_grad=want) + ((),)
+            return _FusedLossFn.apply(input, target, call)[0]
         d = input - target
         if self.ignore_negative:   # (d = 0 under an ignored element as well: autograd's 0 * NaN through where is a NaN)
             d = torch.where(target < 0, torch.zeros_like(d), d)
@@ -79,37 +94,14 @@ class FocalLoss_BCE_2d(nn.Module):
         together: -> (avg: 0-dim tensor without a graph, [d avg / d output]) or None when the heads do not qualify (CPU
         tensors, other dtypes or layouts, more than 8 heads, a target that needs a gradient): the caller then runs the loop.
         Same bits as the loop (tests/test_gpu_caller.py); about 15 launches of ~5 us fewer per step at three or four heads."""
-        from . import _lib, ops
-        if not (isinstance(outputs, (tuple, list)) and 2 <= len(outputs) <= _lib.MAX_HEADS):
+        from . import ops
+        if not _fused_heads_ok(outputs, target):
             return None
-        if not (target.is_cuda and target.dtype == torch.float32 and not target.requires_grad and target.dim() == 4):
-            return None
-        for o in outputs:
-            if not (o.is_cuda and o.dtype == torch.float32 and o.shape == target.shape and o.is_contiguous()
-                    and o.device == target.device):
-                return None
         t = target.contiguous()
         rows = t.numel() if self.size_average else t.shape[0] * t.shape[1]
         loss, grads = ops.focal_bce_heads([o.detach() for o in outputs], t, rows, float(self.gamma),
                                           ignore=self.ignore_negative)
         return loss[0], grads
-
-
-class _TopKFocalBCEFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, pred, target, k, denom, gamma, ignore=False):
-        from . import ops
-        loss, grads, kth = ops.topk_focal_heads([pred.contiguous()], target.contiguous(), k, denom, gamma,
-                                                want_grad=ctx.needs_input_grad[0], ignore=ignore)
-        ctx.save_for_backward(grads[0] if grads is not None else None)
-        kth = kth[0]
-        ctx.mark_non_differentiable(kth)
-        return loss[0], kth
-
-    @staticmethod
-    def backward(ctx, g, _g_kth):
-        (grad,) = ctx.saved_tensors
-        return (grad * g if grad is not None else None), None, None, None, None, None
 
 
 class TopKFocalLoss_BCE_2d(nn.Module):
@@ -164,10 +156,14 @@ class TopKFocalLoss_BCE_2d(nn.Module):
         rows, pixels = target.shape[0], target.shape[1] * target.shape[2]
         k_eff = self.k_for(pixels)
         denom = self._denom(rows, k_eff)
-        if (input.is_cuda and target.is_cuda and input.dtype == torch.float32 and target.dtype == torch.float32
-                and not target.requires_grad):
-            loss, kth = _TopKFocalBCEFn.apply(input, target, k_eff, denom, float(self.gamma), self.ignore_negative)
-            self.last_threshold = kth
+        if _fused_map_ok(input, target):
+            from . import ops
+            gamma, ignore = float(self.gamma), self.ignore_negative
+
+            def call(p, t, want):
+                loss, grads, kth = ops.topk_focal_heads([p], t, k_eff, denom, gamma, want_grad=want, ignore=ignore)
+                return _one_head(loss, grads, kth[0])
+            loss, self.last_threshold = _FusedLossFn.apply(input, target, call)
             return loss
         d = (input - target).reshape(rows, pixels)
         ignored = target.reshape(rows, pixels) < 0 if self.ignore_negative else None
@@ -188,15 +184,9 @@ class TopKFocalLoss_BCE_2d(nn.Module):
         """``FocalLoss_BCE_2d.mean_over_heads`` for this criterion: the trainer's loop over the deep-supervision heads in
         ONE launch, the selection taken per head -> (avg: 0-dim tensor without a graph, [d avg / d output]) or None when
         the heads do not qualify; the caller then runs the loop.  Same bits as the loop (tests/test_gpu_topk.py)."""
-        from . import _lib, ops
-        if not (isinstance(outputs, (tuple, list)) and 2 <= len(outputs) <= _lib.MAX_HEADS):
+        from . import ops
+        if not _fused_heads_ok(outputs, target):
             return None
-        if not (target.is_cuda and target.dtype == torch.float32 and not target.requires_grad and target.dim() == 4):
-            return None
-        for o in outputs:
-            if not (o.is_cuda and o.dtype == torch.float32 and o.shape == target.shape and o.is_contiguous()
-                    and o.device == target.device):
-                return None
         t = target.contiguous()
         rows, pixels = t.shape[0] * t.shape[1], t.shape[2] * t.shape[3]
         k_eff = self.k_for(pixels)
@@ -204,22 +194,6 @@ class TopKFocalLoss_BCE_2d(nn.Module):
                                                 float(self.gamma), ignore=self.ignore_negative)
         self.last_threshold = kth
         return loss[0], grads
-
-
-class _PRFocalFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, pred, target, alpha, beta, eps, positive, ignore=False):
-        from . import ops
-        loss, grads, n_pos = ops.pr_focal_heads([pred.contiguous()], target.contiguous(), alpha, beta, eps, positive,
-                                                want_grad=ctx.needs_input_grad[0], ignore=ignore)
-        ctx.save_for_backward(grads[0] if grads is not None else None)
-        ctx.mark_non_differentiable(n_pos)
-        return loss[0], n_pos
-
-    @staticmethod
-    def backward(ctx, g, _g_n_pos):
-        (grad,) = ctx.saved_tensors
-        return (grad * g if grad is not None else None), None, None, None, None, None, None
 
 
 class PenaltyReducedFocalLoss(nn.Module):
@@ -267,11 +241,11 @@ class PenaltyReducedFocalLoss(nn.Module):
     def forward(self, input, target):
         if input.shape != target.shape:
             raise ValueError("input and target must have the same shape")
-        if (input.is_cuda and target.is_cuda and input.dtype == torch.float32 and target.dtype == torch.float32
-                and not target.requires_grad):
-            loss, n_pos = _PRFocalFn.apply(input, target, self.alpha, self.beta, self.eps, self.positive,
-                                           self.ignore_negative)
-            self.last_num_positives = n_pos
+        if _fused_map_ok(input, target):
+            from . import ops
+            call = lambda p, t, want: _one_head(*ops.pr_focal_heads([p], t, self.alpha, self.beta, self.eps, self.positive,
+                                                                    want_grad=want, ignore=self.ignore_negative))
+            loss, self.last_num_positives = _FusedLossFn.apply(input, target, call)
             return loss
         q = input.clamp(self._lo, self._hi)
         if self.ignore_negative:   # (finite operands under an ignored element: autograd's 0 * NaN through where is a NaN)
@@ -293,15 +267,9 @@ class PenaltyReducedFocalLoss(nn.Module):
         """``FocalLoss_BCE_2d.mean_over_heads`` for this criterion: the trainer's loop over the deep-supervision heads in
         ONE call, the positives counted once -> (avg: 0-dim tensor without a graph, [d avg / d output]) or None when the
         heads do not qualify; the caller then runs the loop.  Same bits as the loop (tests/test_gpu_prfocal.py)."""
-        from . import _lib, ops
-        if not (isinstance(outputs, (tuple, list)) and 2 <= len(outputs) <= _lib.MAX_HEADS):
+        from . import ops
+        if not _fused_heads_ok(outputs, target):
             return None
-        if not (target.is_cuda and target.dtype == torch.float32 and not target.requires_grad and target.dim() == 4):
-            return None
-        for o in outputs:
-            if not (o.is_cuda and o.dtype == torch.float32 and o.shape == target.shape and o.is_contiguous()
-                    and o.device == target.device):
-                return None
         loss, grads, n_pos = ops.pr_focal_heads([o.detach() for o in outputs], target.contiguous(), self.alpha, self.beta,
                                                 self.eps, self.positive, ignore=self.ignore_negative)
         self.last_num_positives = n_pos
@@ -455,10 +423,7 @@ class HeadDistillLoss(nn.Module):
         distillation term."""
         from . import ops
         self._check_heads(outputs, target)
-        fused = (target.is_cuda and target.dtype == torch.float32 and not target.requires_grad and
-                 all(o.is_cuda and o.dtype == torch.float32 and o.is_contiguous() and o.device == target.device
-                     for o in outputs))
-        if fused:
+        if _fused_heads_ok(outputs, target, min_heads=1, any_rank=True):
             t = target.contiguous()
             rows = t.numel() if self.size_average else t.numel() // (t.size(-2) * t.size(-1))
             loss, grads, sup, dis = ops.distill_heads([o.detach() for o in outputs], t, rows, float(self.gamma),

@@ -934,14 +934,34 @@ def _aligned16(t: torch.Tensor) -> torch.Tensor:
     return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
 
 
+def _loss_maps(preds, target: torch.Tensor):
+    """The checks every loss makes on its maps -> (preds, target) on 16-byte boundaries."""
+    _need(target, "target")
+    for p in preds:
+        _need(p, "pred")
+        if p.shape != target.shape:
+            raise ValueError("pred and target must have the same shape")
+    return [_aligned16(p) for p in preds], _aligned16(target)
+
+
+def _loss_heads(preds, target: torch.Tensor, want_grad: bool):
+    """What the fused head losses share -> (aligned preds, aligned target, the filled FocalHeads, grads or None)."""
+    if not 1 <= len(preds) <= _lib.MAX_HEADS:
+        raise ValueError("1 to %d heads" % _lib.MAX_HEADS)
+    preds, target = _loss_maps(preds, target)
+    grads = [torch.empty_like(p) for p in preds] if want_grad else None
+    hd = _lib.FocalHeads()
+    hd.n_heads = len(preds)
+    for i, p in enumerate(preds):
+        hd.pred[i] = p.data_ptr()
+        hd.grad[i] = grads[i].data_ptr() if want_grad else None
+    return preds, target, hd, grads
+
+
 def focal_bce(pred: torch.Tensor, target: torch.Tensor, rows: int, gamma: float, want_grad: bool = True):
     """FocalLoss_BCE_2d value (0-dim tensor) and d loss / d pred in one pass over (pred, target)."""
     lib = _lib.lib()
-    _need(pred, "pred")
-    _need(target, "target")
-    if pred.shape != target.shape:
-        raise ValueError("pred and target must have the same shape")
-    pred, target = _aligned16(pred), _aligned16(target)
+    (pred,), target = _loss_maps([pred], target)
     n = pred.numel()
     blocks = int(lib.unetpp_focal_bce_blocks(n))
     partial = torch.empty(blocks, dtype=torch.float32, device=pred.device)
@@ -958,24 +978,11 @@ def focal_bce_heads(preds, target: torch.Tensor, rows: int, gamma: float, want_g
     Bit for bit what the loop computes with focal_bce and tensor arithmetic (tests/test_gpu_caller.py).
     ignore: a negative target element contributes +0.0 to loss and gradient (unetpp_focal_bce_heads_ignore)."""
     lib = _lib.lib()
-    if not 1 <= len(preds) <= _lib.MAX_HEADS:
-        raise ValueError("1 to %d heads" % _lib.MAX_HEADS)
-    _need(target, "target")
-    for p in preds:
-        _need(p, "pred")
-        if p.shape != target.shape:
-            raise ValueError("pred and target must have the same shape")
-    preds, target = [_aligned16(p) for p in preds], _aligned16(target)
+    preds, target, hd, grads = _loss_heads(preds, target, want_grad)
     n = target.numel()
     blocks = int(lib.unetpp_focal_bce_blocks(n))
     partial = torch.empty(len(preds) * blocks, dtype=torch.float32, device=target.device)
-    grads = [torch.empty_like(p) for p in preds] if want_grad else None
     loss = torch.empty(1 + len(preds), dtype=torch.float32, device=target.device)
-    hd = _lib.FocalHeads()
-    hd.n_heads = len(preds)
-    for i, p in enumerate(preds):
-        hd.pred[i] = p.data_ptr()
-        hd.grad[i] = grads[i].data_ptr() if want_grad else None
     fn = lib.unetpp_focal_bce_heads_ignore if ignore else lib.unetpp_focal_bce_heads
     check(fn(C.byref(hd), _ptr(target), n, rows, float(gamma), _ptr(partial), _ptr(loss), _stream()),
           "unetpp_focal_bce_heads_ignore" if ignore else "unetpp_focal_bce_heads")
@@ -991,32 +998,19 @@ def topk_focal_heads(preds, target: torch.Tensor, k: int, denom: int, gamma: flo
     that is not selected) or None; kth [heads, rows]: the k-th largest |pred - target| of every head and row).
     ignore: a negative target element has key 0 and contributes +0.0 (unetpp_topk_focal_heads_ignore)."""
     lib = _lib.lib()
-    if not 1 <= len(preds) <= _lib.MAX_HEADS:
-        raise ValueError("1 to %d heads" % _lib.MAX_HEADS)
-    _need(target, "target")
+    preds, target, hd, grads = _loss_heads(preds, target, want_grad)
     if target.dim() < 3:
         raise ValueError("target must be [..., H, W]")
-    for p in preds:
-        _need(p, "pred")
-        if p.shape != target.shape:
-            raise ValueError("pred and target must have the same shape")
     if int(k) < 1 or int(denom) < 1:
         raise ValueError("k and denom must be at least 1")
-    preds, target = [_aligned16(p) for p in preds], _aligned16(target)
     pixels = target.shape[-2] * target.shape[-1]
     rows = target.numel() // max(pixels, 1)
     nbytes = int(lib.unetpp_topk_focal_workspace_bytes(len(preds), rows, pixels))
     if nbytes <= 0:
         raise ValueError("topk_focal_heads: %d rows of %d pixels are outside what the kernel takes" % (rows, pixels))
     workspace = torch.empty(nbytes // 4, dtype=torch.float32, device=target.device)
-    grads = [torch.empty_like(p) for p in preds] if want_grad else None
     loss = torch.empty(1 + len(preds), dtype=torch.float32, device=target.device)
     kth = torch.empty(len(preds), rows, dtype=torch.float32, device=target.device)
-    hd = _lib.FocalHeads()
-    hd.n_heads = len(preds)
-    for i, p in enumerate(preds):
-        hd.pred[i] = p.data_ptr()
-        hd.grad[i] = grads[i].data_ptr() if want_grad else None
     fn = lib.unetpp_topk_focal_heads_ignore if ignore else lib.unetpp_topk_focal_heads
     check(fn(C.byref(hd), _ptr(target), rows, pixels, int(k), int(denom), float(gamma), _ptr(workspace), _ptr(kth),
              _ptr(loss), _stream()), "unetpp_topk_focal_heads_ignore" if ignore else "unetpp_topk_focal_heads")
@@ -1031,27 +1025,14 @@ def pr_focal_heads(preds, target: torch.Tensor, alpha: float, beta: float, eps: 
     number of positives, a 0-dim int64 tensor on the device).
     ignore: a negative target element contributes +0.0 to loss and gradient (unetpp_pr_focal_heads_ignore)."""
     lib = _lib.lib()
-    if not 1 <= len(preds) <= _lib.MAX_HEADS:
-        raise ValueError("1 to %d heads" % _lib.MAX_HEADS)
-    _need(target, "target")
-    for p in preds:
-        _need(p, "pred")
-        if p.shape != target.shape:
-            raise ValueError("pred and target must have the same shape")
-    preds, target = [_aligned16(p) for p in preds], _aligned16(target)
+    preds, target, hd, grads = _loss_heads(preds, target, want_grad)
     n = target.numel()
     nbytes = int(lib.unetpp_pr_focal_workspace_bytes(len(preds), n))
     if nbytes <= 0:
         raise ValueError("pr_focal_heads: %d elements are outside what the kernel takes" % n)
     workspace = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=target.device)
-    grads = [torch.empty_like(p) for p in preds] if want_grad else None
     loss = torch.empty(1 + len(preds), dtype=torch.float32, device=target.device)
     n_pos = torch.empty((), dtype=torch.int64, device=target.device)
-    hd = _lib.FocalHeads()
-    hd.n_heads = len(preds)
-    for i, p in enumerate(preds):
-        hd.pred[i] = p.data_ptr()
-        hd.grad[i] = grads[i].data_ptr() if want_grad else None
     fn = lib.unetpp_pr_focal_heads_ignore if ignore else lib.unetpp_pr_focal_heads
     check(fn(C.byref(hd), _ptr(target), n, float(alpha), float(beta), float(eps), float(positive), _ptr(workspace),
              _ptr(n_pos), _ptr(loss), _stream()), "unetpp_pr_focal_heads_ignore" if ignore else "unetpp_pr_focal_heads")
@@ -1073,8 +1054,6 @@ def distill_heads(preds, target: torch.Tensor, rows: int, gamma: float, weight_d
     supervised [heads]: S_h, focal_bce_heads' values bit for bit; distill [heads]: D_h, +0.0 for the deepest head).
     ignore: a negative target element has a supervised term of +0.0, counts as having passed the gate, and keeps its
     distillation term iff distill_ignored."""
-    if not 1 <= len(preds) <= _lib.MAX_HEADS:
-        raise ValueError("1 to %d heads" % _lib.MAX_HEADS)
     if teacher not in DISTILL_TEACHERS:
         raise ValueError("teacher must be one of %s, got %r" % (sorted(DISTILL_TEACHERS), teacher))
     if gate not in DISTILL_GATES:
@@ -1086,22 +1065,11 @@ def distill_heads(preds, target: torch.Tensor, rows: int, gamma: float, weight_d
     if weight_dev.device != target.device:
         raise ValueError("weight_dev must live on the device of the target")
     lib = _lib.lib()
-    _need(target, "target")
-    for p in preds:
-        _need(p, "pred")
-        if p.shape != target.shape:
-            raise ValueError("pred and target must have the same shape")
-    preds, target = [_aligned16(p) for p in preds], _aligned16(target)
+    preds, target, hd, grads = _loss_heads(preds, target, want_grad)
     heads, n = len(preds), target.numel()
     blocks = int(lib.unetpp_focal_bce_blocks(n))
     partial = torch.empty(2 * heads * blocks, dtype=torch.float32, device=target.device)
-    grads = [torch.empty_like(p) for p in preds] if want_grad else None
     loss = torch.empty(1 + 3 * heads, dtype=torch.float32, device=target.device)
-    hd = _lib.FocalHeads()
-    hd.n_heads = heads
-    for i, p in enumerate(preds):
-        hd.pred[i] = p.data_ptr()
-        hd.grad[i] = grads[i].data_ptr() if want_grad else None
     check(lib.unetpp_distill_heads(C.byref(hd), _ptr(target), n, rows, float(gamma), _ptr(weight_dev),
                                    DISTILL_TEACHERS[teacher], DISTILL_GATES[gate], int(bool(ignore)),
                                    int(bool(distill_ignored)), _ptr(partial), _ptr(loss), _stream()), "unetpp_distill_heads")
