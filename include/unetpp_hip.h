@@ -515,6 +515,37 @@ int unetpp_pr_focal_heads_ignore(const unetpp_focal_heads* heads, const float* t
 int unetpp_distill_heads(const unetpp_focal_heads* heads, const float* target, int64_t n, int64_t rows, float gamma,
                          const float* weight, int32_t teacher, int32_t gate, int32_t ignore, int32_t distill_ignored,
                          float* partial, float* loss /* [1 + 3 * n_heads] */, void* stream);
+/* ---- distillation from an external map (csrc/distill.hip; added within v13: new entry points only) ----
+ * unetpp_distill_heads with the teacher taken from outside: EVERY head h in 0 .. n_heads - 1, the deepest included, is held
+ * against the target and, by the same element rule, against one external map q = teacher -- fp32, n elements in the
+ * target's order, read as data (another network's output, a stitched scene map).
+ *   S_h, D_h, L_h = S_h + w * D_h, loss[0] and the layout of loss [1 + 3 * n_heads] are unetpp_distill_heads', formed by
+ *   the same statements in the same order: S_h is unetpp_focal_bce_heads' (ignore = 1: _ignore's) loss[1 + h] bit for
+ *   bit; where every element is admitted D_h is unetpp_focal_bce(pred[h], teacher)'s loss bit for bit; with the deepest
+ *   head's own map as teacher, heads 0 .. n_heads - 2 have the bits of unetpp_distill_heads(UNETPP_DISTILL_LAST).
+ *   grad[h] = g_s + w * g_d on an admitted element (one rounded product, one rounded sum), g_s itself, with its bits, on
+ *             an element that is kept out and where the product w * g_d is a zero (the sum would only turn a g_s of -0.0,
+ *             an exact hit of the target, into +0.0): with weight[0] = 0 on finite inputs loss and gradients are
+ *             unetpp_focal_bce_heads' bit for bit; grad[h] may be NULL.
+ * Admitted: the teacher exists there AND the gate AND the ignore rule.
+ *   void:    an element with q < 0.0f has no teacher and is kept out (-0.0 and a NaN are not negative: a NaN teacher element
+ *            is admitted and reaches D_h and loss[0]; nothing is hidden).  The -1 that fills a cut window outside its
+ *            frame voids the teacher there.
+ *   gate = 1: |q - t| < |p - t|, a float32 comparison of the absolute values of the two float32 differences (false with a
+ *            NaN on either side).
+ *   ignore = 1: an element with t < 0.0f has S term and g_s +0.0, counts as having passed the gate, and is admitted iff
+ *            distill_ignored = 1 and the teacher exists there.
+ * A thread reads its 8 targets and 8 teacher values once and walks the heads: 2 + 2 * n_heads map-sized streams.
+ * partial: workspace of 2 * n_heads * unetpp_focal_bce_blocks(n) floats.  weight: one float32 on the device, finite and
+ * >= 0 (not checked: the call does not read it on the host).  Two launches, no host synchronisation, no atomics: two runs
+ * give the same bits, and a captured call follows later changes of weight[0] and of the teacher buffer's contents.
+ * UNETPP_EINVAL, without touching the device, for every case unetpp_distill_heads refuses (a NULL pointer, grad[h]
+ * excepted; n < 1; rows < 1; n_heads outside 1 .. UNETPP_MAX_HEADS; a negative or NaN gamma; a flag outside its values;
+ * target or a pred[h] / grad[h] not 16-byte aligned; weight not 4-byte aligned), a NULL teacher and a teacher that is not
+ * 16-byte aligned. */
+int unetpp_teacher_heads(const unetpp_focal_heads* heads, const float* target, const float* teacher, int64_t n, int64_t rows,
+                         float gamma, const float* weight, int32_t gate, int32_t ignore, int32_t distill_ignored,
+                         float* partial, float* loss /* [1 + 3 * n_heads] */, void* stream);
 /* ---- ensemble head of an eval forward (added within v12: new entry points only, nothing existing changes) ----
  * The output selection the UNet++ authors left as comments in models/unet.py:293-298: the mean of the first n_heads
  * deep-supervision heads, out = (((s_1 + s_2) + ...) + s_n) / (float)n with s_h = 1 / (1 + exp(-(bias_h + x_h . w_h)))

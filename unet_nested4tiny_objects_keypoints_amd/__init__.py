@@ -11,7 +11,8 @@ include/unetpp_hip.h).  There is no CPU or eager-PyTorch fallback: using the mod
 library, or with CPU tensors, raises.
 """
 from .unet import UNet, UNet_Nested, count_param  # noqa: F401
-from .losses import FocalLoss_BCE_2d, HeadDistillLoss, PenaltyReducedFocalLoss, TopKFocalLoss_BCE_2d  # noqa: F401
+from .losses import (FocalLoss_BCE_2d, HeadDistillLoss, PenaltyReducedFocalLoss, TeacherDistillLoss,  # noqa: F401
+                     TopKFocalLoss_BCE_2d)
 from .step import train_step  # noqa: F401
 from .engine import McMaps, pruned_parameters  # noqa: F401
 from .targets import create_heatmap  # noqa: F401
@@ -33,4 +34,4 @@ __all__ = ["UNet_Nested", "UNet", "count_param", "FocalLoss_BCE_2d", "train_step
            "warp_batch", "SceneInference", "CascadeSceneInference", "PeakDetector", "Detections", "DetectionScore",
            "evaluate", "classes_from_pattern", "SceneCrops", "false_positive_centres", "TopKFocalLoss_BCE_2d",
            "pruned_parameters", "PenaltyReducedFocalLoss", "IgnoreRegions", "IgnoreMask", "IgnoreUnion", "McMaps", "ObjectPaste",
-           "PasteRows", "HeadDistillLoss"]
+           "PasteRows", "HeadDistillLoss", "TeacherDistillLoss"]

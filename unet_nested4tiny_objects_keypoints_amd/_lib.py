@@ -337,6 +337,8 @@ SIGNATURES = {
     # self-distillation across the heads: the deep head's map as a soft target of the shallow ones (distill.hip; added
     # within ABI 13)
     "unetpp_distill_heads": (C.c_int, [C.POINTER(FocalHeads), _P, _I64, _I64, _F, _P, _I32, _I32, _I32, _I32, _P, _P, _P]),
+    # the same with one external map as every head's teacher (distill.hip; added within ABI 13)
+    "unetpp_teacher_heads": (C.c_int, [C.POINTER(FocalHeads), _P, _P, _I64, _I64, _F, _P, _I32, _I32, _I32, _P, _P, _P]),
     # ignore masks: packed bit planes from a raster or from polygon rings, and the per-step mark (mask.hip; added within
     # ABI 13)
     "unetpp_mask_pack": (C.c_int, [_P, _I32, _I64, _I32, _P, _P]),

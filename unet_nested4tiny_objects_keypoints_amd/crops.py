@@ -212,12 +212,21 @@ class SceneCrops:
     with p = 0 the batches are those of an object without paste, bit for bit.
 
     The centre table starts as the valid labels; set_centres / add_centres replace / extend it -- a sampling policy such
-    as class balancing is a matter of what the caller puts there."""
+    as class balancing is a matter of what the caller puts there.
+
+    teacher: float32 [S, n_classes, H, W] on the frames' device and of the frames' size -- what
+    ``SceneInference(...)(frames)`` returns -- as a soft target for ``TeacherDistillLoss``: batch(n) then cuts the same
+    windows out of it by one more unetpp_warp_batch launch (the batch's own index and params rows with gain 1 and bias 0,
+    mul 1, add 0, fill -1) into ``last_teacher`` [n, n_classes, Ho, Wo]: every element is a teacher element, or -1
+    ("no teacher") outside the frame.  Only under the augmentations that resample nothing (rotate = 0, scale = (1, 1)),
+    with at most 8 classes (the warp's channel limit) and without paste (a pasted object is not in the teacher's map):
+    anything else raises ValueError.  The teacher's values are finite.  inputs, target, points and inside are the bits
+    of an object without teacher; the seed stream is untouched."""
 
     def __init__(self, frames, labels, label_class, n_classes: int, crop=(256, 256), p_object: float = 0.75,
                  jitter=(32, 32), augment: Optional[Augment] = None, radius: float = 3.0, mul=1.0 / 255.0, add=0.0,
                  fill: float = 0.0, seed: int = 0, ignore=None, ignore_outside: bool = False,
-                 paste: Optional[ObjectPaste] = None):
+                 paste: Optional[ObjectPaste] = None, teacher: Optional[torch.Tensor] = None):
         self.augment = Augment() if augment is None else augment
         self.crop = (int(crop[0]), int(crop[1]))
         if min(self.crop) < 1:
@@ -283,6 +292,42 @@ class SceneCrops:
                 raise TypeError("paste must be an ObjectPaste")
             paste._bind(self)
             self.paste = paste
+        self.teacher, self.last_teacher = None, None
+        if teacher is not None:
+            self._bind_teacher(teacher)
+
+    def _bind_teacher(self, teacher) -> None:
+        if not isinstance(teacher, torch.Tensor) or not teacher.is_cuda:
+            raise RuntimeError("teacher must live on the GPU: this path has no CPU fallback")
+        if teacher.dtype != torch.float32:
+            raise TypeError("teacher must be float32 [S, n_classes, H, W], got %s" % teacher.dtype)
+        if self.augment.rotate != 0.0 or self.augment.scale != (1.0, 1.0):
+            raise ValueError("a teacher is cut only under augmentations that resample nothing: rotate = 0 and "
+                             "scale = (1, 1), got %r" % (self.augment,))
+        if self.paste is not None:
+            raise ValueError("paste and teacher do not go together: a pasted object is not in the teacher's map")
+        if self.n_classes > _lib.WARP_MAX_C:
+            raise ValueError("a teacher has at most %d classes (the warp's channel limit), got %d"
+                             % (_lib.WARP_MAX_C, self.n_classes))
+        want = (len(self), self.n_classes, int(self.src_size[0]), int(self.src_size[1]))
+        if tuple(teacher.shape) != want:
+            raise ValueError("teacher must be [%d, %d, %d, %d], got %s" % (want + (tuple(teacher.shape),)))
+        if teacher.device != self.device:
+            raise ValueError("teacher must live on the device of the frames")
+        self.teacher = teacher.detach().contiguous()
+        # a drawn row's gain and bias belong to the pixels: a probability keeps its value
+        a = self.augment
+        self._teacher_rows_drawn = a.contrast == (1.0, 1.0) and a.brightness == 0.0   # gain 1 and bias +-0 as drawn
+        self._teacher_unit = torch.tensor([1.0, 0.0], dtype=torch.float32, device=self.device)
+        self._teacher_mul = torch.ones(self.n_classes, dtype=torch.float32, device=self.device)
+        self._teacher_add = torch.zeros(self.n_classes, dtype=torch.float32, device=self.device)
+
+    def _cut_teacher(self, index, params) -> torch.Tensor:
+        rows = params
+        if not self._teacher_rows_drawn:
+            rows = params.clone()
+            rows[:, 12:14] = self._teacher_unit
+        return ops.warp_batch(self.teacher, index, rows, self.crop, self._teacher_mul, self._teacher_add, -1.0)
 
     def __len__(self):
         return int(self.frames.shape[0])
@@ -335,6 +380,8 @@ class SceneCrops:
                                       part.rect_class if part is not None else None, index, params, self.src_size,
                                       outside, n_frames=len(self))
         self.last = (params, index, origin)
+        if self.teacher is not None:
+            self.last_teacher = self._cut_teacher(index, params)
         return inputs, target, points, inside
 
     def batches(self, batch_size: int, steps: int):

@@ -188,10 +188,130 @@ __global__ __launch_bounds__(kFinishThreads) void distill_finish_kernel(const fl
   });
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// A teacher from outside (losses.TeacherDistillLoss, unetpp_teacher_heads): every head, the deepest included, is held
+// against the target and against ONE external map q of the target's shape (another network's output, a stitched scene
+// map), read as data.  The element functions, the two combinations and the finish are the ones above, so S_h, D_h, L_h
+// and the mean are formed exactly as unetpp_distill_heads forms them, and with the deepest head's own map as q heads
+// 0 .. J-2 have unetpp_distill_heads(teacher = last)'s bits.  What is new is the void rule: an element with q < 0.0f
+// has no teacher (-0.0 and a NaN are not negative: a NaN teacher element is admitted and reaches the loss, as t < 0
+// hides nothing either), so the -1 that fills a window outside its frame keeps the term out there.  A thread keeps its
+// 8 targets and its 8 teacher values in registers and walks the heads: 2 + 2 J map-sized streams for J heads.
+struct TeacherFlags {
+  int gate;             // teacher_better
+  int distill_ignored;  // kIgnore only: an ignored element keeps its distillation term
+};
+
+template <bool kLow, bool kIgnore>
+__device__ __forceinline__ void teacher_head(const float (&p)[kVecs][4], const float (&t)[kVecs][4],
+                                             const float (&q)[kVecs][4], float* __restrict__ grad, long base, long n,
+                                             float gamma, float inv_rows, float scale, float w, const TeacherFlags f,
+                                             float& sum_s, float& sum_d) {
+#pragma clang fp contract(off)
+  const bool cube = gamma == 3.f;
+  sum_s = 0.f;
+  sum_d = 0.f;
+#pragma unroll
+  for (int h = 0; h < kVecs; ++h) {
+    const long i = base + 4 * h;
+    if (i >= n) break;
+    float g[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float lg, ug, le, gs, gd;
+      distill_element<kLow>(p[h][e], t[h][e], gamma, cube, inv_rows, scale, lg, ug, le, gs);
+      const bool inside = i + e < n;
+      bool take = inside;
+      bool ignored = false;
+      if constexpr (kIgnore) {
+        if (t[h][e] < 0.f) ignored = true, take = false, gs = 0.f;
+      }
+      if (take) sum_s = distill_add_term<kLow>(sum_s, lg, ug, le);
+      distill_element<kLow>(p[h][e], q[h][e], gamma, cube, inv_rows, scale, lg, ug, le, gd);
+      bool admit = true;
+      if (f.gate) admit = fabsf(q[h][e] - t[h][e]) < fabsf(p[h][e] - t[h][e]);
+      if constexpr (kIgnore) {
+        if (ignored) admit = f.distill_ignored != 0;
+      }
+      if (q[h][e] < 0.f) admit = false;   // void: no teacher here
+      if (admit && inside) sum_d = distill_add_term<kLow>(sum_d, lg, ug, le);
+      // kept out: the supervised gradient's own bits.  The same where w g_d is a zero (w = 0, an exact hit of the
+      // teacher): g_s + 0 is g_s but for g_s = -0.0 at an exact hit of the target, which a sum with +0.0 would turn into
+      // +0.0 -- and weight 0 is unetpp_focal_bce_heads bit for bit.  A NaN product is not a zero and goes through.
+      g[e] = (admit && w * gd != 0.f) ? distill_combine(gs, w, gd) : gs;
+    }
+    store4(grad, i, n, g);
+  }
+}
+
+template <bool kLow, bool kIgnore>
+__global__ __launch_bounds__(kLossThreads) void teacher_heads_kernel(const unetpp_focal_heads hd,
+                                                                    const float* __restrict__ target,
+                                                                    const float* __restrict__ teacher, long n, float gamma,
+                                                                    float inv_rows, float scale,
+                                                                    const float* __restrict__ weight, const TeacherFlags f,
+                                                                    float* __restrict__ partial) {
+  __shared__ float red[2][UNETPP_MAX_HEADS][kLossThreads / 64];
+  const long base = (blockIdx.x * static_cast<long>(kLossThreads) + threadIdx.x) * kLossPerThread;
+  const float w = weight[0];
+  float t[kVecs][4], q[kVecs][4], p[kVecs][4];
+  load_thread(target, base, n, t);
+  load_thread(teacher, base, n, q);
+  for (int h = 0; h < hd.n_heads; ++h) {
+    load_thread(hd.pred[h], base, n, p);
+    float sum_s, sum_d;
+    teacher_head<kLow, kIgnore>(p, t, q, hd.grad[h], base, n, gamma, inv_rows, scale, w, f, sum_s, sum_d);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+      sum_s += __shfl_xor(sum_s, off);
+      sum_d += __shfl_xor(sum_d, off);
+    }
+    if ((threadIdx.x & 63) == 0) {
+      red[0][h][threadIdx.x >> 6] = sum_s;
+      red[1][h][threadIdx.x >> 6] = sum_d;
+    }
+  }
+  __syncthreads();
+  if (static_cast<int>(threadIdx.x) < 2 * hd.n_heads) {
+    const int h = threadIdx.x >> 1, k = threadIdx.x & 1;
+    const float* r = red[k][h];
+    partial[static_cast<long>(threadIdx.x) * gridDim.x + blockIdx.x] = ((r[0] + r[1]) + (r[2] + r[3])) * inv_rows;
+  }
+}
+
 }  // namespace
 }  // namespace unetpp
 
 using namespace unetpp;
+
+extern "C" int unetpp_teacher_heads(const unetpp_focal_heads* heads, const float* target, const float* teacher, int64_t n,
+                                    int64_t rows, float gamma, const float* weight, int32_t gate, int32_t ignore,
+                                    int32_t distill_ignored, float* partial, float* loss, void* stream) {
+  unetpp_focal_heads hd;
+  if (loss_heads_checked(heads, target, hd) != UNETPP_OK) return UNETPP_EINVAL;
+  if (teacher == nullptr || weight == nullptr || partial == nullptr || loss == nullptr || n < 1 || rows < 1)
+    return UNETPP_EINVAL;
+  if ((gate != 0 && gate != 1) || (ignore != 0 && ignore != 1) || (distill_ignored != 0 && distill_ignored != 1))
+    return UNETPP_EINVAL;
+  if (!(gamma >= 0.f)) return UNETPP_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(teacher) & 15) != 0 || (reinterpret_cast<uintptr_t>(weight) & 3) != 0)
+    return UNETPP_EINVAL;
+  const int64_t blocks = loss_blocks(n);
+  if (blocks > 0x7fffffffLL) return UNETPP_EINVAL;
+  const float inv_heads = 1.0f / static_cast<float>(hd.n_heads);
+  TeacherFlags f;
+  f.gate = gate;
+  f.distill_ignored = distill_ignored;
+  const bool low = gamma < 1.f;
+  const auto kernel = ignore ? (low ? teacher_heads_kernel<true, true> : teacher_heads_kernel<false, true>)
+                             : (low ? teacher_heads_kernel<true, false> : teacher_heads_kernel<false, false>);
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(blocks)), dim3(kLossThreads), 0, st, hd, target, teacher,
+                     static_cast<long>(n), gamma, 1.f / static_cast<float>(rows), inv_heads, weight, f, partial);
+  hipLaunchKernelGGL(distill_finish_kernel, dim3(1), dim3(kFinishThreads), 0, st, static_cast<const float*>(partial),
+                     static_cast<long>(blocks), hd.n_heads, inv_heads, weight, loss);
+  return launch_status();
+}
 
 extern "C" int unetpp_distill_heads(const unetpp_focal_heads* heads, const float* target, int64_t n, int64_t rows, float gamma,
                                     const float* weight, int32_t teacher, int32_t gate, int32_t ignore,

@@ -443,3 +443,171 @@ class HeadDistillLoss(nn.Module):
         ``train_step``: one autograd node whose backward is one scaling of the gradients ``mean_over_heads`` produced."""
         self._check_heads(outputs, target)
         return _HeadDistillFn.apply(self, target, *outputs)
+
+
+class TeacherDistillLoss(nn.Module):
+    """Distillation from an external teacher: every head, the deepest included, is trained against the labels as
+    ``FocalLoss_BCE_2d`` trains it and against ONE map from outside -- another network's output, a stitched
+    ``SceneInference`` map cut by ``SceneCrops(teacher=...)``, ``infer_mc``'s mean -- set with ``set_teacher`` and read as
+    data.  For heads p_1 .. p_J (a tuple, shallow to deep), the target t and the teacher's map q:
+
+        S_j = FocalLoss_BCE_2d(gamma, size_average, ignore_negative)(p_j, t);
+        D_j = the FocalLoss_BCE_2d(gamma, size_average) sum of p_j against q over the admitted elements, divided by
+              S_j's divisor;
+        L_j = S_j + weight * D_j;   loss = the trainer's mean over heads of L_j.
+
+    An element is admitted where the teacher exists -- ``q < 0`` means "no teacher here" (-0.0 and a NaN are not
+    negative: a NaN of the teacher reaches the loss), so the -1 that fills a cut window outside its frame keeps the term
+    out -- and where the gate and the ignore rule of ``HeadDistillLoss`` admit it: gate="teacher_better" asks
+    ``|q - t| < |p - t|`` on the float32 differences (a NaN on either side keeps the element out); with
+    ``ignore_negative`` an element with ``t < 0`` has a supervised term and gradient of +0.0, counts as having passed
+    the gate, and keeps its distillation term when ``distill_ignored`` (a frame under one whole-frame ignore rectangle
+    then trains on the teacher alone) or is kept out when not.
+
+    ``set_teacher(maps)`` copies a float32 tensor of the target's shape into a buffer the class keeps per (device,
+    shape): the first call allocates it, every later call with the same device and shape is a ``copy_`` into the same
+    memory without a host synchronisation, so a captured ``GraphedTrainStep`` follows the teacher of each step without a
+    new capture, as it follows ``set_weight``.  A new shape or device allocates a new buffer, and a step captured before
+    does not see it: capture again.  ``mean_over_heads`` raises when no teacher is set for the target's device and
+    shape -- training silently without the term is what the class exists to prevent.
+
+    ``forward(input, target)`` takes ONE map and returns ``FocalLoss_BCE_2d``'s value with the same bits, so a per-head
+    loop (``validate_step``, a ``no_grad`` report) shows the supervised loss.  GPU fp32 heads take one fused HIP call
+    (csrc/distill.hip: unetpp_teacher_heads, 2 + 2 J map-sized streams); anything else the same rule as plain torch ops.
+    ``last_supervised`` and ``last_distill`` hold S_j and D_j as [heads] tensors on the device of the target.
+
+    Deliberately not a subclass of ``FocalLoss_BCE_2d``: code that tests for that class computes the loss without the
+    distillation term."""
+
+    def __init__(self, weight=0.5, gate="none", distill_ignored=True, gamma=3, size_average=False, ignore_negative=False):
+        super().__init__()
+        if gate not in ("none", "teacher_better"):
+            raise ValueError("gate must be 'none' or 'teacher_better', got %r" % (gate,))
+        if not float(gamma) >= 0.0:
+            raise ValueError("gamma must be >= 0, got %r" % (gamma,))
+        self.gate = gate
+        self.distill_ignored = bool(distill_ignored)
+        self.gamma = gamma
+        self.size_average = size_average
+        self.ignore_negative = bool(ignore_negative)
+        self._supervised = FocalLoss_BCE_2d(gamma=gamma, size_average=size_average, ignore_negative=ignore_negative)
+        self._weight_dev = {}   # device -> the one-element float32 tensor the kernel reads
+        self._teacher = {}      # (device, shape) -> the buffer the kernel reads
+        self.weight = self._checked_weight(weight)
+        self.last_supervised = None
+        self.last_distill = None
+
+    _checked_weight = staticmethod(HeadDistillLoss._checked_weight)
+    set_weight = HeadDistillLoss.set_weight
+    weight_tensor = HeadDistillLoss.weight_tensor
+
+    @staticmethod
+    def _device(device):
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        return device
+
+    def set_teacher(self, maps):
+        """The teacher's maps from now on for targets of ``maps``' device and shape: float32, used detached.  The first
+        call for a (device, shape) allocates a private buffer; every later one is a ``copy_`` into it (same
+        ``data_ptr()``, no host synchronisation), which a captured step reads at its next replay.  A new shape or device
+        allocates anew: a step captured before needs a new capture.  -> the buffer."""
+        if not torch.is_tensor(maps):
+            raise TypeError("the teacher's maps must be a tensor")
+        if maps.dtype != torch.float32:
+            raise TypeError("the teacher's maps must be torch.float32, got %s" % maps.dtype)
+        if maps.dim() < 3:
+            raise ValueError("the teacher's maps must be [..., H, W]")
+        key = (self._device(maps.device), tuple(maps.shape))
+        buf = self._teacher.get(key)
+        if buf is None:
+            buf = self._teacher[key] = torch.empty(key[1], dtype=torch.float32, device=key[0])
+        buf.copy_(maps.detach())
+        return buf
+
+    def clear_teacher(self):
+        """forget every teacher buffer"""
+        self._teacher.clear()
+
+    def teacher_tensor(self, target):
+        """the buffer ``set_teacher`` filled for ``target``'s device and shape; RuntimeError when there is none"""
+        buf = self._teacher.get((self._device(target.device), tuple(target.shape)))
+        if buf is None:
+            raise RuntimeError("TeacherDistillLoss: no teacher set for a target of shape %s on %s (set_teacher first)"
+                               % (tuple(target.shape), target.device))
+        return buf
+
+    def forward(self, input, target):
+        return self._supervised(input, target)
+
+    def _rule(self, outputs, target, teacher=None):
+        """the rule as plain torch ops -> (avg with a graph, S [heads], D [heads])"""
+        heads = len(outputs)
+        dtype = outputs[0].dtype
+        rows = target.numel() if self.size_average else target.numel() // (target.size(-2) * target.size(-1))
+        w = self.weight_tensor(target.device)[0].to(dtype)
+        q = (self.teacher_tensor(target) if teacher is None else teacher).detach()
+        exists = ~(q < 0)
+        q = q.to(dtype)
+        ignored = (target < 0) if self.ignore_negative else None
+        sup, dis = [], []
+        avg = 0
+        for p in outputs:
+            s = self._supervised(p, target)
+            admit = torch.ones_like(target, dtype=torch.bool)
+            if self.gate == "teacher_better":
+                admit = (q - target).abs() < (p.detach() - target).abs()
+            if ignored is not None:
+                admit = torch.where(ignored, torch.full_like(admit, self.distill_ignored), admit)
+            admit = admit & exists
+            # (finite operands under an element that is kept out: autograd's 0 * NaN through where is a NaN)
+            d = torch.where(admit, p - q, torch.full_like(p, 0.5))
+            error = 1 - torch.abs(d) + 1e-20
+            term = -1 * (1 - error) ** self.gamma * torch.log(error)
+            dj = torch.where(admit, term, torch.zeros_like(term)).sum() / rows
+            sup.append(s.detach())
+            dis.append(dj.detach())
+            avg = avg + (s + w * dj)
+        avg = 1.0 * avg / heads
+        return avg, torch.stack(sup), torch.stack(dis)
+
+    def _check_heads(self, outputs, target):
+        from . import _lib
+        if not isinstance(outputs, (tuple, list)) or not 1 <= len(outputs) <= _lib.MAX_HEADS:
+            raise ValueError("TeacherDistillLoss takes a tuple of 1 to %d heads" % _lib.MAX_HEADS)
+        if target.dim() < 3:
+            raise ValueError("target must be [..., H, W]")
+        for o in outputs:
+            if o.shape != target.shape:
+                raise ValueError("every head must have the shape of the target")
+
+    def mean_over_heads(self, outputs, target):
+        """The loss over the tuple of heads and its gradients in one call -> (avg: 0-dim tensor without a graph,
+        [d avg / d output]) for 1 to ``MAX_HEADS`` heads; more raise, and so does a target for whose device and shape no
+        teacher is set.  Fp32 contiguous GPU heads take the fused launch; anything else the same rule as torch ops with
+        the gradients from ``torch.autograd.grad``.  Never None: the written-out loop the caller would fall back to
+        calls ``forward`` per head and would train without the distillation term."""
+        from . import ops
+        self._check_heads(outputs, target)
+        teacher = self.teacher_tensor(target)
+        if _fused_heads_ok(outputs, target, min_heads=1, any_rank=True):
+            t = target.contiguous()
+            rows = t.numel() if self.size_average else t.numel() // (t.size(-2) * t.size(-1))
+            loss, grads, sup, dis = ops.teacher_heads([o.detach() for o in outputs], t, teacher, rows, float(self.gamma),
+                                                      self.weight_tensor(t.device), self.gate,
+                                                      ignore=self.ignore_negative, distill_ignored=self.distill_ignored)
+            self.last_supervised, self.last_distill = sup, dis
+            return loss[0], grads
+        with torch.enable_grad():
+            leaves = [o.detach().requires_grad_(True) for o in outputs]
+            avg, sup, dis = self._rule(leaves, target.detach(), teacher)
+            grads = torch.autograd.grad(avg, leaves)
+        self.last_supervised, self.last_distill = sup, dis
+        return avg.detach(), list(grads)
+
+    def heads_loss(self, outputs, target):
+        """The loss over the tuple of heads as a differentiable 0-dim tensor, for callers that do not go through
+        ``train_step``: one autograd node whose backward is one scaling of the gradients ``mean_over_heads`` produced."""
+        self._check_heads(outputs, target)
+        return _HeadDistillFn.apply(self, target, *outputs)

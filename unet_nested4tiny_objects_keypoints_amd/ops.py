@@ -1076,6 +1076,45 @@ def distill_heads(preds, target: torch.Tensor, rows: int, gamma: float, weight_d
     return loss[:1 + heads], grads, loss[1 + heads:1 + 2 * heads], loss[1 + 2 * heads:]
 
 
+def teacher_heads(preds, target: torch.Tensor, teacher: torch.Tensor, rows: int, gamma: float, weight_dev: torch.Tensor,
+                  gate: str = "none", want_grad: bool = True, ignore: bool = False, distill_ignored: bool = True):
+    """focal_bce_heads with distillation from one external map (csrc/distill.hip: unetpp_teacher_heads, one call): every
+    head, the deepest included, is also held against `teacher` -- float32, of the target's shape, read as data -- by the
+    same element rule, over the elements where the teacher exists (an element < 0 has none; -0.0 and a NaN are not
+    negative) and that the gate and the ignore rule admit; L_h = S_h + w D_h with w = weight_dev[0], read on the device.
+    -> (losses [1 + heads]: the mean over heads of L_h, then every L_h; d mean / d pred per head or None;
+    supervised [heads]: S_h, focal_bce_heads' values bit for bit; distill [heads]: D_h).
+    ignore: a negative target element has a supervised term of +0.0, counts as having passed the gate, and keeps its
+    distillation term iff distill_ignored and the teacher exists there."""
+    if gate not in DISTILL_GATES:
+        raise ValueError("gate must be one of %s, got %r" % (sorted(DISTILL_GATES), gate))
+    if not torch.is_tensor(weight_dev) or weight_dev.numel() != 1:
+        raise ValueError("weight_dev must be a tensor of one element")
+    if weight_dev.dtype != torch.float32:
+        raise TypeError("weight_dev must be torch.float32, got %s" % weight_dev.dtype)
+    if weight_dev.device != target.device:
+        raise ValueError("weight_dev must live on the device of the target")
+    if not torch.is_tensor(teacher):
+        raise TypeError("teacher must be a tensor")
+    if teacher.dtype != torch.float32:
+        raise TypeError("teacher must be torch.float32, got %s" % teacher.dtype)
+    if teacher.device != target.device:
+        raise ValueError("teacher must live on the device of the target")
+    if teacher.shape != target.shape:
+        raise ValueError("teacher must have the shape of the target")
+    lib = _lib.lib()
+    preds, target, hd, grads = _loss_heads(preds, target, want_grad)
+    teacher = _aligned16(_need(teacher, "teacher"))
+    heads, n = len(preds), target.numel()
+    blocks = int(lib.unetpp_focal_bce_blocks(n))
+    partial = torch.empty(2 * heads * blocks, dtype=torch.float32, device=target.device)
+    loss = torch.empty(1 + 3 * heads, dtype=torch.float32, device=target.device)
+    check(lib.unetpp_teacher_heads(C.byref(hd), _ptr(target), _ptr(teacher), n, rows, float(gamma), _ptr(weight_dev),
+                                   DISTILL_GATES[gate], int(bool(ignore)), int(bool(distill_ignored)), _ptr(partial),
+                                   _ptr(loss), _stream()), "unetpp_teacher_heads")
+    return loss[:1 + heads], grads, loss[1 + heads:1 + 2 * heads], loss[1 + 2 * heads:]
+
+
 def create_heatmap(points: torch.Tensor, height: int, width: int, radius: float = 3.0) -> torch.Tensor:
     """points [N, P, 2] (x, y) fp32 on the GPU -> target heat maps [N, 4, H, W] (tools/misc/helper.py:87-172)."""
     lib = _lib.lib()
