@@ -671,8 +671,12 @@ int unetpp_heatmap_pattern(const float* points, int32_t N, int32_t P, const int3
  * region step (region_segment_, heatmap.py:100-144: distance-transform cores grown back by a watershed, so that blobs
  * which touch are split) goes between: 0; 3 = 3x3 chamfer distance initialised; 4 = `sweeps` relaxation sweeps, repeat
  * until *changed stays 0; 5 = cores (distance > 0.1 * the map's maximum) as labels; 1.. = components of the cores;
- * 6 = markers (core root / background beyond the two-pixel ring / unknown); 7 = `sweeps` pairs of flood rounds, repeat
- * until *changed stays 0; 8 = region labels; 2.
+ * 6 = markers (core root / background beyond the two-pixel ring / unknown); 7 = `sweeps` pairs of level-0 flood rounds
+ * (labels pass between pixels of the same mask value), repeat until *changed stays 0; 9 = one cross round (the
+ * watershed's level 255: any labelled 4-neighbour passes its label on, which floods a hole enclosed by a region) and one
+ * level-0 round, *changed set when either moved a pixel; alternate 7-until-stable and 9 until a stage 9 leaves *changed
+ * at 0 (at most H*W times: each such stage 9 labels a pixel); 8 = region labels; 2.  Stages 7 and 9 leave the current
+ * state in the marker buffer.  (Stage 9 was added within ABI version 13: a stage number that was an error before.)
  * Workspace layout (for callers that want the regions themselves, region_segment_'s return value): uint64 best
  * [maps*H*W], uint64 [maps*max_regions*2], then int32 label [maps*H*W] (after stage 8 / the last stage 1: raster index
  * of the region's first pixel, -1 outside), int32 distance [maps*H*W] (16-bit fixed point), int32 marker [maps*H*W]. */

@@ -11,7 +11,9 @@
 // distance > float32(0.1 * the map's maximum), 8-connected components of the cores, and the watershed of the BINARY mask
 // image seeded with them: cores grow over 4-neighbours through their blob, the background marker through the two-pixel
 // ring the reference leaves unknown around the mask, a pixel reached by two different labels in the same round becomes a
-// line.  Blobs that touch are split, a blob without a core (thinner than a tenth of the thickest) is no region.  The
+// line; when nothing moves any more, one round across the mask's edge (the watershed's level 255: a hole enclosed by a
+// region takes that region's label), and so on until such a round changes nothing.
+// Blobs that touch are split, a blob without a core (thinner than a tenth of the thickest) is no region.  The
 // round-2 stand-in -- a region = an 8-connected component of the mask -- stays available (stages 0, 1, 2 alone).
 // OpenCV is absent from the build image, so this row is "parity unpinned": checked against oracle/keypoints_oracle.py only.
 //
@@ -240,9 +242,12 @@ __global__ __launch_bounds__(kKpThreads) void kp_marker_kernel(int H, int W, con
 // pixels is level 0): an unknown pixel with a labelled 4-neighbour of its own mask value takes the label its labelled
 // neighbours agree on, or becomes a line (-1) where they differ.  Lines and the background marker do not count as a
 // region later; lines are not propagated.  Rounds are synchronous (src -> dst): the result does not depend on timing.
+// cross != 0 is one round of the image's other level, 255 (cv2.watershed serves it only while level 0 has nothing
+// queued): the neighbour's mask value does not matter, any labelled 4-neighbour passes its label on.  This is what
+// floods a hole that a region encloses (unknown, mask value 0, labelled mask pixels all around) with that region's label.
 __global__ __launch_bounds__(kKpThreads) void kp_flood_kernel(int H, int W, const int* __restrict__ dist,
                                                               const int* __restrict__ src, int* __restrict__ dst,
-                                                              int* __restrict__ changed) {
+                                                              int cross, int* __restrict__ changed) {
   const long hw = static_cast<long>(H) * W;
   const long i = blockIdx.x * static_cast<long>(kKpThreads) + threadIdx.x;
   if (i >= hw) return;
@@ -264,7 +269,7 @@ __global__ __launch_bounds__(kKpThreads) void kp_flood_kernel(int H, int W, cons
       if (l <= 0) continue;
       lo = min(lo, l);
       hi = max(hi, l);
-      active = active || ((d[q] > 0) == inside);
+      active = active || cross != 0 || ((d[q] > 0) == inside);
     }
     if (active) {
       mk = lo == hi ? lo : -1;
@@ -423,7 +428,10 @@ extern "C" int64_t unetpp_keypoints_workspace_bytes(int32_t maps, int32_t H, int
 // points [maps, num, 2] as (x, y), -1 where there is no region; counts [maps] = regions found.
 // The reference's region step sits between 0 and 2: 3 = distance initialised from the mask; 4 = `sweeps` relaxation
 // sweeps (repeat until *changed stays 0); 5 = cores -> labels (then stage 1 until stable: components of the cores);
-// 6 = markers; 7 = `sweeps` pairs of flood rounds (repeat until *changed stays 0); 8 = region labels; then stage 2.
+// 6 = markers; 7 = `sweeps` pairs of level-0 flood rounds (repeat until *changed stays 0); 9 = one cross round (level
+// 255) followed by one level-0 round, *changed set when either moved a pixel (after a stable stage 7: when the cross
+// round did); the caller alternates 7-until-stable and 9 until a stage 9 leaves *changed at 0; 8 = region labels; then
+// stage 2.  Stages 7 and 9 both leave the current state in `marker`.
 extern "C" int unetpp_keypoints_extract(int32_t stage, const float* heat, int32_t maps, int32_t H, int32_t W,
                                         const float* thr_per_map, int32_t num, int32_t max_regions, int32_t sweeps,
                                         void* workspace, int32_t* changed, float* points, int32_t* counts, void* stream) {
@@ -466,9 +474,13 @@ extern "C" int unetpp_keypoints_extract(int32_t stage, const float* heat, int32_
   } else if (stage == 7) {
     if (!changed || sweeps < 1) return UNETPP_EINVAL;
     for (int s = 0; s < sweeps; ++s) {  // pairs: the current state is always in `marker` between calls
-      hipLaunchKernelGGL(kp_flood_kernel, grid, dim3(kKpThreads), 0, st, H, W, dist, marker, label, changed);
-      hipLaunchKernelGGL(kp_flood_kernel, grid, dim3(kKpThreads), 0, st, H, W, dist, label, marker, changed);
+      hipLaunchKernelGGL(kp_flood_kernel, grid, dim3(kKpThreads), 0, st, H, W, dist, marker, label, 0, changed);
+      hipLaunchKernelGGL(kp_flood_kernel, grid, dim3(kKpThreads), 0, st, H, W, dist, label, marker, 0, changed);
     }
+  } else if (stage == 9) {
+    if (!changed) return UNETPP_EINVAL;  // a cross round, then a plain one: the state is back in `marker`, as after stage 7
+    hipLaunchKernelGGL(kp_flood_kernel, grid, dim3(kKpThreads), 0, st, H, W, dist, marker, label, 1, changed);
+    hipLaunchKernelGGL(kp_flood_kernel, grid, dim3(kKpThreads), 0, st, H, W, dist, label, marker, 0, changed);
   } else if (stage == 8) {
     hipLaunchKernelGGL(kp_region_kernel, grid, dim3(kKpThreads), 0, st, H, W, marker, label);
   } else {

@@ -1185,7 +1185,18 @@ def _keypoints_stages(heat, thr, num, max_regions, segmentation, ws, changed, po
     until_stable(1, "keypoints merge", 4)
     if segmentation == "watershed":
         stage(6, "keypoints markers")
-        until_stable(7, "keypoints flood", 4)
+        # The watershed's two levels: level-0 rounds until stable, one cross round (stage 9), level 0 again, until a cross
+        # round moves nothing.  A cross round that moves something labels at least one pixel and no pixel is labelled
+        # twice: h * w bounds the loop.  Stage 9 is the cross round and the first level-0 round after it in one batch
+        # with one read-back (until_stable returns with the flag at 0, and a level-0 round on a stable state moves
+        # nothing, so the flag says whether the cross round did): a batch without holes costs two launches and one read.
+        for _ in range(h * w + 1):
+            until_stable(7, "keypoints flood", 4)
+            stage(9, "keypoints flood across the mask edge")
+            if int(changed.item()) == 0:
+                break
+        else:
+            raise RuntimeError("keypoints_extract: keypoints flood did not converge")
         stage(8, "keypoints regions")
     if select:
         stage(2, "keypoints select")
