@@ -10,11 +10,12 @@
 //   * MFMA row = tile, MFMA k = 4 channels, MFMA column = output column: per transform position xi one accumulator
 //     pair (2 x 16 columns), acc[16][2] float4 = 128 VGPRs per lane.  (16 columns per unit halve that, but the input
 //     transform and the epilogue then cost twice the VALU per MFMA, and VALU issue is what bounds this kernel.)
-//   * A operand: lane (tile t, k-slot g) reads its 4x4 window one channel at a time (16 ds_read_b32), runs the input
+//   * A operand: lane (tile t, k-slot g) reads its 4x4 window one channel at a time (general kernel: 16 ds_read_b32 from a
+//     pixel-major patch, 10 floats per pixel; LEAN: 8 ds_read_b64 from a channel-planar patch, below), runs the input
 //     transform B^T d B IN REGISTERS (32 add/sub per channel) and feeds the 16 results straight to 32 MFMAs -- the
 //     transformed input never exists in memory;
 //   * B operand: the transformed weights U = G g G^T are precomputed per launch (weight_image.hip) as an LDS image
-//     whose lane-linear 8-byte reads each feed two MFMAs;
+//     whose lane-linear 16-byte reads (ds_read_b128, conflict-free) each feed four MFMAs: two steps x two column halves;
 //   * all 16 xi of a (tile, column) land in the same lane and register index, so the output transform A^T M A is
 //     lane-local (24 add/sub per 2x2 tile); bias/ReLU/gate/accumulate/BatchNorm partial sums and 16-byte transposed
 //     stores follow as in the direct kernel;
@@ -31,8 +32,14 @@
 //     for out-of-image halo pixels (their offset is simply out of range), so the staging of a chunk is three loads and
 //     three LDS stores per thread -- no clamping, no selects -- issued inside the first MFMA groups of the chunk
 //     before.  MODE 2 adds the BatchNorm fold / ReLU on load: the chunk's coefficients are requested with the cursor,
-//     a chunk ahead, and the padding is restored by a bitwise AND with the in-image mask.  MODE 0 is the general
-//     kernel (any view geometry, partial chunks, per-element padding select).
+//     a chunk ahead, and the padding is restored by a bitwise AND with the in-image mask.  The LEAN patch is channel
+//     planar, [8 channels][WPL = 400], pixel slot hy * HWp + hx: lane (t16, g) reads channel 2g + s at
+//     (2g + s) * WPL + row * HWp + 2 * t16, so with 32-pixel-wide patches the g = 0 lanes of a 32-lane half cover 32
+//     consecutive banks and the g = 1 lanes the other 32 (2 * WPL = 32 mod 64; ds_read_b64 is banked mod 64): no
+//     conflicts, where the pixel-major patch read through ds_read2_b32 was 2-way conflicted on every read (tiles t and
+//     t + 8 on one bank).  The narrower patches (16 and 8 pixels wide) keep a partial 2-way conflict.  The staging
+//     writes a thread's four channels to four planes (12 ds_write_b32 per chunk).  MODE 0 is the general kernel (any
+//     view geometry, partial chunks, per-element padding select, pixel-major patch).
 #include <cstdlib>
 #include <utility>
 
@@ -95,6 +102,14 @@ constexpr int WKC = 8;      // channels per K chunk
 constexpr int WNC = 32;     // columns per unit
 constexpr int WP = 10;      // LDS pixel stride of the input patch (floats): 8 channels + 2 pad
 constexpr int WIMG = 4096;  // floats of one (column tile, chunk) weight image
+// LEAN instantiations keep the patch channel-planar, [8 channels][WPL], pixel slot hy * HWp + hx inside a plane.  The pitch
+// is at least 384, so that the dummy staging items behind the patch (pixel slots up to 383) stay in their own plane, and
+// 2 * WPL = 32 (mod 64), so that the k-slot lanes g and g + 1 of a 32-lane half read opposite halves of the 64-bank row.
+constexpr int WPL = 400;
+
+// max(v, floor) that keeps a NaN and returns +0 for (-0, +0): one v_maximum3_f32 where common.h's floor_keep_nan is a
+// compare and a select.  The same bits for every input but a signalling NaN, which comes out quiet.
+__device__ __forceinline__ float floor_max(float v, float floor_v) { return __builtin_elementwise_maximum(v, floor_v); }
 
 #define WINO_FENCE() __builtin_amdgcn_sched_barrier(0)
 
@@ -115,6 +130,9 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_wino_kernel(const FastArgs a
   static_assert(IN_ITEMS == 3 && W_ITEMS == 4, "the staging lambdas' default ranges");
   static_assert(kMaxHaloPixels * WP <= IN_FLOATS, "input patch does not fit");
   static_assert(((IN_ITEMS * kThreads - 1) >> 1) * WP + 8 <= IN_FLOATS, "staging items past the patch must stay inside the buffer");
+  static_assert(WKC * WPL <= IN_FLOATS && NPIX <= WPL, "planar input patch does not fit");
+  static_assert(((IN_ITEMS * kThreads - 1) >> 1) < WPL, "staging items past the patch must stay inside their own plane");
+  static_assert((2 * WPL) % 64 == 32 && WPL % 2 == 0 && HWp % 2 == 0, "conflict-free, 8-byte aligned ds_read_b64 of the window rows");
   // Two (input patch, weight image) buffers: the next chunk is written into the other buffer at the top of the
   // current chunk (its loads were issued a whole chunk earlier), so a chunk costs one barrier.
   constexpr int BUF = IN_FLOATS + WIMG;
@@ -154,8 +172,9 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_wino_kernel(const FastArgs a
 
   // compute side: this lane's tile (A operand / input transform) and weight-image slot (B operand)
   const int my_tile = 16 * wave + t16;
-  const int a_base = ((2 * (my_tile / TXN)) * HWp + 2 * (my_tile % TXN)) * WP + 2 * g;  // channel 2g (+s)
-  const int b_base = (g * 16 + t16) * 2;
+  const int a_pixel = (2 * (my_tile / TXN)) * HWp + 2 * (my_tile % TXN);
+  const int a_base = LEAN ? 2 * g * WPL + a_pixel : a_pixel * WP + 2 * g;  // channel 2g (+s)
+  const int b_base = (g * 16 + t16) * 4;  // lane-linear 16-byte pieces
 
   f32x4 acc[16][NH];
 #pragma unroll
@@ -361,10 +380,11 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_wino_kernel(const FastArgs a
           const unsigned inside = ~static_cast<unsigned>(pix[q] >> 31);
 #pragma unroll
           for (int e = 0; e < 4; ++e)
-            v[e] = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, floor_keep_nan(fmaf(v[e], co_sc[e], co_sh[e]), co_floor)) & inside);
+            v[e] = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, floor_max(fmaf(v[e], co_sc[e], co_sh[e]), co_floor)) & inside);
         }
-        *reinterpret_cast<f32x2*>(&in_dst[(it >> 1) * WP + cc]) = f32x2{v[0], v[1]};
-        *reinterpret_cast<f32x2*>(&in_dst[(it >> 1) * WP + cc + 2]) = f32x2{v[2], v[3]};
+        // four planes, ds_write_b32: the two lanes of a pixel share a bank, which costs a ds_write_b32 nothing
+#pragma unroll
+        for (int e = 0; e < 4; ++e) in_dst[(cc + e) * WPL + (it >> 1)] = v[e];
       }
       return;
     }
@@ -444,8 +464,8 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_wino_kernel(const FastArgs a
       for (int b = 0; b < 4; ++b)
         tb[b] = (ap == 0) ? (acc[b][nh][rr] + acc[4 + b][nh][rr]) + acc[8 + b][nh][rr]
                           : (acc[4 + b][nh][rr] - acc[8 + b][nh][rr]) - acc[12 + b][nh][rr];
-      y[0] = floor_keep_nan((tb[0] + tb[1]) + tb[2], floor_v);
-      y[1] = floor_keep_nan((tb[1] - tb[2]) - tb[3], floor_v);
+      y[0] = floor_max((tb[0] + tb[1]) + tb[2], floor_v);
+      y[1] = floor_max((tb[1] - tb[2]) - tb[3], floor_v);
     };
     if (interior && vec_out && tc.n_cnt == 16 * NH) {
       // ---- lean path (whole patch inside the image, all columns, 16-byte stores): no per-element predicates ----
@@ -490,8 +510,8 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_wino_kernel(const FastArgs a
             const f32x2 t0 = (tb[0] + tb[1]) + tb[2], t1 = (tb[1] - tb[2]) - tb[3];
             // the floor per element, not v_pk_max_f32: it keeps a NaN.  (One uniform `if (O.relu)` block instead, which
             // launches without the ReLU branch past, measured SLOWER than this: profiles/nonfinite/.)
-            y[0][cp] = f32x2{floor_keep_nan(t0.x, floor_v), floor_keep_nan(t0.y, floor_v)};
-            y[1][cp] = f32x2{floor_keep_nan(t1.x, floor_v), floor_keep_nan(t1.y, floor_v)};
+            y[0][cp] = f32x2{floor_max(t0.x, floor_v), floor_max(t0.y, floor_v)};
+            y[1][cp] = f32x2{floor_max(t1.x, floor_v), floor_max(t1.y, floor_v)};
           }
           yv[0][nh] = f32x4{y[0][0].x, y[0][0].y, y[0][1].x, y[0][1].y};
           yv[1][nh] = f32x4{y[1][0].x, y[1][0].y, y[1][1].x, y[1][1].y};
@@ -629,17 +649,14 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_wino_kernel(const FastArgs a
     // ---- this chunk's first LDS operands are requested before the staging work below, which covers their latency
     const unsigned in_b = lds_offset(in_tile) + a_base * 4, w_b = lds_offset(w_tile) + b_base * 4;
     float dd[16], ddn[16], V[16];
-    // LEAN: the window is read pairwise (ds_read2_b32: elements j, j + 1 of a row are WP floats apart) into register
-    // pairs, one base register per window row, and transformed with packed adds: half the LDS and VALU instructions
+    // LEAN: a window row of one channel is four consecutive floats of its plane, read as two ds_read_b64 (8-byte aligned:
+    // HWp and the tile column are even) into register pairs and transformed with packed adds; every offset is an immediate
     f32x2_t dp[8], dpn[8];
-    unsigned row_b[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) row_b[i] = in_b + i * HWp * WP * 4;
     f32x4 us[2][2];  // two register sets of four weight fragments (steps 4g .. 4g+3), read one group ahead
     if constexpr (LEAN) {
       static_for<8>([&](auto ic) {
-        constexpr int e = decltype(ic)::v, j = 2 * (e & 1);
-        lds_read2_b32<j * WP, (j + 1) * WP>(dp[e], row_b[e >> 1]);
+        constexpr int e = decltype(ic)::v;
+        lds_read_b64<((e >> 1) * HWp + 2 * (e & 1)) * 4>(dp[e], in_b);
       });
     } else {
       static_for<16>([&](auto ic) {
@@ -647,8 +664,8 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_wino_kernel(const FastArgs a
         lds_read_b32<((e / 4) * HWp + (e % 4)) * WP * 4>(dd[e], in_b);
       });
     }
-    lds_read2st64_b64<0, 1>(us[0][0], w_b);
-    lds_read2st64_b64<2, 3>(us[0][1], w_b);
+    lds_read_b128<0>(us[0][0], w_b);  // steps 0, 1: both column halves of each
+    lds_read_b128<1024>(us[0][1], w_b);
 
     float* other = smem + (cur ^ 1) * BUF;
     if constexpr (!LEAN) {
@@ -697,14 +714,14 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_wino_kernel(const FastArgs a
     static_for<8>([&](auto gc) {  // group g = steps 4g .. 4g+3 of the chunk's 32 ([s][xi]); 8 MFMAs each
       constexpr int g = decltype(gc)::v, cs = g & 1, ns = cs ^ 1;
       if constexpr (g + 1 < 8) {
-        lds_read2st64_b64<4 * (g + 1), 4 * (g + 1) + 1>(us[ns][0], w_b);
-        lds_read2st64_b64<4 * (g + 1) + 2, 4 * (g + 1) + 3>(us[ns][1], w_b);
+        lds_read_b128<2048 * (g + 1)>(us[ns][0], w_b);  // steps 4(g+1), 4(g+1)+1
+        lds_read_b128<2048 * (g + 1) + 1024>(us[ns][1], w_b);
       }
       if constexpr (g == 0) {  // the second channel's window, needed from group 4 on
         if constexpr (LEAN) {
           static_for<8>([&](auto ic) {
-            constexpr int e = decltype(ic)::v, j = 2 * (e & 1);
-            lds_read2_b32<j * WP + 1, (j + 1) * WP + 1>(dpn[e], row_b[e >> 1]);
+            constexpr int e = decltype(ic)::v;
+            lds_read_b64<(WPL + (e >> 1) * HWp + 2 * (e & 1)) * 4>(dpn[e], in_b);
           });
         } else {
           static_for<16>([&](auto ic) {

@@ -32,11 +32,15 @@ template <int OFF>
 __device__ __forceinline__ void lds_read_b32(float& v, unsigned addr) {
   asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
 }
-template <int O0, int O1>  // two 8-byte reads 512 * O0 and 512 * O1 bytes above addr
-__device__ __forceinline__ void lds_read2st64_b64(f32x4& v, unsigned addr) {
-  asm volatile("ds_read2st64_b64 %0, %1 offset0:%2 offset1:%3" : "=v"(v) : "v"(addr), "n"(O0), "n"(O1));
+template <int OFF>  // sixteen bytes OFF bytes above addr (16-byte aligned)
+__device__ __forceinline__ void lds_read_b128(f32x4& v, unsigned addr) {
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
 }
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
+template <int OFF>  // eight bytes OFF bytes above addr (8-byte aligned) into a register pair
+__device__ __forceinline__ void lds_read_b64(f32x2_t& v, unsigned addr) {
+  asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
+}
 template <int O0, int O1>  // two 4-byte reads 4 * O0 and 4 * O1 bytes above addr (O0, O1 <= 255) into a register pair
 __device__ __forceinline__ void lds_read2_b32(f32x2_t& v, unsigned addr) {
   asm volatile("ds_read2_b32 %0, %1 offset0:%2 offset1:%3" : "=v"(v) : "v"(addr), "n"(O0), "n"(O1));

@@ -2,8 +2,8 @@
 //
 // A fast kernel reads its B operand as an LDS image per (column tile, K chunk): the direct kernels
 // (gemm_fast.hip) [tap][g 2][col 32][half' 2][4] over 16-channel chunks, the Winograd kernel (gemm_wino.hip)
-// [s 2][xi 16][g 4][col 16][nh 2] of U = G g G^T over 8-channel chunks.  The element of the GEMM weight that lands in
-// an image slot is W[tap][k][n]; `unetpp_weight_src` says where that element sits in memory:
+// [s 2][xi / 2][g 4][col 16][xi % 2][nh 2] of U = G g G^T over 8-channel chunks (16 bytes per lane (g, col) and pair of
+// transform positions).  The element of the GEMM weight that lands in an image slot is W[tap][k][n]; `unetpp_weight_src` says where that element sits in memory:
 //     src[tap' * s_t + (k % k_inner) * s_k + (k / k_inner) * s_ko + (n % n_inner) * s_n + (n / n_inner) * s_no],
 // tap' = flip ? taps - 1 - tap : tap, which covers the packed [taps][K][N] operand as well as nn.Conv2d
 // ([co,ci,3,3]: forward and 180-degree-rotated input-gradient form) and nn.ConvTranspose2d ([ci,co,2,2]: forward
@@ -81,10 +81,12 @@ __device__ __forceinline__ void fill_image_row(const PackGeom& g, const unetpp_w
     const RowOrigin o = row_origin(g, static_cast<int>(row / g.n_chunks), static_cast<int>(row % g.n_chunks));
     const int t = tid;  // nh | col << 1 | gq << 5 | s << 7
     const int kk = 2 * ((t >> 5) & 3) + ((t >> 7) & 1), cl = 16 * (t & 1) + ((t >> 1) & 15);
-    float* dst = img + row * 4096 + (t & 127) + (static_cast<long>(t >> 7) << 11);
+    // slot of (xi, lane = gq | col, nh): nh | (xi & 1) << 1 | lane << 2 | (xi >> 1) << 8 | s << 11
+    float* dst = img + row * 4096 + (t & 1) + (((t >> 1) & 63) << 2) + (static_cast<long>(t >> 7) << 11);
+    auto slot = [](int xi) { return ((xi & 1) << 1) + ((xi >> 1) << 8); };
     if (kk >= o.k_room || cl >= o.n_room) {
 #pragma unroll
-      for (int xi = 0; xi < 16; ++xi) dst[xi << 7] = 0.f;
+      for (int xi = 0; xi < 16; ++xi) dst[slot(xi)] = 0.f;
       return;
     }
     const int k = o.k0 + kk, n = o.n0 + cl;
@@ -99,10 +101,10 @@ __device__ __forceinline__ void fill_image_row(const PackGeom& g, const unetpp_w
     }
 #pragma unroll
     for (int ra = 0; ra < 4; ++ra) {
-      dst[(4 * ra + 0) << 7] = tr[ra][0];
-      dst[(4 * ra + 1) << 7] = 0.5f * (tr[ra][0] + tr[ra][1] + tr[ra][2]);
-      dst[(4 * ra + 2) << 7] = 0.5f * (tr[ra][0] - tr[ra][1] + tr[ra][2]);
-      dst[(4 * ra + 3) << 7] = tr[ra][2];
+      dst[slot(4 * ra + 0)] = tr[ra][0];
+      dst[slot(4 * ra + 1)] = 0.5f * (tr[ra][0] + tr[ra][1] + tr[ra][2]);
+      dst[slot(4 * ra + 2)] = 0.5f * (tr[ra][0] - tr[ra][1] + tr[ra][2]);
+      dst[slot(4 * ra + 3)] = tr[ra][2];
     }
     return;
   }
@@ -189,9 +191,9 @@ __device__ __forceinline__ void fill_bf16_3x3_block(const PackGeom& g, const une
 __device__ __forceinline__ float image_element(const PackGeom& g, const unetpp_weight_src& w, long i) {
   int kk, cin_local, tap = 0, xi = 0;
   long r;
-  if (g.kind == kKindWino) {  // [s 2][xi 16][g 4][col 16][nh 2]
-    const int nh = i & 1, col = (i >> 1) & 15, gq = (i >> 5) & 3, s = (i >> 11) & 1;
-    xi = (i >> 7) & 15;
+  if (g.kind == kKindWino) {  // [s 2][xi / 2 8][g 4][col 16][xi % 2 2][nh 2]
+    const int nh = i & 1, col = (i >> 2) & 15, gq = (i >> 6) & 3, s = (i >> 11) & 1;
+    xi = (((i >> 8) & 7) << 1) | ((i >> 1) & 1);
     kk = 2 * gq + s;
     cin_local = 16 * nh + col;
     r = i >> 12;
