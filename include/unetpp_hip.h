@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define UNETPP_ABI_VERSION 13
+#define UNETPP_ABI_VERSION 14
 #define UNETPP_MAX_VIEWS 8
 
 #define UNETPP_OK 0
@@ -320,8 +320,9 @@ int unetpp_bn_bwd_apply(const float* d_act, const float* y, const float* scale, 
  * consumer's gradient d_pooled [N, H/2, W/2, C] is routed to the argmax recorded by unetpp_affine_relu_pool WHILE
  * d_act is read, in both passes, instead of a separate unetpp_maxpool_bwd pass over d_act.  Needs
  * unetpp_bn_bwd_pool_ok(N, H, W, C) (4-aligned C with a power-of-two C/4 <= 256, even H and W, < 2^31 elements);
- * otherwise call unetpp_maxpool_bwd and the plain functions.  partial: unetpp_bn_bwd_blocks(N*H*W, C) rows, finished
- * by unetpp_bn_bwd_finalize as usual. */
+ * and every operand but `partial` 16-byte aligned (pool_idx: 4 bytes); otherwise call unetpp_maxpool_bwd and the plain
+ * functions.  unetpp_bn_bwd_plan (below) answers both questions for a whole call.  partial:
+ * unetpp_bn_bwd_blocks(N*H*W, C) rows, finished by unetpp_bn_bwd_finalize as usual. */
 int unetpp_bn_bwd_pool_ok(int32_t N, int32_t H, int32_t W, int32_t C);
 int unetpp_bn_bwd_reduce_pool(const float* d_act, const float* y, const float* scale, const float* shift,
                               const float* mean, const float* invstd, const float* d_pooled, const uint8_t* pool_idx,
@@ -348,6 +349,38 @@ int64_t unetpp_bn_frozen_bwd_blocks(int64_t pixels, int32_t C);
 int unetpp_bn_frozen_bwd(const float* d_act, const float* y, const float* scale, const float* shift,
                          const float* mean, const float* invstd, const float* d_pooled, const uint8_t* pool_idx,
                          int32_t N, int32_t H, int32_t W, int32_t C, float* dy, float* partial, void* stream);
+
+/* What one BatchNorm + ReLU backward needs settled before it runs (v14).  The library looks at the call once, with the
+ * selection its launchers use, and says how the pool gradient travels and how large `partial` is:
+ *   training: unetpp_bn_bwd_reduce[_pool|_bf16], unetpp_bn_bwd_finalize, unetpp_bn_bwd_apply[_pool|_bf16]
+ *   frozen:   unetpp_bn_frozen_bwd[_bf16], and unetpp_bn_bwd_finalize when want_sums. */
+typedef struct unetpp_bn_bwd_query {
+  int32_t frozen;     /* != 0: running statistics (unetpp_bn_frozen_bwd), else training mode */
+  int32_t bf16;       /* != 0: d_act / y / dy / d_pooled address bf16 */
+  int32_t want_sums;  /* frozen only: the gamma / beta sums are wanted (training mode always takes them) */
+  int32_t N, H, W, C;
+  int32_t reserved;
+  /* every pointer the launches will get: only the addresses are looked at (their alignment selects kernels).  d_pooled
+   * and pool_idx both NULL: no pooled consumer.  gamma / dgamma / dbeta: training mode only.  mean / invstd may be NULL
+   * for a frozen layer without sums. */
+  const void *d_act, *y, *dy, *scale, *shift, *mean, *invstd, *gamma, *dgamma, *dbeta, *d_pooled, *pool_idx;
+} unetpp_bn_bwd_query;
+typedef struct unetpp_bn_bwd_sizes {
+  int32_t route;          /* 0: no pool gradient.  1: pass d_pooled / pool_idx to the launches (unetpp_bn_bwd_reduce_pool and
+                             unetpp_bn_bwd_apply_pool in fp32 training mode), which route it while they read d_act.
+                             2: unetpp_maxpool_bwd[_bf16] into d_act first, then the launches without a pool gradient */
+  int32_t reserved;
+  int64_t partial_rows;   /* rows of `partial` and n_blocks of unetpp_bn_bwd_finalize: what the unetpp_bn_*_blocks[_bf16]
+                             function of the mode and storage type returns; 0 for a shape none of the kernels takes */
+  int64_t partial_floats; /* partial_rows * C * 2 */
+} unetpp_bn_bwd_sizes;
+/* route is 1 exactly when EVERY launch of the sequence accepts the routing form for these shapes and addresses (fp32:
+ * unetpp_bn_bwd_pool_ok and 16-byte aligned operands, coefficients and parameter gradients, 4-byte aligned pool_idx),
+ * otherwise 2 where unetpp_maxpool_bwd[_bf16] and the plain forms accept.  UNETPP_EINVAL for a NULL argument, half a
+ * pool gradient, or a call some launch of every route would refuse (bf16 storage with C != 8 * 2^k, or with a pool
+ * gradient on odd H or W); partial_rows and partial_floats are filled all the same.
+ * Touches no device memory and launches nothing. */
+int unetpp_bn_bwd_plan(const unetpp_bn_bwd_query* q, unetpp_bn_bwd_sizes* out);
 
 /* ---- deep-supervision head: sigmoid(Conv1x1(Dropout(x))) (models/unet.py:242-244,254,283-286) ---- */
 /* x NHWC [P, C]; weight [n_cls, C]; out NCHW [N, n_cls, H, W].  Dropout: keep mask regenerated from

@@ -114,7 +114,7 @@ HOST_TABLE = [
 @dataclass(frozen=True)
 class PoolCell:
     """affine_relu_pool with scale / shift / ReLU and act, pooled, pool_idx requested, then maxpool_bwd on its winners
-    (fp32 NHWC, C = 128): both sides of rows_form_ok (pointwise.hip)."""
+    (fp32 NHWC, C = 128): both sides of stream_rows_form_ok (stream_select.h)."""
     id: str
     n: int
     h: int
@@ -159,7 +159,7 @@ BILINEAR_CELLS = [
 @dataclass(frozen=True)
 class BnCell:
     """ops.bn_backward (reduce, finalize, apply; dy in place, as the engine calls it) on C = 128, with and without the
-    gradient of the max-pool routed through it, on both sides of bn_bwd_pool_ok (pointwise.hip): below 2^31 elements the
+    gradient of the max-pool routed through it, on both sides of stream_bn_pool_ok (stream_select.h): below 2^31 elements the
     pool-fused row kernels run, at 2^31 a maxpool_bwd pass and then the plain kernels.  label: the apply's, the last
     launch; adds: the form of tests/test_gpu_streaming.reduce_adds that counts the additions of a partial row."""
     id: str

@@ -19,7 +19,7 @@ def built_lib():
 
 
 def test_abi_version_is_unchanged(built_lib):
-    assert built_lib.lib().unetpp_abi_version() == built_lib.ABI_VERSION == 13
+    assert built_lib.lib().unetpp_abi_version() == built_lib.ABI_VERSION == 14
 
 
 def test_entry_point_rejects_bad_arguments(built_lib):

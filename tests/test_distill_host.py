@@ -345,13 +345,13 @@ def test_entry_point_refuses_bad_arguments_without_touching_the_device(built_lib
 
 def test_header_declares_the_entry_point_and_the_abi_is_still_13(built_lib):
     text = open(os.path.join(ROOT, "include", "unetpp_hip.h")).read()
-    assert re.search(r"#define UNETPP_ABI_VERSION 13\b", text)
+    assert re.search(r"#define UNETPP_ABI_VERSION 14\b", text)
     code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     assert re.search(r"\bint unetpp_distill_heads\s*\(", code)
     assert re.search(r"#define UNETPP_DISTILL_LAST 0\b", code) and re.search(r"#define UNETPP_DISTILL_NEXT 1\b", code)
     assert "added within v13: new entry points only" in text[:text.index("int unetpp_distill_heads")].rsplit("/*", 1)[1]
     assert "unetpp_distill_heads" in built_lib.SIGNATURES and "distill.hip" in built_lib.SOURCES
-    assert built_lib.ABI_VERSION == 13 and built_lib.lib().unetpp_abi_version() == 13
+    assert built_lib.ABI_VERSION == 14 and built_lib.lib().unetpp_abi_version() == 14
     assert (built_lib.DISTILL_LAST, built_lib.DISTILL_NEXT) == (0, 1)
 
 
@@ -361,5 +361,5 @@ def test_library_builds_from_scratch_with_distill(tmp_path):
     assert os.path.exists(str(tmp_path / "obj" / "distill.o"))
     handle = C.CDLL(out)
     handle.unetpp_abi_version.restype = C.c_int
-    assert handle.unetpp_abi_version() == 13
+    assert handle.unetpp_abi_version() == 14
     assert hasattr(handle, "unetpp_distill_heads")

@@ -14,7 +14,7 @@ def _lib():
 
 def test_new_entry_points_validate_without_a_device():
     mod, lib = _lib()
-    assert lib.unetpp_abi_version() == 13 == mod.ABI_VERSION
+    assert lib.unetpp_abi_version() == 14 == mod.ABI_VERSION
     buf = (ctypes.c_float * 64)()
     p = ctypes.cast(buf, ctypes.c_void_p)
     for fn in (lib.unetpp_bn_frozen_bwd, lib.unetpp_bn_frozen_bwd_bf16):

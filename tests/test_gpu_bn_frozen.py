@@ -20,12 +20,12 @@ import pytest
 import torch
 
 from tests.helpers import U32, bound_ratio, close_bf16, gamma, report_ratio
+from tests.stream_rules import (FROZEN_CAP, K_THREADS, al16, bn_bwd_pool_ok, fin_threads, frozen_blocks, frozen_blocks_bf16,  # noqa: F401
+                                frozen_blocks_for, octets_ok, ref_route, shifted, windows)
 
 pytestmark = pytest.mark.gpu
 
 BF = torch.bfloat16
-K_THREADS = 256
-FROZEN_CAP = 2048                 # bn_frozen_blocks_for / unetpp_bn_frozen_bwd_blocks_bf16: workgroups before the grid-stride loop
 GATE_MARGIN = 8 * U32
 GRID = 2.0 ** 24
 EVAL_DIV_SQRT_ULPS = 2.0          # as tests/test_gpu_streaming.py: sqrtf and the fp32 division, in u each (an estimate)
@@ -68,51 +68,7 @@ def stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-def al16(t):
-    return t is None or t.data_ptr() % 16 == 0
-
-
-def shifted(t, nbytes=4):
-    """The same values in a slice of a longer tensor that starts `nbytes` past a 16-byte boundary."""
-    k = nbytes // t.element_size()
-    buf = torch.empty(t.numel() + 16, dtype=t.dtype, device=t.device)
-    v = buf[k:k + t.numel()].view(t.shape)
-    v.copy_(t)
-    assert v.data_ptr() % 16 == nbytes and v.is_contiguous()
-    return v
-
-
 # ------------------------------------------------------------------------------- the launcher's conditions, restated
-def frozen_blocks_for(pixels, c, vec):   # pointwise.hip bn_frozen_blocks_for
-    cg = c // 4 if vec else c
-    want = max(1, min(FROZEN_CAP, -(-pixels * cg // K_THREADS)))
-    return -(-want // cg) * cg
-
-
-def frozen_blocks(pixels, c):   # unetpp_bn_frozen_bwd_blocks
-    return max(frozen_blocks_for(pixels, c, True) if c % 4 == 0 else 0, frozen_blocks_for(pixels, c, False))
-
-
-def frozen_blocks_bf16(pixels, c):   # unetpp_bn_frozen_bwd_blocks_bf16
-    return max(1, min(FROZEN_CAP, -(-pixels * (c // 8) // K_THREADS)))
-
-
-def bn_bwd_pool_ok(n, h, w, c):   # pointwise.hip bn_bwd_pool_ok
-    if n < 1 or h < 2 or w < 2 or c < 4 or h & 1 or w & 1 or c & 3:
-        return False
-    cg = c >> 2
-    return cg & (cg - 1) == 0 and cg <= K_THREADS and n * h * w * c < 0x7fffffff
-
-
-def octets_ok(c):   # pointwise_bf16.hip octets_ok
-    cg = c >> 3
-    return c >= 8 and c & 7 == 0 and cg & (cg - 1) == 0 and cg <= 256
-
-
-def fin_threads(rows):   # pointwise.hip fin_threads
-    return 1024 if rows >= 4096 else 512 if rows >= 1024 else 256
-
-
 def plan(n, h, w, c, form):
     """(adds, items or rows of the launch, items or rows one pass of the grid covers) of a form."""
     pixels = n * h * w
@@ -127,20 +83,6 @@ def plan(n, h, w, c, form):
     cg = c // 4 if form == "vec" else c
     span = frozen_blocks_for(pixels, c, form == "vec") * K_THREADS
     return -(-pixels * cg // span) + -(-K_THREADS // cg), pixels * cg, span
-
-
-def windows(t):
-    h2, w2 = t.shape[1] // 2 * 2, t.shape[2] // 2 * 2
-    return [t[:, (q >> 1):h2:2, (q & 1):w2:2, :] for q in range(4)]
-
-
-def ref_route(d_pooled, idx, shape):
-    """float64 NHWC tensor of `shape`: d_pooled at the recorded winner of every window, zero elsewhere."""
-    out = torch.zeros(shape, dtype=torch.float64, device=d_pooled.device)
-    dp = d_pooled.double()
-    for q, v in enumerate(windows(out)):
-        v.copy_(torch.where(idx == q, dp, torch.zeros_like(dp)))
-    return out
 
 
 # ------------------------------------------------------------------------------- one launch through the C ABI

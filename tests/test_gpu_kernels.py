@@ -758,6 +758,71 @@ def test_batchnorm_backward_with_pool_routing(dev, b, h, w, c):
     assert rel_err(dg.cpu(), ref_dg.cpu()) < 1e-5 and rel_err(db.cpu(), ref_db.cpu()) < 1e-5
 
 
+@pytest.mark.parametrize("shape", [(2, 6, 10, 8), (2, 6, 16, 32)], ids=["2x6x10x8", "2x6x16x32"])
+@pytest.mark.parametrize("mode,off", [("train", None), ("train", "dgamma"), ("train", "dbeta"), ("train", "gamma"),
+                                      ("train", "pool_idx"), ("frozen", None), ("frozen", "mean"), ("frozen", "invstd"),
+                                      ("frozen", "scale")])
+def test_bn_backward_with_a_misaligned_operand_routes_by_a_pool_pass(dev, shape, mode, off):
+    """fp32 BatchNorm backward with a pool gradient on a shape the routing kernels take, one operand they demand in
+    16-byte pieces 4 bytes off (the winners: 1 byte off their 4-byte words).  Before unetpp_bn_bwd_plan such a call ran
+    into the launcher's UNETPP_EINVAL: ops.py asked about the shape alone (frozen: and three of the pointers).  The one
+    deliberate difference of the plan: the call now takes route 2, so it IS ops.maxpool_bwd into d_act followed by the same
+    call without `pool` on the same tensors, bit for bit, and its last streaming launch is the plain form's.  off = None
+    is the aligned control, which still runs the routing kernels."""
+    from tests.stream_rules import shifted
+    from unet_nested4tiny_objects_keypoints_amd import ops
+    b, h, w, c = shape
+    g = torch.Generator().manual_seed(29)
+    y = (torch.randn(b, h, w, c, generator=g) * 1.5 + 0.2).to(dev)
+    t = {"gamma": (1 + 0.1 * torch.randn(c, generator=g)).to(dev), "dgamma": torch.empty(c, device=dev),
+         "dbeta": torch.empty(c, device=dev)}
+    beta = (0.1 * torch.randn(c, generator=g)).to(dev)
+    rm, rv = (0.2 * torch.randn(c, generator=g)).to(dev), (0.5 + torch.rand(c, generator=g)).to(dev)
+    if mode == "train":
+        part = torch.stack([y.view(-1, c).sum(0), (y.view(-1, c) ** 2).sum(0)], 1).reshape(1, c, 2).contiguous()
+        stats = ops.bn_finalize(part.view(-1), 1, c, b * h * w, t["gamma"], beta, 1e-5, 0.1, rm, rv)
+    else:
+        stats = ops.bn_eval_coeffs_stats(t["gamma"], beta, rm, rv, 1e-5)
+    t.update(zip(("mean", "invstd", "scale", "shift"), stats))
+    pooled = torch.empty(b, h // 2, w // 2, c, device=dev)
+    t["pool_idx"] = torch.empty(b, h // 2, w // 2, c, dtype=torch.uint8, device=dev)
+    ops.affine_relu_pool(y, t["scale"], t["shift"], True, torch.empty_like(y), pooled, t["pool_idx"])
+    if off is not None:
+        t[off] = shifted(t[off], 1 if off == "pool_idx" else 4)
+    d_act = torch.randn(y.shape, generator=g).to(dev)
+    d_pool = torch.randn(pooled.shape, generator=g).to(dev)
+
+    def run(d_in, pool):
+        """-> (dy, dgamma, dbeta, label of the last streaming launch)"""
+        dy = torch.empty_like(y)
+        timer = ops.LaunchTimer()
+        ops.set_timer(timer)
+        try:
+            if mode == "train":
+                dg, db = ops.bn_backward(d_in, y, t["scale"], t["shift"], t["mean"], t["invstd"], t["gamma"], dy, t["dgamma"],
+                                         t["dbeta"], pool=pool)
+                label = ops._lib.lib().unetpp_last_kernel_name().decode()
+            else:
+                dg, db = ops.bn_frozen_backward(d_in, y, t["scale"], t["shift"], t["mean"], t["invstd"], dy, t["dgamma"],
+                                                t["dbeta"], pool=pool)
+                label = timer.launches[-1][0]
+        finally:
+            ops.set_timer(None)
+        return dy, dg.clone(), db.clone(), label
+
+    ref_in = d_act.clone()
+    ops.maxpool_bwd(d_pool, t["pool_idx"], ref_in)
+    ref_dy, ref_dg, ref_db, plain = run(ref_in, None)
+    dy, dg, db, label = run(d_act.clone(), (d_pool, t["pool_idx"]))
+    assert plain == ("bn_bwd_apply<4>" if mode == "train" else "bn_frozen_bwd<4>/sums")
+    if off is None:
+        assert label == ("bn_bwd_apply_pool" if mode == "train" else "bn_frozen_bwd_pool/sums")
+        assert rel_err(dy.cpu(), ref_dy.cpu()) < 1e-5 and rel_err(dg.cpu(), ref_dg.cpu()) < 1e-5
+    else:
+        assert label == plain
+        assert torch.equal(dy, ref_dy) and torch.equal(dg, ref_dg) and torch.equal(db, ref_db)
+
+
 @pytest.mark.parametrize("c,ncls", [(32, 4), (8, 5), (6, 3)])
 def test_head_fwd_bwd_with_mask(dev, c, ncls):
     from unet_nested4tiny_objects_keypoints_amd import ops

@@ -52,6 +52,9 @@ import torch
 import torch.nn.functional as F
 
 from tests.helpers import U32, bound_ratio, close_bf16, gamma, rel_err, report_ratio
+from tests.stream_rules import (GRID_CAP, K_THREADS, REDUCE_CAP, ROW_CAP, al16, bn_bwd_blocks, bn_bwd_blocks_bf16,  # noqa: F401
+                                bn_bwd_blocks_for, bn_bwd_pool_ok, expect_affine, expect_maxpool_bwd, fin_threads, octets_ok,
+                                ref_route, rows_form_ok, shifted, windows)
 
 pytestmark = pytest.mark.gpu
 
@@ -59,10 +62,6 @@ TOL = 1e-4
 BF = torch.bfloat16
 U64 = 2.0 ** -53
 CAST = U32 * (1 + 2.0 ** -20)     # one float64 -> fp32 cast of a value that differs from the reference by float64 terms
-K_THREADS = 256
-GRID_CAP = 2048 * 8               # grid_for / grid_for8
-ROW_CAP = 16384                   # row-structured kernels
-REDUCE_CAP = 2048                 # bn_bwd_blocks_for / unetpp_bn_bwd_blocks_bf16
 GATE_MARGIN = 8 * U32             # no gate argument closer to zero than this, relative to |y scale| + |shift|
 EVAL_DIV_SQRT_ULPS = 2.0          # estimate (not derived): sqrtf and the fp32 division of bn_eval_coeffs, in u each
 GRID = 2.0 ** 24
@@ -129,20 +128,6 @@ def ok(rc, what):
     assert rc == 0, (what, rc)
 
 
-def al16(t):
-    return t is None or t.data_ptr() % 16 == 0
-
-
-def shifted(t, nbytes=4):
-    """The same values in a slice of a longer tensor that starts `nbytes` past a 16-byte boundary."""
-    k = nbytes // t.element_size()
-    buf = torch.empty(t.numel() + 16, dtype=t.dtype, device=t.device)
-    v = buf[k:k + t.numel()].view(t.shape)
-    v.copy_(t)
-    assert v.data_ptr() % 16 == nbytes and v.is_contiguous()
-    return v
-
-
 def ratio(got, want, bound):
     """bound_ratio on the tensors' own device (the production cases hold > 1e8 elements)."""
     got, want, bound = got.double(), want.double(), bound.double()
@@ -151,48 +136,7 @@ def ratio(got, want, bound):
     return float(((got - want).abs() / bound.clamp_min(1e-300)).max())
 
 
-def fin_threads(rows):   # pointwise.hip fin_threads
-    return 1024 if rows >= 4096 else 512 if rows >= 1024 else 256
-
-
-def rows_form_ok(n, h, w, c):   # pointwise.hip rows_form_ok
-    return n * h * w * c < 0x7fffffff and (w // 2) * (c // 4) >= 64
-
-
-def bn_bwd_blocks_for(pixels, c, vec):   # pointwise.hip bn_bwd_blocks_for
-    cg = c // 4 if vec else c
-    want = max(1, min(REDUCE_CAP, -(-pixels * cg // (K_THREADS * 16))))
-    return -(-want // cg) * cg
-
-
-def bn_bwd_blocks(pixels, c):   # unetpp_bn_bwd_blocks
-    return max(bn_bwd_blocks_for(pixels, c, True) if c % 4 == 0 else 0, bn_bwd_blocks_for(pixels, c, False))
-
-
-def bn_bwd_blocks_bf16(pixels, c):   # unetpp_bn_bwd_blocks_bf16
-    return max(1, min(REDUCE_CAP, -(-pixels * (c // 8) // (4 * K_THREADS))))
-
-
-def bn_bwd_pool_ok(n, h, w, c):   # pointwise.hip bn_bwd_pool_ok
-    if n < 1 or h < 2 or w < 2 or c < 4 or h & 1 or w & 1 or c & 3:
-        return False
-    cg = c >> 2
-    return cg & (cg - 1) == 0 and cg <= K_THREADS and n * h * w * c < 0x7fffffff
-
-
-def octets_ok(c):   # pointwise_bf16.hip octets_ok
-    cg = c >> 3
-    return c >= 8 and c & 7 == 0 and cg & (cg - 1) == 0 and cg <= 256
-
-
 # --------------------------------------------------------------------------------------------- pool passes
-def windows(t):
-    """NHWC -> the four candidates of every 2x2 window in scan order (0,0),(0,1),(1,0),(1,1): views [N, H//2, W//2, C]
-    (odd H / W: the last row / column is in no window)."""
-    h2, w2 = t.shape[1] // 2 * 2, t.shape[2] // 2 * 2
-    return [t[:, (q >> 1):h2:2, (q & 1):w2:2, :] for q in range(4)]
-
-
 def ref_affine_pool(y, scale, shift, relu):
     """-> (act, pooled, argmax byte) in the storage type of y: one fma rounded once (float64 holds the product exactly),
     ReLU, for bf16 one round-to-nearest-even; the winner is the first maximum of the STORED values in scan order."""
@@ -211,42 +155,6 @@ def ref_affine_pool(y, scale, shift, relu):
         best = torch.where(m, cand[q], best)
         bi = torch.where(m, torch.full_like(bi, q), bi)
     return a, best, bi
-
-
-def ref_route(d_pooled, idx, shape):
-    """float64 NHWC tensor of `shape`: d_pooled at the recorded winner of every window, zero elsewhere."""
-    out = torch.zeros(shape, dtype=torch.float64, device=d_pooled.device)
-    dp = d_pooled.double()
-    for q, v in enumerate(windows(out)):
-        v.copy_(torch.where(idx == q, dp, torch.zeros_like(dp)))
-    return out
-
-
-def expect_affine(y, scale, shift, act, pooled, idx):
-    """Label of unetpp_affine_relu_pool[_bf16] from the launcher's conditions."""
-    n, h, w, c = y.shape
-    if y.dtype == BF:
-        return "affine_relu_bf16" if pooled is None else "affine_relu_pool_bf16"
-    vec = c % 4 == 0 and al16(y) and al16(act) and al16(pooled)
-    if pooled is None:
-        return "affine_relu<4>" if vec else "affine_relu<1>"
-    if h & 1 or w & 1:   # apply pass over the whole tensor (when act is wanted), then the window kernel on it
-        src = y if act is None else act
-        return "affine_relu_pool<4>" if c % 4 == 0 and al16(src) and al16(pooled) else "affine_relu_pool<1>"
-    if (vec and rows_form_ok(n, h, w, c) and (scale is None or (al16(scale) and al16(shift)))
-            and (idx is None or idx.data_ptr() % 4 == 0)):
-        return "affine_relu_pool_rows"
-    return "affine_relu_pool<4>" if vec else "affine_relu_pool<1>"
-
-
-def expect_maxpool_bwd(d_pooled, idx, d_act):
-    n, h, w, c = d_act.shape
-    if d_act.dtype == BF:
-        return "maxpool_bwd_bf16"
-    if (not (h & 1) and not (w & 1) and c % 4 == 0 and rows_form_ok(n, h, w, c) and al16(d_pooled) and al16(d_act)
-            and idx.data_ptr() % 4 == 0):
-        return "maxpool_bwd_rows"
-    return "maxpool_bwd<4>" if c % 4 == 0 else "maxpool_bwd<1>"
 
 
 def run_affine(y, scale, shift, relu, want_act=True, want_pool=True, want_idx=True, mode=""):

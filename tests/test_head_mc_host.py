@@ -44,7 +44,7 @@ def test_header_and_signature_table_agree(built_lib):
     assert re.search(r"#define\s+UNETPP_MC_MAX_SAMPLES\s+32\b", text)
     assert built_lib.MC_MAX_SAMPLES == mo.MAX_SAMPLES == 32 and built_lib.MC_SEED_STEP == mo.SEED_STEP
     lib = built_lib.lib()
-    assert lib.unetpp_abi_version() == built_lib.ABI_VERSION == 13
+    assert lib.unetpp_abi_version() == built_lib.ABI_VERSION == 14
     assert hasattr(ctypes.CDLL(built_lib.LIB_PATH), "unetpp_head_mc")
 
 

@@ -132,7 +132,7 @@ def built_lib():
 def test_heads_mean_abi_argument_checks(built_lib):
     L = built_lib
     lib = L.lib()
-    assert lib.unetpp_abi_version() == L.ABI_VERSION == 13     # additive entry points: the version stays
+    assert lib.unetpp_abi_version() == L.ABI_VERSION == 14     # additive entry points: the version stays
     out = ctypes.c_void_p(0x1000)                             # never dereferenced: every call below fails its checks
     for fn in (lib.unetpp_heads_mean_fwd, lib.unetpp_heads_mean_fwd_bf16):
         d = L.HeadsMean()

@@ -184,7 +184,7 @@ def test_the_entry_points_are_declared_listed_and_built():
         assert re.search(r"\bint %s\s*\(" % name, header), name
         assert name in _lib.SIGNATURES and hasattr(_lib.lib(), name)
     assert "mask.hip" in _lib.SOURCES and os.path.exists(os.path.join(_lib.CSRC, "mask.hip"))
-    assert _lib.lib().unetpp_abi_version() == _lib.ABI_VERSION == 13
+    assert _lib.lib().unetpp_abi_version() == _lib.ABI_VERSION == 14
     text = open(os.path.join(_lib.CSRC, "mask.hip")).read()
     assert "#pragma clang fp contract(off)" in text
     assert int(re.search(r"kEdgeChunk = (\d+)", text).group(1)) == mo.EDGE_CHUNK

@@ -166,7 +166,7 @@ def test_class_argument_validation():
 
 def test_abi_stays_13_and_the_new_names_are_declared():
     from unet_nested4tiny_objects_keypoints_amd import _lib
-    assert _lib.ABI_VERSION == 13
+    assert _lib.ABI_VERSION == 14
     header = open(os.path.join(_lib.INCLUDE, "unetpp_hip.h")).read()
     for name in ("unetpp_pr_focal_workspace_bytes", "unetpp_pr_focal_heads"):
         assert name in _lib.SIGNATURES and name + "(" in header
@@ -179,7 +179,7 @@ def test_entry_point_argument_validation_without_gpu():
     import __graft_entry__ as entry
     entry.build()
     lib = _lib.lib()
-    assert lib.unetpp_abi_version() == 13
+    assert lib.unetpp_abi_version() == 14
     assert lib.unetpp_pr_focal_workspace_bytes(3, 1) == 256 * 8 + 3 * 4
     assert lib.unetpp_pr_focal_workspace_bytes(8, PO.BIG_N) == 256 * 8 + 8 * 1026 * 4
     for bad in ((0, 1), (9, 1), (-1, 1), (1, 0), (1, -5), (1, 2 ** 43)):

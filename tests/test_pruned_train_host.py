@@ -108,7 +108,7 @@ def _descriptors(L, n_heads):
 def test_heads_mean_bwd_abi_argument_checks(built_lib):
     L = built_lib
     lib = L.lib()
-    assert lib.unetpp_abi_version() == L.ABI_VERSION == 13     # additive entry points: the version stays
+    assert lib.unetpp_abi_version() == L.ABI_VERSION == 14     # additive entry points: the version stays
     d_out = ctypes.c_void_p(0x6000)
     ok = (1, 8, 8, 32, 4)
     for fn in (lib.unetpp_heads_mean_bwd, lib.unetpp_heads_mean_bwd_bf16):

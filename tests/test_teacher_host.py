@@ -406,10 +406,10 @@ def test_entry_point_refuses_bad_arguments_without_touching_the_device(built_lib
 
 def test_header_declares_the_entry_point_and_the_abi_is_still_13(built_lib):
     text = open(os.path.join(ROOT, "include", "unetpp_hip.h")).read()
-    assert re.search(r"#define UNETPP_ABI_VERSION 13\b", text)
+    assert re.search(r"#define UNETPP_ABI_VERSION 14\b", text)
     code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     assert re.search(r"\bint unetpp_teacher_heads\s*\(", code)
     assert "added within v13: new entry points only" in text[:text.index("int unetpp_teacher_heads")].rsplit("/*", 1)[1]
     assert "unetpp_teacher_heads" in built_lib.SIGNATURES and "distill.hip" in built_lib.SOURCES
     assert len(built_lib.SIGNATURES["unetpp_teacher_heads"][1]) == 13
-    assert built_lib.ABI_VERSION == 13 and built_lib.lib().unetpp_abi_version() == 13
+    assert built_lib.ABI_VERSION == 14 and built_lib.lib().unetpp_abi_version() == 14

@@ -18,9 +18,9 @@ INCLUDE = os.path.join(_REPO, "include")
 SOURCES = ("gemm_pix.hip", "gemm_fast.hip", "gemm_pw.hip", "gemm_pw_bf16.hip", "gemm_wino.hip", "gemm_bf16.hip", "gemm_bf16_dma.hip", "wgrad_bf16.hip", "pointwise_bf16.hip", "keypoints.hip", "weight_image.hip", "wgrad.hip", "wgrad_fast.hip", "wgrad_dma.hip", "wgrad_pw.hip", "wgrad_wino.hip", "first_layer.hip", "pointwise.hip", "heads.hip", "caller.hip", "optim.hip", "validate.hip", "average.hip", "loader.hip", "scene.hip",
            "detect.hip", "crops.hip", "topk_loss.hip", "pr_focal.hip", "paste.hip", "distill.hip", "mask.hip")
 HEADERS = ("common.h", "gemm_units.h", "wgrad_reduce.h", "lds_asm.h", "bf16_common.h", "dropout.h", "bn_fused.h",
-           "wino_experiments.h", "dma_experiments.h", "heads_mean.h", "head_select.h", "head_mc_select.h", "focal_element.h", "multi_tensor.h", "loss_heads.h")
+           "wino_experiments.h", "dma_experiments.h", "heads_mean.h", "head_select.h", "stream_select.h", "head_mc_select.h", "focal_element.h", "multi_tensor.h", "loss_heads.h")
 MAX_VIEWS = 8
-ABI_VERSION = 13
+ABI_VERSION = 14
 # packed-f32 VALU (SLP-vectorised add pairs) costs issue slots beside MFMAs: keep the Winograd transforms scalar
 EXTRA_FLAGS = {"gemm_wino.hip": ("-fno-slp-vectorize",), "wgrad_wino.hip": ("-fno-slp-vectorize",)}
 GEMM_DIRECT = 1  # unetpp_gemm_desc.flags: direct summation only (no Winograd)
@@ -137,6 +137,18 @@ class WgradSizes(C.Structure):
         ("slab_floats", C.c_int64),
         ("kernel", C.c_char_p),
     ]
+
+
+class BnBwdQuery(C.Structure):
+    """mirror of struct unetpp_bn_bwd_query"""
+    POINTERS = ("d_act", "y", "dy", "scale", "shift", "mean", "invstd", "gamma", "dgamma", "dbeta", "d_pooled", "pool_idx")
+    _fields_ = [(n, C.c_int32) for n in ("frozen", "bf16", "want_sums", "N", "H", "W", "C", "reserved")] + \
+               [(n, C.c_void_p) for n in POINTERS]
+
+
+class BnBwdSizes(C.Structure):
+    """mirror of struct unetpp_bn_bwd_sizes"""
+    _fields_ = [("route", C.c_int32), ("reserved", C.c_int32), ("partial_rows", C.c_int64), ("partial_floats", C.c_int64)]
 
 
 class GemmSizes(C.Structure):
@@ -264,6 +276,8 @@ SIGNATURES = {
     "unetpp_bn_frozen_bwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P]),
     "unetpp_bn_frozen_bwd_blocks_bf16": (_I64, [_I64, _I32]),
     "unetpp_bn_frozen_bwd_bf16": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P]),
+    # route of the pool gradient and rows of `partial` for one BatchNorm backward (ABI 14)
+    "unetpp_bn_bwd_plan": (C.c_int, [C.POINTER(BnBwdQuery), C.POINTER(BnBwdSizes)]),
     "unetpp_copy_jobs": (C.c_int, [_P, _I32, _I64, _P]),
     "unetpp_heatmap_workspace_bytes": (_I64, [_I32, _I32, _I32]),
     "unetpp_create_heatmap": (C.c_int, [_P, _I32, _I32, _I32, _I32, _F, _P, _P, _P]),

@@ -4,6 +4,7 @@
 // accesses whenever the channel count is a multiple of 4, scalar fallback otherwise.  (The heads: heads.hip.)
 #include "common.h"
 #include "lds_asm.h"
+#include "stream_select.h"
 
 namespace unetpp {
 namespace {
@@ -548,7 +549,7 @@ __global__ __launch_bounds__(kThreads) void bn_frozen_bwd_kernel(const float* d_
 }
 
 // the pooled consumer's gradient routed to its argmax while d_act is read (routed_grad); row structured, conditions of
-// bn_bwd_pool_ok.  thread t holds quad t & (CG - 1) for all its items
+// stream_bn_pool_ok.  thread t holds quad t & (CG - 1) for all its items
 template <bool SUMS>
 __global__ __launch_bounds__(kThreads) void bn_frozen_bwd_pool_kernel(
     const f32x4* d_act, const f32x4* __restrict__ y, const f32x4* __restrict__ scale, const f32x4* __restrict__ shift,
@@ -763,116 +764,16 @@ extern "C" int unetpp_bn_eval_coeffs_stats(const float* gamma, const float* beta
   return launch_status();
 }
 
+// ---- the streaming launchers: NULL checks here, every other decision in stream_select.h ----
 namespace {
-// the row-structured pool kernels: 32-bit element offsets, rows long enough to occupy a workgroup
-inline bool rows_form_ok(int N, int H, int W, int C) {
-  return static_cast<long>(N) * H * W * C < 0x7fffffffL && static_cast<long>(W / 2) * (C / 4) >= 64;
-}
-}  // namespace
+static_assert(kStreamThreads == kThreads, "stream_select sizes its grids for kThreads threads per workgroup");
 
-extern "C" int unetpp_affine_relu_pool(const float* y, const float* scale, const float* shift, int32_t relu, int32_t N,
-                                       int32_t H, int32_t W, int32_t C, float* act, float* pooled, uint8_t* pool_idx,
-                                       void* stream) {
-  if (!y || N < 1 || H < 1 || W < 1 || C < 1) return UNETPP_EINVAL;
-  if ((scale == nullptr) != (shift == nullptr)) return UNETPP_EINVAL;
-  if (act == nullptr && pooled == nullptr) return UNETPP_EINVAL;
-  const bool vec = (C % 4 == 0) && aligned16(y) && (!act || aligned16(act)) && (!pooled || aligned16(pooled));
-  if (pooled == nullptr) {
-    const long pixels = static_cast<long>(N) * H * W;
-    if (vec) {
-      const long items = pixels * (C / 4);
-      note_kernel("affine_relu<4>");
-      hipLaunchKernelGGL(affine_relu_kernel<4>, dim3(grid_for(items)), dim3(kThreads), 0, ST(stream), y, scale, shift,
-                         relu, items, C / 4, act);
-    } else {
-      const long items = pixels * C;
-      note_kernel("affine_relu<1>");
-      hipLaunchKernelGGL(affine_relu_kernel<1>, dim3(grid_for(items)), dim3(kThreads), 0, ST(stream), y, scale, shift,
-                         relu, items, C, act);
-    }
-    return launch_status();
-  }
-  if (H < 2 || W < 2) return UNETPP_EINVAL;  // (pool_idx may be NULL: forward-only callers need no winners)
-  if ((H & 1) || (W & 1)) {
-    // nn.MaxPool2d(2) floors (the classic UNet on sizes that are not multiples of 16, models/unet.py:40-46): the last
-    // odd row / column is in no window, but the activation is wanted for ALL pixels -- apply pass over the whole
-    // tensor first, then the window kernel on the activation (its index arithmetic uses H, W as strides and H/2, W/2 as
-    // the window grid; the winners are those of the transformed values either way)
-    const float* src = y;
-    if (act != nullptr) {
-      const int rc = unetpp_affine_relu_pool(y, scale, shift, relu, N, H, W, C, act, nullptr, nullptr, stream);
-      if (rc != UNETPP_OK) return rc;
-      src = act;
-      scale = shift = nullptr;
-      relu = 0;
-    }
-    const long win = static_cast<long>(N) * (H / 2) * (W / 2);
-    const bool v4 = (C % 4 == 0) && aligned16(src) && aligned16(pooled);
-    note_kernel(v4 ? "affine_relu_pool<4>" : "affine_relu_pool<1>");
-    if (v4)
-      hipLaunchKernelGGL(affine_relu_pool_kernel<4>, dim3(grid_for(win * (C / 4))), dim3(kThreads), 0, ST(stream), src, scale,
-                         shift, relu, N, H, W, C / 4, static_cast<float*>(nullptr), pooled, pool_idx);
-    else
-      hipLaunchKernelGGL(affine_relu_pool_kernel<1>, dim3(grid_for(win * C)), dim3(kThreads), 0, ST(stream), src, scale, shift,
-                         relu, N, H, W, C, static_cast<float*>(nullptr), pooled, pool_idx);
-    return launch_status();
-  }
-  const long windows = static_cast<long>(N) * (H / 2) * (W / 2);
-  const unsigned rows = static_cast<unsigned>(N * (H / 2)), row_items = static_cast<unsigned>((W / 2) * (C / 4));
-  const bool rows_form = vec && rows_form_ok(N, H, W, C) && (scale == nullptr || (aligned16(scale) && aligned16(shift))) &&
-                         (reinterpret_cast<uintptr_t>(pool_idx) & 3) == 0;
-  note_kernel(rows_form ? "affine_relu_pool_rows" : vec ? "affine_relu_pool<4>" : "affine_relu_pool<1>");
-  if (rows_form)
-    hipLaunchKernelGGL(affine_relu_pool_rows_kernel, dim3(rows < 16384u ? rows : 16384u), dim3(kThreads), 0, ST(stream),
-                       reinterpret_cast<const f32x4*>(y), reinterpret_cast<const f32x4*>(scale),
-                       reinterpret_cast<const f32x4*>(shift), relu, rows, static_cast<unsigned>(W / 2),
-                       static_cast<unsigned>(C / 4), reinterpret_cast<f32x4*>(act), reinterpret_cast<f32x4*>(pooled),
-                       reinterpret_cast<uint32_t*>(pool_idx));
-  else if (vec)
-    hipLaunchKernelGGL(affine_relu_pool_kernel<4>, dim3(grid_for(windows * (C / 4))), dim3(kThreads), 0, ST(stream), y,
-                       scale, shift, relu, N, H, W, C / 4, act, pooled, pool_idx);
-  else
-    hipLaunchKernelGGL(affine_relu_pool_kernel<1>, dim3(grid_for(windows * C)), dim3(kThreads), 0, ST(stream), y, scale,
-                       shift, relu, N, H, W, C, act, pooled, pool_idx);
-  return launch_status();
+inline unsigned ilog2(unsigned v) {
+  unsigned l = 0;
+  while ((1u << l) < v) ++l;
+  return l;
 }
 
-extern "C" int unetpp_maxpool_bwd(const float* d_pooled, const uint8_t* pool_idx, int32_t N, int32_t H, int32_t W,
-                                  int32_t C, float* d_act, void* stream) {
-  if (!d_pooled || !pool_idx || !d_act || N < 1 || H < 2 || W < 2 || C < 1) return UNETPP_EINVAL;
-  const long windows = static_cast<long>(N) * (H / 2) * (W / 2);  // odd H / W: the last row / column is in no window (floor)
-  const unsigned rows = static_cast<unsigned>(N * (H / 2));
-  const bool rows_form = !(H & 1) && !(W & 1) && C % 4 == 0 && rows_form_ok(N, H, W, C) && aligned16(d_pooled) &&
-                         aligned16(d_act) && (reinterpret_cast<uintptr_t>(pool_idx) & 3) == 0;
-  note_kernel(rows_form ? "maxpool_bwd_rows" : C % 4 == 0 ? "maxpool_bwd<4>" : "maxpool_bwd<1>");
-  if (rows_form)
-    hipLaunchKernelGGL(maxpool_bwd_rows_kernel, dim3(rows < 16384u ? rows : 16384u), dim3(kThreads), 0, ST(stream),
-                       reinterpret_cast<const f32x4*>(d_pooled), reinterpret_cast<const uint32_t*>(pool_idx), rows,
-                       static_cast<unsigned>(W / 2), static_cast<unsigned>(C / 4), reinterpret_cast<f32x4*>(d_act));
-  else if (C % 4 == 0)
-    hipLaunchKernelGGL(maxpool_bwd_kernel<4>, dim3(grid_for(windows * (C / 4))), dim3(kThreads), 0, ST(stream), d_pooled,
-                       pool_idx, N, H, W, C / 4, d_act);
-  else
-    hipLaunchKernelGGL(maxpool_bwd_kernel<1>, dim3(grid_for(windows * C)), dim3(kThreads), 0, ST(stream), d_pooled,
-                       pool_idx, N, H, W, C, d_act);
-  return launch_status();
-}
-
-namespace {
-// blocks for the BN-backward reduction: a multiple of the channel-group count so that the grid stride
-// keeps every thread on one channel group.
-inline long bn_bwd_blocks_for(long pixels, int C, bool vec) {
-  const int CG = vec ? C / 4 : C;
-  const long items = pixels * CG;
-  long want = (items + kThreads * 16L - 1) / (kThreads * 16L);
-  if (want > 2048) want = 2048;
-  if (want < 1) want = 1;
-  long blocks = ((want + CG - 1) / CG) * CG;
-  return blocks;
-}
-}  // namespace
-
-namespace {
 // Unused rows of a partial-sum workspace are zeroed by a KERNEL, not by hipMemsetAsync.  History: round 4 saw non-finite
 // BatchNorm gradients from the second replay of a captured training step and blamed the ordering of memset NODES; round 5
 // read the captured graph back (tools/probes/graph_topology.py): memset nodes sit in the chain like any kernel node and
@@ -891,32 +792,111 @@ inline void zero_rows(float* p, long n, hipStream_t st) {
   const long want = (n + kThreads - 1) / kThreads;
   hipLaunchKernelGGL(zero_rows_kernel, dim3(static_cast<unsigned>(want < 1024 ? want : 1024)), dim3(kThreads), 0, st, p, n);
 }
+// the partial buffer [buf_rows][C][2] always has stream_partial_rows() rows; those beyond this launch's grid are zeroed
+inline void zero_unwritten_rows(float* partial, const StreamSel& s, int C, hipStream_t st) {
+  if (s.rows < s.buf_rows) zero_rows(partial + s.rows * C * 2, (s.buf_rows - s.rows) * C * 2, st);
+}
 }  // namespace
 
-extern "C" int64_t unetpp_bn_bwd_blocks(int64_t pixels, int32_t C) {
-  if (pixels < 1 || C < 1) return 0;
-  // upper bound over both code paths (vector / scalar) so one workspace size serves either
-  const long a = (C % 4 == 0) ? bn_bwd_blocks_for(pixels, C, true) : 0;
-  const long b = bn_bwd_blocks_for(pixels, C, false);
-  return a > b ? a : b;
+extern "C" int unetpp_affine_relu_pool(const float* y, const float* scale, const float* shift, int32_t relu, int32_t N,
+                                       int32_t H, int32_t W, int32_t C, float* act, float* pooled, uint8_t* pool_idx,
+                                       void* stream) {
+  if (!y) return UNETPP_EINVAL;
+  StreamQuery q = stream_query(STREAM_AFFINE, false, N, H, W, C);
+  q.has_scale = scale != nullptr, q.has_shift = shift != nullptr, q.has_act = act != nullptr;
+  q.has_pooled = pooled != nullptr, q.has_idx = pool_idx != nullptr;
+  q.in_lo = stream_lo4(y), q.out_lo = stream_lo4(act), q.pooled_lo = stream_lo4(pooled), q.idx_lo = stream_lo4(pool_idx);
+  q.coef_lo = stream_lo4(scale, shift);
+  StreamSel s;
+  if (stream_select(q, s) != UNETPP_OK) return UNETPP_EINVAL;
+  if (s.two_pass) {
+    // odd H or W (models/unet.py:40-46): the apply pass over the whole tensor, then the window kernel on the activation
+    // (its index arithmetic uses H, W as strides and H/2, W/2 as the window grid; the winners are those of the
+    // transformed values either way)
+    const int rc = unetpp_affine_relu_pool(y, scale, shift, relu, N, H, W, C, act, nullptr, nullptr, stream);
+    if (rc != UNETPP_OK) return rc;
+    y = act;
+    act = nullptr;
+    scale = shift = nullptr;
+    relu = 0;
+  }
+  const dim3 grid(s.grid), block(s.block);
+  note_kernel(s.label);
+  if (pooled == nullptr) {
+    if (s.form == STREAM_VEC)
+      hipLaunchKernelGGL(affine_relu_kernel<4>, grid, block, 0, ST(stream), y, scale, shift, relu, s.items, s.cg, act);
+    else
+      hipLaunchKernelGGL(affine_relu_kernel<1>, grid, block, 0, ST(stream), y, scale, shift, relu, s.items, s.cg, act);
+  } else if (s.form == STREAM_ROWS) {
+    hipLaunchKernelGGL(affine_relu_pool_rows_kernel, grid, block, 0, ST(stream), reinterpret_cast<const f32x4*>(y),
+                       reinterpret_cast<const f32x4*>(scale), reinterpret_cast<const f32x4*>(shift), relu,
+                       static_cast<unsigned>(s.items), static_cast<unsigned>(W / 2), static_cast<unsigned>(s.cg),
+                       reinterpret_cast<f32x4*>(act), reinterpret_cast<f32x4*>(pooled),
+                       reinterpret_cast<uint32_t*>(pool_idx));
+  } else if (s.form == STREAM_VEC) {
+    hipLaunchKernelGGL(affine_relu_pool_kernel<4>, grid, block, 0, ST(stream), y, scale, shift, relu, N, H, W, s.cg, act,
+                       pooled, pool_idx);
+  } else {
+    hipLaunchKernelGGL(affine_relu_pool_kernel<1>, grid, block, 0, ST(stream), y, scale, shift, relu, N, H, W, s.cg, act,
+                       pooled, pool_idx);
+  }
+  return launch_status();
+}
+
+extern "C" int unetpp_maxpool_bwd(const float* d_pooled, const uint8_t* pool_idx, int32_t N, int32_t H, int32_t W,
+                                  int32_t C, float* d_act, void* stream) {
+  if (!d_pooled || !pool_idx || !d_act) return UNETPP_EINVAL;
+  StreamQuery q = stream_query(STREAM_POOL_BWD, false, N, H, W, C);
+  q.pooled_lo = stream_lo4(d_pooled), q.idx_lo = stream_lo4(pool_idx), q.out_lo = stream_lo4(d_act);
+  StreamSel s;
+  if (stream_select(q, s) != UNETPP_OK) return UNETPP_EINVAL;
+  const dim3 grid(s.grid), block(s.block);
+  note_kernel(s.label);
+  if (s.form == STREAM_ROWS)
+    hipLaunchKernelGGL(maxpool_bwd_rows_kernel, grid, block, 0, ST(stream), reinterpret_cast<const f32x4*>(d_pooled),
+                       reinterpret_cast<const uint32_t*>(pool_idx), static_cast<unsigned>(s.items),
+                       static_cast<unsigned>(W / 2), static_cast<unsigned>(s.cg), reinterpret_cast<f32x4*>(d_act));
+  else if (s.form == STREAM_VEC)
+    hipLaunchKernelGGL(maxpool_bwd_kernel<4>, grid, block, 0, ST(stream), d_pooled, pool_idx, N, H, W, s.cg, d_act);
+  else
+    hipLaunchKernelGGL(maxpool_bwd_kernel<1>, grid, block, 0, ST(stream), d_pooled, pool_idx, N, H, W, s.cg, d_act);
+  return launch_status();
+}
+
+extern "C" int64_t unetpp_bn_bwd_blocks(int64_t pixels, int32_t C) { return stream_partial_rows(false, false, pixels, C); }
+extern "C" int64_t unetpp_bn_frozen_bwd_blocks(int64_t pixels, int32_t C) { return stream_partial_rows(false, true, pixels, C); }
+extern "C" int unetpp_bn_bwd_pool_ok(int32_t N, int32_t H, int32_t W, int32_t C) { return stream_bn_pool_ok(N, H, W, C) ? 1 : 0; }
+
+extern "C" int unetpp_bn_bwd_plan(const unetpp_bn_bwd_query* b, unetpp_bn_bwd_sizes* out) {
+  if (!b || !out || (b->d_pooled == nullptr) != (b->pool_idx == nullptr)) return UNETPP_EINVAL;
+  BnBwdQuery q{};
+  q.frozen = b->frozen != 0, q.bf16 = b->bf16 != 0, q.sums = b->want_sums != 0, q.pool = b->d_pooled != nullptr;
+  q.N = b->N, q.H = b->H, q.W = b->W, q.C = b->C;
+  q.in_lo = stream_lo4(b->d_act, b->y), q.out_lo = stream_lo4(b->dy), q.pooled_lo = stream_lo4(b->d_pooled);
+  q.idx_lo = stream_lo4(b->pool_idx), q.coef_lo = stream_lo4(b->scale, b->shift), q.stat_lo = stream_lo4(b->mean, b->invstd);
+  q.gamma_lo = stream_lo4(b->gamma, b->dgamma, b->dbeta);
+  BnBwdPlan p;
+  const int rc = bn_bwd_plan(q, p);
+  *out = unetpp_bn_bwd_sizes{p.route, 0, p.partial_rows, p.partial_floats};
+  return rc;
 }
 
 extern "C" int unetpp_bn_bwd_reduce(const float* d_act, const float* y, const float* scale, const float* shift,
                                     const float* mean, const float* invstd, int64_t pixels, int32_t C, float* partial,
                                     void* stream) {
-  if (!d_act || !y || !scale || !shift || !mean || !invstd || !partial || pixels < 1 || C < 1) return UNETPP_EINVAL;
-  const bool vec = (C % 4 == 0) && aligned16(d_act) && aligned16(y);
-  // the partial buffer always has unetpp_bn_bwd_blocks() rows; rows beyond this launch's grid are zeroed
-  const long rows = unetpp_bn_bwd_blocks(pixels, C);
-  const long blocks = bn_bwd_blocks_for(pixels, C, vec);
-  if (blocks < rows) zero_rows(partial + blocks * C * 2, (rows - blocks) * C * 2, ST(stream));
-  note_kernel(vec ? "bn_bwd_reduce<4>" : "bn_bwd_reduce<1>");
-  if (vec)
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel<4>, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, ST(stream),
-                       d_act, y, scale, shift, mean, invstd, pixels * (C / 4), C / 4, partial);
+  if (!d_act || !y || !scale || !shift || !mean || !invstd || !partial) return UNETPP_EINVAL;
+  const StreamQuery q = stream_bn_query(STREAM_BN_REDUCE, false, pixels, 1, 1, C, d_act, y, nullptr, scale, shift, mean,
+                                        invstd, nullptr, nullptr, nullptr, nullptr, nullptr, partial);
+  StreamSel s;
+  if (stream_select(q, s) != UNETPP_OK) return UNETPP_EINVAL;
+  zero_unwritten_rows(partial, s, C, ST(stream));
+  note_kernel(s.label);
+  if (s.form == STREAM_VEC)
+    hipLaunchKernelGGL(bn_bwd_reduce_kernel<4>, dim3(s.grid), dim3(s.block), 0, ST(stream), d_act, y, scale, shift, mean,
+                       invstd, s.items, s.cg, partial);
   else
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel<1>, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, ST(stream),
-                       d_act, y, scale, shift, mean, invstd, pixels * C, C, partial);
+    hipLaunchKernelGGL(bn_bwd_reduce_kernel<1>, dim3(s.grid), dim3(s.block), 0, ST(stream), d_act, y, scale, shift, mean,
+                       invstd, s.items, s.cg, partial);
   return launch_status();
 }
 
@@ -933,61 +913,39 @@ extern "C" int unetpp_bn_bwd_finalize(const float* partial, int64_t n_blocks, in
 extern "C" int unetpp_bn_bwd_apply(const float* d_act, const float* y, const float* scale, const float* shift,
                                    const float* mean, const float* invstd, const float* gamma, const float* dgamma,
                                    const float* dbeta, int64_t pixels, int32_t C, float* dy, void* stream) {
-  if (!d_act || !y || !scale || !shift || !mean || !invstd || !gamma || !dgamma || !dbeta || !dy || pixels < 1 || C < 1)
-    return UNETPP_EINVAL;
-  const bool vec = (C % 4 == 0) && aligned16(d_act) && aligned16(y) && aligned16(dy);
+  if (!d_act || !y || !scale || !shift || !mean || !invstd || !gamma || !dgamma || !dbeta || !dy) return UNETPP_EINVAL;
+  const StreamQuery q = stream_bn_query(STREAM_BN_APPLY, false, pixels, 1, 1, C, d_act, y, dy, scale, shift, mean, invstd,
+                                        gamma, dgamma, dbeta, nullptr, nullptr, nullptr);
+  StreamSel s;
+  if (stream_select(q, s) != UNETPP_OK) return UNETPP_EINVAL;
   const float inv_count = 1.0f / static_cast<float>(pixels);
-  note_kernel(vec ? "bn_bwd_apply<4>" : "bn_bwd_apply<1>");
-  if (vec) {
-    const long items = pixels * (C / 4);
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<4>, dim3(grid_for(items)), dim3(kThreads), 0, ST(stream), d_act, y, scale,
-                       shift, mean, invstd, gamma, dgamma, dbeta, inv_count, items, C / 4, dy);
-  } else {
-    const long items = pixels * C;
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<1>, dim3(grid_for(items)), dim3(kThreads), 0, ST(stream), d_act, y, scale,
-                       shift, mean, invstd, gamma, dgamma, dbeta, inv_count, items, C, dy);
-  }
+  note_kernel(s.label);
+  if (s.form == STREAM_VEC)
+    hipLaunchKernelGGL(bn_bwd_apply_kernel<4>, dim3(s.grid), dim3(s.block), 0, ST(stream), d_act, y, scale, shift, mean,
+                       invstd, gamma, dgamma, dbeta, inv_count, s.items, s.cg, dy);
+  else
+    hipLaunchKernelGGL(bn_bwd_apply_kernel<1>, dim3(s.grid), dim3(s.block), 0, ST(stream), d_act, y, scale, shift, mean,
+                       invstd, gamma, dgamma, dbeta, inv_count, s.items, s.cg, dy);
   return launch_status();
 }
-
-namespace {
-// eligibility of the pool-routing BatchNorm backward (see bn_bwd_reduce_pool_kernel)
-inline bool bn_bwd_pool_ok(int N, int H, int W, int C) {
-  if (N < 1 || H < 2 || W < 2 || C < 4 || (H & 1) || (W & 1) || (C & 3)) return false;
-  const int CG = C >> 2;
-  if ((CG & (CG - 1)) != 0 || CG > kThreads) return false;
-  return static_cast<long>(N) * H * W * C < 0x7fffffffL;
-}
-inline unsigned ilog2(unsigned v) {
-  unsigned l = 0;
-  while ((1u << l) < v) ++l;
-  return l;
-}
-}  // namespace
-
-extern "C" int unetpp_bn_bwd_pool_ok(int32_t N, int32_t H, int32_t W, int32_t C) { return bn_bwd_pool_ok(N, H, W, C) ? 1 : 0; }
 
 extern "C" int unetpp_bn_bwd_reduce_pool(const float* d_act, const float* y, const float* scale, const float* shift,
                                          const float* mean, const float* invstd, const float* d_pooled,
                                          const uint8_t* pool_idx, int32_t N, int32_t H, int32_t W, int32_t C,
                                          float* partial, void* stream) {
   if (!d_act || !y || !scale || !shift || !mean || !invstd || !d_pooled || !pool_idx || !partial) return UNETPP_EINVAL;
-  if (!bn_bwd_pool_ok(N, H, W, C)) return UNETPP_EINVAL;
-  if (!aligned16(d_act) || !aligned16(y) || !aligned16(scale) || !aligned16(shift) || !aligned16(mean) ||
-      !aligned16(invstd) || !aligned16(d_pooled) || (reinterpret_cast<uintptr_t>(pool_idx) & 3) != 0)
-    return UNETPP_EINVAL;
-  const long pixels = static_cast<long>(N) * H * W;
-  const long rows_buf = unetpp_bn_bwd_blocks(pixels, C);  // rows of the partial buffer; unused ones are zeroed
-  const long img_rows = static_cast<long>(N) * H;
-  const long grid = img_rows < rows_buf ? img_rows : rows_buf;
-  if (grid < rows_buf) zero_rows(partial + grid * C * 2, (rows_buf - grid) * C * 2, ST(stream));
-  note_kernel("bn_bwd_reduce_pool");
-  hipLaunchKernelGGL(bn_bwd_reduce_pool_kernel, dim3(static_cast<unsigned>(grid)), dim3(kThreads), 0, ST(stream),
+  const StreamQuery q = stream_bn_query(STREAM_BN_REDUCE, false, N, H, W, C, d_act, y, nullptr, scale, shift, mean, invstd,
+                                        nullptr, nullptr, nullptr, d_pooled, pool_idx, partial);
+  StreamSel s;
+  if (stream_select(q, s) != UNETPP_OK) return UNETPP_EINVAL;
+  zero_unwritten_rows(partial, s, C, ST(stream));
+  note_kernel(s.label);
+  hipLaunchKernelGGL(bn_bwd_reduce_pool_kernel, dim3(s.grid), dim3(s.block), 0, ST(stream),
                      reinterpret_cast<const f32x4*>(d_act), reinterpret_cast<const f32x4*>(y),
                      reinterpret_cast<const f32x4*>(scale), reinterpret_cast<const f32x4*>(shift),
                      reinterpret_cast<const f32x4*>(mean), reinterpret_cast<const f32x4*>(invstd),
                      reinterpret_cast<const f32x4*>(d_pooled), reinterpret_cast<const uint32_t*>(pool_idx),
-                     static_cast<unsigned>(img_rows), static_cast<unsigned>(W), ilog2(static_cast<unsigned>(C >> 2)),
+                     static_cast<unsigned>(s.items), static_cast<unsigned>(W), ilog2(static_cast<unsigned>(s.cg)),
                      partial);
   return launch_status();
 }
@@ -998,75 +956,42 @@ extern "C" int unetpp_bn_bwd_apply_pool(const float* d_act, const float* y, cons
                                         int32_t H, int32_t W, int32_t C, float* dy, void* stream) {
   if (!d_act || !y || !scale || !shift || !mean || !invstd || !gamma || !dgamma || !dbeta || !d_pooled || !pool_idx || !dy)
     return UNETPP_EINVAL;
-  if (!bn_bwd_pool_ok(N, H, W, C)) return UNETPP_EINVAL;
-  if (!aligned16(d_act) || !aligned16(y) || !aligned16(dy) || !aligned16(scale) || !aligned16(shift) ||
-      !aligned16(mean) || !aligned16(invstd) || !aligned16(gamma) || !aligned16(dgamma) || !aligned16(dbeta) ||
-      !aligned16(d_pooled) || (reinterpret_cast<uintptr_t>(pool_idx) & 3) != 0)
-    return UNETPP_EINVAL;
-  const long img_rows = static_cast<long>(N) * H;
-  const float inv_count = 1.0f / static_cast<float>(img_rows * W);
-  note_kernel("bn_bwd_apply_pool");
-  hipLaunchKernelGGL(bn_bwd_apply_pool_kernel, dim3(static_cast<unsigned>(img_rows < 16384 ? img_rows : 16384)),
-                     dim3(kThreads), 0, ST(stream), reinterpret_cast<const f32x4*>(d_act),
-                     reinterpret_cast<const f32x4*>(y), reinterpret_cast<const f32x4*>(scale),
-                     reinterpret_cast<const f32x4*>(shift), reinterpret_cast<const f32x4*>(mean),
-                     reinterpret_cast<const f32x4*>(invstd), reinterpret_cast<const f32x4*>(gamma),
-                     reinterpret_cast<const f32x4*>(dgamma), reinterpret_cast<const f32x4*>(dbeta),
-                     reinterpret_cast<const f32x4*>(d_pooled), reinterpret_cast<const uint32_t*>(pool_idx), inv_count,
-                     static_cast<unsigned>(img_rows), static_cast<unsigned>(W), ilog2(static_cast<unsigned>(C >> 2)),
-                     reinterpret_cast<f32x4*>(dy));
+  const StreamQuery q = stream_bn_query(STREAM_BN_APPLY, false, N, H, W, C, d_act, y, dy, scale, shift, mean, invstd, gamma,
+                                        dgamma, dbeta, d_pooled, pool_idx, nullptr);
+  StreamSel s;
+  if (stream_select(q, s) != UNETPP_OK) return UNETPP_EINVAL;
+  const float inv_count = 1.0f / static_cast<float>(s.items * W);
+  note_kernel(s.label);
+  hipLaunchKernelGGL(bn_bwd_apply_pool_kernel, dim3(s.grid), dim3(s.block), 0, ST(stream),
+                     reinterpret_cast<const f32x4*>(d_act), reinterpret_cast<const f32x4*>(y),
+                     reinterpret_cast<const f32x4*>(scale), reinterpret_cast<const f32x4*>(shift),
+                     reinterpret_cast<const f32x4*>(mean), reinterpret_cast<const f32x4*>(invstd),
+                     reinterpret_cast<const f32x4*>(gamma), reinterpret_cast<const f32x4*>(dgamma),
+                     reinterpret_cast<const f32x4*>(dbeta), reinterpret_cast<const f32x4*>(d_pooled),
+                     reinterpret_cast<const uint32_t*>(pool_idx), inv_count, static_cast<unsigned>(s.items),
+                     static_cast<unsigned>(W), ilog2(static_cast<unsigned>(s.cg)), reinterpret_cast<f32x4*>(dy));
   return launch_status();
-}
-
-namespace {
-// blocks of the frozen BatchNorm backward: one item per thread up to kFrozenCap workgroups, then a grid-stride loop; a
-// multiple of the channel-group count so that the grid stride keeps every thread on one channel group
-constexpr long kFrozenCap = 2048;
-inline long bn_frozen_blocks_for(long pixels, int C, bool vec) {
-  const int CG = vec ? C / 4 : C;
-  const long items = pixels * CG;
-  long want = (items + kThreads - 1) / kThreads;
-  if (want > kFrozenCap) want = kFrozenCap;
-  if (want < 1) want = 1;
-  return ((want + CG - 1) / CG) * CG;
-}
-}  // namespace
-
-extern "C" int64_t unetpp_bn_frozen_bwd_blocks(int64_t pixels, int32_t C) {
-  if (pixels < 1 || C < 1) return 0;
-  // rows of the partial buffer: the upper bound over the vector, scalar and pool-routing forms (the last runs
-  // min(N * H, this) workgroups)
-  const long a = (C % 4 == 0) ? bn_frozen_blocks_for(pixels, C, true) : 0;
-  const long b = bn_frozen_blocks_for(pixels, C, false);
-  return a > b ? a : b;
 }
 
 extern "C" int unetpp_bn_frozen_bwd(const float* d_act, const float* y, const float* scale, const float* shift,
                                     const float* mean, const float* invstd, const float* d_pooled,
                                     const uint8_t* pool_idx, int32_t N, int32_t H, int32_t W, int32_t C, float* dy,
                                     float* partial, void* stream) {
-  if (!d_act || !y || !scale || !shift || !dy || C < 1 || N < 1 || H < 1 || W < 1) return UNETPP_EINVAL;
-  if (partial != nullptr && (!mean || !invstd)) return UNETPP_EINVAL;
-  if ((d_pooled == nullptr) != (pool_idx == nullptr)) return UNETPP_EINVAL;
-  const long pixels = static_cast<long>(N) * H * W;
-  const long rows_buf = unetpp_bn_frozen_bwd_blocks(pixels, C);  // rows of the partial buffer; unused ones are zeroed
-  if (d_pooled != nullptr) {
-    if (!bn_bwd_pool_ok(N, H, W, C)) return UNETPP_EINVAL;
-    if (!aligned16(d_act) || !aligned16(y) || !aligned16(dy) || !aligned16(scale) || !aligned16(shift) ||
-        !aligned16(d_pooled) || (reinterpret_cast<uintptr_t>(pool_idx) & 3) != 0 ||
-        (partial != nullptr && (!aligned16(mean) || !aligned16(invstd))))
-      return UNETPP_EINVAL;
-    const long img_rows = static_cast<long>(N) * H;
-    const long grid = img_rows < rows_buf ? img_rows : rows_buf;
-    if (partial != nullptr && grid < rows_buf) zero_rows(partial + grid * C * 2, (rows_buf - grid) * C * 2, ST(stream));
-    note_kernel(partial != nullptr ? "bn_frozen_bwd_pool/sums" : "bn_frozen_bwd_pool");
+  if (!d_act || !y || !scale || !shift || !dy) return UNETPP_EINVAL;
+  const StreamQuery q = stream_bn_query(STREAM_BN_FROZEN, false, N, H, W, C, d_act, y, dy, scale, shift, mean, invstd,
+                                        nullptr, nullptr, nullptr, d_pooled, pool_idx, partial);
+  StreamSel s;
+  if (stream_select(q, s) != UNETPP_OK) return UNETPP_EINVAL;
+  zero_unwritten_rows(partial, s, C, ST(stream));
+  note_kernel(s.label);
+  if (s.form == STREAM_ROWS) {
 #define UNETPP_FROZEN_POOL(SUMS)                                                                                       \
-  hipLaunchKernelGGL(bn_frozen_bwd_pool_kernel<SUMS>, dim3(static_cast<unsigned>(grid)), dim3(kThreads), 0, ST(stream),  \
+  hipLaunchKernelGGL(bn_frozen_bwd_pool_kernel<SUMS>, dim3(s.grid), dim3(s.block), 0, ST(stream),                      \
                      reinterpret_cast<const f32x4*>(d_act), reinterpret_cast<const f32x4*>(y),                         \
                      reinterpret_cast<const f32x4*>(scale), reinterpret_cast<const f32x4*>(shift),                     \
                      reinterpret_cast<const f32x4*>(mean), reinterpret_cast<const f32x4*>(invstd),                     \
                      reinterpret_cast<const f32x4*>(d_pooled), reinterpret_cast<const uint32_t*>(pool_idx),            \
-                     static_cast<unsigned>(img_rows), static_cast<unsigned>(W), ilog2(static_cast<unsigned>(C >> 2)),  \
+                     static_cast<unsigned>(s.items), static_cast<unsigned>(W), ilog2(static_cast<unsigned>(s.cg)),     \
                      reinterpret_cast<f32x4*>(dy), partial)
     if (partial != nullptr)
       UNETPP_FROZEN_POOL(true);
@@ -1075,18 +1000,10 @@ extern "C" int unetpp_bn_frozen_bwd(const float* d_act, const float* y, const fl
 #undef UNETPP_FROZEN_POOL
     return launch_status();
   }
-  const bool vec = (C % 4 == 0) && aligned16(d_act) && aligned16(y) && aligned16(dy);
-  const long blocks = bn_frozen_blocks_for(pixels, C, vec);
-  if (partial != nullptr && blocks < rows_buf)
-    zero_rows(partial + blocks * C * 2, (rows_buf - blocks) * C * 2, ST(stream));
-  note_kernel(vec ? (partial != nullptr ? "bn_frozen_bwd<4>/sums" : "bn_frozen_bwd<4>")
-                  : (partial != nullptr ? "bn_frozen_bwd<1>/sums" : "bn_frozen_bwd<1>"));
-  const int CG = vec ? C / 4 : C;
-  const long items = pixels * CG;
 #define UNETPP_FROZEN(VEC, SUMS)                                                                                       \
-  hipLaunchKernelGGL((bn_frozen_bwd_kernel<VEC, SUMS>), dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0,         \
-                     ST(stream), d_act, y, scale, shift, mean, invstd, items, CG, dy, partial)
-  if (vec) {
+  hipLaunchKernelGGL((bn_frozen_bwd_kernel<VEC, SUMS>), dim3(s.grid), dim3(s.block), 0, ST(stream), d_act, y, scale,    \
+                     shift, mean, invstd, s.items, s.cg, dy, partial)
+  if (s.form == STREAM_VEC) {
     if (partial != nullptr)
       UNETPP_FROZEN(4, true);
     else

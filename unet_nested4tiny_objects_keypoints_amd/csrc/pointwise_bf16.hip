@@ -14,6 +14,7 @@
 #include "bf16_common.h"
 #include "common.h"
 #include "lds_asm.h"
+#include "stream_select.h"
 
 namespace unetpp {
 namespace {
@@ -242,11 +243,6 @@ __global__ __launch_bounds__(kThreads) void bn_frozen_bwd_bf16_kernel(const bf16
   }
 }
 
-inline bool octets_ok(int C) {  // C = 8 * CG, CG a power of two <= 256 (a thread keeps its octet across a grid stride)
-  const int cg = C >> 3;
-  return C >= 8 && (C & 7) == 0 && (cg & (cg - 1)) == 0 && cg <= 256;
-}
-
 
 // ---- max-pool backward without a BatchNorm to route through (is_batchnorm=False): thread = (pixel, octet) ----
 __global__ __launch_bounds__(kThreads) void maxpool_bwd_bf16_kernel(const bf16_t* __restrict__ d_pooled,
@@ -387,51 +383,46 @@ __global__ __launch_bounds__(kThreads) void bilinear2x_bwd_bf16_kernel(const bf1
 
 using namespace unetpp;
 
+// ---- the streaming launchers: NULL checks here, every other decision in stream_select.h ----
+static_assert(kStreamThreads == kThreads, "stream_select sizes its grids for kThreads threads per workgroup");
+
 extern "C" int unetpp_affine_relu_pool_bf16(const void* y, const float* scale, const float* shift, int32_t relu, int32_t N,
                                             int32_t H, int32_t W, int32_t C, void* act, void* pooled, uint8_t* pool_idx,
                                             void* stream) {
-  if (!y || N < 1 || H < 1 || W < 1 || C < 8 || (C & 7) || !aligned16(y) || (act && !aligned16(act))) return UNETPP_EINVAL;
-  if ((scale == nullptr) != (shift == nullptr) || (act == nullptr && pooled == nullptr)) return UNETPP_EINVAL;
-  const int CG = C >> 3;
-  if (pooled == nullptr) {
-    const long items = static_cast<long>(N) * H * W * CG;
-    note_kernel("affine_relu_bf16");
-    hipLaunchKernelGGL(affine_relu_bf16_kernel, dim3(grid_for(items)), dim3(kThreads), 0, ST(stream),
-                       static_cast<const bf16_t*>(y), scale, shift, relu, items, CG, static_cast<bf16_t*>(act));
-    return launch_status();
-  }
-  if ((H & 1) || (W & 1) || !pool_idx || !aligned16(pooled) || (reinterpret_cast<uintptr_t>(pool_idx) & 7)) return UNETPP_EINVAL;
-  const long items = static_cast<long>(N) * (H / 2) * (W / 2) * CG;
-  if (items >= 0x7fffffffL) return UNETPP_EINVAL;
-  note_kernel("affine_relu_pool_bf16");
-  hipLaunchKernelGGL(affine_relu_pool_bf16_kernel, dim3(grid_for(items)), dim3(kThreads), 0, ST(stream),
-                     static_cast<const bf16_t*>(y), scale, shift, relu, N, H, W, CG, static_cast<bf16_t*>(act),
-                     static_cast<bf16_t*>(pooled), pool_idx);
+  if (!y) return UNETPP_EINVAL;
+  StreamQuery q = stream_query(STREAM_AFFINE, true, N, H, W, C);
+  q.has_scale = scale != nullptr, q.has_shift = shift != nullptr, q.has_act = act != nullptr;
+  q.has_pooled = pooled != nullptr, q.has_idx = pool_idx != nullptr;
+  q.in_lo = stream_lo4(y), q.out_lo = stream_lo4(act), q.pooled_lo = stream_lo4(pooled), q.idx_lo = stream_lo4(pool_idx);
+  StreamSel s;
+  if (stream_select(q, s) != UNETPP_OK) return UNETPP_EINVAL;
+  note_kernel(s.label);
+  if (pooled == nullptr)
+    hipLaunchKernelGGL(affine_relu_bf16_kernel, dim3(s.grid), dim3(s.block), 0, ST(stream), static_cast<const bf16_t*>(y),
+                       scale, shift, relu, s.items, s.cg, static_cast<bf16_t*>(act));
+  else
+    hipLaunchKernelGGL(affine_relu_pool_bf16_kernel, dim3(s.grid), dim3(s.block), 0, ST(stream),
+                       static_cast<const bf16_t*>(y), scale, shift, relu, N, H, W, s.cg, static_cast<bf16_t*>(act),
+                       static_cast<bf16_t*>(pooled), pool_idx);
   return launch_status();
 }
 
-extern "C" int64_t unetpp_bn_bwd_blocks_bf16(int64_t pixels, int32_t C) {
-  if (pixels < 1 || !octets_ok(C)) return 0;
-  const long items = pixels * (C >> 3);
-  long b = (items + 4L * kThreads - 1) / (4L * kThreads);  // >= 4 items per thread
-  if (b > 2048) b = 2048;
-  return b < 1 ? 1 : b;
-}
+extern "C" int64_t unetpp_bn_bwd_blocks_bf16(int64_t pixels, int32_t C) { return stream_partial_rows(true, false, pixels, C); }
+extern "C" int64_t unetpp_bn_frozen_bwd_blocks_bf16(int64_t pixels, int32_t C) { return stream_partial_rows(true, true, pixels, C); }
 
 extern "C" int unetpp_bn_bwd_reduce_bf16(const void* d_act, const void* y, const float* scale, const float* shift,
                                          const float* mean, const float* invstd, const void* d_pooled,
                                          const uint8_t* pool_idx, int32_t N, int32_t H, int32_t W, int32_t C, float* partial,
                                          void* stream) {
-  if (!d_act || !y || !scale || !shift || !mean || !invstd || !partial || N < 1 || H < 1 || W < 1 || !octets_ok(C))
-    return UNETPP_EINVAL;
-  if ((d_pooled == nullptr) != (pool_idx == nullptr) || (d_pooled != nullptr && ((H | W) & 1))) return UNETPP_EINVAL;
-  const long pixels = static_cast<long>(N) * H * W;
-  if (pixels * (C >> 3) >= 0x7fffffffL) return UNETPP_EINVAL;
-  note_kernel(d_pooled != nullptr ? "bn_bwd_reduce_bf16/pool" : "bn_bwd_reduce_bf16");
-  hipLaunchKernelGGL(bn_bwd_reduce_bf16_kernel, dim3(static_cast<unsigned>(unetpp_bn_bwd_blocks_bf16(pixels, C))),
-                     dim3(kThreads), 0, ST(stream), static_cast<const bf16_t*>(d_act), static_cast<const bf16_t*>(y), scale,
-                     shift, mean, invstd, static_cast<const bf16_t*>(d_pooled), pool_idx, pixels * (C >> 3), C >> 3, H, W,
-                     partial);
+  if (!d_act || !y || !scale || !shift || !mean || !invstd || !partial) return UNETPP_EINVAL;
+  const StreamQuery q = stream_bn_query(STREAM_BN_REDUCE, true, N, H, W, C, d_act, y, nullptr, scale, shift, mean, invstd,
+                                        nullptr, nullptr, nullptr, d_pooled, pool_idx, partial);
+  StreamSel s;
+  if (stream_select(q, s) != UNETPP_OK) return UNETPP_EINVAL;
+  note_kernel(s.label);
+  hipLaunchKernelGGL(bn_bwd_reduce_bf16_kernel, dim3(s.grid), dim3(s.block), 0, ST(stream),
+                     static_cast<const bf16_t*>(d_act), static_cast<const bf16_t*>(y), scale, shift, mean, invstd,
+                     static_cast<const bf16_t*>(d_pooled), pool_idx, s.items, s.cg, H, W, partial);
   return launch_status();
 }
 
@@ -439,67 +430,54 @@ extern "C" int unetpp_bn_bwd_apply_bf16(const void* d_act, const void* y, const 
                                         const float* mean, const float* invstd, const float* gamma, const float* dgamma,
                                         const float* dbeta, const void* d_pooled, const uint8_t* pool_idx, int32_t N,
                                         int32_t H, int32_t W, int32_t C, void* dy, void* stream) {
-  if (!d_act || !y || !scale || !shift || !mean || !invstd || !gamma || !dgamma || !dbeta || !dy || N < 1 || H < 1 ||
-      W < 1 || !octets_ok(C))
-    return UNETPP_EINVAL;
-  if ((d_pooled == nullptr) != (pool_idx == nullptr) || (d_pooled != nullptr && ((H | W) & 1))) return UNETPP_EINVAL;
+  if (!d_act || !y || !scale || !shift || !mean || !invstd || !gamma || !dgamma || !dbeta || !dy) return UNETPP_EINVAL;
+  const StreamQuery q = stream_bn_query(STREAM_BN_APPLY, true, N, H, W, C, d_act, y, dy, scale, shift, mean, invstd, gamma,
+                                        dgamma, dbeta, d_pooled, pool_idx, nullptr);
+  StreamSel s;
+  if (stream_select(q, s) != UNETPP_OK) return UNETPP_EINVAL;
   const long pixels = static_cast<long>(N) * H * W;
-  const long items = pixels * (C >> 3);
-  if (items >= 0x7fffffffL) return UNETPP_EINVAL;
-  note_kernel(d_pooled != nullptr ? "bn_bwd_apply_bf16/pool" : "bn_bwd_apply_bf16");
-  hipLaunchKernelGGL(bn_bwd_apply_bf16_kernel, dim3(grid_for(items)), dim3(kThreads), 0, ST(stream),
+  note_kernel(s.label);
+  hipLaunchKernelGGL(bn_bwd_apply_bf16_kernel, dim3(s.grid), dim3(s.block), 0, ST(stream),
                      static_cast<const bf16_t*>(d_act), static_cast<const bf16_t*>(y), scale, shift, mean, invstd, gamma,
-                     dgamma, dbeta, static_cast<const bf16_t*>(d_pooled), pool_idx, 1.0f / static_cast<float>(pixels), items,
-                     C >> 3, H, W, static_cast<bf16_t*>(dy));
+                     dgamma, dbeta, static_cast<const bf16_t*>(d_pooled), pool_idx, 1.0f / static_cast<float>(pixels),
+                     s.items, s.cg, H, W, static_cast<bf16_t*>(dy));
   return launch_status();
-}
-
-extern "C" int64_t unetpp_bn_frozen_bwd_blocks_bf16(int64_t pixels, int32_t C) {
-  if (pixels < 1 || !octets_ok(C)) return 0;
-  const long items = pixels * (C >> 3);
-  long b = (items + kThreads - 1) / kThreads;  // one item per thread up to the cap, then a grid-stride loop
-  if (b > 2048) b = 2048;
-  return b < 1 ? 1 : b;
 }
 
 extern "C" int unetpp_bn_frozen_bwd_bf16(const void* d_act, const void* y, const float* scale, const float* shift,
                                          const float* mean, const float* invstd, const void* d_pooled,
                                          const uint8_t* pool_idx, int32_t N, int32_t H, int32_t W, int32_t C, void* dy,
                                          float* partial, void* stream) {
-  if (!d_act || !y || !scale || !shift || !dy || N < 1 || H < 1 || W < 1 || !octets_ok(C)) return UNETPP_EINVAL;
-  if (partial != nullptr && (!mean || !invstd)) return UNETPP_EINVAL;
-  if ((d_pooled == nullptr) != (pool_idx == nullptr) || (d_pooled != nullptr && ((H | W) & 1))) return UNETPP_EINVAL;
-  if (!aligned16(d_act) || !aligned16(y) || !aligned16(dy) || (d_pooled && !aligned16(d_pooled)) || (reinterpret_cast<uintptr_t>(pool_idx) & 7))
-    return UNETPP_EINVAL;
-  const long pixels = static_cast<long>(N) * H * W;
-  const long items = pixels * (C >> 3);
-  if (items >= 0x7fffffffL) return UNETPP_EINVAL;
-  const unsigned blocks = static_cast<unsigned>(unetpp_bn_frozen_bwd_blocks_bf16(pixels, C));
-  if (partial != nullptr) {
-    note_kernel(d_pooled != nullptr ? "bn_frozen_bwd_bf16/pool/sums" : "bn_frozen_bwd_bf16/sums");
-    hipLaunchKernelGGL(bn_frozen_bwd_bf16_kernel<true>, dim3(blocks), dim3(kThreads), 0, ST(stream),
-                       static_cast<const bf16_t*>(d_act), static_cast<const bf16_t*>(y), scale, shift, mean, invstd,
-                       static_cast<const bf16_t*>(d_pooled), pool_idx, items, C >> 3, H, W, static_cast<bf16_t*>(dy),
-                       partial);
-  } else {
-    note_kernel(d_pooled != nullptr ? "bn_frozen_bwd_bf16/pool" : "bn_frozen_bwd_bf16");
-    hipLaunchKernelGGL(bn_frozen_bwd_bf16_kernel<false>, dim3(blocks), dim3(kThreads), 0, ST(stream),
-                       static_cast<const bf16_t*>(d_act), static_cast<const bf16_t*>(y), scale, shift, mean, invstd,
-                       static_cast<const bf16_t*>(d_pooled), pool_idx, items, C >> 3, H, W, static_cast<bf16_t*>(dy),
-                       partial);
-  }
+  if (!d_act || !y || !scale || !shift || !dy) return UNETPP_EINVAL;
+  const StreamQuery q = stream_bn_query(STREAM_BN_FROZEN, true, N, H, W, C, d_act, y, dy, scale, shift, mean, invstd,
+                                        nullptr, nullptr, nullptr, d_pooled, pool_idx, partial);
+  StreamSel s;
+  if (stream_select(q, s) != UNETPP_OK) return UNETPP_EINVAL;
+  note_kernel(s.label);
+#define UNETPP_FROZEN_BF16(SUMS)                                                                                       \
+  hipLaunchKernelGGL(bn_frozen_bwd_bf16_kernel<SUMS>, dim3(s.grid), dim3(s.block), 0, ST(stream),                      \
+                     static_cast<const bf16_t*>(d_act), static_cast<const bf16_t*>(y), scale, shift, mean, invstd,     \
+                     static_cast<const bf16_t*>(d_pooled), pool_idx, s.items, s.cg, H, W, static_cast<bf16_t*>(dy),    \
+                     partial)
+  if (partial != nullptr)
+    UNETPP_FROZEN_BF16(true);
+  else
+    UNETPP_FROZEN_BF16(false);
+#undef UNETPP_FROZEN_BF16
   return launch_status();
 }
 
 extern "C" int unetpp_maxpool_bwd_bf16(const void* d_pooled, const uint8_t* pool_idx, int32_t N, int32_t H, int32_t W,
                                        int32_t C, void* d_act, const void* gate, void* stream) {
-  if (!d_pooled || !pool_idx || !d_act || N < 1 || H < 2 || W < 2 || (H & 1) || (W & 1) || C < 8 || (C & 7)) return UNETPP_EINVAL;
-  if (!aligned16(d_pooled) || !aligned16(d_act) || (gate && !aligned16(gate)) || (reinterpret_cast<uintptr_t>(pool_idx) & 7)) return UNETPP_EINVAL;
-  const long items = static_cast<long>(N) * H * W * (C >> 3);
-  if (items >= 0x7fffffffL) return UNETPP_EINVAL;
-  note_kernel("maxpool_bwd_bf16");
-  hipLaunchKernelGGL(maxpool_bwd_bf16_kernel, dim3(grid_for(items)), dim3(kThreads), 0, ST(stream),
-                     static_cast<const bf16_t*>(d_pooled), pool_idx, N, H, W, C >> 3, static_cast<bf16_t*>(d_act),
+  if (!d_pooled || !pool_idx || !d_act) return UNETPP_EINVAL;
+  StreamQuery q = stream_query(STREAM_POOL_BWD, true, N, H, W, C);
+  q.has_gate = gate != nullptr;
+  q.pooled_lo = stream_lo4(d_pooled), q.idx_lo = stream_lo4(pool_idx), q.out_lo = stream_lo4(d_act), q.gate_lo = stream_lo4(gate);
+  StreamSel s;
+  if (stream_select(q, s) != UNETPP_OK) return UNETPP_EINVAL;
+  note_kernel(s.label);
+  hipLaunchKernelGGL(maxpool_bwd_bf16_kernel, dim3(s.grid), dim3(s.block), 0, ST(stream),
+                     static_cast<const bf16_t*>(d_pooled), pool_idx, N, H, W, s.cg, static_cast<bf16_t*>(d_act),
                      static_cast<const bf16_t*>(gate));
   return launch_status();
 }

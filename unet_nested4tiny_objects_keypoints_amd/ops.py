@@ -609,61 +609,69 @@ def maxpool_bwd(d_pooled, pool_idx, d_act, gate=None):
           "unetpp_maxpool_bwd")
 
 
-def _bn_backward_bf16(d_act, y, scale, shift, mean, invstd, gamma, dy_out, dgamma, dbeta, pool):
+def _bn_backward(frozen, d_act, y, scale, shift, mean, invstd, gamma, dy_out, dgamma, dbeta, pool, want_sums):
+    """The one body of bn_backward and bn_frozen_backward.  unetpp_bn_bwd_plan says how the pool gradient travels (inside
+    the passes, or by a maxpool_bwd pass into d_act first) and how large the partial buffer is; then the pass or passes
+    and the finalize."""
     lib = _lib.lib()
     n, h, w, c = y.shape
-    blocks = int(lib.unetpp_bn_bwd_blocks_bf16(n * h * w, c))
-    if blocks < 1:
+    bf16 = _is_bf16(y)
+    if want_sums and dgamma is None:
+        dgamma = torch.empty(c, dtype=torch.float32, device=y.device)
+    if want_sums and dbeta is None:
+        dbeta = torch.empty(c, dtype=torch.float32, device=y.device)
+    d_pooled, pool_idx = (None, None) if pool is None else pool
+    # every address once, in BnBwdQuery.POINTERS order: the plan looks at them, the launches get the same ones
+    addr = [None if t is None else t.data_ptr()
+            for t in (d_act, y, dy_out, scale, shift, mean, invstd, gamma, dgamma, dbeta, d_pooled, pool_idx)]
+    plan = _lib.BnBwdSizes()
+    rc = lib.unetpp_bn_bwd_plan(_lib.BnBwdQuery(frozen, bf16, want_sums, n, h, w, c, 0, *addr), plan)
+    rows = plan.partial_rows
+    if rows < 1 and (bf16 or frozen):
         raise ValueError("bf16 BatchNorm backward needs C = 8 * 2^k channels, got %d" % c)
-    partial = torch.empty(blocks * c * 2, dtype=torch.float32, device=y.device)
-    dp, pi = (None, None) if pool is None else (_need(pool[0], "d_pooled", torch.bfloat16), _need(pool[1], "pool_idx", torch.uint8))
+    if rc != 0:  # a refused plan is reported under the name of the launch that used to refuse
+        check(rc, "unetpp_maxpool_bwd" if pool is not None and not bf16 else
+              "unetpp_bn_frozen_bwd" if frozen else "unetpp_bn_bwd_reduce" + ("_bf16" if bf16 else ""))
+    a_dact, a_y, a_dy, a_scale, a_shift, a_mean, a_invstd, a_gamma, a_dgamma, a_dbeta, a_pooled, a_idx = addr
+    route = plan.route
+    if route == 2:
+        maxpool_bwd(d_pooled, pool_idx, d_act)
+        a_pooled = a_idx = None
+    elif route == 1:
+        _need(d_pooled, "d_pooled", y.dtype), _need(pool_idx, "pool_idx", torch.uint8)
+    a_partial = None
+    if want_sums:
+        partial = torch.empty(plan.partial_floats, dtype=torch.float32, device=y.device)
+        a_partial = partial.data_ptr()
     st = _stream()
-    check(lib.unetpp_bn_bwd_reduce_bf16(_ptr(d_act), _ptr(y), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(invstd), _ptr(dp),
-                                        _ptr(pi), n, h, w, c, _ptr(partial), st), "unetpp_bn_bwd_reduce_bf16")
-    check(lib.unetpp_bn_bwd_finalize(_ptr(partial), blocks, c, _ptr(dgamma), _ptr(dbeta), st), "unetpp_bn_bwd_finalize")
-    check(lib.unetpp_bn_bwd_apply_bf16(_ptr(d_act), _ptr(y), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(invstd), _ptr(gamma),
-                                       _ptr(dgamma), _ptr(dbeta), _ptr(dp), _ptr(pi), n, h, w, c, _ptr(dy_out), st),
-          "unetpp_bn_bwd_apply_bf16")
+    if frozen:
+        fn = lib.unetpp_bn_frozen_bwd_bf16 if bf16 else lib.unetpp_bn_frozen_bwd
+        _timed_call(None, 0.0, lambda: check(fn(a_dact, a_y, a_scale, a_shift, a_mean, a_invstd, a_pooled, a_idx, n, h, w, c,
+                                                a_dy, a_partial, st), "unetpp_bn_frozen_bwd"),
+                    (2.0 if bf16 else 4.0) * n * h * w * c * 3)
+        if want_sums:
+            check(lib.unetpp_bn_bwd_finalize(a_partial, rows, c, a_dgamma, a_dbeta, st), "unetpp_bn_bwd_finalize")
+        return (dgamma, dbeta) if want_sums else (None, None)
+    # the plain fp32 passes take a pixel count, the routing and the bf16 ones the pool pair (NULL: none) and the shape
+    suffix = "_bf16" if bf16 else "_pool" if route == 1 else ""
+    shape = (a_pooled, a_idx, n, h, w, c) if suffix else (n * h * w, c)
+    check(getattr(lib, "unetpp_bn_bwd_reduce" + suffix)(a_dact, a_y, a_scale, a_shift, a_mean, a_invstd, *shape, a_partial, st),
+          "unetpp_bn_bwd_reduce" + suffix)
+    check(lib.unetpp_bn_bwd_finalize(a_partial, rows, c, a_dgamma, a_dbeta, st), "unetpp_bn_bwd_finalize")
+    check(getattr(lib, "unetpp_bn_bwd_apply" + suffix)(a_dact, a_y, a_scale, a_shift, a_mean, a_invstd, a_gamma, a_dgamma, a_dbeta,
+                                                       *shape, a_dy, st), "unetpp_bn_bwd_apply" + suffix)
     return dgamma, dbeta
+
+
+def _bn_backward_bf16(d_act, y, scale, shift, mean, invstd, gamma, dy_out, dgamma, dbeta, pool):
+    return _bn_backward(False, d_act, y, scale, shift, mean, invstd, gamma, dy_out, dgamma, dbeta, pool, True)
 
 
 def bn_backward(d_act, y, scale, shift, mean, invstd, gamma, dy_out, dgamma=None, dbeta=None, pool=None):
     """Training-mode BatchNorm+ReLU backward.  Returns (dgamma, dbeta); dy_out may alias d_act.
     pool = (d_pooled, pool_idx): the gradient of the 2x2 max-pool of this activation, routed to the argmax while
     d_act is read (both passes) when the shape allows, else by a maxpool_bwd pass into d_act first."""
-    lib = _lib.lib()
-    n, h, w, c = y.shape
-    pixels = n * h * w
-    if dgamma is None:
-        dgamma = torch.empty(c, dtype=torch.float32, device=y.device)
-    if dbeta is None:
-        dbeta = torch.empty(c, dtype=torch.float32, device=y.device)
-    if _is_bf16(y):
-        return _bn_backward_bf16(d_act, y, scale, shift, mean, invstd, gamma, dy_out, dgamma, dbeta, pool)
-    if pool is not None and not lib.unetpp_bn_bwd_pool_ok(n, h, w, c):
-        maxpool_bwd(pool[0], pool[1], d_act)
-        pool = None
-    blocks = int(lib.unetpp_bn_bwd_blocks(pixels, c))
-    partial = torch.empty(blocks * c * 2, dtype=torch.float32, device=y.device)
-    st = _stream()
-    if pool is None:
-        check(lib.unetpp_bn_bwd_reduce(_ptr(d_act), _ptr(y), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(invstd), pixels,
-                                       c, _ptr(partial), st), "unetpp_bn_bwd_reduce")
-    else:
-        d_pooled, pool_idx = _need(pool[0], "d_pooled"), _need(pool[1], "pool_idx", torch.uint8)
-        check(lib.unetpp_bn_bwd_reduce_pool(_ptr(d_act), _ptr(y), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(invstd),
-                                            _ptr(d_pooled), _ptr(pool_idx), n, h, w, c, _ptr(partial), st),
-              "unetpp_bn_bwd_reduce_pool")
-    check(lib.unetpp_bn_bwd_finalize(_ptr(partial), blocks, c, _ptr(dgamma), _ptr(dbeta), st), "unetpp_bn_bwd_finalize")
-    if pool is None:
-        check(lib.unetpp_bn_bwd_apply(_ptr(d_act), _ptr(y), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(invstd),
-                                      _ptr(gamma), _ptr(dgamma), _ptr(dbeta), pixels, c, _ptr(dy_out), st),
-              "unetpp_bn_bwd_apply")
-    else:
-        check(lib.unetpp_bn_bwd_apply_pool(_ptr(d_act), _ptr(y), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(invstd),
-                                           _ptr(gamma), _ptr(dgamma), _ptr(dbeta), _ptr(pool[0]), _ptr(pool[1]), n, h,
-                                           w, c, _ptr(dy_out), st), "unetpp_bn_bwd_apply_pool")
-    return dgamma, dbeta
+    return _bn_backward(False, d_act, y, scale, shift, mean, invstd, gamma, dy_out, dgamma, dbeta, pool, True)
 
 
 def bn_frozen_backward(d_act, y, scale, shift, mean, invstd, dy_out, dgamma=None, dbeta=None, pool=None, want_sums=True):
@@ -671,40 +679,13 @@ def bn_frozen_backward(d_act, y, scale, shift, mean, invstd, dy_out, dgamma=None
     in ONE streaming launch (g = d_act plus the routed pool gradient); dy_out may alias d_act.  want_sums: also dgamma =
     sum gg*xhat and dbeta = sum gg (per-workgroup rows + bn_bwd_finalize); returns (dgamma, dbeta), or (None, None) without
     sums (gamma and beta frozen too: mean / invstd may then be None).  pool = (d_pooled, pool_idx) as in bn_backward."""
-    lib = _lib.lib()
-    n, h, w, c = y.shape
-    pixels = n * h * w
-    bf16 = _is_bf16(y)
-    adt = torch.bfloat16 if bf16 else torch.float32
+    adt = torch.bfloat16 if _is_bf16(y) else torch.float32
     _need(d_act, "d_act", adt), _need(y, "y", adt), _need(dy_out, "dy", adt)
     if tuple(d_act.shape) != tuple(y.shape) or tuple(dy_out.shape) != tuple(y.shape):
         raise ValueError("d_act, y and dy must have one shape")
     if want_sums and (mean is None or invstd is None):
         raise ValueError("the gamma / beta sums need the running mean snapshot and invstd")
-    blocks_fn = lib.unetpp_bn_frozen_bwd_blocks_bf16 if bf16 else lib.unetpp_bn_frozen_bwd_blocks
-    blocks = int(blocks_fn(pixels, c))
-    if blocks < 1:
-        raise ValueError("bf16 BatchNorm backward needs C = 8 * 2^k channels, got %d" % c)
-    if pool is not None and not bf16 and not (lib.unetpp_bn_bwd_pool_ok(n, h, w, c) and scale.data_ptr() % 16 == 0
-                                              and shift.data_ptr() % 16 == 0 and pool[1].data_ptr() % 4 == 0):
-        maxpool_bwd(pool[0], pool[1], d_act)
-        pool = None
-    dp, pi = (None, None) if pool is None else (_need(pool[0], "d_pooled", adt), _need(pool[1], "pool_idx", torch.uint8))
-    partial = torch.empty(blocks * c * 2, dtype=torch.float32, device=y.device) if want_sums else None
-    st = _stream()
-    fn = lib.unetpp_bn_frozen_bwd_bf16 if bf16 else lib.unetpp_bn_frozen_bwd
-    _timed_call(None, 0.0, lambda: check(fn(_ptr(d_act), _ptr(y), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(invstd),
-                                             _ptr(dp), _ptr(pi), n, h, w, c, _ptr(dy_out), _ptr(partial), st),
-                                          "unetpp_bn_frozen_bwd"),
-                (2.0 if bf16 else 4.0) * pixels * c * 3)
-    if not want_sums:
-        return None, None
-    if dgamma is None:
-        dgamma = torch.empty(c, dtype=torch.float32, device=y.device)
-    if dbeta is None:
-        dbeta = torch.empty(c, dtype=torch.float32, device=y.device)
-    check(lib.unetpp_bn_bwd_finalize(_ptr(partial), blocks, c, _ptr(dgamma), _ptr(dbeta), st), "unetpp_bn_bwd_finalize")
-    return dgamma, dbeta
+    return _bn_backward(True, d_act, y, scale, shift, mean, invstd, None, dy_out, dgamma, dbeta, pool, want_sums)
 
 
 def head_fwd(x, weight, bias, p_drop, seed, mask, out_nchw, seed_dev=None):
