@@ -203,6 +203,9 @@ int unetpp_gemm_fwd(const unetpp_gemm_desc* d, void* stream);
  * multiples of 4; an affine + ReLU load transform is allowed).  Returns the image size in floats, or 0 when the
  * descriptor must use the generic kernel. */
 int64_t unetpp_gemm_weight_image_floats(const unetpp_gemm_desc* d);
+/* The image of d, one launch of the packer on the job (taps, flags, channel counts of d's views; source; image) passed as
+ * the kernel argument: stream-ordered, no allocation, copy or synchronisation (capturable).  UNETPP_EINVAL, and no launch,
+ * for a NULL operand or a descriptor without an image (unetpp_gemm_weight_image_floats(d) == 0). */
 int unetpp_gemm_pack_weight_image(const unetpp_gemm_desc* d, float* image, void* stream); /* from d->weight (packed) */
 /* The same image built straight from a parameter in its torch layout (no unetpp_pack_weight pass; d->weight may be
  * NULL for a launch that carries a weight image).  Element W[tap][k][n] of the GEMM weight is read at
@@ -217,10 +220,11 @@ typedef struct unetpp_weight_src {
   int32_t k_inner, n_inner, flip, reserved;
 } unetpp_weight_src;
 int unetpp_gemm_pack_weight_image_from(const unetpp_gemm_desc* d, const unetpp_weight_src* src, float* image, void* stream);
-/* Many images in ONE launch (all launches of a forward or backward pass): a table of jobs in DEVICE memory.  A job
- * carries what the image layout depends on -- taps, flags and the channel counts of the launch's input / output views
+/* Many images in ONE launch (all launches of a forward or backward pass) of the same packer: a table of jobs in DEVICE
+ * memory.  A job carries what the image layout depends on -- taps, flags and the channel counts of the launch's input / output views
  * (must describe a launch for which unetpp_gemm_weight_image_floats() > 0) -- plus source and destination.
- * max_image_floats = the largest image of the table (sizes the grid). */
+ * max_image_floats = the largest image of the table (sizes the grid the jobs share, by the rule that sizes a single
+ * image's). */
 typedef struct unetpp_pack_job {
   unetpp_weight_src src;
   float* image;

@@ -1,16 +1,17 @@
-"""Both weight-image packers of csrc/weight_image.hip, slot by slot, against tests/weight_image_oracle.py.
+"""Both entry points of the weight-image packer of csrc/weight_image.hip, slot by slot, against tests/weight_image_oracle.py.
 
-(a) Per image.  Every row of CASES is one image, built twice over the C ABI: by the single packer (pack_image_one_kernel:
-unetpp_gemm_pack_weight_image for the packed operand, ..._from for a parameter in its torch layout) and by the batched
-packer (pack_image_jobs_kernel: unetpp_gemm_pack_weight_images), ALL jobs of a group in one launch -- the largest image
-sizes the grid, so the small ones see more workgroups than rows.  Both destinations start as a NaN bit pattern, with
-64 words of it behind the image.  Afterwards: the size unetpp_gemm_weight_image_floats gives (gemm_image_of) equals the
-oracle's slot count (the batched kernel derives kind, chunk width and counts from the job by itself: a disagreement
-shows as an unwritten or overrun word); no word of the image holds the pattern, the 64 behind it still do; the two images
-are equal as integers; both equal the oracle; pad slots are +0.0.  fast / bf16 images are copies (roundings to bf16
+(a) Per image.  Every row of CASES is one image, built twice over the C ABI by the one packer body (pack_image): singly
+(pack_image_job_kernel, the job passed by value, a grid of its own size: unetpp_gemm_pack_weight_image for the packed
+operand, ..._from for a parameter in its torch layout) and batched (pack_image_jobs_kernel, a job table in device memory:
+unetpp_gemm_pack_weight_images), ALL jobs of a group in one launch -- the largest image sizes the shared grid, so the
+small ones see more workgroups than rows.  Both destinations start as a NaN bit pattern, with 64 words of it behind the
+image.  Afterwards: the size unetpp_gemm_weight_image_floats gives (gemm_image_of) equals the oracle's slot count (host
+selection and kernel size and walk the image by the same image_layout of csrc/gemm_units.h; the oracle restates it: a
+disagreement shows as an unwritten or overrun word); no word of the image holds the pattern, the 64 behind it still do;
+the two images are equal as integers; both equal the oracle; pad slots are +0.0.  fast / bf16 images are copies (roundings to bf16
 aside), so the data are arbitrary bit patterns: full-mantissa values, +-0, denormals, exact bf16 ties towards both
 neighbours, values that round up into the next binade (NaN is left out: its bf16 pattern is the hardware's choice).
-Winograd images run on two data sets: integers times 4 (G g G^T is then an integer: both packers must EQUAL float64) and
+Winograd images run on two data sets: integers times 4 (G g G^T is then an integer: both images must EQUAL float64) and
 full-mantissa floats (bit-equal to each other and to the float32 restatement ((w0 +- w1) + w2) * 0.5, rows then columns,
 and within gamma(4) (|G| |g| |G^T|) of float64: each of the two stages is two roundings and an exact halving).
 
@@ -51,7 +52,7 @@ with NaN; the second begin("fwd") is ONE batched launch that must reproduce the 
 rerun on them must give the float64 results exactly.
 
 (c) unetpp_pack_weight against `gather` for the five factories' pack= stride sets, and the argument refusals of
-unetpp_gemm_pack_weight_images.
+unetpp_gemm_pack_weight_images and of the two single entry points.
 """
 import contextlib
 import ctypes as C
@@ -575,3 +576,34 @@ def test_batched_packer_refuses_bad_arguments(dev):
     assert lib.unetpp_gemm_pack_weight_images(ptr, 65536, 512, None) == -1
     assert lib.unetpp_gemm_pack_weight_images(ptr, 1, 0, None) == -1
     torch.cuda.synchronize()
+
+
+def test_single_entry_points_refuse_bad_arguments(dev):
+    """(a refusal launches nothing: the destination keeps its pattern)"""
+    from unet_nested4tiny_objects_keypoints_amd import _lib
+    lib = _lib.lib()
+    act = torch.zeros(8 * 8 * 16, dtype=torch.float32, device=dev)
+    param = torch.ones(9 * 8 * 8, dtype=torch.float32, device=dev)
+    image = _pattern(512, dev)
+    img = C.c_void_p(image.data_ptr())
+
+    def desc(c_in):
+        d = _lib.GemmDesc()
+        d.N, d.H, d.W, d.taps, d.flags, d.n_in, d.n_out = 1, 8, 8, 9, GEMM_DIRECT, 1, 1
+        for v, n in ((d.inp[0], c_in), (d.out[0], 8)):
+            v.ptr, v.C, v.c_off, v.c_len, v.Hs, v.Ws, v.sy, v.sx = act.data_ptr(), n, 0, n, 8, 8, 1, 1
+        return d
+    good, odd = desc(8), desc(6)      # 6 channels: no multiple of 4, so no image kernel takes the view
+    assert lib.unetpp_gemm_weight_image_floats(C.byref(good)) == 9 * 512 and lib.unetpp_gemm_weight_image_floats(C.byref(odd)) == 0
+    src, no_src = _lib.WeightSrc(), _lib.WeightSrc()
+    src.src, src.s_t, src.s_k, src.s_n = param.data_ptr(), 64, 8, 1
+    no_src.s_t, no_src.s_k, no_src.s_n = 64, 8, 1
+    assert no_src.src is None
+    assert lib.unetpp_gemm_pack_weight_image_from(C.byref(good), None, img, None) == -1
+    assert lib.unetpp_gemm_pack_weight_image_from(C.byref(good), C.byref(no_src), img, None) == -1
+    assert lib.unetpp_gemm_pack_weight_image_from(C.byref(good), C.byref(src), None, None) == -1
+    assert lib.unetpp_gemm_pack_weight_image_from(C.byref(odd), C.byref(src), img, None) == -1
+    assert good.weight is None
+    assert lib.unetpp_gemm_pack_weight_image(C.byref(good), img, None) == -1
+    torch.cuda.synchronize()
+    assert bool((image == NAN_WORD).all()), "a refused call wrote to the destination"

@@ -554,7 +554,7 @@ __global__ __launch_bounds__(kThreads, STATS ? UNETPP_BF16_STATS_WGS : UNETPP_BF
 
 bool bf16_gemm_args(const unetpp_gemm_desc* d, FastArgs& a) {
   if (d == nullptr || (d->flags & UNETPP_GEMM_BF16) == 0) return false;
-  if (!fast_args(d, a, BKC, 32)) return false;
+  if (!fast_args(d, a, image_layout(d->taps, d->flags))) return false;
   // 3x3 launches without a statistics epilogue feed TWO column tiles from one staged input patch when they can
   // (input gradients into several views, layers with >= 64 output channels)
   if (d->taps == 9 && d->stats_partial == nullptr && a.n_tiles % 2 == 0) {

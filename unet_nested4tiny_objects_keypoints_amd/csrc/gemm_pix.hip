@@ -301,18 +301,16 @@ extern "C" int64_t unetpp_gemm_stats_rows(int32_t N, int32_t H, int32_t W) {
   return blocks > kBnFusedRows ? blocks : kBnFusedRows;  // per-workgroup rows (bn_fused.h) or per-block rows
 }
 
-// The weight image of a descriptor's fast kernels: bf16 storage has one layout, fp32 3x3 without UNETPP_GEMM_DIRECT the
-// Winograd one, everything else the direct one.  Does not look at d->weight_image: the caller sizes the image by it.
+// The weight image of a descriptor's fast kernels, by the layout rule (image_layout, gemm_units.h).  Does not look at
+// d->weight_image: the caller sizes the image by it.
 bool unetpp::gemm_image_of(const unetpp_gemm_desc* d, GemmSel& s) {
-  s.image_kind = s.image_kc = 0;
+  s.image_kind = 0;
   s.image_floats = 0;
   if (d == nullptr) return false;
-  const bool bf = (d->flags & UNETPP_GEMM_BF16) != 0, wino = wino_applies(d);
-  const int kc = bf ? 32 : (wino ? 8 : 16);
-  if (bf ? !bf16_gemm_args(d, s.fa) : !fast_args(d, s.fa, kc, 32)) return false;
-  s.image_kind = bf ? kKindBf16 : (wino ? kKindWino : kKindFast);
-  s.image_kc = kc;
-  s.image_floats = static_cast<long>(s.fa.n_tiles) * s.fa.n_chunks * (wino ? 4096 : d->taps * 512L);
+  const ImageLayout l = image_layout(d->taps, d->flags);
+  if (l.kind == kKindBf16 ? !bf16_gemm_args(d, s.fa) : !fast_args(d, s.fa, l)) return false;
+  s.image_kind = l.kind;
+  s.image_floats = s.fa.n_tiles * s.fa.n_chunks * l.unit_floats();
   return true;
 }
 

@@ -78,6 +78,40 @@ __device__ __forceinline__ UnitGeom decode_unit(const FastArgs& a, long lb) {
 // ---- forward / input-gradient GEMM: gemm_select (gemm_pix.hip) decides ONCE, from the descriptor and a CU count, which
 // kernel takes it and everything that follows from that; unetpp_gemm_plan reports it, unetpp_gemm_fwd launches what it says.
 constexpr int kKindFast = 0, kKindWino = 1, kKindBf16 = 2;  // weight image layouts (weight_image.hip)
+// The one statement of which image a launch reads and how it is cut up.  bf16 storage has one layout, fp32 3x3 without
+// UNETPP_GEMM_DIRECT the Winograd one, everything else the direct one.  An image is [tile][chunk] units; every view
+// starts a new chunk (input views) or tile (output views).  A unit of the direct layouts is `taps` rows of 512
+// four-byte slots, a Winograd unit one row of 4096.  The selection (gemm_image_of, fast_args) and the packer
+// (weight_image.hip) both size and walk the image by this.
+struct ImageLayout {
+  int kind;                 // kKind*
+  int log2_kc, log2_ncol;   // channels per K chunk, columns per tile (powers of two: the packer decodes by shifts)
+  int row_slots, unit_rows; // four-byte slots of an image row, rows of a (tile, chunk)
+  __host__ __device__ int kc() const { return 1 << log2_kc; }
+  __host__ __device__ int ncol() const { return 1 << log2_ncol; }
+  __host__ __device__ int chunks(int c_len) const { return (c_len + kc() - 1) >> log2_kc; }
+  __host__ __device__ int tiles(int c_len) const { return (c_len + ncol() - 1) >> log2_ncol; }
+  __host__ __device__ long unit_floats() const { return static_cast<long>(unit_rows) * row_slots; }
+};
+__host__ __device__ inline ImageLayout image_layout(int taps, int flags) {
+  ImageLayout l;
+  l.log2_ncol = 5;
+  l.row_slots = 512;
+  l.unit_rows = taps;
+  if ((flags & UNETPP_GEMM_BF16) != 0) {
+    l.kind = kKindBf16;
+    l.log2_kc = 5;
+  } else if (taps == 9 && (flags & UNETPP_GEMM_DIRECT) == 0) {
+    l.kind = kKindWino;
+    l.log2_kc = 3;
+    l.row_slots = 4096;
+    l.unit_rows = 1;
+  } else {
+    l.kind = kKindFast;
+    l.log2_kc = 4;
+  }
+  return l;
+}
 enum GemmKernel {
   GEMM_SMALL_CIN, GEMM_BF16_PW, GEMM_BF16_DMA8, GEMM_BF16_DMA4, GEMM_BF16, GEMM_PW, GEMM_WINO, GEMM_FAST, GEMM_GENERIC
 };
@@ -86,7 +120,7 @@ struct GemmSel {
   const char* label;   // what unetpp_last_kernel_name() reports after the launch
   int cus;             // the CU count the choice was made for
   // the weight image the descriptor's fast kernels read -- whether or not d->weight_image is set (gemm_image_of)
-  int image_kind, image_kc;  // kKind*, channels per K chunk; image_floats == 0: no image kernel applies
+  int image_kind;      // kKind* (image_layout); image_floats == 0: no image kernel applies
   long image_floats;
   FastArgs fa;         // the descriptor and its unit geometry, chunked and tiled for the chosen kernel
   unsigned grid_x, grid_y, threads;
@@ -97,9 +131,9 @@ struct GemmSel {
   int plain_out;                  // 4-wave LDS-DMA form: the three-per-CU pointwise instantiation
 };
 
-// Host side: validates a descriptor for the fast kernels and fills the unit geometry; kc = channels per K chunk,
-// ncol = columns per tile.
-inline bool fast_args(const unetpp_gemm_desc* d, FastArgs& a, int kc, int ncol = 32) {
+// Host side: validates a descriptor for the fast kernels and fills the unit geometry, chunked and tiled as its weight
+// image is (l = image_layout(d->taps, d->flags)).
+inline bool fast_args(const unetpp_gemm_desc* d, FastArgs& a, const ImageLayout& l) {
   if (d == nullptr || d->N <= 0 || d->H <= 0 || d->W <= 0) return false;
   if (d->taps != 9 && d->taps != 1) return false;
   if (d->n_in < 1 || d->n_in > UNETPP_MAX_VIEWS || d->n_out < 1 || d->n_out > UNETPP_MAX_VIEWS) return false;
@@ -115,13 +149,13 @@ inline bool fast_args(const unetpp_gemm_desc* d, FastArgs& a, int kc, int ncol =
     if (((v.C | v.c_off | v.c_len) & 3) != 0 || (reinterpret_cast<uintptr_t>(v.ptr) & 15) != 0) return false;
     if (static_cast<long>(d->N) * v.Hs * v.Ws * v.C >= 0x7fffffffL) return false;  // 32-bit element offsets
     a.Ktot += v.c_len;
-    a.n_chunks += (v.c_len + kc - 1) / kc;
+    a.n_chunks += l.chunks(v.c_len);
   }
   for (int i = 0; i < d->n_out; ++i) {
     if (!view_ok(d->out[i]) || !view_covers(d->out[i], d->H, d->W)) return false;
     if (static_cast<long>(d->N) * d->out[i].Hs * d->out[i].Ws * d->out[i].C >= 0x7fffffffL) return false;
     a.Ncols += d->out[i].c_len;
-    a.n_tiles += (d->out[i].c_len + ncol - 1) / ncol;
+    a.n_tiles += l.tiles(d->out[i].c_len);
   }
   const TileGeom g = tile_geom(d->H, d->W);
   a.log2tw = g.log2tw;

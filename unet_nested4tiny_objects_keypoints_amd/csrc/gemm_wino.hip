@@ -809,7 +809,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_wino_kernel(const FastArgs a
 }  // namespace
 
 bool wino_applies(const unetpp_gemm_desc* d) {
-  return d != nullptr && d->taps == 9 && (d->flags & (UNETPP_GEMM_DIRECT | UNETPP_GEMM_BF16)) == 0;
+  return d != nullptr && image_layout(d->taps, d->flags).kind == kKindWino;
 }
 
 // takes every descriptor with a Winograd image (gemm_image_of: s.fa is fast_args with 8-channel chunks)

@@ -8,8 +8,10 @@
 // tap' = flip ? taps - 1 - tap : tap, which covers the packed [taps][K][N] operand as well as nn.Conv2d
 // ([co,ci,3,3]: forward and 180-degree-rotated input-gradient form) and nn.ConvTranspose2d ([ci,co,2,2]: forward
 // with N = 4 phases x co, input gradient with K = 4 phases x co) parameters -- no intermediate re-layout launch.
-// unetpp_gemm_pack_weight_images builds the images of many launches (a whole forward or backward pass) in ONE launch
-// from a table of jobs in device memory.
+// There is ONE packer body (pack_image): it derives the layout from a job's taps and flags by the rule the selection uses
+// (image_layout, gemm_units.h) and walks whole image rows.  unetpp_gemm_pack_weight_images runs it over a table of jobs in
+// device memory -- the images of many launches (a whole forward or backward pass) in ONE launch;
+// unetpp_gemm_pack_weight_image[_from] runs it on one job passed by value as the kernel argument.
 #include "bf16_common.h"
 #include "common.h"
 #include "gemm_units.h"
@@ -19,23 +21,14 @@ namespace {
 
 // image kinds (gemm_units.h): kKindFast, kKindWino, kKindBf16 = gemm_bf16.hip, [tap][g 2][col 32][h 2][8 bf16], 32-channel chunks
 
-struct PackGeom {  // what the image layout depends on: the channel structure of the launch
-  int kind, taps, kc, ncol;  // kc = channels per K chunk, ncol = columns per tile
+struct PackGeom {  // a job's layout and channel structure, decoded once per workgroup
+  ImageLayout l;
+  int taps;
   int n_in, n_out;
   int in_len[UNETPP_MAX_VIEWS], out_len[UNETPP_MAX_VIEWS];
   int n_chunks, n_tiles;
-  long floats;
+  int rows;  // image rows of l.row_slots slots each (< 2^31: an image of 2^31 rows would be 4 TB)
 };
-
-__host__ __device__ inline long image_floats_per_tile_chunk(int kind, int taps) { return kind == kKindWino ? 4096 : taps * 512L; }
-
-__host__ __device__ inline void finish_geom(PackGeom& g) {
-  g.n_chunks = 0;
-  g.n_tiles = 0;
-  for (int i = 0; i < g.n_in; ++i) g.n_chunks += (g.in_len[i] + g.kc - 1) / g.kc;
-  for (int i = 0; i < g.n_out; ++i) g.n_tiles += (g.out_len[i] + g.ncol - 1) / g.ncol;
-  g.floats = static_cast<long>(g.n_tiles) * g.n_chunks * image_floats_per_tile_chunk(g.kind, g.taps);
-}
 
 __device__ __forceinline__ float wsrc_at(const unetpp_weight_src& w, int taps, int tap, int k, int n) {
   const int tt = w.flip ? taps - 1 - tap : tap;
@@ -52,37 +45,37 @@ struct RowOrigin {
 __device__ __forceinline__ RowOrigin row_origin(const PackGeom& g, int nt, int chunk) {
   int kbase = 0, v = 0;
   for (; v < g.n_in - 1; ++v) {
-    const int ch = (g.in_len[v] + g.kc - 1) / g.kc;
+    const int ch = g.l.chunks(g.in_len[v]);
     if (chunk < ch) break;
     chunk -= ch;
     kbase += g.in_len[v];
   }
   int col_base = 0, ov = 0;
   for (; ov < g.n_out - 1; ++ov) {
-    const int tv = (g.out_len[ov] + g.ncol - 1) / g.ncol;
+    const int tv = g.l.tiles(g.out_len[ov]);
     if (nt < tv) break;
     nt -= tv;
     col_base += g.out_len[ov];
   }
   RowOrigin o;
-  o.k0 = kbase + chunk * g.kc;
-  o.k_room = g.in_len[v] - chunk * g.kc;
-  o.n0 = col_base + nt * g.ncol;
-  o.n_room = g.out_len[ov] - nt * g.ncol;
+  o.k0 = kbase + (chunk << g.l.log2_kc);
+  o.k_room = g.in_len[v] - (chunk << g.l.log2_kc);
+  o.n0 = col_base + (nt << g.l.log2_ncol);
+  o.n_room = g.out_len[ov] - (nt << g.l.log2_ncol);
   return o;
 }
 
-// The batched pack kernel walks whole image rows: row = (tile, chunk[, tap]) is decoded once per workgroup iteration
+// The packer walks whole image rows: row = (tile, chunk[, tap]) is decoded once per workgroup iteration
 // (uniform: scalar unit), a thread only splits its slot's bit fields.  (Decoding per element cost ~80 instructions
 // per 4 bytes written: 175 us per launch for the 73 MB of bf16 images of the depth-5 network.)
-__device__ __forceinline__ void fill_image_row(const PackGeom& g, const unetpp_weight_src& w, long row, float* __restrict__ img) {
+__device__ __forceinline__ void fill_image_row(const PackGeom& g, const unetpp_weight_src& w, int row, float* __restrict__ img) {
   const int tid = threadIdx.x;
-  if (g.kind == kKindWino) {  // row = (tile, chunk): 256 (channel, column) pairs x 16 transform elements
-    const RowOrigin o = row_origin(g, static_cast<int>(row / g.n_chunks), static_cast<int>(row % g.n_chunks));
+  if (g.l.kind == kKindWino) {  // row = (tile, chunk): 256 (channel, column) pairs x 16 transform elements
+    const RowOrigin o = row_origin(g, row / g.n_chunks, row % g.n_chunks);
     const int t = tid;  // nh | col << 1 | gq << 5 | s << 7
     const int kk = 2 * ((t >> 5) & 3) + ((t >> 7) & 1), cl = 16 * (t & 1) + ((t >> 1) & 15);
     // slot of (xi, lane = gq | col, nh): nh | (xi & 1) << 1 | lane << 2 | (xi >> 1) << 8 | s << 11
-    float* dst = img + row * 4096 + (t & 1) + (((t >> 1) & 63) << 2) + (static_cast<long>(t >> 7) << 11);
+    float* dst = img + row * 4096L + (t & 1) + (((t >> 1) & 63) << 2) + (static_cast<long>(t >> 7) << 11);
     auto slot = [](int xi) { return ((xi & 1) << 1) + ((xi >> 1) << 8); };
     if (kk >= o.k_room || cl >= o.n_room) {
 #pragma unroll
@@ -109,14 +102,13 @@ __device__ __forceinline__ void fill_image_row(const PackGeom& g, const unetpp_w
     return;
   }
   // direct kernels: row = (tile, chunk, tap), 512 four-byte slots
-  const int tap = static_cast<int>(row % g.taps);
-  const long rc = row / g.taps;
-  const RowOrigin o = row_origin(g, static_cast<int>(rc / g.n_chunks), static_cast<int>(rc % g.n_chunks));
-  float* dst = img + row * 512;
+  const int tap = row % g.taps, rc = row / g.taps;
+  const RowOrigin o = row_origin(g, rc / g.n_chunks, rc % g.n_chunks);
+  float* dst = img + row * 512L;
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
     const int e = tid + q * 256;
-    if (g.kind == kKindBf16) {  // slot = two bf16: elements 2e, 2e+1 of [g 2][col 32][h 2][8]
+    if (g.l.kind == kKindBf16) {  // slot = two bf16: elements 2e, 2e+1 of [g 2][col 32][h 2][8]
       const int i0 = 2 * e;
       const int kk = 16 * ((i0 >> 9) & 1) + 8 * ((i0 >> 3) & 1) + (i0 & 7), cl = (i0 >> 4) & 31;
       float a = 0.f, b = 0.f;
@@ -137,10 +129,10 @@ __device__ __forceinline__ void fill_image_row(const PackGeom& g, const unetpp_w
 // order it lies in memory (the taps of a (channel, column) pair are adjacent, then whichever of channel / column has
 // the smaller stride) -- fill_image_row reads it as 4-byte pieces 36 bytes apart, nine times over (once per tap) --
 // and leaves as 16-byte stores.
-__device__ __forceinline__ void fill_bf16_3x3_block(const PackGeom& g, const unetpp_weight_src& w, long rc,
+__device__ __forceinline__ void fill_bf16_3x3_block(const PackGeom& g, const unetpp_weight_src& w, int rc,
                                                      float* __restrict__ img, float* lds /* [9][32][33] */) {
   const int tid = threadIdx.x;
-  const RowOrigin o = row_origin(g, static_cast<int>(rc / g.n_chunks), static_cast<int>(rc % g.n_chunks));
+  const RowOrigin o = row_origin(g, rc / g.n_chunks, rc % g.n_chunks);
   const bool k_inner_most = w.s_k < w.s_n;  // forward layout [co][ci][3][3]: channel k = ci runs faster than column n = co
   __syncthreads();  // the previous block's readers are done
   // 16-byte reads where the nine taps of 32 consecutive inner indices form one aligned 1152-byte run (plain conv
@@ -174,7 +166,7 @@ __device__ __forceinline__ void fill_bf16_3x3_block(const PackGeom& g, const une
   }
   __syncthreads();
   // one 16-byte store per thread and round: four slots = the eight channels 16 gq + 8 hs .. + 7 of one column
-  f32x4* dst4 = reinterpret_cast<f32x4*>(img + rc * 9 * 512);
+  f32x4* dst4 = reinterpret_cast<f32x4*>(img + rc * (9 * 512L));
 #pragma unroll 3
   for (int s4 = tid; s4 < 9 * 128; s4 += 256) {
     const int tap = s4 >> 7, e4 = s4 & 127;  // slots 4 e4 .. 4 e4 + 3 of the tap's row
@@ -187,122 +179,42 @@ __device__ __forceinline__ void fill_bf16_3x3_block(const PackGeom& g, const une
   }
 }
 
-// value of image element i
-__device__ __forceinline__ float image_element(const PackGeom& g, const unetpp_weight_src& w, long i) {
-  int kk, cin_local, tap = 0, xi = 0;
-  long r;
-  if (g.kind == kKindWino) {  // [s 2][xi / 2 8][g 4][col 16][xi % 2 2][nh 2]
-    const int nh = i & 1, col = (i >> 2) & 15, gq = (i >> 6) & 3, s = (i >> 11) & 1;
-    xi = (((i >> 8) & 7) << 1) | ((i >> 1) & 1);
-    kk = 2 * gq + s;
-    cin_local = 16 * nh + col;
-    r = i >> 12;
-  } else if (g.kind == kKindBf16) {  // i counts bf16 elements: [tap][g 2][col 32][h 2][8]
-    const int e = i & 7, hs = (i >> 3) & 1, j = (i >> 4) & 31, gq = (i >> 9) & 1;
-    r = i >> 10;
-    tap = static_cast<int>(r % g.taps);
-    r /= g.taps;
-    kk = 16 * gq + 8 * hs + e;
-    cin_local = j;
-  } else {  // [tap][g 2][col 32][half' 2][4], half' = half ^ ((col>>3)&1)
-    const int e = i & 3, hs = (i >> 2) & 1, j = (i >> 3) & 31, gq = (i >> 8) & 1;
-    r = i >> 9;
-    tap = static_cast<int>(r % g.taps);
-    r /= g.taps;
-    kk = 8 * gq + 4 * (hs ^ ((j >> 3) & 1)) + e;
-    cin_local = j;
-  }
-  int chunk = static_cast<int>(r % g.n_chunks);
-  int nt = static_cast<int>(r / g.n_chunks);
-  int kbase = 0, v = 0;
-  for (; v < g.n_in - 1; ++v) {
-    const int ch = (g.in_len[v] + g.kc - 1) / g.kc;
-    if (chunk < ch) break;
-    chunk -= ch;
-    kbase += g.in_len[v];
-  }
-  const int kin = chunk * g.kc + kk;
-  int col_base = 0, ov = 0;
-  for (; ov < g.n_out - 1; ++ov) {
-    const int tv = (g.out_len[ov] + g.ncol - 1) / g.ncol;
-    if (nt < tv) break;
-    nt -= tv;
-    col_base += g.out_len[ov];
-  }
-  const int cin = nt * g.ncol + cin_local;
-  if (kin >= g.in_len[v] || cin >= g.out_len[ov]) return 0.f;
-  const int k = kbase + kin, n = col_base + cin;
-  if (g.kind != kKindWino) return wsrc_at(w, g.taps, tap, k, n);
-  // U = G g G^T: row ra of G down the filter rows, then row rb of G along the filter columns
-  const int ra = xi >> 2, rb = xi & 3;
-  float t[3];
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const float w0 = wsrc_at(w, 9, 0 * 3 + c, k, n), w1 = wsrc_at(w, 9, 1 * 3 + c, k, n), w2 = wsrc_at(w, 9, 2 * 3 + c, k, n);
-    t[c] = ra == 0 ? w0 : (ra == 1 ? 0.5f * (w0 + w1 + w2) : (ra == 2 ? 0.5f * (w0 - w1 + w2) : w2));
-  }
-  return rb == 0 ? t[0] : (rb == 1 ? 0.5f * (t[0] + t[1] + t[2]) : (rb == 2 ? 0.5f * (t[0] - t[1] + t[2]) : t[2]));
-}
-
-// slot i of the image: one float, or two bf16 (elements 2i, 2i+1) in the same 4 bytes
-__device__ __forceinline__ float image_slot(const PackGeom& g, const unetpp_weight_src& w, long i) {
-  if (g.kind != kKindBf16) return image_element(g, w, i);
-  return __uint_as_float(pack_bf2(image_element(g, w, 2 * i), image_element(g, w, 2 * i + 1)));
-}
-
-__global__ void pack_image_one_kernel(const PackGeom g, const unetpp_weight_src w, float* __restrict__ img) {
-  const long i = blockIdx.x * static_cast<long>(blockDim.x) + threadIdx.x;
-  if (i < g.floats) img[i] = image_slot(g, w, i);
-}
-
-// blockIdx.y = job; every job derives its geometry from its own channel lists
-__global__ void pack_image_jobs_kernel(const unetpp_pack_job* __restrict__ jobs) {
-  const unetpp_pack_job& j = jobs[blockIdx.y];
+// One job: the geometry follows from its taps, flags and channel lists alone; the workgroups of gridDim.x share its rows.
+__device__ __forceinline__ void pack_image(const unetpp_pack_job& j) {
   __shared__ PackGeom g;
   if (threadIdx.x == 0) {
-    const bool bf = (j.flags & UNETPP_GEMM_BF16) != 0;
-    const bool wino = !bf && j.taps == 9 && (j.flags & UNETPP_GEMM_DIRECT) == 0;
-    g.kind = bf ? kKindBf16 : (wino ? kKindWino : kKindFast);
+    g.l = image_layout(j.taps, j.flags);
     g.taps = j.taps;
-    g.kc = bf ? 32 : (wino ? 8 : 16);
-    g.ncol = 32;
     g.n_in = j.n_in;
     g.n_out = j.n_out;
+    int n_chunks = 0, n_tiles = 0;
     for (int i = 0; i < UNETPP_MAX_VIEWS; ++i) {
       g.in_len[i] = j.in_len[i];
       g.out_len[i] = j.out_len[i];
+      if (i < j.n_in) n_chunks += g.l.chunks(j.in_len[i]);
+      if (i < j.n_out) n_tiles += g.l.tiles(j.out_len[i]);
     }
-    finish_geom(g);
+    g.n_chunks = n_chunks;
+    g.n_tiles = n_tiles;
+    g.rows = n_tiles * n_chunks * g.l.unit_rows;
   }
   __syncthreads();
-  if (g.kind == kKindBf16 && g.taps == 9) {
+  const int rows = g.rows;
+  if (g.l.kind == kKindBf16 && g.taps == 9) {
     __shared__ float stage[9 * 32 * 33];
-    const long blocks = g.floats / (9 * 512);
-    for (long rc = blockIdx.x; rc < blocks; rc += gridDim.x) fill_bf16_3x3_block(g, j.src, rc, j.image, stage);
+    for (int rc = blockIdx.x; rc < rows / 9; rc += gridDim.x) fill_bf16_3x3_block(g, j.src, rc, j.image, stage);
     return;
   }
-  const long rows = g.floats / (g.kind == kKindWino ? 4096 : 512);
-  for (long row = blockIdx.x; row < rows; row += gridDim.x) fill_image_row(g, j.src, row, j.image);
+  for (int row = blockIdx.x; row < rows; row += gridDim.x) fill_image_row(g, j.src, row, j.image);
 }
 
-// the layout is the selection's (gemm_image_of): kind, chunk width, chunk and tile counts, size
-bool geom_of(const unetpp_gemm_desc* d, PackGeom& g) {
-  GemmSel s;
-  if (!gemm_image_of(d, s)) return false;
-  g.kind = s.image_kind;
-  g.taps = d->taps;
-  g.kc = s.image_kc;
-  g.ncol = 32;
-  g.n_in = d->n_in;
-  g.n_out = d->n_out;
-  for (int i = 0; i < UNETPP_MAX_VIEWS; ++i) {
-    g.in_len[i] = i < d->n_in ? d->in[i].c_len : 0;
-    g.out_len[i] = i < d->n_out ? d->out[i].c_len : 0;
-  }
-  g.n_chunks = s.fa.n_chunks;
-  g.n_tiles = s.fa.n_tiles;
-  g.floats = s.image_floats;
-  return true;
+__global__ void pack_image_jobs_kernel(const unetpp_pack_job* __restrict__ jobs) { pack_image(jobs[blockIdx.y]); }  // blockIdx.y = job
+__global__ void pack_image_job_kernel(const unetpp_pack_job j) { pack_image(j); }
+
+// workgroups per job: ~8 slots per thread for an image of this size, 256 at most
+unsigned pack_grid_x(long image_floats) {
+  const long bx = (image_floats + 256L * 8 - 1) / (256L * 8);
+  return static_cast<unsigned>(bx > 256 ? 256 : bx);
 }
 
 }  // namespace
@@ -311,16 +223,24 @@ bool geom_of(const unetpp_gemm_desc* d, PackGeom& g) {
 using namespace unetpp;
 
 extern "C" int64_t unetpp_gemm_weight_image_floats(const unetpp_gemm_desc* d) {
-  PackGeom g;
-  return geom_of(d, g) ? g.floats : 0;
+  GemmSel s;
+  return gemm_image_of(d, s) ? s.image_floats : 0;
 }
 
 extern "C" int unetpp_gemm_pack_weight_image_from(const unetpp_gemm_desc* d, const unetpp_weight_src* src, float* image,
                                                   void* stream) {
-  PackGeom g;
-  if (src == nullptr || src->src == nullptr || image == nullptr || !geom_of(d, g)) return UNETPP_EINVAL;
-  hipLaunchKernelGGL(pack_image_one_kernel, dim3(static_cast<unsigned>((g.floats + 255) / 256)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), g, *src, image);
+  GemmSel s;
+  if (src == nullptr || src->src == nullptr || image == nullptr || !gemm_image_of(d, s)) return UNETPP_EINVAL;
+  unetpp_pack_job j = {};  // what PackPlan records for this launch
+  j.src = *src;
+  j.image = image;
+  j.taps = d->taps;
+  j.flags = d->flags;
+  j.n_in = d->n_in;
+  j.n_out = d->n_out;
+  for (int i = 0; i < d->n_in; ++i) j.in_len[i] = d->in[i].c_len;
+  for (int i = 0; i < d->n_out; ++i) j.out_len[i] = d->out[i].c_len;
+  hipLaunchKernelGGL(pack_image_job_kernel, dim3(pack_grid_x(s.image_floats)), dim3(256), 0, static_cast<hipStream_t>(stream), j);
   return launch_status();
 }
 
@@ -340,9 +260,7 @@ extern "C" int unetpp_gemm_pack_weight_image(const unetpp_gemm_desc* d, float* i
 extern "C" int unetpp_gemm_pack_weight_images(const unetpp_pack_job* jobs_device, int32_t n_jobs, int64_t max_image_floats,
                                               void* stream) {
   if (jobs_device == nullptr || n_jobs < 1 || n_jobs > 65535 || max_image_floats < 1) return UNETPP_EINVAL;
-  long bx = (max_image_floats + 256L * 8 - 1) / (256L * 8);  // ~8 elements per thread for the largest image
-  if (bx > 256) bx = 256;
-  hipLaunchKernelGGL(pack_image_jobs_kernel, dim3(static_cast<unsigned>(bx), static_cast<unsigned>(n_jobs)), dim3(256), 0,
+  hipLaunchKernelGGL(pack_image_jobs_kernel, dim3(pack_grid_x(max_image_floats), static_cast<unsigned>(n_jobs)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), jobs_device);
   return launch_status();
 }

@@ -226,18 +226,18 @@ class PackPlan:
     calls from ``load_state_dict``, ``_apply`` (.to()/.float()/.cuda()) and ``train()``.  Entries keep their source
     tensor alive and are dropped when unused for a few passes."""
 
-    class _Entry:
-        __slots__ = ("image", "n_img", "job", "src", "phase", "fresh", "used")
+    class _Entry:  # one weight image; like _Copy: jobs, size (of the largest job: sizes the grid) and device feed _run_jobs
+        __slots__ = ("image", "n_img", "jobs", "size", "device", "src", "phase", "fresh", "used")
 
     class _Copy:  # a group of strided copies into one destination buffer (unetpp_copy_jobs), redone with the images
-        __slots__ = ("dst", "jobs", "srcs", "srcsig", "phase", "fresh", "used", "elems")
+        __slots__ = ("dst", "jobs", "size", "device", "srcs", "srcsig", "phase", "fresh", "used")
 
     def __init__(self):
         self.entries = {}
         self.copies = {}     # key -> _Copy
-        self._copy_tables = {}  # phase -> (device table, keys, max elements)
+        self._copy_tables = {}  # phase -> (keys, device table, jobs, max elements)
         self.copy_launches = 0  # batched copy launches issued (tests)
-        self._tables = {}    # phase -> (device table, host array, signatures, max floats)
+        self._tables = {}    # phase -> (signatures, device table, jobs, max floats)
         self._packed = set()  # phases whose images are current (only consulted while frozen)
         self.frozen = False
         self.phase = None
@@ -270,58 +270,44 @@ class PackPlan:
         self.phase = phase
         self.pass_id += 1
         if not self.pinned:
-            # an evicted entry takes its phase's job table with it: the table's rows hold the address of the entry's
-            # image (of the copy's destination), and a pass that records the same launches again gets the same keys --
-            # a table kept by key alone would make the batched launch write into the freed buffers
-            stale = [k for k, e in self.entries.items() if self.pass_id - e.used > 16]
-            for k in stale:
-                self._tables.pop(self.entries[k].phase, None)
-                del self.entries[k]
-            for k in [k for k, c in self.copies.items() if self.pass_id - c.used > 16]:
-                self._copy_tables.pop(self.copies[k].phase, None)
-                del self.copies[k]
-        self._begin_copies(phase)   # (first: weight images of this pass may be packed FROM a copied buffer)
-        sigs = tuple(k for k, e in self.entries.items() if e.phase == phase)
-        if not sigs:
-            return
-        ents = [self.entries[k] for k in sigs]
-        tab = self._tables.get(phase)
-        if tab is None or tab[2] != sigs:
-            arr = (PackJob * len(ents))(*[e.job for e in ents])
-            dev = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(ents[0].image.device)
-            if self.pinned and phase in self._tables:
-                self._retired.append(self._tables[phase])
-            tab = (dev, arr, sigs, max(e.n_img for e in ents))
-            self._tables[phase] = tab
-            self._packed.discard(phase)
-        if not (self.frozen and phase in self._packed):
-            check(_lib.lib().unetpp_gemm_pack_weight_images(_ptr(tab[0]), len(ents), tab[3], _stream()),
-                  "unetpp_gemm_pack_weight_images")
+            self._evict(self.entries, self._tables)
+            self._evict(self.copies, self._copy_tables)
+        # (copies first: weight images of this pass may be packed FROM a copied buffer)
+        self.copy_launches += self._run_jobs(phase, self.copies, self._copy_tables, _lib.CopyJob, "unetpp_copy_jobs")
+        if self._run_jobs(phase, self.entries, self._tables, PackJob, "unetpp_gemm_pack_weight_images"):
             self.launches += 1
             self._packed.add(phase)
-        for e in ents:
-            e.fresh = self.pass_id
 
-    def _begin_copies(self, phase: str) -> None:
-        keys = tuple(k for k, c in self.copies.items() if c.phase == phase)
+    def _evict(self, items, tables) -> None:
+        """Drop what no pass used for 16 passes.  An evicted record takes its phase's job table with it: the table's rows
+        hold the address of the entry's image (of the copy's destination), and a pass that records the same launches again
+        gets the same keys -- a table kept by key alone would make the batched launch write into the freed buffers."""
+        for k in [k for k, x in items.items() if self.pass_id - x.used > 16]:
+            tables.pop(items[k].phase, None)
+            del items[k]
+
+    def _run_jobs(self, phase: str, items, tables, job_type, entry_point: str) -> bool:
+        """ONE launch of `entry_point` (job table in device memory, jobs, size of the largest) for all that `items` holds
+        under `phase`; -> launched.  The table is rebuilt when the phase's keys changed (the replaced one is kept while
+        pinned); while frozen, a phase whose images are current launches nothing."""
+        keys = tuple(k for k, x in items.items() if x.phase == phase)
         if not keys:
-            return
-        cps = [self.copies[k] for k in keys]
-        tab = self._copy_tables.get(phase)
-        if tab is None or tab[1] != keys:
-            jobs = [j for c in cps for j in c.jobs]
-            arr = (_lib.CopyJob * len(jobs))(*jobs)
-            dev = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(cps[0].dst.device)
-            if self.pinned and phase in self._copy_tables:
-                self._retired.append(self._copy_tables[phase])
-            tab = (dev, keys, max(c.elems for c in cps), len(jobs))
-            self._copy_tables[phase] = tab
+            return False
+        recs = [items[k] for k in keys]
+        tab = tables.get(phase)
+        if tab is None or tab[0] != keys:
+            if self.pinned and tab is not None:
+                self._retired.append(tab)
+            jobs = [j for x in recs for j in x.jobs]
+            dev = torch.frombuffer(bytearray(bytes((job_type * len(jobs))(*jobs))), dtype=torch.uint8).to(recs[0].device)
+            tab = tables[phase] = (keys, dev, len(jobs), max(x.size for x in recs))
             self._packed.discard(phase)
-        if not (self.frozen and phase in self._packed):
-            check(_lib.lib().unetpp_copy_jobs(_ptr(tab[0]), tab[3], tab[2], _stream()), "unetpp_copy_jobs")
-            self.copy_launches += 1
-        for c in cps:
-            c.fresh = self.pass_id
+        launched = not (self.frozen and phase in self._packed)
+        if launched:
+            check(getattr(_lib.lib(), entry_point)(_ptr(tab[1]), tab[2], tab[3], _stream()), entry_point)
+        for x in recs:
+            x.fresh = self.pass_id
+        return launched
 
     def copy_for(self, key, phase: str, srcsig, make):
         """A destination buffer filled by strided copies that ``begin(phase)`` redoes in ONE launch from the second pass on.
@@ -333,8 +319,8 @@ class PackPlan:
         if c is None or c.srcsig != srcsig or c.phase != phase:
             dst, srcs, items = make()
             c = PackPlan._Copy()
-            c.dst, c.srcs, c.srcsig, c.phase, c.fresh = dst, srcs, srcsig, phase, -1
-            c.jobs, c.elems = [], 1
+            c.dst, c.device, c.srcs, c.srcsig, c.phase, c.fresh = dst, dst.device, srcs, srcsig, phase, -1
+            c.jobs, c.size = [], 1
             for (src, s_off, d_off, n_outer, n_inner, s_stride, d_stride) in items:
                 j = _lib.CopyJob()
                 j.src, j.dst = src.data_ptr() + 4 * s_off, dst.data_ptr() + 4 * d_off
@@ -342,7 +328,7 @@ class PackPlan:
                 if n_outer * n_inner >= 2 ** 31:
                     raise ValueError("copy job too large")
                 c.jobs.append(j)
-                c.elems = max(c.elems, n_outer * n_inner)
+                c.size = max(c.size, n_outer * n_inner)
             self.copies[key] = c
             old_tab = self._copy_tables.pop(phase, None)   # same keys, other jobs: the table is rebuilt by the next begin()
             if old_tab is not None and self.pinned:
@@ -361,7 +347,7 @@ class PackPlan:
         if e is None:
             e = PackPlan._Entry()
             e.image = torch.empty(n_img, dtype=torch.float32, device=weight.device)
-            e.n_img, e.src, e.phase, e.fresh = n_img, weight.t, self.phase, -1
+            e.n_img, e.size, e.device, e.src, e.phase, e.fresh = n_img, n_img, weight.device, weight.t, self.phase, -1
             job = PackJob()
             weight.fill(job.src)
             job.image = e.image.data_ptr()
@@ -370,7 +356,7 @@ class PackPlan:
                 job.in_len[i] = d.inp[i].c_len
             for i in range(d.n_out):
                 job.out_len[i] = d.out[i].c_len
-            e.job = job
+            e.jobs = [job]
             self.entries[sig] = e
         e.used = self.pass_id
         return e.image, e.fresh == self.pass_id
