@@ -18,7 +18,7 @@ INCLUDE = os.path.join(_REPO, "include")
 SOURCES = ("gemm_pix.hip", "gemm_fast.hip", "gemm_pw.hip", "gemm_pw_bf16.hip", "gemm_wino.hip", "gemm_bf16.hip", "gemm_bf16_dma.hip", "wgrad_bf16.hip", "pointwise_bf16.hip", "keypoints.hip", "weight_image.hip", "wgrad.hip", "wgrad_fast.hip", "wgrad_dma.hip", "wgrad_pw.hip", "wgrad_wino.hip", "first_layer.hip", "pointwise.hip", "heads.hip", "caller.hip", "optim.hip", "validate.hip", "average.hip", "loader.hip", "scene.hip",
            "detect.hip", "crops.hip", "topk_loss.hip", "pr_focal.hip", "paste.hip", "distill.hip", "mask.hip")
 HEADERS = ("common.h", "gemm_units.h", "wgrad_reduce.h", "lds_asm.h", "bf16_common.h", "dropout.h", "bn_fused.h",
-           "wino_experiments.h", "dma_experiments.h", "heads_mean.h", "head_select.h", "stream_select.h", "head_mc_select.h", "focal_element.h", "multi_tensor.h", "loss_heads.h")
+           "wino_experiments.h", "dma_experiments.h", "heads_mean.h", "head_select.h", "stream_select.h", "head_mc_select.h", "focal_element.h", "multi_tensor.h", "loss_heads.h", "window.h")
 MAX_VIEWS = 8
 ABI_VERSION = 14
 # packed-f32 VALU (SLP-vectorised add pairs) costs issue slots beside MFMAs: keep the Winograd transforms scalar

@@ -1,12 +1,13 @@
 // Training on large scenes: where the windows of a batch are (crops_draw_kernel), the target maps of those windows
 // from the frames' variable-length label lists (points_target_kernel) and their ignored elements
-// (target_ignore_kernel).  The warp between the draw and the targets is loader.hip's.
+// (target_ignore_kernel).  The warp between the draw and the targets is loader.hip's.  What these kernels share with
+// loader.hip, paste.hip and mask.hip -- the parameter row and its draw, the two window maps, the label rule, the
+// nearest-label value -- is window.h's; the tile decode is typed out in each tile kernel (DESIGN.md 5g says why).
 //
-// points_target_kernel: out[n, c, y, x] = float32(exp(-0.5 * sqrt(m) / radius)), m = the least dx*dx + dy*dy (float64, the
-// expression of the two heat-map kernels) over the valid labels of class c of frame index[n], each at its position under
-// the sample's forward map (float32, the warp's own expression, so it is the labels_out the warp reports); exactly 0
-// where the class has no valid label.  The maximum of exp(-k d) over points is exp(-k d_min): an exact nearest-label
-// search with one sqrt and one exp per pixel, no cutoff radius and no normalisation pass.
+// points_target_kernel: out[n, c, y, x] = nearest_value(m), m = the least dx*dx + dy*dy (float64) over the valid labels
+// of class c of frame index[n], each at its position under map_forward (so it is the labels_out the warp reports);
+// exactly 0 where the class has no valid label.  The maximum of exp(-k d) over points is exp(-k d_min): an exact
+// nearest-label search with one sqrt and one exp per pixel, no cutoff radius and no normalisation pass.
 //
 // A workgroup of 256 threads owns a 64 x 16 pixel tile (one thread: 4 consecutive x of one row) and kClasses classes of
 // it -- all of them for C <= 4, so the label list is read by one workgroup per tile; a wider C takes ceil(C / 4) class
@@ -27,22 +28,17 @@
 // target_ignore_kernel: writes -1.0f into the elements of such a target whose source position lies in an ignore
 // rectangle of the frame or outside the frame; stores only, described at the kernel.
 //
-// crops_draw_kernel: one thread per sample, the uniforms and the transform of loader.hip's draw_kernel; uniforms 9..12
-// choose between an object window (a row of the centre table plus jitter) and a uniform one.
-#include "common.h"
-#include "dropout.h"
+// crops_draw_kernel: one thread per sample; uniforms 9..12 choose between an object window (a row of the centre table
+// plus jitter) and a uniform one, and augment_row writes the row about that window's centre.
+#include "window.h"
 
 #pragma clang fp contract(off)
 
 namespace unetpp {
 namespace {
 
-constexpr int kThreads256 = 256;
-constexpr int kMaxSide = 1 << 24;   // pixel indices are exact in fp32 up to here
-constexpr int kTileW = 64, kTileH = 16;   // 16 quads x 16 rows = 256 threads
 constexpr int kClasses = 4;         // classes a workgroup serves at once
 constexpr int kCand = 256;          // candidates per class held in LDS: what one chunk of labels can add
-constexpr int kMaxClasses = 65535;
 
 __device__ __forceinline__ double wave_min(double v) {
 #pragma unroll
@@ -53,13 +49,12 @@ __device__ __forceinline__ double wave_min(double v) {
   return v;
 }
 
-// one label of the frame under the sample's forward map; false: not a label (sentinel)
+// label l of the frame under the sample's forward map (P: its parameter row); false: not a label (sentinel)
 __device__ __forceinline__ bool label_at(const float* __restrict__ lab, const float* __restrict__ P, int64_t l,
                                          float& xo, float& yo) {
   const float x = lab[2 * l], y = lab[2 * l + 1];
-  xo = (P[0] * x + P[1] * y) + P[2];
-  yo = (P[3] * x + P[4] * y) + P[5];
-  return !(x < 0.f) && !(y < 0.f);
+  map_forward(P, x, y, xo, yo);
+  return label_valid(x, y);
 }
 
 // least / greatest squared distance along one axis from position p to the pixel centres a..b (a <= b)
@@ -109,7 +104,7 @@ __global__ void __launch_bounds__(kThreads256) points_target_kernel(
     if (idx >= 0 && idx < M) {   // (uniform over the workgroup)
       const float* lab = labels + idx * L * 2;
       const int32_t* cls = label_class + idx * L;
-      const float* P = params + int64_t(n) * UNETPP_WARP_PARAMS + 6;
+      const float* P = params + int64_t(n) * UNETPP_WARP_PARAMS;
 
       // sweep 1: U[k] = min over the labels of class c0 + k of up_l
       double U[kClasses];
@@ -186,6 +181,8 @@ __global__ void __launch_bounds__(kThreads256) points_target_kernel(
           has[j] = has[j] || total > 0;
         }
         __syncthreads();   // (the wave counts are free for the next chunk)
+        // (the fold below and the store at the end are spelled out here and again in paste_target_kernel: behind a
+        // function this kernel takes 131 vector registers, past the 128 at which a SIMD holds one wave fewer)
         const double yd = static_cast<double>(py);
 #pragma unroll
         for (int j = 0; j < kClasses; ++j) {
@@ -210,8 +207,7 @@ __global__ void __launch_bounds__(kThreads256) points_target_kernel(
         if (c0 + k >= C) continue;
         f32x4 v;
 #pragma unroll
-        for (int p = 0; p < 4; ++p)
-          v[p] = has[k] ? static_cast<float>(exp(-0.5 * sqrt(m[k][p]) / radius)) : 0.f;
+        for (int p = 0; p < 4; ++p) v[p] = has[k] ? nearest_value(m[k][p], radius) : 0.f;
         float* dst = out + ((int64_t(n) * C + (c0 + k)) * Ho + py) * Wo + px;
         if (px + 3 <= x_hi && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
           *reinterpret_cast<f32x4*>(dst) = v;
@@ -228,14 +224,14 @@ __global__ void __launch_bounds__(kThreads256) points_target_kernel(
 
 // target_ignore_kernel: marks the ignored elements of a target that points_target_kernel (or anything else) wrote.
 // A unit is (sample, 64 x 16 tile), a thread 4 consecutive x of one row, all classes.  The source position of a window
-// pixel is the warp's own float32 expression (loader.hip) under the inverse map P = params[n]; the tests are plain
-// float32 comparisons, so a NaN position or a NaN / reversed rectangle (padding) is never inside a rectangle and always
+// pixel is window.h's map_inverse, the function the warp samples by; the frame test and the stores of -1 are this
+// kernel's own, as they are target_ignore_mask_kernel's in mask.hip.  The tests are plain float32
+// comparisons, so a NaN position or a NaN / reversed rectangle (padding) is never inside a rectangle and always
 // outside the frame.  The frame's R rectangles pass through LDS kRectChunk at a time; per pixel a thread keeps one bit
 // per class of the current group of 32 classes (one group for C <= 32) and one for "every class".  The kernel only
 // stores -1.0f where it ignores and reads nothing of target: idempotent stores of one constant, no atomics, the same
 // bits on any grid.
 constexpr int kRectChunk = 256;
-constexpr int kClassGroup = 32;
 
 __global__ void __launch_bounds__(kThreads256) target_ignore_kernel(
     const float* __restrict__ rects, const int32_t* __restrict__ rect_class, int64_t M, int R,
@@ -266,8 +262,9 @@ __global__ void __launch_bounds__(kThreads256) target_ignore_kernel(
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
       const float xf = static_cast<float>(px + p);
-      xs[p] = (P[0] * xf + P[1] * yf) + P[2];
-      ys[p] = (P[3] * xf + P[4] * yf) + P[5];
+      float x, y;
+      map_inverse(P, xf, yf, x, y);
+      xs[p] = x, ys[p] = y;
       const bool in = live && 0.f <= xs[p] && xs[p] <= x_max && 0.f <= ys[p] && ys[p] <= y_max;
       every |= (outside != 0 && !in) ? (1u << p) : 0u;
     }
@@ -323,17 +320,6 @@ __global__ void __launch_bounds__(kThreads256) target_ignore_kernel(
   }
 }
 
-__device__ __forceinline__ double uniform24(uint64_t seed, int n, int k) {
-  const uint64_t bits = mix64(seed + 0x9E3779B97F4A7C15ULL * (static_cast<uint64_t>(n) * 16 + k + 1));
-  return static_cast<double>(static_cast<float>(bits >> 40) * 0x1p-24f);   // 24 bits: exact in fp32
-}
-
-// floor(u * count) limited to count - 1, as a double
-__device__ __forceinline__ double pick(double u, int count) {
-  const double v = floor(u * static_cast<double>(count));
-  return v < static_cast<double>(count - 1) ? v : static_cast<double>(count - 1);
-}
-
 // window origin along one axis from its centre pixel: inside the frame, or a centred pad of a frame below the window
 __device__ __forceinline__ int window_origin(double centre, int src, int win) {
   if (src < win) return -((win - src) / 2);
@@ -347,19 +333,9 @@ __global__ void __launch_bounds__(kThreads256) crops_draw_kernel(
     float p_object, float jitter_x, float jitter_y, unetpp_augment a) {
   const int n = blockIdx.x * kThreads256 + threadIdx.x;
   if (n >= N) return;
-  const double dx = static_cast<float>(uniform24(seed, n, 0)) < a.p_flip_h ? -1.0 : 1.0;
-  const double dy = static_cast<float>(uniform24(seed, n, 1)) < a.p_flip_v ? -1.0 : 1.0;
-  const int q = a.rot90 != 0 ? static_cast<int>(4.0 * uniform24(seed, n, 2)) : 0;
-  const double theta = (2.0 * uniform24(seed, n, 3) - 1.0) * static_cast<double>(a.max_deg) * (M_PI / 180.0);
-  const double ln_lo = log(static_cast<double>(a.scale_lo)), ln_hi = log(static_cast<double>(a.scale_hi));
-  const double s = exp(ln_lo + uniform24(seed, n, 4) * (ln_hi - ln_lo));
-  const double lo = a.gain_lo, hi = a.gain_hi;
-  const double gain = lo + uniform24(seed, n, 7) * (hi - lo);
-  const double bias = (2.0 * uniform24(seed, n, 8) - 1.0) * static_cast<double>(a.max_bias);
-
   // which window: a row of the centre table with jitter, or any pixel of any frame
-  const bool object = V > 0 && static_cast<float>(uniform24(seed, n, 9)) < p_object;
-  const double u10 = uniform24(seed, n, 10), u11 = uniform24(seed, n, 11), u12 = uniform24(seed, n, 12);
+  const bool object = V > 0 && static_cast<float>(sample_uniform(seed, n, 9)) < p_object;
+  const double u10 = sample_uniform(seed, n, 10), u11 = sample_uniform(seed, n, 11), u12 = sample_uniform(seed, n, 12);
   int frame;
   double cx, cy;
   if (object) {
@@ -379,35 +355,10 @@ __global__ void __launch_bounds__(kThreads256) crops_draw_kernel(
   origin[2 * int64_t(n)] = ox;
   origin[2 * int64_t(n) + 1] = oy;
 
-  // R(theta) Q^q with Q^q as whole numbers: Q^q = [[qc, -qs], [qs, qc]], (qc, qs) = (1, 0), (0, 1), (-1, 0), (0, -1)
-  const double qc = q == 0 ? 1.0 : q == 2 ? -1.0 : 0.0;
-  const double qs = q == 1 ? 1.0 : q == 3 ? -1.0 : 0.0;
-  const double ct = cos(theta), st = sin(theta);
-  const double r00 = ct * qc - st * qs, r01 = -ct * qs - st * qc;   // R Q^q, again a rotation [[r00, r01], [-r01, r00]]
-  const double r10 = -r01, r11 = r00;
-  // forward A = s D (R Q^q); inverse B = (1/s) (R Q^q)^T D; both about the window's centre in the frame
-  const double a00 = s * dx * r00, a01 = s * dx * r01, a10 = s * dy * r10, a11 = s * dy * r11;
-  const double is = 1.0 / s;
-  const double b00 = is * r00 * dx, b01 = is * r10 * dy, b10 = is * r01 * dx, b11 = is * r11 * dy;
+  // the source centre: the window's centre in the frame
   const double cox = 0.5 * (Wo - 1), coy = 0.5 * (Ho - 1);
-  const double csx = static_cast<double>(ox) + cox, csy = static_cast<double>(oy) + coy;
-  float* P = params + int64_t(n) * UNETPP_WARP_PARAMS;
-  P[0] = static_cast<float>(b00);
-  P[1] = static_cast<float>(b01);
-  P[2] = static_cast<float>(csx - b00 * cox - b01 * coy);
-  P[3] = static_cast<float>(b10);
-  P[4] = static_cast<float>(b11);
-  P[5] = static_cast<float>(csy - b10 * cox - b11 * coy);
-  P[6] = static_cast<float>(a00);
-  P[7] = static_cast<float>(a01);
-  P[8] = static_cast<float>(cox - a00 * csx - a01 * csy);
-  P[9] = static_cast<float>(a10);
-  P[10] = static_cast<float>(a11);
-  P[11] = static_cast<float>(coy - a10 * csx - a11 * csy);
-  P[12] = static_cast<float>(gain);
-  P[13] = static_cast<float>(bias);
-  P[14] = 0.f;
-  P[15] = 0.f;
+  augment_row(params + int64_t(n) * UNETPP_WARP_PARAMS, seed, n, a, static_cast<double>(ox) + cox,
+              static_cast<double>(oy) + coy, cox, coy);
 }
 
 }  // namespace
@@ -426,12 +377,9 @@ extern "C" int unetpp_points_target(const float* labels, const int32_t* label_cl
   const int tiles_x = (Wo + kTileW - 1) / kTileW, tiles_y = (Ho + kTileH - 1) / kTileH;
   const int groups = (C + kClasses - 1) / kClasses;
   const int64_t units = int64_t(N) * groups * tiles_y * tiles_x;
-  const int cus = device_cu_count();
-  const int64_t cap = int64_t(cus > 0 ? cus : 256) * 8;   // the rest of the units are grid-strided
-  const unsigned grid = static_cast<unsigned>(units < cap ? units : cap);
-  hipLaunchKernelGGL(points_target_kernel, dim3(grid), dim3(kThreads256), 0, static_cast<hipStream_t>(stream), labels,
-                     label_class, M, L, index, N, params, C, Ho, Wo, static_cast<double>(radius), out, tiles_x, tiles_y,
-                     groups, units);
+  hipLaunchKernelGGL(points_target_kernel, dim3(capped_grid(units)), dim3(kThreads256), 0,
+                     static_cast<hipStream_t>(stream), labels, label_class, M, L, index, N, params, C, Ho, Wo,
+                     static_cast<double>(radius), out, tiles_x, tiles_y, groups, units);
   note_kernel("points_target");
   return launch_status();
 }
@@ -446,11 +394,9 @@ extern "C" int unetpp_target_ignore(const float* rects, const int32_t* rect_clas
   if (R == 0 && outside == 0) return UNETPP_OK;   // nothing to mark
   const int tiles_x = (Wo + kTileW - 1) / kTileW, tiles_y = (Ho + kTileH - 1) / kTileH;
   const int64_t units = int64_t(N) * tiles_y * tiles_x;
-  const int cus = device_cu_count();
-  const int64_t cap = int64_t(cus > 0 ? cus : 256) * 8;   // the rest of the units are grid-strided
-  const unsigned grid = static_cast<unsigned>(units < cap ? units : cap);
-  hipLaunchKernelGGL(target_ignore_kernel, dim3(grid), dim3(kThreads256), 0, static_cast<hipStream_t>(stream), rects,
-                     rect_class, M, R, index, params, C, Ho, Wo, Hs, Ws, outside, target, tiles_x, tiles_y, units);
+  hipLaunchKernelGGL(target_ignore_kernel, dim3(capped_grid(units)), dim3(kThreads256), 0,
+                     static_cast<hipStream_t>(stream), rects, rect_class, M, R, index, params, C, Ho, Wo, Hs, Ws,
+                     outside, target, tiles_x, tiles_y, units);
   note_kernel("target_ignore");
   return launch_status();
 }

@@ -1,7 +1,9 @@
 // Device-resident input pipeline: the decoded data set stays in HBM (uint8 [M, Hs, Ws, C] or float32 [M, C, Hs, Ws]) and
 // ONE launch produces a training batch from it -- gather by a device index, affine warp (bilinear, constant fill),
 // per-channel normalisation, contrast / brightness, NCHW fp32 out -- and carries the key-point labels through the same
-// transform.  A second, tiny launch draws the per-sample transforms from a 64-bit seed.
+// transform.  A second, tiny launch draws the per-sample transforms from a 64-bit seed.  The parameter row and its draw,
+// the two maps, the label rule, the frame store's layout and the pixel's normalisation are window.h's: crops.hip,
+// paste.hip and mask.hip place their labels, ignore marks and pasted pixels by the same definitions.
 //
 // warp_kernel: one thread produces 4 consecutive xo of one output row and loops over the channels; one 16-byte store per
 // channel plane where the address is 16-byte aligned and the 4 pixels are inside the row, scalar stores otherwise (the row
@@ -11,31 +13,21 @@
 // once, on the vector and on the scalar path alike.  No atomics, no LDS; every store offset is 64-bit.
 // A neighbour outside the frame contributes `fill`; its address is never formed into a load.  A position so far outside
 // that its floor does not fit the frame's index range (or a NaN) is an all-fill pixel.
-#include "common.h"
-#include "dropout.h"
+#include "window.h"
 
 #pragma clang fp contract(off)
 
 namespace unetpp {
 namespace {
 
-constexpr int kWarpThreads = 256;
-constexpr int kMaxSide = 1 << 24;   // pixel indices are exact in fp32 up to here
-
 template <bool U8>
-__device__ __forceinline__ float load_src(const void* __restrict__ store, int64_t off) {
-  if (U8) return static_cast<float>(static_cast<const uint8_t*>(store)[off]);
-  return static_cast<const float*>(store)[off];
-}
-
-template <bool U8>
-__global__ void __launch_bounds__(kWarpThreads) warp_kernel(
+__global__ void __launch_bounds__(kThreads256) warp_kernel(
     const void* __restrict__ store, int64_t M, int Hs, int Ws, int C, const int64_t* __restrict__ index, int N,
     const float* __restrict__ params, const float* __restrict__ mul, const float* __restrict__ add, float fill,
     float* __restrict__ out, int Ho, int Wo, const float* __restrict__ labels, int S, float* __restrict__ labels_out,
     uint8_t* __restrict__ inside) {
-  const int64_t n_threads = int64_t(gridDim.x) * kWarpThreads;
-  const int64_t tid = int64_t(blockIdx.x) * kWarpThreads + threadIdx.x;
+  const int64_t n_threads = int64_t(gridDim.x) * kThreads256;
+  const int64_t tid = int64_t(blockIdx.x) * kThreads256 + threadIdx.x;
 
   if (labels != nullptr) {   // one label per thread: forward map, frame test, sentinel
     const int64_t n_labels = int64_t(N) * S;
@@ -48,10 +40,8 @@ __global__ void __launch_bounds__(kWarpThreads) warp_kernel(
       if (idx >= 0 && idx < M) {
         const float* L = labels + (idx * S + s) * 2;
         const float x = L[0], y = L[1];
-        if (!(x < 0.f) && !(y < 0.f)) {
-          const float* P = params + int64_t(n) * UNETPP_WARP_PARAMS + 6;
-          xo = (P[0] * x + P[1] * y) + P[2];
-          yo = (P[3] * x + P[4] * y) + P[5];
+        if (label_valid(x, y)) {
+          map_forward(params + int64_t(n) * UNETPP_WARP_PARAMS, x, y, xo, yo);
           in = xo >= 0.f && xo <= static_cast<float>(Wo - 1) && yo >= 0.f && yo <= static_cast<float>(Ho - 1);
         }
       }
@@ -74,7 +64,7 @@ __global__ void __launch_bounds__(kWarpThreads) warp_kernel(
     const int yo = static_cast<int>(row % Ho);
     const int n = static_cast<int>(row / Ho);
     const float* P = params + int64_t(n) * UNETPP_WARP_PARAMS;
-    const float m0 = P[0], m1 = P[1], m2 = P[2], m3 = P[3], m4 = P[4], m5 = P[5], gain = P[12], bias = P[13];
+    const float inv[6] = {P[0], P[1], P[2], P[3], P[4], P[5]}, gain = P[12], bias = P[13];   // read once per quad
     const int64_t idx = index[n];
     const bool live = idx >= 0 && idx < M;
     const int64_t base = live ? idx * sample : 0;
@@ -85,9 +75,8 @@ __global__ void __launch_bounds__(kWarpThreads) warp_kernel(
     const float yf = static_cast<float>(yo);
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
-      const float xf = static_cast<float>(xo0 + p);
-      const float xs = (m0 * xf + m1 * yf) + m2;
-      const float ys = (m3 * xf + m4 * yf) + m5;
+      float xs, ys;
+      map_inverse(inv, static_cast<float>(xo0 + p), yf, xs, ys);
       const float x0f = floorf(xs), y0f = floorf(ys);
       const bool in_reach = x0f >= -2.f && x0f <= static_cast<float>(Ws) && y0f >= -2.f && y0f <= static_cast<float>(Hs);
       const int x0 = in_reach ? static_cast<int>(x0f) : -2;
@@ -115,7 +104,7 @@ __global__ void __launch_bounds__(kWarpThreads) warp_kernel(
         if (ok[p][2]) v10 = load_src<U8>(store, o + sy);
         if (ok[p][3]) v11 = load_src<U8>(store, o + sy + sx);
         const float v = (w[p][0] * v00 + w[p][1] * v01) + (w[p][2] * v10 + w[p][3] * v11);
-        r[p] = gain * (v * mc + ac) + bias;
+        r[p] = window_value(v, mc, ac, gain, bias);
       }
       float* dst = out + ((int64_t(n) * C + c) * Ho + yo) * Wo + xo0;
       if (row_full && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
@@ -129,55 +118,15 @@ __global__ void __launch_bounds__(kWarpThreads) warp_kernel(
   }
 }
 
-__device__ __forceinline__ double uniform24(uint64_t seed, int n, int k) {
-  const uint64_t bits = mix64(seed + 0x9E3779B97F4A7C15ULL * (static_cast<uint64_t>(n) * 16 + k + 1));
-  return static_cast<double>(static_cast<float>(bits >> 40) * 0x1p-24f);   // 24 bits: exact in fp32
-}
-
-__global__ void __launch_bounds__(kWarpThreads) draw_kernel(float* __restrict__ params, int N, uint64_t seed, int Hs,
-                                                            int Ws, int Ho, int Wo, unetpp_augment a) {
-  const int n = blockIdx.x * kWarpThreads + threadIdx.x;
+__global__ void __launch_bounds__(kThreads256) draw_kernel(float* __restrict__ params, int N, uint64_t seed, int Hs,
+                                                           int Ws, int Ho, int Wo, unetpp_augment a) {
+  const int n = blockIdx.x * kThreads256 + threadIdx.x;
   if (n >= N) return;
-  const double dx = static_cast<float>(uniform24(seed, n, 0)) < a.p_flip_h ? -1.0 : 1.0;
-  const double dy = static_cast<float>(uniform24(seed, n, 1)) < a.p_flip_v ? -1.0 : 1.0;
-  const int q = a.rot90 != 0 ? static_cast<int>(4.0 * uniform24(seed, n, 2)) : 0;
-  const double theta = (2.0 * uniform24(seed, n, 3) - 1.0) * static_cast<double>(a.max_deg) * (M_PI / 180.0);
-  const double ln_lo = log(static_cast<double>(a.scale_lo)), ln_hi = log(static_cast<double>(a.scale_hi));
-  const double s = exp(ln_lo + uniform24(seed, n, 4) * (ln_hi - ln_lo));
-  const double tx = floor((2.0 * uniform24(seed, n, 5) - 1.0) * static_cast<double>(a.max_tx) + 0.5);
-  const double ty = floor((2.0 * uniform24(seed, n, 6) - 1.0) * static_cast<double>(a.max_ty) + 0.5);
-  const double lo = a.gain_lo, hi = a.gain_hi;
-  const double gain = lo + uniform24(seed, n, 7) * (hi - lo);
-  const double bias = (2.0 * uniform24(seed, n, 8) - 1.0) * static_cast<double>(a.max_bias);
-
-  // R(theta) Q^q with Q^q as whole numbers: Q^q = [[qc, -qs], [qs, qc]], (qc, qs) = (1, 0), (0, 1), (-1, 0), (0, -1)
-  const double qc = q == 0 ? 1.0 : q == 2 ? -1.0 : 0.0;
-  const double qs = q == 1 ? 1.0 : q == 3 ? -1.0 : 0.0;
-  const double ct = cos(theta), st = sin(theta);
-  const double r00 = ct * qc - st * qs, r01 = -ct * qs - st * qc;   // R Q^q, again a rotation [[r00, r01], [-r01, r00]]
-  const double r10 = -r01, r11 = r00;
-  // forward A = s D (R Q^q); inverse B = (1/s) (R Q^q)^T D
-  const double a00 = s * dx * r00, a01 = s * dx * r01, a10 = s * dy * r10, a11 = s * dy * r11;
-  const double is = 1.0 / s;
-  const double b00 = is * r00 * dx, b01 = is * r10 * dy, b10 = is * r01 * dx, b11 = is * r11 * dy;
-  const double csx = 0.5 * (Ws - 1), csy = 0.5 * (Hs - 1), cox = 0.5 * (Wo - 1), coy = 0.5 * (Ho - 1);
-  float* P = params + int64_t(n) * UNETPP_WARP_PARAMS;
-  P[0] = static_cast<float>(b00);
-  P[1] = static_cast<float>(b01);
-  P[2] = static_cast<float>(csx + tx - b00 * cox - b01 * coy);
-  P[3] = static_cast<float>(b10);
-  P[4] = static_cast<float>(b11);
-  P[5] = static_cast<float>(csy + ty - b10 * cox - b11 * coy);
-  P[6] = static_cast<float>(a00);
-  P[7] = static_cast<float>(a01);
-  P[8] = static_cast<float>(cox - a00 * (csx + tx) - a01 * (csy + ty));
-  P[9] = static_cast<float>(a10);
-  P[10] = static_cast<float>(a11);
-  P[11] = static_cast<float>(coy - a10 * (csx + tx) - a11 * (csy + ty));
-  P[12] = static_cast<float>(gain);
-  P[13] = static_cast<float>(bias);
-  P[14] = 0.f;
-  P[15] = 0.f;
+  // the source centre: the frame's, moved by a whole number of pixels (uniforms 5 and 6)
+  const double tx = floor((2.0 * sample_uniform(seed, n, 5) - 1.0) * static_cast<double>(a.max_tx) + 0.5);
+  const double ty = floor((2.0 * sample_uniform(seed, n, 6) - 1.0) * static_cast<double>(a.max_ty) + 0.5);
+  const double csx = 0.5 * (Ws - 1), csy = 0.5 * (Hs - 1);
+  augment_row(params + int64_t(n) * UNETPP_WARP_PARAMS, seed, n, a, csx + tx, csy + ty, 0.5 * (Wo - 1), 0.5 * (Ho - 1));
 }
 
 }  // namespace
@@ -202,17 +151,15 @@ extern "C" int unetpp_warp_batch(const void* store, int32_t store_type, int64_t 
   const int64_t n_quads = int64_t(N) * Ho * ((Wo + 3) >> 2);
   const int64_t n_labels = int64_t(N) * S;
   const int64_t work = n_quads > n_labels ? n_quads : n_labels;
-  const int64_t blocks = (work + kWarpThreads - 1) / kWarpThreads;
-  const int cus = device_cu_count();
-  const int64_t cap = int64_t(cus > 0 ? cus : 256) * 8;   // the rest of the work is grid-strided
-  const unsigned grid = static_cast<unsigned>(blocks < cap ? blocks : cap);
+  const int64_t blocks = (work + kThreads256 - 1) / kThreads256;
+  const unsigned grid = capped_grid(blocks);   // the rest of the work is grid-strided
   const hipStream_t st = static_cast<hipStream_t>(stream);
   if (store_type == UNETPP_STORE_U8) {
-    hipLaunchKernelGGL(warp_kernel<true>, dim3(grid), dim3(kWarpThreads), 0, st, store, M, Hs, Ws, C, index, N, params,
+    hipLaunchKernelGGL(warp_kernel<true>, dim3(grid), dim3(kThreads256), 0, st, store, M, Hs, Ws, C, index, N, params,
                        mul, add, fill, out, Ho, Wo, labels, S, labels_out, inside);
     note_kernel("warp_u8");
   } else {
-    hipLaunchKernelGGL(warp_kernel<false>, dim3(grid), dim3(kWarpThreads), 0, st, store, M, Hs, Ws, C, index, N, params,
+    hipLaunchKernelGGL(warp_kernel<false>, dim3(grid), dim3(kThreads256), 0, st, store, M, Hs, Ws, C, index, N, params,
                        mul, add, fill, out, Ho, Wo, labels, S, labels_out, inside);
     note_kernel("warp_f32");
   }
@@ -224,8 +171,8 @@ extern "C" int unetpp_augment_draw(float* params, int32_t N, uint64_t seed, int3
   if (params == nullptr || augment == nullptr) return UNETPP_EINVAL;
   if (N <= 0 || Hs <= 0 || Ws <= 0 || Ho <= 0 || Wo <= 0) return UNETPP_EINVAL;
   if (!(augment->scale_lo > 0.f) || !(augment->scale_hi > 0.f)) return UNETPP_EINVAL;
-  const unsigned grid = static_cast<unsigned>((N + kWarpThreads - 1) / kWarpThreads);
-  hipLaunchKernelGGL(draw_kernel, dim3(grid), dim3(kWarpThreads), 0, static_cast<hipStream_t>(stream), params, N, seed,
+  const unsigned grid = static_cast<unsigned>((N + kThreads256 - 1) / kThreads256);
+  hipLaunchKernelGGL(draw_kernel, dim3(grid), dim3(kThreads256), 0, static_cast<hipStream_t>(stream), params, N, seed,
                      Hs, Ws, Ho, Wo, *augment);
   note_kernel("augment_draw");
   return launch_status();

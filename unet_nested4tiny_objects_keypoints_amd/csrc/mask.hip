@@ -32,32 +32,21 @@
 // same bits on any grid.
 //
 // target_ignore_mask_kernel: the unit and thread shape of target_ignore_kernel -- (sample, 64 x 16 tile), 4 consecutive
-// x of one row per thread, all classes.  The source position is the warp's own float32 expression; a position is in the
-// frame iff 0 <= xs <= Ws - 1 and 0 <= ys <= Hs - 1 (a NaN is outside), its pixel is the nearest one, clamped.  Under
-// the exact augmentation family the 4 pixels of a thread lie in one row or one column of the frame: a thread keeps the
-// last word it loaded per plane walk, so neighbours in a row share a load.  Stores of -1.0f only, nothing of target is
-// read: idempotent stores of one constant, the same bits on any grid.
-#include "common.h"
+// x of one row per thread, all classes.  The source position is window.h's map_inverse, as in that kernel; a position
+// is in the frame iff 0 <= xs <= Ws - 1 and 0 <= ys <= Hs - 1 (a NaN is outside), its pixel is the nearest one,
+// clamped.  Under the exact augmentation family the 4 pixels of a thread lie in one row or one column of the frame: a
+// thread keeps the last word it loaded per plane walk, so neighbours in a row share a load.  Stores of -1.0f only,
+// nothing of target is read: idempotent stores of one constant, the same bits on any grid.
+#include "window.h"
 
 #pragma clang fp contract(off)
 
 namespace unetpp {
 namespace {
 
-constexpr int kThreads256 = 256;
-constexpr int kMaxSide = 1 << 24;   // pixel indices are exact in fp32 up to here
-constexpr int kTileW = 64, kTileH = 16;
-constexpr int kMaxClasses = 65535;
-constexpr int kClassGroup = 32;
 constexpr int kRingChunk = 256;     // rings examined at a time: one per thread
 constexpr int kEdgeChunk = 256;     // edges of a ring held in LDS at a time: one per thread
 constexpr int64_t kMaxElems = 2147483647;   // elements / words one launch indexes
-
-inline unsigned persistent_grid(int64_t units) {
-  const int cus = device_cu_count();
-  const int64_t cap = int64_t(cus > 0 ? cus : 256) * 8;   // the rest of the units are grid-strided
-  return static_cast<unsigned>(units < cap ? units : cap);
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 template <typename T>
@@ -229,9 +218,8 @@ __global__ void __launch_bounds__(kThreads256) target_ignore_mask_kernel(
     unsigned every = 0;   // bit p: pixel px + p is ignored for every class
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
-      const float xf = static_cast<float>(px + p);
-      const float xs = (Pm[0] * xf + Pm[1] * yf) + Pm[2];
-      const float ys = (Pm[3] * xf + Pm[4] * yf) + Pm[5];
+      float xs, ys;
+      map_inverse(Pm, static_cast<float>(px + p), yf, xs, ys);
       const bool in = live && 0.f <= xs && xs <= x_max && 0.f <= ys && ys <= y_max;
       every |= (outside != 0 && !in) ? (1u << p) : 0u;
       at[p] = -1;
@@ -301,7 +289,7 @@ extern "C" int unetpp_mask_pack(const void* mask, int32_t kind, int64_t rows, in
   if (rows > kMaxElems / W) return UNETPP_EINVAL;
   const int Wd = (W + 31) / 32, chunks = (W + 63) / 64;
   const int64_t units = rows * chunks;   // one per wave
-  const unsigned grid = persistent_grid((units + 3) / 4);
+  const unsigned grid = capped_grid((units + 3) / 4);
   if (kind == UNETPP_MASK_U8) {
     hipLaunchKernelGGL(mask_pack_kernel<uint8_t>, dim3(grid), dim3(kThreads256), 0, static_cast<hipStream_t>(stream),
                        static_cast<const uint8_t*>(mask), W, Wd, chunks, bits, units);
@@ -325,7 +313,7 @@ extern "C" int unetpp_mask_polygons(const float* vertices, const int32_t* counts
   if (G > 0 && V > 0 && int64_t(S) * G > kMaxElems / (2 * int64_t(V))) return UNETPP_EINVAL;
   const int tiles_x = (W + kTileW - 1) / kTileW, tiles_y = (H + kTileH - 1) / kTileH;
   const int64_t units = int64_t(S) * P * tiles_y * tiles_x;
-  hipLaunchKernelGGL(mask_polygons_kernel, dim3(persistent_grid(units)), dim3(kThreads256), 0,
+  hipLaunchKernelGGL(mask_polygons_kernel, dim3(capped_grid(units)), dim3(kThreads256), 0,
                      static_cast<hipStream_t>(stream), vertices, counts, poly_plane, poly_clear, G, V, P, H, W, Wd, bits,
                      tiles_x, tiles_y, units);
   note_kernel("mask_polygons");
@@ -345,7 +333,7 @@ extern "C" int unetpp_target_ignore_mask(const int32_t* bits, const int32_t* pla
   if (P == 0 && outside == 0) return UNETPP_OK;   // nothing to mark
   const int tiles_x = (Wo + kTileW - 1) / kTileW, tiles_y = (Ho + kTileH - 1) / kTileH;
   const int64_t units = int64_t(N) * tiles_y * tiles_x;
-  hipLaunchKernelGGL(target_ignore_mask_kernel, dim3(persistent_grid(units)), dim3(kThreads256), 0,
+  hipLaunchKernelGGL(target_ignore_mask_kernel, dim3(capped_grid(units)), dim3(kThreads256), 0,
                      static_cast<hipStream_t>(stream), bits, plane_class, M, P, Hs, Ws, Wd, index, params, C, Ho, Wo,
                      outside, target, tiles_x, tiles_y, units);
   note_kernel("target_ignore_mask");

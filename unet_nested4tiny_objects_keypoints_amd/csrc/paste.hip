@@ -6,7 +6,7 @@
 // A patch is the (2R+1) x (2R+1) whole pixels about the rounded centre of a row of the source table, under one of the
 // eight flips and quarter turns (a code), blended into the window by a radial weight table the host made.  Code c:
 // q = c & 3 quarter turns, then a flip in x when c & 4 -- T_c = D Q^q with Q^q = [[qc, -qs], [qs, qc]] as whole numbers,
-// the matrices of crops_draw_kernel.  A source offset (i, j) from the source centre lands at T_c (i, j) from the
+// the matrices of window.h's augment_row.  A source offset (i, j) from the source centre lands at T_c (i, j) from the
 // destination centre, so destination offset (i, j) reads source offset T_c^-1 (i, j) = Q^-q D (i, j); the label's
 // sub-pixel offset goes through T_c like the pixels.
 //
@@ -20,36 +20,27 @@
 // is checked again against the table, the frame, the window and the code range before an address is formed.
 //
 // paste_target_kernel: the tiles and thread layout of target_ignore_kernel; the K rows of a window pass through LDS
-// once per unit; per class that has a live slot, the least squared distance (the float64 expression of
-// points_target_kernel), one sqrt and one exp per pixel, stored only where it exceeds a target that is not negative.
+// once per unit; per class that has a live slot, the least squared distance (float64, the fold of
+// points_target_kernel) and its nearest_value, one sqrt and one exp per pixel, stored only where it exceeds a target
+// that is not negative.
+//
+// The label positions, the frame store, the pixel's normalisation, the draws and the grid are window.h's, shared with
+// loader.hip, crops.hip and mask.hip.
 //
 // No atomics; implicit contraction is off; every offset into a store, the inputs or the target is 64-bit; a unit's
 // result does not depend on which workgroup computes it: the same bits on any grid.
-#include "common.h"
-#include "dropout.h"
+#include "window.h"
 
 #pragma clang fp contract(off)
 
 namespace unetpp {
 namespace {
 
-constexpr int kThreads256 = 256;
-constexpr int kMaxSide = 1 << 24;   // pixel indices are exact in fp32 up to here
-constexpr int kTileW = 64, kTileH = 16;   // 16 quads x 16 rows = 256 threads
-constexpr int kMaxClasses = 65535;
 constexpr int kSlots = UNETPP_PASTE_MAX_SLOTS;
 
-// uniform j of slot k of window n: 24 bits, exact in fp32
-__device__ __forceinline__ double paste_uniform24(uint64_t seed, int n, int k, int j) {
-  const uint64_t ctr = (static_cast<uint64_t>(n) * kSlots + k) * 8 + j + 1;
-  const uint64_t bits = mix64(seed + 0x9E3779B97F4A7C15ULL * ctr);
-  return static_cast<double>(static_cast<float>(bits >> 40) * 0x1p-24f);
-}
-
-// floor(u * count) limited to count - 1
-__device__ __forceinline__ int pick(double u, int count) {
-  const double v = floor(u * static_cast<double>(count));
-  return static_cast<int>(v < static_cast<double>(count - 1) ? v : static_cast<double>(count - 1));
+// uniform j (0..7) of slot k of window n
+__device__ __forceinline__ double slot_uniform(uint64_t seed, int n, int k, int j) {
+  return uniform24(seed, (static_cast<uint64_t>(n) * kSlots + k) * 8 + j + 1);
 }
 
 // (qc, qs, dx) of a code: Q^q = [[qc, -qs], [qs, qc]], dx = -1 with the flip in x
@@ -93,15 +84,15 @@ __global__ void __launch_bounds__(kThreads256) paste_draw_kernel(
     const bool live = idx >= 0 && idx < M;   // (uniform over the workgroup)
     int my_code = 0;
     if (tid < K) {
-      const double u0 = paste_uniform24(seed, n, tid, 0), u1 = paste_uniform24(seed, n, tid, 1);
-      const double u2 = paste_uniform24(seed, n, tid, 2), u3 = paste_uniform24(seed, n, tid, 3);
-      const double u4 = paste_uniform24(seed, n, tid, 4);
-      const int t = pick(u1, T);
+      const double u0 = slot_uniform(seed, n, tid, 0), u1 = slot_uniform(seed, n, tid, 1);
+      const double u2 = slot_uniform(seed, n, tid, 2), u3 = slot_uniform(seed, n, tid, 3);
+      const double u4 = slot_uniform(seed, n, tid, 4);
+      const int t = static_cast<int>(pick(u1, T));
       my_code = dihedral != 0 ? static_cast<int>(8.0 * u2) : 0;
       int frame, cx, cy, c;
       const bool row_ok = source_row(src_frame, src_xy, src_class, t, M, C, Hs, Ws, R, frame, cx, cy, c);
-      s_px[tid] = R + pick(u3, Wo - 2 * R);
-      s_py[tid] = R + pick(u4, Ho - 2 * R);
+      s_px[tid] = R + static_cast<int>(pick(u3, Wo - 2 * R));
+      s_py[tid] = R + static_cast<int>(pick(u4, Ho - 2 * R));
       s_row[tid] = t;
       s_ok[tid] = (static_cast<float>(u0) < p && live && row_ok) ? 1 : 0;
       s_near[tid] = 0;
@@ -113,12 +104,12 @@ __global__ void __launch_bounds__(kThreads256) paste_draw_kernel(
     if (live) {
       const float* lab = labels + idx * L * 2;
       const int32_t* lc = label_class + idx * L;
-      const float* P = params + int64_t(n) * UNETPP_WARP_PARAMS + 6;
+      const float* P = params + int64_t(n) * UNETPP_WARP_PARAMS;
       for (int64_t l = tid; l < L; l += kThreads256) {
         const float x = lab[2 * l], y = lab[2 * l + 1];
-        if (lc[l] < 0 || x < 0.f || y < 0.f) continue;
-        const float xo = (P[0] * x + P[1] * y) + P[2];   // label_at of crops.hip
-        const float yo = (P[3] * x + P[4] * y) + P[5];
+        if (lc[l] < 0 || x < 0.f || y < 0.f) continue;   // (!label_valid(x, y) spelled out: 2 scalar spills fewer)
+        float xo, yo;
+        map_forward(P, x, y, xo, yo);
         for (int k = 0; k < K; ++k) {
           if (s_ok[k] == 0) continue;   // (uniform: an LDS broadcast)
           const double dx = static_cast<double>(xo) - static_cast<double>(s_px[k]);
@@ -173,12 +164,6 @@ __global__ void __launch_bounds__(kThreads256) paste_draw_kernel(
 }
 
 template <bool U8>
-__device__ __forceinline__ float load_src(const void* __restrict__ store, int64_t off) {
-  if (U8) return static_cast<float>(static_cast<const uint8_t*>(store)[off]);
-  return static_cast<const float*>(store)[off];
-}
-
-template <bool U8>
 __global__ void __launch_bounds__(kThreads256) paste_apply_kernel(
     float* __restrict__ inputs, int N, int K, int Cin, int Ho, int Wo, const int32_t* __restrict__ src,
     const int32_t* __restrict__ dst, const int32_t* __restrict__ code, const int32_t* __restrict__ src_frame,
@@ -217,7 +202,7 @@ __global__ void __launch_bounds__(kThreads256) paste_apply_kernel(
       const int fi = dx * i;
       const int si = qc * fi + qs * j, sj = qc * j - qs * fi;
       const float v = load_src<U8>(store, base + int64_t(sj) * sy + int64_t(si) * sx + c * sc);
-      const float pv = gain * (v * mul[c] + add[c]) + bias;   // warp_kernel's expression
+      const float pv = window_value(v, mul[c], add[c], gain, bias);
       float* out = inputs + ((int64_t(n) * Cin + c) * Ho + (py + j)) * Wo + (px + i);
       const float d = *out;
       *out = a == 1.f ? pv : a == 0.f ? d : d + a * (pv - d);
@@ -296,7 +281,7 @@ __global__ void __launch_bounds__(kThreads256) paste_target_kernel(
       unsigned change = 0;
 #pragma unroll
       for (int p = 0; p < kQuad; ++p) {
-        const float v = static_cast<float>(exp(-0.5 * sqrt(m[p]) / radius));
+        const float v = nearest_value(m[p], radius);
         if (v > t[p] && !(t[p] < 0.f) && px + p <= x_hi) {
           t[p] = v;
           change |= 1u << p;
@@ -312,12 +297,6 @@ __global__ void __launch_bounds__(kThreads256) paste_target_kernel(
       }
     }
   }
-}
-
-inline unsigned capped_grid(int64_t units) {
-  const int cus = device_cu_count();
-  const int64_t cap = int64_t(cus > 0 ? cus : 256) * 8;   // the rest of the units are grid-strided
-  return static_cast<unsigned>(units < cap ? units : cap);
 }
 
 }  // namespace

@@ -111,6 +111,34 @@ def _need(t: torch.Tensor, what: str, dtype=torch.float32):
     return t
 
 
+def _window_rows(index: torch.Tensor, params: torch.Tensor, n: Optional[int] = None) -> int:
+    """N of index [N] / params [N, 16], the rows of a warp; n: the N they must have (a target's)."""
+    rows = int(index.numel())
+    if index.dim() != 1 or (n is not None and rows != n) or tuple(params.shape) != (rows, _lib.WARP_PARAMS):
+        raise ValueError("index [N] and params [N, %d]" % _lib.WARP_PARAMS
+                         + ("" if n is None else " for a target of N = %d samples" % n))
+    return rows
+
+
+def _frame_store(store: torch.Tensor, shape_error: str = "store must be a contiguous 4-d tensor"):
+    """store -> (u8, M, Hs, Ws, C): the frames as uint8 [M, Hs, Ws, C] or float32 [M, C, Hs, Ws]."""
+    if not store.is_cuda:
+        raise RuntimeError("store must live on the GPU: this path has no CPU fallback")
+    if store.dtype not in (torch.uint8, torch.float32):
+        raise TypeError("store must be uint8 [M, Hs, Ws, C] or float32 [M, C, Hs, Ws], got %s" % store.dtype)
+    if store.dim() != 4 or not store.is_contiguous():
+        raise ValueError(shape_error)
+    u8 = store.dtype == torch.uint8
+    hs, ws, c = store.shape[1:] if u8 else (store.shape[2], store.shape[3], store.shape[1])
+    return u8, int(store.shape[0]), int(hs), int(ws), int(c)
+
+
+def _label_table(labels: torch.Tensor, label_class: torch.Tensor):   # -> (M, L)
+    if labels.dim() != 3 or labels.shape[2] != 2 or tuple(label_class.shape) != tuple(labels.shape[:2]):
+        raise ValueError("labels must be [M, L, 2] and label_class [M, L]")
+    return int(labels.shape[0]), int(labels.shape[1])
+
+
 _ACT_DTYPES = (torch.float32, torch.bfloat16)  # storage types of activations (bf16: UNETPP_GEMM_BF16 launches)
 
 
@@ -1298,24 +1326,14 @@ def warp_batch(store: torch.Tensor, index: torch.Tensor, params: torch.Tensor, o
     """One launch: gather index [N] from the store (uint8 [M, Hs, Ws, C] or float32 [M, C, Hs, Ws]), warp by params
     [N, 16], normalise by mul / add [C] -> float32 [N, C, Ho, Wo]; with labels [M, S, 2] also (labels_out [N, S, 2],
     inside [N, S] uint8) (include/unetpp_hip.h: unetpp_warp_batch).  out: a contiguous float32 [N, C, Ho, Wo] to write."""
-    if not store.is_cuda:
-        raise RuntimeError("store must live on the GPU: this path has no CPU fallback")
-    if store.dtype not in (torch.uint8, torch.float32):
-        raise TypeError("store must be uint8 [M, Hs, Ws, C] or float32 [M, C, Hs, Ws], got %s" % store.dtype)
-    if store.dim() != 4 or not store.is_contiguous():
-        raise ValueError("store must be a contiguous 4-d tensor")
-    u8 = store.dtype == torch.uint8
-    m, (hs, ws, c) = int(store.shape[0]), (store.shape[1:] if u8 else (store.shape[2], store.shape[3], store.shape[1]))
-    hs, ws, c = int(hs), int(ws), int(c)
+    u8, m, hs, ws, c = _frame_store(store)
     if not 1 <= c <= _lib.WARP_MAX_C:
         raise ValueError("a store has 1 to %d channels, got %d" % (_lib.WARP_MAX_C, c))
     _need(index, "index", torch.int64)
     _need(params, "params")
     _need(mul, "mul")
     _need(add, "add")
-    n = int(index.numel())
-    if index.dim() != 1 or tuple(params.shape) != (n, _lib.WARP_PARAMS):
-        raise ValueError("index [N] and params [N, %d]" % _lib.WARP_PARAMS)
+    n = _window_rows(index, params)
     if tuple(mul.shape) != (c,) or tuple(add.shape) != (c,):
         raise ValueError("mul and add must be [%d]" % c)
     ho, wo = int(out_size[0]), int(out_size[1])
@@ -1510,12 +1528,8 @@ def points_target(labels: torch.Tensor, label_class: torch.Tensor, index: torch.
     _need(label_class, "label_class", torch.int32)
     _need(index, "index", torch.int64)
     _need(params, "params")
-    if labels.dim() != 3 or labels.shape[2] != 2 or tuple(label_class.shape) != tuple(labels.shape[:2]):
-        raise ValueError("labels must be [M, L, 2] and label_class [M, L]")
-    m, n_labels = int(labels.shape[0]), int(labels.shape[1])
-    n = int(index.numel())
-    if index.dim() != 1 or tuple(params.shape) != (n, _lib.WARP_PARAMS):
-        raise ValueError("index [N] and params [N, %d]" % _lib.WARP_PARAMS)
+    m, n_labels = _label_table(labels, label_class)
+    n = _window_rows(index, params)
     c, (ho, wo) = int(n_classes), (int(out_size[0]), int(out_size[1]))
     radius = float(radius)
     if not radius > 0.0:
@@ -1536,6 +1550,30 @@ def points_target(labels: torch.Tensor, label_class: torch.Tensor, index: torch.
     return out
 
 
+def _ignore_rows(target: torch.Tensor, index: torch.Tensor, params: torch.Tensor):
+    """(N, C, Ho, Wo) of a target [N, C, Ho, Wo] and the check of the warp rows index / params that belong to it."""
+    _need(target, "target")
+    _need(index, "index", torch.int64)
+    _need(params, "params")
+    if target.dim() != 4:
+        raise ValueError("target must be [N, C, Ho, Wo]")
+    n, c, ho, wo = (int(v) for v in target.shape)
+    _window_rows(index, params, n)
+    return n, c, ho, wo
+
+
+def _ignore_frames(m, n_frames, things: str, tensors, target: torch.Tensor, src_size):
+    """(M, Hs, Ws) of an ignore launch.  m: the table's M, else n_frames; things: its rows' name; tensors: on target's device."""
+    if m is None or (n_frames is not None and int(n_frames) != m):
+        raise ValueError("the number of frames: give n_frames without %s, and the %s' own M with them" % (things, things))
+    if any(t.device != target.device for t in tensors):
+        raise ValueError("all tensors must live on one device")
+    hs, ws = int(src_size[0]), int(src_size[1])
+    if min(int(m), hs, ws, *target.shape) < 1 or target.shape[1] > 65535:
+        raise ValueError("N, the window and the frame must be positive and C in 1..65535")
+    return int(m), hs, ws
+
+
 def target_ignore(target: torch.Tensor, rects: Optional[torch.Tensor], rect_class: Optional[torch.Tensor],
                   index: torch.Tensor, params: torch.Tensor, src_size, outside: bool = False,
                   n_frames: Optional[int] = None) -> torch.Tensor:
@@ -1544,15 +1582,7 @@ def target_ignore(target: torch.Tensor, rects: Optional[torch.Tensor], rect_clas
     for no rectangles -- then n_frames says how many frames there are (an index outside [0, M) is an all-fill sample);
     index [N] int64 and params [N, 16]: the rows of the warp; src_size = (Hs, Ws); outside: also mark what lies outside
     the frame (include/unetpp_hip.h: unetpp_target_ignore).  Nothing else of target is touched."""
-    _need(target, "target")
-    _need(index, "index", torch.int64)
-    _need(params, "params")
-    if target.dim() != 4:
-        raise ValueError("target must be [N, C, Ho, Wo]")
-    n, c, ho, wo = (int(v) for v in target.shape)
-    if index.dim() != 1 or int(index.numel()) != n or tuple(params.shape) != (n, _lib.WARP_PARAMS):
-        raise ValueError("index [N] and params [N, %d] for a target of N = %d samples" % (_lib.WARP_PARAMS, n))
-    dev = target.device
+    n, c, ho, wo = _ignore_rows(target, index, params)
     m, r = n_frames, 0
     if rects is not None and rects.numel() > 0:
         _need(rects, "rects")
@@ -1562,14 +1592,7 @@ def target_ignore(target: torch.Tensor, rects: Optional[torch.Tensor], rect_clas
         m, r = int(rects.shape[0]), int(rects.shape[1])
     elif rects is not None and rects.dim() == 3 and rects.shape[0] > 0:
         m = int(rects.shape[0])
-    if m is None or (n_frames is not None and int(n_frames) != m):
-        raise ValueError("the number of frames: give n_frames without rectangles, and the rectangles' own M with them")
-    m = int(m)
-    if any(t.device != dev for t in (index, params) + ((rects, rect_class) if r else ())):
-        raise ValueError("all tensors must live on one device")
-    hs, ws = int(src_size[0]), int(src_size[1])
-    if min(m, n, c, ho, wo, hs, ws) < 1 or c > 65535:
-        raise ValueError("N, the window and the frame must be positive and C in 1..65535")
+    m, hs, ws = _ignore_frames(m, n_frames, "rectangles", (index, params) + ((rects, rect_class) if r else ()), target, src_size)
     _timed_call("target_ignore", 0.0, lambda: check(_lib.lib().unetpp_target_ignore(
         _ptr(rects) if r else None, _ptr(rect_class) if r else None, m, r, _ptr(index), n, _ptr(params), c, ho, wo, hs, ws,
         1 if outside else 0, _ptr(target), _stream()), "unetpp_target_ignore"), 4.0 * n * c * ho * wo)
@@ -1639,15 +1662,7 @@ def target_ignore_mask(target: torch.Tensor, bits: Optional[torch.Tensor], plane
     [M, P, Hs, ceil(Ws / 32)] with plane_class int32 [P], or None / P = 0 for the `outside` rule alone -- then n_frames
     says how many frames there are; index [N] int64, params [N, 16]; src_size = (Hs, Ws) must be the planes' size
     (include/unetpp_hip.h: unetpp_target_ignore_mask)."""
-    _need(target, "target")
-    _need(index, "index", torch.int64)
-    _need(params, "params")
-    if target.dim() != 4:
-        raise ValueError("target must be [N, C, Ho, Wo]")
-    n, c, ho, wo = (int(v) for v in target.shape)
-    if index.dim() != 1 or int(index.numel()) != n or tuple(params.shape) != (n, _lib.WARP_PARAMS):
-        raise ValueError("index [N] and params [N, %d] for a target of N = %d samples" % (_lib.WARP_PARAMS, n))
-    dev = target.device
+    n, c, ho, wo = _ignore_rows(target, index, params)
     hs, ws = int(src_size[0]), int(src_size[1])
     m, p = n_frames, 0
     if bits is not None and bits.numel() > 0:
@@ -1660,13 +1675,7 @@ def target_ignore_mask(target: torch.Tensor, bits: Optional[torch.Tensor], plane
         m, p = int(bits.shape[0]), int(bits.shape[1])
     elif bits is not None and bits.dim() == 4 and bits.shape[0] > 0:
         m = int(bits.shape[0])
-    if m is None or (n_frames is not None and int(n_frames) != m):
-        raise ValueError("the number of frames: give n_frames without planes, and the planes' own M with them")
-    m = int(m)
-    if any(t.device != dev for t in (index, params) + ((bits, plane_class) if p else ())):
-        raise ValueError("all tensors must live on one device")
-    if min(m, n, c, ho, wo, hs, ws) < 1 or c > 65535:
-        raise ValueError("N, the window and the frame must be positive and C in 1..65535")
+    m, hs, ws = _ignore_frames(m, n_frames, "planes", (index, params) + ((bits, plane_class) if p else ()), target, src_size)
     _timed_call("target_ignore_mask", 0.0, lambda: check(_lib.lib().unetpp_target_ignore_mask(
         _ptr(bits) if p else None, _ptr(plane_class) if p else None, m, p, hs, ws, _ptr(index), n, _ptr(params), c, ho, wo,
         1 if outside else 0, _ptr(target), _stream()), "unetpp_target_ignore_mask"), 4.0 * n * c * ho * wo)
@@ -1736,12 +1745,9 @@ def paste_draw(max_pastes: int, seed: int, src_frame: torch.Tensor, src_xy: torc
     _need(params, "params")
     dev = params.device
     t = _paste_sources(src_frame, src_xy, src_class, dev)
-    if labels.dim() != 3 or labels.shape[2] != 2 or tuple(label_class.shape) != tuple(labels.shape[:2]):
-        raise ValueError("labels must be [M, L, 2] and label_class [M, L]")
-    m, n_labels = int(labels.shape[0]), int(labels.shape[1])
-    n, k, r = int(index.numel()), int(max_pastes), _paste_radius(patch_radius)
-    if index.dim() != 1 or tuple(params.shape) != (n, _lib.WARP_PARAMS):
-        raise ValueError("index [N] and params [N, %d]" % _lib.WARP_PARAMS)
+    m, n_labels = _label_table(labels, label_class)
+    k, r = int(max_pastes), _paste_radius(patch_radius)
+    n = _window_rows(index, params)
     if any(v.device != dev for v in (labels, label_class, index)):
         raise ValueError("all tensors must live on one device")
     if not 1 <= k <= _lib.PASTE_MAX_SLOTS:
@@ -1777,15 +1783,9 @@ def paste_apply(inputs: torch.Tensor, src: torch.Tensor, dst: torch.Tensor, code
         _need(v, name, torch.int32)
     for name, v in (("params", params), ("mul", mul), ("add", add), ("alpha", alpha)):
         _need(v, name)
-    if not store.is_cuda:
-        raise RuntimeError("store must live on the GPU: this path has no CPU fallback")
-    if store.dtype not in (torch.uint8, torch.float32):
-        raise TypeError("store must be uint8 [M, Hs, Ws, C] or float32 [M, C, Hs, Ws], got %s" % store.dtype)
-    if store.dim() != 4 or not store.is_contiguous() or inputs.dim() != 4:
+    u8, m, hs, ws, cin = _frame_store(store, "store must be a contiguous 4-d tensor and inputs [N, C, Ho, Wo]")
+    if inputs.dim() != 4:
         raise ValueError("store must be a contiguous 4-d tensor and inputs [N, C, Ho, Wo]")
-    u8 = store.dtype == torch.uint8
-    m, (hs, ws, cin) = int(store.shape[0]), (store.shape[1:] if u8 else (store.shape[2], store.shape[3], store.shape[1]))
-    hs, ws, cin = int(hs), int(ws), int(cin)
     n, ci, ho, wo = (int(v) for v in inputs.shape)
     dev = inputs.device
     t = _paste_sources(src_frame, src_xy, src_class, dev)
